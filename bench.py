@@ -1,7 +1,18 @@
 #!/usr/bin/env python3
 """bench.py - Mrays/s of the HIP ray-trace hot path on BASELINE.json's headline config.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and no more: scene set-up, W warmup steps, exactly K timed steps, the outputs of the
+last timed step when --dump-outputs is given, and the JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step and
+the timed frames' configuration).  Everything else - the roofline block and its counting render, the live HBM traffic passes,
+the CPU baseline and its parity check, the other workloads, two frames in flight, the multi-GPU bit-identity check - runs
+only with --full (the objects of the line it fills are null without it).
+
+--dump-outputs DIR writes, after the timed steps, what the timed path handed its caller in the last step: DIR/framebuffer.npy
+(float32, height x width x 4, the resolved RGBA frame; rank 0's assembled frame for N > 1) and DIR/ray_count.npy (float64, the
+frame's ray count over all ranks).  A frame larger than DUMP_MAX_BYTES is written as a fixed, seeded sample of its pixels
+instead: DIR/framebuffer_sample.npy (float32, n x 4) and DIR/framebuffer_sample_index.npy (float64, the flat pixel indices).
 
 N > 1 needs no launcher: the process starts its own N ranks as child processes (one per GPU, RANK / LOCAL_RANK / WORLD_SIZE /
 MASTER_* set, rendezvous on 127.0.0.1) before it has imported torch or touched HIP, relays rank 0's JSON line and exits
@@ -22,14 +33,14 @@ next frame fills that.  Every frame is rendered, gathered and assembled inside t
 the per-frame device latency.  With N > 1 the render streams leave 8 compute units to the RCCL gather (PRT_RESERVE_CUS).
 Total work is fixed as N grows -> "scaling": "strong".
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full):
   roofline      the dominant kernel (k_pool: one launch = one frame): SURVEY.md §8d algorithmic bytes of a launch (rays x 52 B +
                 BVH nodes fetched x the build's node size (64 B, 4-wide) + triangle tests x 36 B + shaded hits x 80 B + pixels
                 x 16 B) / its duration, measured with HIP events on the kernel's own stream inside the timed region.  That
                 figure counts every per-lane node fetch, most of which the caches serve, so its label says what it is
                 ("cache-inclusive algorithmic bytes") and `hbm_measured` / `limiter` say what the memory system and the
                 kernel really do.  `traffic` = HBM bytes per launch, FETCH_SIZE x 2 + WRITE_SIZE as the gfx950 guide prescribes,
-                MEASURED IN THIS RUN (since round 4): before it touches the GPU the default command runs two short children of
+                MEASURED IN THIS RUN (since round 4): before it touches the GPU a --full run starts two short children of
                 itself under `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` (a pass each, counters only; ~6 s each) and takes
                 the timed frames' kernel from their counter files (`traffic_source` says so).  Where that is not possible (no
                 rocprofv3, a refused or failing pass, N > 1, the quick forms with --no-cpu-baseline / --no-other-workloads) the
@@ -82,6 +93,8 @@ B_TRI_BUILD, B_SHADE_BUILD = 48, 144
 #   key: (workload, golden fixture, adaptive max_spp or 0)
 OTHER_WORKLOADS = [("C2", "c2_cornell_512_l4", 0), ("C3", "c3_icosphere_1080p_l24", 0), ("C5", "c5_terrain1m_4k_l120", 0),
                    ("C4-adaptive", "c4_terrain1m_adaptive_l60", 50)]
+# --dump-outputs writes at most 64 MB: a full C4 frame (33 MB) whole, a larger one (C5: 133 MB) as a seeded pixel sample
+DUMP_MAX_BYTES = 48 << 20
 
 
 def log(msg):
@@ -235,7 +248,7 @@ def measure_traffic_live(workload, pipeline):
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             cmd = [exe, "--pmc", counter, "--output-format", "csv", "-d", os.path.join(out, counter), "--",
                    sys.executable, os.path.abspath(__file__), "--workload", workload, "--pipeline", str(pipeline), "--steps", "3", "--warmup", "1",
-                   "--no-cpu-baseline", "--no-other-workloads", "--no-live-traffic"]
+                   "--full", "--no-cpu-baseline", "--no-other-workloads", "--no-live-traffic"]
             env = dict(os.environ, TMPDIR="/tmp")
             # its own session, so that a pass that hangs is ended WITH its children (a pass takes ~6 s; a profiler that hangs costs
             # the bench 90 s, not its line)
@@ -273,11 +286,30 @@ def measure_traffic_live(workload, pipeline):
                            "process as children before it touched the GPU")
 
 
+def dump_outputs(d, fb, ray_count):
+    """--dump-outputs: the last timed step's frame (fb: float32 [height, width, 4]) and ray count, as .npy files in `d`."""
+    os.makedirs(d, exist_ok=True)
+    px = fb.reshape(-1, 4)
+    if px.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(d, "framebuffer.npy"), fb)
+    else:
+        n = DUMP_MAX_BYTES // (16 + 8)                  # a pixel (4 x float32) and its index (float64)
+        idx = np.sort(np.random.default_rng(SEED).choice(px.shape[0], n, replace=False))
+        np.save(os.path.join(d, "framebuffer_sample.npy"), px[idx])
+        np.save(os.path.join(d, "framebuffer_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(d, "ray_count.npy"), np.array([ray_count], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: roofline, live HBM traffic, CPU baseline and "
+                         "parity, the other workloads, two frames in flight, the multi-GPU bit-identity check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's frame and ray count to DIR/*.npy")
     ap.add_argument("--workload", default="C4", choices=sorted(WORKLOADS))
     ap.add_argument("--pipeline", type=int, default=0)
     ap.add_argument("--cpu-lattice", type=int, default=0, help="lattice stride of the CPU baseline (0 = auto)")
@@ -305,6 +337,8 @@ def main():
                          "GPU (a full frame gains 2 %% and the kernel timings of the roofline would be taken under "
                          "contention), 2 on several (a 1/8-frame shard gains 13 %%)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` by itself: this process becomes the launcher.  It has not imported torch or touched HIP
@@ -342,7 +376,7 @@ def main():
         _dir = tempfile.mkdtemp(prefix="prt_bench_%s_" % scene_name)
         _scenes.write_obj(_sc, _dir, "scene.obj")
         pre = (_dir, list(_sc.camera_position), list(_sc.camera_facing), float(_sc.fov), time.time() - t0)
-        if not args.no_cpu_baseline and args.cpu_baseline in ("auto", "reference"):
+        if args.full and not args.no_cpu_baseline and args.cpu_baseline in ("auto", "reference"):
             ref_run = time_reference_on_host(_dir, pre[1], pre[2], pre[3], width, height, spp, depth, args.cpu_seconds, args.cpu_lattice)
             if ref_run is None and args.cpu_baseline == "reference":
                 raise SystemExit("--cpu-baseline reference: oracle/_ref/ref_harness is missing or does not run on this host")
@@ -353,7 +387,7 @@ def main():
     live_traffic, live_traffic_note = None, None
     under_profiler = "rocprof" in os.environ.get("LD_PRELOAD", "") or any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ)
     # (the quick forms of this command that the A/B scripts use - no CPU baseline, no other workloads - skip it too)
-    if world == 1 and rank == 0 and not collective and not args.no_live_traffic and not under_profiler and not args.no_cpu_baseline and not args.no_other_workloads:
+    if args.full and world == 1 and rank == 0 and not collective and not args.no_live_traffic and not under_profiler and not args.no_cpu_baseline and not args.no_other_workloads:
         t0 = time.time()
         live_traffic, live_traffic_note = measure_traffic_live(args.workload, args.pipeline)
         log("live HBM traffic passes: %s (%.0f s)" % ("ok, %d kernels" % len(live_traffic) if live_traffic else live_traffic_note, time.time() - t0))
@@ -517,7 +551,7 @@ def main():
     trace_ms = [c.trace_kernel_ms for c in counters]
     render_ms = [c.render_ms for c in counters]
 
-    t = torch.tensor([elapsed, float(rays_local)], dtype=torch.float64, device=cdev)
+    t = torch.tensor([elapsed, float(rays_local), float(counters[-1].ray_count)], dtype=torch.float64, device=cdev)
     if collective:
         tmax = t.clone()
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -525,8 +559,10 @@ def main():
         dist.all_reduce(tsum, op=dist.ReduceOp.SUM)
         elapsed = float(tmax[0].item())
         rays_total = float(tsum[1].item())
+        rays_last_step = float(tsum[2].item())
     else:
         rays_total = float(rays_local)
+        rays_last_step = float(counters[-1].ray_count)
     ms_per_step = elapsed * 1e3 / args.steps
     value = rays_total / elapsed / 1e6
     ranks_seen = 1
@@ -535,119 +571,127 @@ def main():
         dist.all_reduce(one, op=dist.ReduceOp.SUM)                 # every rank of the group took part in the collective path
         ranks_seen = int(one.item())
 
-    # ---- roofline of the dominant kernel: one extra, untimed render with visit counting (identical pixels)
-    pcount = api.default_params(spp, SEED, bounce_depth=depth, pipeline=args.pipeline | capi.FLAG_COUNT_VISITS)
-    if not collective:
-        cc = r.render_device(cam, pcount, width, height, 0, width * height, shard.data_ptr(), True)
-    else:
-        cc = r.render_shard_device(cam, pcount, width, height, SHARD_BLOCK_ROWS, rank, world, shard.data_ptr(), True)
-    st = r.render_stats()
-    n_px_local = my_rows * width if world > 1 else width * height
-    used = int(cc.pipeline)                       # what PRT_PIPELINE_DEFAULT resolved to for this shard size
+    used = int(counters[-1].pipeline)              # what PRT_PIPELINE_DEFAULT resolved to for this shard size
     pipeline_name = {1: "megakernel", 2: "wavefront", 3: "persistent", 4: "pool"}[used]
-    kernel_name = {1: "k_render_mega", 2: "k_trace", 3: "k_render_persistent", 4: "k_pool"}[used]
-    fused = used != 2
-    # k_trace moves rays, nodes and triangle records; shading records and the framebuffer belong to k_shade / k_resolve.
-    # The single-launch pipelines do all of it in the one kernel that is timed.
-    # Shadow rays whose radiance-if-unoccluded is exactly zero are counted (ray_count is the reference's) but not traced: they
-    # have no ray record, so they are not priced either
-    rays_elided = int(st.elided_shadow_rays)
-    rays_traced = int(cc.ray_count) - rays_elided
-    B_NODE = int(info.bvh_node_bytes)           # the build's node: 64 B (4-wide), 80 B for a -DPRT_BVH8 library
-    def algorithmic_bytes(b_tri, b_shade):
-        n = rays_traced * B_RAY + cc.node_visits * B_NODE + cc.tri_tests * b_tri
-        if fused:
-            n += cc.shaded_hits * b_shade + n_px_local * B_PIXEL
-        return n
-    alg_bytes = algorithmic_bytes(B_TRI, B_SHADE)
-    alg_bytes_build = algorithmic_bytes(B_TRI_BUILD, B_SHADE_BUILD)
-    kernel_ms = float(np.mean(trace_ms))
-    achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else 0.0
-    # The PMC figures come from a committed file (counters cannot be collected inside this run).  They are only printed when
-    # the file says it was taken with THIS library: tools/profile_summary.py stamps it with the sha256 of libprt_hip.so, its ABI
-    # version and build flags; anything else and traffic / the counter-derived fields are null, with the reason beside them.
-    traffic = valu_busy = ta_busy = wait_frac = l1_latency = None
-    traffic_note = "no profiles/traffic_%s.json" % args.workload
-    tpath = os.path.join(ROOT, "profiles", "traffic_%s.json" % args.workload)
-    if os.path.exists(tpath) and world == 1 and used in (2, 4):
-        try:
-            import hashlib
-            with open(tpath) as f:
-                tj = json.load(f)
-            with open(os.path.join(ROOT, "par_raytracer_amd", os.path.basename(os.environ.get("PRT_HIP_LIB", "libprt_hip.so"))), "rb") as f:
-                lib_sha = hashlib.sha256(f.read()).hexdigest()
-            stamp = tj.get("library", {})
-            if stamp.get("sha256") != lib_sha or stamp.get("abi_version") != int(capi.hip_lib().prt_abi_version()):
-                traffic_note = "profiles/traffic_%s.json was taken with another build of libprt_hip.so (%s..., this one is %s...): not printed" % (
-                    args.workload, str(stamp.get("sha256"))[:12], lib_sha[:12])
-            else:
-                traffic_note = "profiles/traffic_%s.json, taken with this library (sha256 %s..., commit %s)" % (args.workload, lib_sha[:12], stamp.get("commit"))
-                traffic = tj.get("hbm_bytes_per_frame_" + kernel_name)
-                valu_busy = tj.get("valu_busy_" + kernel_name)      # SQ_ACTIVE_INST_VALU / SQ_WAVE_CYCLES x resident waves per SIMD (PMC)
-                ta_busy = tj.get("ta_busy_" + kernel_name)          # TA_TA_BUSY / (GRBM_GUI_ACTIVE per XCD x compute units)
-                wait_frac = tj.get("wait_frac_" + kernel_name)      # SQ_WAIT_ANY / SQ_WAVE_CYCLES: share of a wave's cycles parked on s_waitcnt
-                l1_latency = tj.get("l1_latency_clk_" + kernel_name)  # TCP_TCP_LATENCY_sum / TCP_TA_TCP_STATE_READ_sum
-        except Exception as e:
-            traffic = None
-            traffic_note = "profiles/traffic_%s.json unreadable: %r" % (args.workload, e)
-    if live_traffic:
-        # this run's own measurement wins over the file: the timed frames' kernel is the instantiation of `kernel_name` that was
-        # launched most often and, among those, moved the most bytes (the counting render's instantiation runs once; the EXACT
-        # follow-up launch of the same template runs as often as the fast kernel and moves next to nothing)
-        cand = [((v["launches"], v["bytes_corrected"]), k, v) for k, v in live_traffic.items() if k.startswith(kernel_name + "<") or k == kernel_name]
-        if cand:
-            _, lk, lv = max(cand)
-            traffic = lv["bytes_corrected"] * max(1, int(cc.trace_kernel_launches))      # per frame: mean launch x launches of a frame
-            traffic_note = "measured in this run: %s; kernel %s, %d launches, %.2f GB per launch corrected (2 x FETCH + WRITE), %.2f GB raw" % (
-                live_traffic_note, lk, lv["launches"], lv["bytes_corrected"] / 1e9, lv["bytes_raw"] / 1e9)
-    elif live_traffic_note:
-        traffic_note += "; live measurement: " + live_traffic_note
-    launches = max(1, int(cc.trace_kernel_launches))
-    lane_util = None
-    if st.wave_node_steps and st.wave_tri_steps:
-        # what actually bounds the kernel: vector issue with divergent lanes.  Lane-level work / (64 x
-        # wave-level steps) of the two traversal loops, from the counting render above.
-        lane_util = {"node_loop": round(st.node_visits / (64.0 * st.wave_node_steps), 4),
-                     "triangle_loop": round(st.tri_tests / (64.0 * st.wave_tri_steps), 4),
-                     "wave_node_steps": int(st.wave_node_steps), "wave_triangle_steps": int(st.wave_tri_steps),
-                     "rays_parked_for_the_exact_launch": int(st.parked_rays)}
-    # `achieved` = algorithmic bytes per launch / mean launch duration; `traffic` = measured HBM bytes per launch.  Both are
-    # also given per frame (launches_per_frame launches of the kernel make one frame).
-    roofline = {"bound": "cache-inclusive algorithmic bytes", "kernel": kernel_name, "launches_per_frame": launches,
-                "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": int(traffic / launches) if traffic else None,
-                "traffic_per_frame": traffic, "algorithmic_bytes_per_launch": int(alg_bytes / launches),
-                "launch_ms_mean": round(kernel_ms / launches, 4),
-                "algorithmic_bytes_per_frame": int(alg_bytes), "kernel_ms_per_frame": round(kernel_ms, 4),
-                "per_frame": {"rays": int(cc.ray_count), "rays_traced": rays_traced, "rays_counted_not_traced": rays_elided,
-                               "node_visits": int(cc.node_visits), "tri_tests": int(cc.tri_tests),
-                               "shaded_hits": int(cc.shaded_hits), "pixels": int(n_px_local)},
-                "bytes_per_unit": {"ray": B_RAY, "node": B_NODE, "tri_test": B_TRI, "shaded_hit": B_SHADE, "pixel": B_PIXEL},
-                "with_this_builds_record_sizes": {"bytes_per_unit": {"tri_test": B_TRI_BUILD, "shaded_hit": B_SHADE_BUILD},
-                                                  "achieved": round(alg_bytes_build / (kernel_ms * 1e-3) / 1e9, 2) if kernel_ms > 0 else 0.0,
-                                                  "frac": round(alg_bytes_build / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if kernel_ms > 0 else 0.0},
-                # The algorithmic figure counts every per-lane node fetch; most are served by L1 / L2 / Infinity Cache.  What
-                # the kernel is bounded by is vector issue with divergent lanes, with the texture addresser not far behind:
-                "lane_utilisation": lane_util, "valu_busy": valu_busy, "ta_busy": ta_busy,
-                # what bounds the kernel: not HBM (hbm_measured below) and not one unit - its waves hold 5 per SIMD (96 VGPRs) and
-                # issue vector instructions for lanes of which little more than half carry a walking ray, while each waits on
-                # its node-to-node chain for about half its cycles; profiles/r03_ab_bvh8.txt shows vector instructions, vector
-                # memory instructions and chain length each returning a quarter of what they cost
-                "limiter": {"kind": "vector issue at partial lane occupancy, latency of the dependent node chain at 5 waves per SIMD",
-                            "valu_busy": valu_busy, "lane_utilisation": ({"node_loop": lane_util["node_loop"], "triangle_loop": lane_util["triangle_loop"]} if lane_util else None),
-                            "wait_frac": wait_frac, "l1_latency_clk": l1_latency, "ta_busy": ta_busy},
-                "traffic_source": traffic_note,
-                # SURVEY.md §8d asks for these two beside the algorithmic figure: what the kernel really moved through HBM
-                # (PMC, per second of kernel time, as a fraction of the 8 TB/s peak) and the compulsory minimum of a frame
-                # (every ray record once, the resident scene once, the framebuffer once)
-                "hbm_measured": ({"GBps": round(traffic / (kernel_ms * 1e-3) / 1e9, 1),
-                                  "frac_of_peak": round(traffic / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)} if traffic and kernel_ms > 0 else None),
-                "compulsory_bytes_per_frame": int(rays_traced * B_RAY + info.device_bytes + n_px_local * B_PIXEL)}
+
+    # ---- outputs of the last timed step, as its caller received them (before anything below renders into the buffers)
+    if args.dump_outputs and rank == 0:
+        fb = frame if collective else shards[(args.steps - 1) % NB]
+        dump_outputs(args.dump_outputs, fb.cpu().numpy(), rays_last_step)
+
+    # ---- roofline of the dominant kernel: one extra, untimed render with visit counting (identical pixels)
+    roofline = rays_traced = rays_elided = cc = None
+    if args.full:
+        pcount = api.default_params(spp, SEED, bounce_depth=depth, pipeline=args.pipeline | capi.FLAG_COUNT_VISITS)
+        if not collective:
+            cc = r.render_device(cam, pcount, width, height, 0, width * height, shard.data_ptr(), True)
+        else:
+            cc = r.render_shard_device(cam, pcount, width, height, SHARD_BLOCK_ROWS, rank, world, shard.data_ptr(), True)
+        st = r.render_stats()
+        n_px_local = my_rows * width if world > 1 else width * height
+        kernel_name = {1: "k_render_mega", 2: "k_trace", 3: "k_render_persistent", 4: "k_pool"}[used]
+        fused = used != 2
+        # k_trace moves rays, nodes and triangle records; shading records and the framebuffer belong to k_shade / k_resolve.
+        # The single-launch pipelines do all of it in the one kernel that is timed.
+        # Shadow rays whose radiance-if-unoccluded is exactly zero are counted (ray_count is the reference's) but not traced: they
+        # have no ray record, so they are not priced either
+        rays_elided = int(st.elided_shadow_rays)
+        rays_traced = int(cc.ray_count) - rays_elided
+        B_NODE = int(info.bvh_node_bytes)           # the build's node: 64 B (4-wide), 80 B for a -DPRT_BVH8 library
+        def algorithmic_bytes(b_tri, b_shade):
+            n = rays_traced * B_RAY + cc.node_visits * B_NODE + cc.tri_tests * b_tri
+            if fused:
+                n += cc.shaded_hits * b_shade + n_px_local * B_PIXEL
+            return n
+        alg_bytes = algorithmic_bytes(B_TRI, B_SHADE)
+        alg_bytes_build = algorithmic_bytes(B_TRI_BUILD, B_SHADE_BUILD)
+        kernel_ms = float(np.mean(trace_ms))
+        achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else 0.0
+        # The PMC figures come from a committed file (counters cannot be collected inside this run).  They are only printed when
+        # the file says it was taken with THIS library: tools/profile_summary.py stamps it with the sha256 of libprt_hip.so, its ABI
+        # version and build flags; anything else and traffic / the counter-derived fields are null, with the reason beside them.
+        traffic = valu_busy = ta_busy = wait_frac = l1_latency = None
+        traffic_note = "no profiles/traffic_%s.json" % args.workload
+        tpath = os.path.join(ROOT, "profiles", "traffic_%s.json" % args.workload)
+        if os.path.exists(tpath) and world == 1 and used in (2, 4):
+            try:
+                import hashlib
+                with open(tpath) as f:
+                    tj = json.load(f)
+                with open(os.path.join(ROOT, "par_raytracer_amd", os.path.basename(os.environ.get("PRT_HIP_LIB", "libprt_hip.so"))), "rb") as f:
+                    lib_sha = hashlib.sha256(f.read()).hexdigest()
+                stamp = tj.get("library", {})
+                if stamp.get("sha256") != lib_sha or stamp.get("abi_version") != int(capi.hip_lib().prt_abi_version()):
+                    traffic_note = "profiles/traffic_%s.json was taken with another build of libprt_hip.so (%s..., this one is %s...): not printed" % (
+                        args.workload, str(stamp.get("sha256"))[:12], lib_sha[:12])
+                else:
+                    traffic_note = "profiles/traffic_%s.json, taken with this library (sha256 %s..., commit %s)" % (args.workload, lib_sha[:12], stamp.get("commit"))
+                    traffic = tj.get("hbm_bytes_per_frame_" + kernel_name)
+                    valu_busy = tj.get("valu_busy_" + kernel_name)      # SQ_ACTIVE_INST_VALU / SQ_WAVE_CYCLES x resident waves per SIMD (PMC)
+                    ta_busy = tj.get("ta_busy_" + kernel_name)          # TA_TA_BUSY / (GRBM_GUI_ACTIVE per XCD x compute units)
+                    wait_frac = tj.get("wait_frac_" + kernel_name)      # SQ_WAIT_ANY / SQ_WAVE_CYCLES: share of a wave's cycles parked on s_waitcnt
+                    l1_latency = tj.get("l1_latency_clk_" + kernel_name)  # TCP_TCP_LATENCY_sum / TCP_TA_TCP_STATE_READ_sum
+            except Exception as e:
+                traffic = None
+                traffic_note = "profiles/traffic_%s.json unreadable: %r" % (args.workload, e)
+        if live_traffic:
+            # this run's own measurement wins over the file: the timed frames' kernel is the instantiation of `kernel_name` that was
+            # launched most often and, among those, moved the most bytes (the counting render's instantiation runs once; the EXACT
+            # follow-up launch of the same template runs as often as the fast kernel and moves next to nothing)
+            cand = [((v["launches"], v["bytes_corrected"]), k, v) for k, v in live_traffic.items() if k.startswith(kernel_name + "<") or k == kernel_name]
+            if cand:
+                _, lk, lv = max(cand)
+                traffic = lv["bytes_corrected"] * max(1, int(cc.trace_kernel_launches))      # per frame: mean launch x launches of a frame
+                traffic_note = "measured in this run: %s; kernel %s, %d launches, %.2f GB per launch corrected (2 x FETCH + WRITE), %.2f GB raw" % (
+                    live_traffic_note, lk, lv["launches"], lv["bytes_corrected"] / 1e9, lv["bytes_raw"] / 1e9)
+        elif live_traffic_note:
+            traffic_note += "; live measurement: " + live_traffic_note
+        launches = max(1, int(cc.trace_kernel_launches))
+        lane_util = None
+        if st.wave_node_steps and st.wave_tri_steps:
+            # what actually bounds the kernel: vector issue with divergent lanes.  Lane-level work / (64 x
+            # wave-level steps) of the two traversal loops, from the counting render above.
+            lane_util = {"node_loop": round(st.node_visits / (64.0 * st.wave_node_steps), 4),
+                         "triangle_loop": round(st.tri_tests / (64.0 * st.wave_tri_steps), 4),
+                         "wave_node_steps": int(st.wave_node_steps), "wave_triangle_steps": int(st.wave_tri_steps),
+                         "rays_parked_for_the_exact_launch": int(st.parked_rays)}
+        # `achieved` = algorithmic bytes per launch / mean launch duration; `traffic` = measured HBM bytes per launch.  Both are
+        # also given per frame (launches_per_frame launches of the kernel make one frame).
+        roofline = {"bound": "cache-inclusive algorithmic bytes", "kernel": kernel_name, "launches_per_frame": launches,
+                    "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": int(traffic / launches) if traffic else None,
+                    "traffic_per_frame": traffic, "algorithmic_bytes_per_launch": int(alg_bytes / launches),
+                    "launch_ms_mean": round(kernel_ms / launches, 4),
+                    "algorithmic_bytes_per_frame": int(alg_bytes), "kernel_ms_per_frame": round(kernel_ms, 4),
+                    "per_frame": {"rays": int(cc.ray_count), "rays_traced": rays_traced, "rays_counted_not_traced": rays_elided,
+                                   "node_visits": int(cc.node_visits), "tri_tests": int(cc.tri_tests),
+                                   "shaded_hits": int(cc.shaded_hits), "pixels": int(n_px_local)},
+                    "bytes_per_unit": {"ray": B_RAY, "node": B_NODE, "tri_test": B_TRI, "shaded_hit": B_SHADE, "pixel": B_PIXEL},
+                    "with_this_builds_record_sizes": {"bytes_per_unit": {"tri_test": B_TRI_BUILD, "shaded_hit": B_SHADE_BUILD},
+                                                      "achieved": round(alg_bytes_build / (kernel_ms * 1e-3) / 1e9, 2) if kernel_ms > 0 else 0.0,
+                                                      "frac": round(alg_bytes_build / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if kernel_ms > 0 else 0.0},
+                    # The algorithmic figure counts every per-lane node fetch; most are served by L1 / L2 / Infinity Cache.  What
+                    # the kernel is bounded by is vector issue with divergent lanes, with the texture addresser not far behind:
+                    "lane_utilisation": lane_util, "valu_busy": valu_busy, "ta_busy": ta_busy,
+                    # what bounds the kernel: not HBM (hbm_measured below) and not one unit - its waves hold 5 per SIMD (96 VGPRs) and
+                    # issue vector instructions for lanes of which little more than half carry a walking ray, while each waits on
+                    # its node-to-node chain for about half its cycles; profiles/r03_ab_bvh8.txt shows vector instructions, vector
+                    # memory instructions and chain length each returning a quarter of what they cost
+                    "limiter": {"kind": "vector issue at partial lane occupancy, latency of the dependent node chain at 5 waves per SIMD",
+                                "valu_busy": valu_busy, "lane_utilisation": ({"node_loop": lane_util["node_loop"], "triangle_loop": lane_util["triangle_loop"]} if lane_util else None),
+                                "wait_frac": wait_frac, "l1_latency_clk": l1_latency, "ta_busy": ta_busy},
+                    "traffic_source": traffic_note,
+                    # SURVEY.md §8d asks for these two beside the algorithmic figure: what the kernel really moved through HBM
+                    # (PMC, per second of kernel time, as a fraction of the 8 TB/s peak) and the compulsory minimum of a frame
+                    # (every ray record once, the resident scene once, the framebuffer once)
+                    "hbm_measured": ({"GBps": round(traffic / (kernel_ms * 1e-3) / 1e9, 1),
+                                      "frac_of_peak": round(traffic / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)} if traffic and kernel_ms > 0 else None),
+                    "compulsory_bytes_per_frame": int(rays_traced * B_RAY + info.device_bytes + n_px_local * B_PIXEL)}
 
     # ---- CPU baseline + parity on a sparse lattice of the same frame (rank 0, N = 1 only)
     cpu_baseline = None
     parity = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle_py as orc
         # one thread per physical core of socket 0, pinned; the CPU model is part of the record
@@ -707,7 +751,7 @@ def main():
 
     # ---- the other BASELINE configs, in the same run: time a few frames, check a lattice against the reference's own pixels
     other = None
-    if world == 1 and rank == 0 and args.workload == "C4" and not args.no_other_workloads:
+    if args.full and world == 1 and rank == 0 and args.workload == "C4" and not args.no_other_workloads:
         other = []
         golden_dir = os.path.join(ROOT, "tests", "golden")
         for wl, fixture, max_spp in OTHER_WORKLOADS:
@@ -768,7 +812,7 @@ def main():
     # the exact-phase launches behind it overlap the start of frame k + 1).  Not `value`: the roofline's kernel durations are
     # taken one frame at a time.
     pipelined = None
-    if world == 1 and rank == 0 and F == 1 and args.workload == "C4" and not args.no_other_workloads:
+    if args.full and world == 1 and rank == 0 and F == 1 and args.workload == "C4" and not args.no_other_workloads:
         try:
             r_b = api.Renderer(local_rank)
             r_b.upload(hs)
@@ -825,7 +869,7 @@ def main():
                            "gather_and_assemble_ms_max": round(float(np.max(gms)), 4) if gms else None,
                            "note": "device time from the gather's enqueue to the end of the assembly on the side stream (they run beside "
                                    "the next frame's render kernels, so this is latency, not time added to a frame)"}
-    if collective and rank == 0 and frame is not None:
+    if args.full and collective and rank == 0 and frame is not None:
         # the assembled multi-GPU frame must be bit-identical to what one GPU computes for the same pixels
         lat = 16
         one, _ = r.render_lattice(cam, params, width, height, lat)
@@ -838,10 +882,10 @@ def main():
         out = {
             "metric": "Mrays/s at 1920x1080x8spp, 1M-tri OBJ" if args.workload == "C4" else "Mrays/s (%s)" % args.workload,
             "value": round(value, 3), "unit": "Mrays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "full": args.full, "scaling": "strong", "vs_baseline": None,
             # `value` divides the reference's ray_count (which the device reproduces exactly) by the time; the device does not
             # trace the shadow rays that cannot change the image: the rate over the rays it really traces, for the same frames
-            "value_traced_rays_only": round(value * rays_traced / max(1, int(cc.ray_count)), 3) if world == 1 else None,
+            "value_traced_rays_only": round(value * rays_traced / max(1, int(cc.ray_count)), 3) if world == 1 and cc is not None else None,
             "ranks_seen": ranks_seen,
             "dtype": "f32", "data": "synthetic",
             "config": {"workload": descr, "seed": SEED, "triangles": int(info.triangle_count), "width": width, "height": height,
@@ -853,7 +897,7 @@ def main():
                        "ray_definition": "one TraceRay call of the reference (raytracer.cpp:161): `value` divides the reference's ray_count, which the "
                                          "device reproduces exactly, by the time; value_traced_rays_only and the roofline count only the rays the device traces",
                        "rays_counted_not_traced_per_frame": rays_elided if world == 1 else None,
-                       "value_traced_rays_only": round(value * rays_traced / max(1, int(cc.ray_count)), 3) if world == 1 else None,
+                       "value_traced_rays_only": round(value * rays_traced / max(1, int(cc.ray_count)), 3) if world == 1 and cc is not None else None,
                        "parallelism": "pixel rows sharded in %d-row blocks over %d GPU(s)%s" % (
                            SHARD_BLOCK_ROWS, world, (", RCCL gather to rank 0" if args.backend == "nccl" else ", gloo gather (rehearsal)") if collective else ""),
                        "pipeline": pipeline_name, "frames_in_flight": F},

@@ -76,6 +76,13 @@ FIXTURES = {
     "gallery_adaptive_10_50": dict(scene="textured_gallery", width=64, height=48, spp=10, max_spp=50, lattice=1),      # reference defaults
     "terrain64_adaptive_3_12_d4": dict(scene="terrain_64", width=80, height=60, spp=3, max_spp=12, lattice=1, depth=4, light_mode=1),
     "c4_terrain1m_adaptive_l60": dict(scene="terrain_1m", width=1920, height=1080, spp=10, max_spp=50, lattice=60),
+    # tests/test_oracle_golden.py::test_live_against_compiled_reference: odd sizes, depths, light modes and sample counts
+    "live_cornell_box_40x30": dict(scene="cornell_box", width=40, height=30, spp=3, lattice=1, depth=4, light_mode=1, rs=1, ss=2, seed=99),
+    "live_sphere_plane_48x48": dict(scene="sphere_plane", width=48, height=48, spp=2, lattice=1, depth=2, light_mode=2, rs=2, ss=1, seed=7),
+    "live_terrain_64_32x24": dict(scene="terrain_64", width=32, height=24, spp=2, lattice=1, depth=6, light_mode=0, rs=1, ss=1, seed=424242),
+    "live_textured_gallery_56x40": dict(scene="textured_gallery", width=56, height=40, spp=3, lattice=1, depth=5, light_mode=2, rs=1, ss=2,
+                                        seed=31337),
+    "live_coincident_64x48": dict(scene="coincident", width=64, height=48, spp=3, lattice=1, depth=4, light_mode=1, rs=1, ss=1, seed=2025),
 }
 
 

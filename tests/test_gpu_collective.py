@@ -27,7 +27,7 @@ def test_collective_path_runs_with_rccl_at_world_size_one():
         env.pop(k, None)
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-collective", "--backend", "nccl",
-                          "--workload", "tiny", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-other-workloads"],
+                          "--workload", "tiny", "--steps", "6", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-other-workloads"],
                          env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     line = json.loads(out.stdout.decode().strip().splitlines()[-1])

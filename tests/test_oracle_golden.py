@@ -3,8 +3,8 @@
 tests/golden/*.npz hold the UNMODIFIED reference's float RGB and DebugCounters for every BASELINE config
 (full frames for C1/C2, sparse lattices for C3-C5) plus path-coverage scenes (two lights, point light,
 deep trees, multi-sample bounces).  The oracle must reproduce them BIT FOR BIT, counters included - that is
-what pins it.  When oracle/_ref/ref_harness exists (build container) the same comparison is
-also run live on freshly chosen parameters.
+what pins it.  tests/golden/live_*.npz hold the reference's output for five more parameter sets; where
+oracle/_ref/ref_harness has been built, the reference is also run live on those and must reproduce them.
 """
 from __future__ import annotations
 
@@ -65,7 +65,6 @@ def test_lattice_is_a_subset_of_the_full_frame():
     assert np.array_equal(full[::4, ::4].view(np.uint32), lat.view(np.uint32))
 
 
-@pytest.mark.skipif(not orc.have_reference(), reason="compiled reference only exists in the build container")
 @pytest.mark.parametrize("scene,w,h,spp,depth,lm,rs,ss,seed", [
     ("cornell_box", 40, 30, 3, 4, 1, 1, 2, 99),
     ("sphere_plane", 48, 48, 2, 2, 2, 2, 1, 7),
@@ -74,15 +73,26 @@ def test_lattice_is_a_subset_of_the_full_frame():
     ("coincident", 64, 48, 3, 4, 1, 1, 1, 2025),                 # coplanar / ulp-offset / doubled faces: visit order decides
 ])
 def test_live_against_compiled_reference(scene, w, h, spp, depth, lm, rs, ss, seed):
+    """The reference's output for these parameters is stored in tests/golden/live_<scene>_<w>x<h>.npz (oracle/gen_golden.py);
+    where oracle/_ref/ref_harness exists the reference is also run here and must still give exactly that output."""
     from par_raytracer_amd import api
+    g = load_golden("live_%s_%dx%d" % (scene, w, h))
+    assert (str(g["scene"]), int(g["width"]), int(g["height"]), int(g["spp"]), int(g["bounce_depth"]), int(g["light_mode"]),
+            int(g["reflection_samples"]), int(g["spec_samples"]), int(g["seed"]), int(g["lattice"])) == (
+        scene, w, h, spp, depth, lm, rs, ss, seed, 1)
+    want_rgb = g["rgb"]
+    want_counts = (int(g["ray_count"]), int(g["sphere_check_count"]), int(g["mesh_check_count"]))
     s, d = scene_dir(scene)
-    ref = orc.run_reference(d, "scene.obj", w, h, spp, seed, s.camera_position, s.camera_facing, s.fov, bounce_depth=depth,
-                            reflection_samples=rs, spec_samples=ss, light_mode=lm)
+    if orc.have_reference():
+        ref = orc.run_reference(d, "scene.obj", w, h, spp, seed, s.camera_position, s.camera_facing, s.fov, bounce_depth=depth,
+                                reflection_samples=rs, spec_samples=ss, light_mode=lm)
+        st = ref["stats"]
+        assert np.array_equal(np.ascontiguousarray(ref["pixels"][:, :, :3]).view(np.uint32), want_rgb.view(np.uint32))
+        assert (st["ray_count"], st["sphere_check_count"], st["mesh_check_count"]) == want_counts
     hs = host_scene(scene, lm)
     cam = api.make_camera(s.fov, w, h, s.camera_position, s.camera_facing)
     p = api.default_params(spp, seed, bounce_depth=depth, reflection_samples=rs, spec_samples=ss)
     img, ctr = orc.render(hs.desc, cam, p, w, h, 1, 4)
-    assert np.array_equal(img.view(np.uint32), ref["pixels"].view(np.uint32))
-    st = ref["stats"]
-    assert (ctr.ray_count, ctr.sphere_check_count, ctr.mesh_check_count) == (
-        st["ray_count"], st["sphere_check_count"], st["mesh_check_count"])
+    assert np.all(img[:, :, 3] == 1.0)
+    assert np.array_equal(np.ascontiguousarray(img[:, :, :3]).view(np.uint32), want_rgb.view(np.uint32))
+    assert (ctr.ray_count, ctr.sphere_check_count, ctr.mesh_check_count) == want_counts

@@ -108,7 +108,7 @@ def test_bench_two_ranks_on_one_gpu_rehearsal():
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-device",
-                        "--steps", "3", "--warmup", "1", "--workload", "tiny"], env=env, stdout=subprocess.PIPE,
+                        "--steps", "3", "--warmup", "1", "--workload", "tiny", "--full"], env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     line = [l for l in p.stdout.decode().splitlines() if l.startswith("{")][-1]

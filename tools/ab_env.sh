@@ -4,7 +4,7 @@
 cd "$(dirname "$0")/.."
 sw="$1"; shift
 run() {
-    env $1 python bench.py --no-cpu-baseline --no-other-workloads --pipeline 4 --steps ${AB_STEPS:-8} --warmup 2 "${@:2}" 2>/dev/null | python -c "
+    env $1 python bench.py --full --no-cpu-baseline --no-other-workloads --pipeline 4 --steps ${AB_STEPS:-8} --warmup 2 "${@:2}" 2>/dev/null | python -c "
 import json,sys
 j=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=j['roofline']
 print('%-28s %8.1f Mrays/s  %7.3f ms/frame  kernel %7.3f ms  rays %d' % ('$1', j['value'], j['ms_per_step'], r['kernel_ms_per_frame'], r['per_frame']['rays']))"

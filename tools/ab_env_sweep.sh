@@ -8,7 +8,7 @@ if [ "$1" = default ]; then export PRT_HIP_LIB=libprt_hip.so; else export PRT_HI
 name=$2; shift 2
 for val in "$@"; do
     if [ "$val" = "-" ]; then unset $name; else export $name=$val; fi
-    python bench.py --no-cpu-baseline --no-other-workloads --pipeline 4 --steps ${AB_STEPS:-8} --warmup 2 2>/dev/null | python -c "
+    python bench.py --full --no-cpu-baseline --no-other-workloads --pipeline 4 --steps ${AB_STEPS:-8} --warmup 2 2>/dev/null | python -c "
 import json,sys
 j=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=j['roofline']

@@ -6,7 +6,7 @@ cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 for v in "$@"; do
     lib=libprt_hip.so; [ "$v" != default ] && lib=libprt_hip_$v.so
-    PRT_HIP_LIB=$lib python bench.py --no-cpu-baseline --no-other-workloads --pipeline 4 --steps ${AB_STEPS:-10} --warmup 2 ${AB_ARGS} 2>/dev/null | python -c "
+    PRT_HIP_LIB=$lib python bench.py --full --no-cpu-baseline --no-other-workloads --pipeline 4 --steps ${AB_STEPS:-10} --warmup 2 ${AB_ARGS} 2>/dev/null | python -c "
 import json,sys
 j=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=j['roofline']

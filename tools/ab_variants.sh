@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 for v in "$@"; do
     lib=libprt_hip.so; [ "$v" != default ] && lib=libprt_hip_$v.so
     for p in 4 2; do
-        PRT_HIP_LIB=$lib python bench.py --no-cpu-baseline --pipeline $p --steps 8 --warmup 2 2>/dev/null | python -c "
+        PRT_HIP_LIB=$lib python bench.py --full --no-cpu-baseline --pipeline $p --steps 8 --warmup 2 2>/dev/null | python -c "
 import json,sys
 j=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=j['roofline']

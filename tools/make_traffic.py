@@ -21,7 +21,7 @@ fetch_dir, write_dir, workload, out_path = sys.argv[1:5]
 fetch, nf = per_kernel(fetch_dir, "FETCH_SIZE")
 write, _ = per_kernel(write_dir, "WRITE_SIZE")
 frames = int(sys.argv[5]) if len(sys.argv) > 5 else max(nf.get("k_resolve", 1), 1)
-out = {"command": "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (separate passes) --output-format csv -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline",
+out = {"command": "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (separate passes) --output-format csv -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline",
        "workload": workload, "frames_in_profile": frames,
        "unit_note": "FETCH_SIZE / WRITE_SIZE are KiB; raw = FETCH + WRITE (lower bound), corrected = 2*FETCH + WRITE (gfx950 FETCH_SIZE halving, upper bound)",
        "kernels": {}}

@@ -4,7 +4,7 @@ root="$(cd "$(dirname "$0")/.." && pwd)"
 out="$root/gpurun_out/pmc_cache"
 rm -rf "$out"; mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $root/bench.py --no-cpu-baseline --no-other-workloads --steps 3 --warmup 1"
+BENCH="python3 $root/bench.py --full --no-cpu-baseline --no-other-workloads --steps 3 --warmup 1"
 pass() {
     name="$1"; shift
     echo "pmc pass $name: $*" | tee -a "$out/progress.txt"

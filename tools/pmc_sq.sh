@@ -9,7 +9,7 @@ for v in "$@"; do
     tag="$v"
     if [ "$v" = default ]; then export PRT_HIP_LIB=libprt_hip.so; else export PRT_HIP_LIB=libprt_hip_$v.so; fi
     out="$root/gpurun_out/pmc_sq_$tag"; rm -rf "$out"; mkdir -p "$out"
-    BENCH="python3 $root/bench.py --no-cpu-baseline --no-other-workloads --pipeline 4 --steps 3 --warmup 1"
+    BENCH="python3 $root/bench.py --full --no-cpu-baseline --no-other-workloads --pipeline 4 --steps 3 --warmup 1"
     rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVES --output-format csv -d "$out/sq1" -- $BENCH > "$out/sq1.log" 2>&1
     rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS GRBM_GUI_ACTIVE TA_TA_BUSY_sum --output-format csv -d "$out/sq2" -- $BENCH > "$out/sq2.log" 2>&1
     python3 - "$out" "$tag" <<'PY'

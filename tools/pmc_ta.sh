@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 rocprofv3 -L > "$out/counters_available.txt" 2>&1
 pass() {
     name="$1"; shift
-    rocprofv3 --pmc "$@" --output-format csv -d "$out/$name" -- python3 "$root/bench.py" --no-cpu-baseline --steps 3 --warmup 1 $BENCH_ARGS > "$out/$name.log" 2>&1 || echo "pass $name failed" >> "$out/failed.txt"
+    rocprofv3 --pmc "$@" --output-format csv -d "$out/$name" -- python3 "$root/bench.py" --full --no-cpu-baseline --steps 3 --warmup 1 $BENCH_ARGS > "$out/$name.log" 2>&1 || echo "pass $name failed" >> "$out/failed.txt"
 }
 pass a GRBM_GUI_ACTIVE TA_TA_BUSY_sum TA_BUSY_avr
 pass b TA_ADDR_STALLED_BY_TC_CYCLES_sum TA_ADDR_STALLED_BY_TD_CYCLES_sum TA_DATA_STALLED_BY_TC_CYCLES_sum

@@ -5,7 +5,7 @@ root="$(cd "$(dirname "$0")/.." && pwd)"
 out="$root/gpurun_out/pmc_env"
 rm -rf "$out"; mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $root/bench.py --no-cpu-baseline --no-other-workloads --steps 3 --warmup 1"
+BENCH="python3 $root/bench.py --full --no-cpu-baseline --no-other-workloads --steps 3 --warmup 1"
 for tag in default switched; do
     if [ $tag = switched ]; then export "$1"; fi
     for c in FETCH_SIZE WRITE_SIZE; do

@@ -35,7 +35,7 @@ except Exception:
     commit = None
 sys.path.insert(0, ROOT)
 from par_raytracer_amd import capi
-out = {"command": "rocprofv3 --pmc <one counter group per pass> --output-format csv -- python3 bench.py --no-cpu-baseline --no-other-workloads --steps 5 --warmup 1",
+out = {"command": "rocprofv3 --pmc <one counter group per pass> --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-other-workloads --steps 5 --warmup 1",
        "round": rnd, "workload": "C4",
        # bench.py prints these figures only while the library it runs is the one they were measured on
        "library": {"sha256": hashlib.sha256(open(lib, "rb").read()).hexdigest(), "abi_version": int(capi.hip_lib().prt_abi_version()),

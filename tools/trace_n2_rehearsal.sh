@@ -8,7 +8,7 @@ out="$root/gpurun_out/trace_n2"
 rm -rf "$out"; mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
 export MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 WORLD_SIZE=2 LOCAL_WORLD_SIZE=2 PRT_RESERVE_CUS=8 HSA_ENABLE_IPC_MODE_LEGACY=0
-ARGS="--gpus 2 --backend gloo --share-device --steps 8 --warmup 2"
+ARGS="--full --gpus 2 --backend gloo --share-device --steps 8 --warmup 2"
 RANK=1 LOCAL_RANK=1 timeout -k 10 300 python3 $root/bench.py $ARGS > "$out/rank1.log" 2>&1 &
 r1=$!
 RANK=0 LOCAL_RANK=0 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d "$out/rank0" -- python3 $root/bench.py $ARGS > "$out/rank0.log" 2>&1
