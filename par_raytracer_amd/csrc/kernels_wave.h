@@ -601,6 +601,9 @@ PRT_D void shade_entry_on(const DevScene & sc, const DevParams & P, const WaveBu
     }
 
     // ---- step 2: walk the bounce tree in depth-first order until the next ray or the end of the sample ----
+    // The three steps follow each other in ONE pass of the loop (not one step per pass): a lane's own sequence of steps is
+    // the same, but the lanes of a wave, each at its own step, no longer pay for the union of all three on every pass -
+    // spawning a child and entering it, or retiring a frame and resuming its parent, take one pass instead of two.
     while (mode != M_DONE) {
         if (mode == M_NEXT_CHILD) {                       // frame f at `level` spawns its next child, if any
             const int iters = depth - level;
@@ -648,11 +651,16 @@ PRT_D void shade_entry_on(const DevScene & sc, const DevParams & P, const WaveBu
                 const bool more_spec = kind == 0 ? P.spec_samples > 0u : (unsigned int)f.idx < P.spec_samples;
                 if (!more_refl && !more_spec && !(TRANS && f.alpha < 1.0f)) f.stage = WF_STAGE_DONE;
             }
-            if (!spawned) { f_held = false; mode = M_RETURN_UP; continue; }
-            f_held = true;                                // f (at `level`) stays in registers until the child's fate is known
-            next_level = level + 1;
-            mode = M_ENTER;
-        } else if (mode == M_ENTER) {                     // TraceRayColor entry (raytracer.cpp:415-420) for (next_*, next_level)
+            if (!spawned) {
+                f_held = false;
+                mode = M_RETURN_UP;
+            } else {
+                f_held = true;                            // f (at `level`) stays in registers until the child's fate is known
+                next_level = level + 1;
+                mode = M_ENTER;
+            }
+        }
+        if (mode == M_ENTER) {                     // TraceRayColor entry (raytracer.cpp:415-420) for (next_*, next_level)
             const int iters = depth - next_level;
             bool dead = iters < 0;
             if (!dead && next_level != 0) dead = rng_float01<RING>(rng, ring, ring_stride) < 0.5f;
@@ -669,12 +677,16 @@ PRT_D void shade_entry_on(const DevScene & sc, const DevParams & P, const WaveBu
             } else {
                 mode = M_RETURN_UP;
             }
-        } else {                                          // M_RETURN_UP: resume the deepest parked frame
-            if (pending == 0u) { mode = M_DONE; break; }
-            level = 31 - __clz((int)pending);
-            pending &= ~(1u << level);
-            wframe_load<POS, TEX>(B, level, s, f);
-            mode = M_NEXT_CHILD;
+        }
+        if (mode == M_RETURN_UP) {                        // resume the deepest parked frame
+            if (pending == 0u) {
+                mode = M_DONE;
+            } else {
+                level = 31 - __clz((int)pending);
+                pending &= ~(1u << level);
+                wframe_load<POS, TEX>(B, level, s, f);
+                mode = M_NEXT_CHILD;
+            }
         }
     }
 
