@@ -245,6 +245,53 @@ int prt_render_pixel_list(prt_ctx * ctx, const prt_camera * cam, const prt_param
                           uint32_t width, uint32_t height, const uint32_t * pixel_ids, uint32_t n_pixels,
                           float * rgba_out, prt_counters * counters);
 
+/* ---- ray queries: the reference's TraceRay (raytracer.cpp:159-232) on the caller's rays, against the uploaded scene ----
+ * One call traces `count` independent rays, no shading.
+ *   PRT_QUERY_CLOSEST   the closest hit, bit for bit what the reference's TraceRay returns for the same ray and ray_bias -
+ *                       near-tied hits included (decided in the reference's visit order, as the render pipelines do).  A miss is
+ *                       the reference's zero-filled record with t = FLT_MAX, except group = -1 and vertex0 = 0xFFFFFFFF.
+ *   PRT_QUERY_OCCLUDED  occluded = 1 exactly when some front-facing triangle, tested with the reference's IntersectRayTriangle
+ *                       against t = FLT_MAX, gives a hit with t < tmax (independent of visit order; with tmax NULL it equals
+ *                       TraceRay(...) == true).  Any-hit traversal.
+ * A ray with a non-finite origin or direction component (or biased origin), or a zero direction, is a miss / not occluded; it is
+ * not an error and does not affect the other rays.  The box padding is computed from
+ * max(scene extent, max |biased origin component| of the batch), so origins may lie anywhere.  The reference's sphere test assumes
+ * a unit direction and an origin near the scene: CLOSEST rays with |d|^2 further than 2^-18 from 1, or an origin beyond 64 x the
+ * scene's largest coordinate, are replayed in the reference's visit order (exact, slower); OCCLUDED rays from such origins take
+ * a walk that does not cull by tmax.
+ * Counters: ray_count = count (one TraceRay call per ray); node_visits / tri_tests with PRT_FLAG_COUNT_VISITS in `flags`;
+ * render_ms = the call's device time, trace_kernel_ms = the traversal kernels'; pipeline = 0.  A query leaves
+ * prt_get_render_stats (the last render's) unchanged.
+ * Errors: -1 NULL origins / directions with count > 0, unknown mode, NULL batch; -2 no scene; -8 near ties unresolved;
+ * -10 a HIP call failed.  count == 0 does nothing and returns 0.
+ * The first query after an upload builds a leaf -> (group, vertex0) table on the device (8 B per triangle; not in
+ * prt_scene_info.device_bytes; freed by the next upload). */
+enum { PRT_QUERY_CLOSEST = 0, PRT_QUERY_OCCLUDED = 1 };
+typedef struct prt_ray_batch {
+    const float * origins;         /* count x 3 */
+    const float * directions;      /* count x 3, need not be unit length */
+    const float * tmax;            /* count floats, OCCLUDED only; NULL = no limit */
+    uint32_t count;
+    float ray_bias;                /* origin += direction * ray_bias first, as TraceRay does (raytracer.cpp:163) */
+} prt_ray_batch;
+/* Every pointer may be NULL: that field is not written.  CLOSEST writes t .. normal, OCCLUDED writes occluded only. */
+typedef struct prt_hit_buffers {
+    float * t;                     /* FLT_MAX on a miss */
+    float * bw;                    /* x3: (1 - v - w, v, w) */
+    uint32_t * vertex0;            /* first corner of the triangle in its group's index run (the reference's field); 0xFFFFFFFF on a miss */
+    int32_t * group;               /* stands for SceneObject*; -1 on a miss */
+    float * position;              /* x3: biased origin + direction * t */
+    float * normal;                /* x3: Normalize(Cross(ab, ac)) */
+    uint8_t * occluded;            /* OCCLUDED: 0 / 1 */
+} prt_hit_buffers;
+/* Host pointers (batch arrays and hit buffers). */
+int prt_trace_rays(prt_ctx * ctx, int mode, const prt_ray_batch * batch, const prt_hit_buffers * hits, uint32_t flags,
+                   prt_counters * counters);
+/* Device pointers on the context's device (hipMalloc'ed or torch tensors' data_ptr); the stream contract of prt_render_device:
+ * the call returns after the context's stream has drained, and the caller's work on the buffers must be finished before it. */
+int prt_trace_rays_device(prt_ctx * ctx, int mode, const prt_ray_batch * batch, const prt_hit_buffers * hits, uint32_t flags,
+                          prt_counters * counters);
+
 /* ---- several devices behind one handle --------------------------------------------------------------------------------
  * SURVEY.md 8(b)'s prt_create(const int * device_ids, int n_dev): what the host mirror's Render() uses for n GPUs, in place
  * of the reference's one-rank-per-core partition + MPI_Gather (main.cpp:311-347).  The scene is replicated (as every MPI rank

@@ -308,6 +308,89 @@ class Renderer:
                                                    C.byref(cam) if cam is not None else None), "prt_debug_device_kat")
         return out
 
+    # (name, components per ray, numpy dtype) of prt_hit_buffers' fields
+    HIT_FIELDS = (("t", 1, np.float32), ("bw", 3, np.float32), ("vertex0", 1, np.uint32), ("group", 1, np.int32),
+                  ("position", 3, np.float32), ("normal", 3, np.float32), ("occluded", 1, np.uint8))
+    CLOSEST_FIELDS = ("t", "bw", "vertex0", "group", "position", "normal")
+
+    def trace_rays(self, origins, directions, *, mode: str = "closest", tmax=None, ray_bias: float = 0.0,
+                   fields: Optional[Sequence[str]] = None, count_visits: bool = False) -> dict:
+        """The reference's TraceRay on n rays against the uploaded scene (prt_trace_rays, include/prt.h).
+
+        origins, directions: float32 (n, 3), contiguous - numpy arrays (host entry point, numpy results) or torch tensors on
+        this context's device (device entry point, tensors on that device).  mode "closest" returns the closest hit's fields
+        (default all of t, bw, vertex0, group, position, normal), "occluded" the field `occluded` (1 when some front-facing
+        triangle is hit below tmax; tmax None = no limit).  Returns {field: array} plus "counters" (PrtCounters)."""
+        modes = {"closest": capi.QUERY_CLOSEST, "occluded": capi.QUERY_OCCLUDED}
+        if mode not in modes:
+            raise ValueError("mode must be 'closest' or 'occluded', not %r" % (mode,))
+        m = modes[mode]
+        if fields is None:
+            fields = self.CLOSEST_FIELDS if m == capi.QUERY_CLOSEST else ("occluded",)
+        spec = {name: (k, dt) for name, k, dt in self.HIT_FIELDS}
+        for f in fields:
+            if f not in spec:
+                raise ValueError("unknown hit field %r" % (f,))
+            if (f == "occluded") != (m == capi.QUERY_OCCLUDED):
+                raise ValueError("field %r is not written in mode %r" % (f, mode))
+        is_torch = type(origins).__module__.split(".")[0] == "torch"
+        if is_torch:
+            import torch
+
+            def check(x, what, cols):
+                if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or not x.is_contiguous():
+                    raise ValueError("%s must be a contiguous float32 torch tensor" % what)
+                if x.device.type != "cuda" or (x.device.index or 0) != self.device_id:
+                    raise ValueError("%s must live on this context's device (cuda:%d)" % (what, self.device_id))
+                if (cols and (x.dim() != 2 or x.shape[1] != 3)) or (not cols and x.dim() != 1):
+                    raise ValueError("%s has shape %s" % (what, tuple(x.shape)))
+            check(origins, "origins", True)
+            check(directions, "directions", True)
+            n = origins.shape[0]
+            if directions.shape[0] != n:
+                raise ValueError("origins and directions differ in length")
+            if tmax is not None:
+                check(tmax, "tmax", False)
+                if tmax.shape[0] != n:
+                    raise ValueError("tmax has %d entries for %d rays" % (tmax.shape[0], n))
+            # torch has no uint32: vertex0 comes back as int32 holding the same bits (a miss, 0xFFFFFFFF, reads -1)
+            tdt = {np.float32: torch.float32, np.uint32: torch.int32, np.int32: torch.int32, np.uint8: torch.uint8}
+            out = {f: torch.empty((n, spec[f][0]) if spec[f][0] > 1 else (n,), dtype=tdt[spec[f][1]], device=origins.device)
+                   for f in fields}
+            ptr = lambda x: x.data_ptr() if x is not None else None    # noqa: E731
+            # the library's stream is not ordered against torch's: whatever torch still has queued on the inputs must be done
+            torch.cuda.current_stream(origins.device).synchronize()
+            entry = self._lib.prt_trace_rays_device
+        else:
+            def as_np(x, what, cols):
+                a = np.asarray(x)
+                if a.dtype != np.float32 or not a.flags["C_CONTIGUOUS"]:
+                    raise ValueError("%s must be a contiguous float32 array" % what)
+                if (cols and (a.ndim != 2 or a.shape[1] != 3)) or (not cols and a.ndim != 1):
+                    raise ValueError("%s has shape %s" % (what, a.shape))
+                return a
+            origins = as_np(origins, "origins", True)
+            directions = as_np(directions, "directions", True)
+            n = origins.shape[0]
+            if directions.shape[0] != n:
+                raise ValueError("origins and directions differ in length")
+            if tmax is not None:
+                tmax = as_np(tmax, "tmax", False)
+                if tmax.shape[0] != n:
+                    raise ValueError("tmax has %d entries for %d rays" % (tmax.shape[0], n))
+            out = {f: np.empty((n, spec[f][0]) if spec[f][0] > 1 else (n,), dtype=spec[f][1]) for f in fields}
+            ptr = lambda x: x.ctypes.data if x is not None else None    # noqa: E731
+            entry = self._lib.prt_trace_rays
+        batch = capi.PrtRayBatch(ptr(origins), ptr(directions), ptr(tmax) if m == capi.QUERY_OCCLUDED else None, n,
+                                 float(ray_bias))
+        hb = capi.PrtHitBuffers(*[ptr(out[name]) if name in out else None for name, _, _ in self.HIT_FIELDS])
+        counters = PrtCounters()
+        flags = capi.FLAG_COUNT_VISITS if count_visits else 0
+        self._check(entry(self._ctx, m, C.byref(batch), C.byref(hb), flags, C.byref(counters)),
+                    "prt_trace_rays_device" if is_torch else "prt_trace_rays")
+        out["counters"] = counters
+        return out
+
     def close(self):
         if self._ctx:
             self._lib.prt_destroy(self._ctx)

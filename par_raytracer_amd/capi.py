@@ -95,6 +95,17 @@ class PrtRenderStats(C.Structure):
                 ("parked_shadow_rays", C.c_uint64), ("elided_shadow_rays", C.c_uint64), ("variance_close_calls", C.c_uint64), ("stack_lds_entries", C.c_uint32), ("stack_bound", C.c_uint32)]
 
 
+class PrtRayBatch(C.Structure):
+    _fields_ = [("origins", C.c_void_p), ("directions", C.c_void_p), ("tmax", C.c_void_p), ("count", C.c_uint32),
+                ("ray_bias", C.c_float)]
+
+
+class PrtHitBuffers(C.Structure):
+    _fields_ = [("t", C.c_void_p), ("bw", C.c_void_p), ("vertex0", C.c_void_p), ("group", C.c_void_p),
+                ("position", C.c_void_p), ("normal", C.c_void_p), ("occluded", C.c_void_p)]
+
+
+QUERY_CLOSEST, QUERY_OCCLUDED = 0, 1
 PIPELINE_DEFAULT, PIPELINE_MEGAKERNEL, PIPELINE_WAVEFRONT, PIPELINE_PERSISTENT, PIPELINE_POOL = 0, 1, 2, 3, 4
 FLAG_COUNT_VISITS = 0x100
 FLAG_TRYOUT = 0x200
@@ -104,7 +115,8 @@ BUILD_EXPERIMENTAL, BUILD_BVH4 = 1, 2
 PRT_SYMBOLS = ["prt_create", "prt_destroy", "prt_last_error", "prt_abi_version", "prt_set_option", "prt_build_flags", "prt_upload_scene", "prt_render",
                "prt_render_device", "prt_shard_rows", "prt_render_shard_device", "prt_render_shard", "prt_render_pixel_list", "prt_get_scene_info", "prt_get_render_stats", "prt_debug_check_bvh", "prt_debug_check_bvh_lbvh", "prt_debug_device_kat",
                "prt_multi_create", "prt_multi_destroy", "prt_multi_last_error", "prt_multi_device_count", "prt_multi_context",
-               "prt_multi_upload_scene", "prt_multi_render", "prt_multi_depth", "prt_multi_submit", "prt_multi_wait", "prt_debug_throw"]
+               "prt_multi_upload_scene", "prt_multi_render", "prt_multi_depth", "prt_multi_submit", "prt_multi_wait", "prt_debug_throw",
+               "prt_trace_rays", "prt_trace_rays_device"]
 PRT_HOST_SYMBOLS = ["prt_host_load_obj", "prt_host_free_scene", "prt_host_scene_desc", "prt_host_scene_hierarchy_seconds",
                     "prt_host_scene_parse_seconds", "prt_host_last_error", "prt_host_make_camera",
                     "prt_host_default_params", "prt_host_render", "prt_host_render_error", "prt_host_write_image", "prt_host_tonemap",
@@ -176,6 +188,9 @@ def hip_lib() -> C.CDLL:
                                          C.c_void_p, C.POINTER(C.c_uint64)]
         lib.prt_multi_wait.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(PrtCounters)]
         lib.prt_debug_throw.argtypes = [C.c_void_p, C.c_int]
+        lib.prt_trace_rays.argtypes = [C.c_void_p, C.c_int, C.POINTER(PrtRayBatch), C.POINTER(PrtHitBuffers), C.c_uint32,
+                                       C.POINTER(PrtCounters)]
+        lib.prt_trace_rays_device.argtypes = lib.prt_trace_rays.argtypes
         _hip = lib
     return _hip
 

@@ -1,0 +1,318 @@
+// kernels_query.h - batched ray queries (prt_trace_rays): the reference's TraceRay (raytracer.cpp:159-232) on rays the caller
+// supplies, without shading.
+//
+//   k_query_pad    max |biased origin component| over the batch, one word (device entry point only: the host entry point
+//                  computes it on the host).  The box pad of dev_trace_common.h assumes origins near the scene; query origins
+//                  can be anywhere, so the pad is 2^-16 x max(scene, origins of this batch).
+//   k_query        PERSISTENT waves shaped like k_trace: a per-lane LDS stack column, chunked atomic fetch of ray indices,
+//                  ballot / mbcnt refill of idle lanes under the context's KEEP_MIN / NODE_MIN, the traversal of dev_trace.h.
+//                  CLOSEST: closest hit; OCCLUDED: any hit below tmax (the best hit starts at tmax: tri_test accepts th < best_t).
+//                  Rays that end flagged (a near tie, or a push that did not fit the LDS column) go to a list, as do CLOSEST rays
+//                  whose direction is not unit length or whose origin is far from the scene (query_replays), and OCCLUDED rays
+//                  from far origins (query_any_unculled).
+//   k_query_exact  traces the listed rays again on a full-height global stack: trace_ray (near ties decided in the reference's
+//                  visit order by resolve_near_ties), the full replay of TraceRay for non-unit directions, or the any-hit walk
+//                  below tmax.
+// Only the fields the caller asked for are written (a wave-uniform mask), with plain vector stores.
+#pragma once
+
+#include "dev_trace.h"
+#include "kernels_wave.h"            // lane_id
+
+namespace prt {
+
+enum { QUERY_CLOSEST = 0, QUERY_OCCLUDED = 1 };
+enum { QF_T = 1, QF_BW = 2, QF_VERTEX0 = 4, QF_GROUP = 8, QF_POSITION = 16, QF_NORMAL = 32, QF_OCCLUDED = 64 };
+
+struct QueryArgs {
+    const float * origins;           // count x 3
+    const float * dirs;              // count x 3
+    const float * tmax;              // count, OCCLUDED only; null = no limit
+    unsigned int count;
+    float ray_bias;
+    // outputs (null unless the field's bit is in the mask)
+    float * t;
+    float * bw;                      // x3
+    unsigned int * vertex0;
+    int * group;
+    float * position;                // x3
+    float * normal;                  // x3
+    unsigned char * occluded;
+    // [0] fetch head, [1] length of `slow`, [2] max |biased origin component| as float bits (k_query_pad)
+    unsigned int * work;
+    unsigned int * slow;             // ray indices for k_query_exact
+    float replay_beyond;             // CLOSEST rays whose biased origin lies further out are replayed (query_replays)
+    float pad_max;                   // max(scene, origins) when the host computed it, else the scene's; pad = 2^-16 x max(this, work[2])
+    unsigned int stack_lds_entries;
+    int * exact_stack;               // k_query_exact's full-height global stack columns
+    unsigned int exact_stack_stride;
+};
+
+PRT_D float query_pad(const QueryArgs & A) {
+    return fmaxf(A.pad_max, __uint_as_float(A.work[2])) * (1.0f / 65536.0f);
+}
+
+// Ray i, origin biased as TraceRay does (raytracer.cpp:163).  False for a ray that is a miss by definition: a non-finite
+// origin or direction component, a zero direction.
+PRT_D bool query_ray(const QueryArgs & A, unsigned int i, f3 & ob, f3 & d) {
+    const f3 o = mk3(A.origins[3u * i], A.origins[3u * i + 1u], A.origins[3u * i + 2u]);
+    d = mk3(A.dirs[3u * i], A.dirs[3u * i + 1u], A.dirs[3u * i + 2u]);
+    ob = o + d * A.ray_bias;
+    const bool finite = isfinite(o.x) && isfinite(o.y) && isfinite(o.z) && isfinite(d.x) && isfinite(d.y) && isfinite(d.z) &&
+                        isfinite(ob.x) && isfinite(ob.y) && isfinite(ob.z);
+    return finite && !(d.x == 0.0f && d.y == 0.0f && d.z == 0.0f);
+}
+
+// The reference's sphere test (IntersectRaySphere, raytracer.cpp:32-60) assumes a unit direction: for other lengths its entry
+// distance is not in the units of the ray's t, and TraceRay skips groups whose triangles would give the closest hit.  The fast
+// traversal finds the closest hit over all triangles, which is TraceRay's answer only where that test is sound, i.e. for
+// (float-normalised) unit directions.  A CLOSEST ray whose |d|^2 is further than 2^-18 from 1 is therefore replayed in full on
+// the slow path: resolve_near_ties with an unbounded candidate set offers every triangle the ray's line meets to the
+// reference's filter in the reference's visit order, sphere tests included (RefSphereWalk) - TraceRay, step for step.  The same
+// holds for an origin far from the scene (beyond 64 x its largest coordinate): there IntersectRaySphere's c = m.m - r^2 cancels
+// and the reference drops groups at random.
+PRT_D bool query_far(const QueryArgs & A, f3 ob) { return fmaxf(fmaxf(fabsf(ob.x), fabsf(ob.y)), fabsf(ob.z)) > A.replay_beyond; }
+PRT_D bool query_replays(const QueryArgs & A, f3 ob, f3 d) {
+    const float l2 = dot3(d, d);
+    const bool unit = l2 >= 1.0f - 3.814697265625e-6f && l2 <= 1.0f + 3.814697265625e-6f;
+    return !unit || query_far(A, ob);
+}
+
+// The RaycastHit of ray i (raytracer.cpp:20-30, 82-125) into the requested fields.  h.tri < 0: a miss - the reference's
+// zero-filled record with t = FLT_MAX, except group = -1 and vertex0 = 0xFFFFFFFF.
+template <int MODE>
+PRT_D void query_emit(const DevScene & sc, const QueryArgs & A, const uint2 * leaf_map, unsigned int fields, unsigned int i,
+                      f3 ob, f3 d, const HitRec & h) {
+    const bool hit = h.tri >= 0;
+    if (MODE == QUERY_OCCLUDED) {
+        if (fields & QF_OCCLUDED) A.occluded[i] = hit ? 1 : 0;
+        return;
+    }
+    if (fields & QF_T) A.t[i] = hit ? h.t : 3.402823466e+38f;
+    if (fields & QF_BW) {
+        A.bw[3u * i] = hit ? 1.0f - h.v - h.w : 0.0f;                       // raytracer.cpp:120
+        A.bw[3u * i + 1u] = hit ? h.v : 0.0f;
+        A.bw[3u * i + 2u] = hit ? h.w : 0.0f;
+    }
+    if (fields & (QF_VERTEX0 | QF_GROUP)) {
+        const uint2 m = hit ? leaf_map[h.tri] : make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);      // (group, vertex0)
+        if (fields & QF_GROUP) A.group[i] = (int)m.x;
+        if (fields & QF_VERTEX0) A.vertex0[i] = m.y;
+    }
+    if (fields & QF_POSITION) {
+        const f3 p = hit ? ob + d * h.t : mk3(0.0f, 0.0f, 0.0f);           // raytracer.cpp:121
+        A.position[3u * i] = p.x; A.position[3u * i + 1u] = p.y; A.position[3u * i + 2u] = p.z;
+    }
+    if (fields & QF_NORMAL) {
+        f3 n = mk3(0.0f, 0.0f, 0.0f);
+        if (hit) {
+            const float4 r2 = sc.tris[3u * (unsigned int)h.tri + 2u];       // (ac.z, n.xyz), n = Cross(ab, ac) from the host
+            n = normalize3(mk3(r2.y, r2.z, r2.w));                          // raytracer.cpp:122
+        }
+        A.normal[3u * i] = n.x; A.normal[3u * i + 1u] = n.y; A.normal[3u * i + 2u] = n.z;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// max |biased origin component| of the valid rays -> work[2] (non-negative floats order like their bits: one atomicMax)
+__global__ __launch_bounds__(256) void k_query_pad(QueryArgs A) {
+    float m = 0.0f;
+    for (unsigned int i = blockIdx.x * blockDim.x + threadIdx.x; i < A.count; i += gridDim.x * blockDim.x) {
+        f3 ob, d;
+        if (query_ray(A, i, ob, d)) m = fmaxf(m, fmaxf(fmaxf(fabsf(ob.x), fabsf(ob.y)), fabsf(ob.z)));
+    }
+    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+    if ((threadIdx.x & 63u) == 0u && m > 0.0f) atomicMax(A.work + 2, __float_as_uint(m));
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Persistent traversal of the batch.  grid = resident blocks; dynamic LDS = stack_lds_entries * BLOCK * 4.
+template <int BLOCK, int MODE, bool COUNT>
+__global__ __launch_bounds__(BLOCK, 6) void k_query(DevScene sc, QueryArgs A, const uint2 * leaf_map, unsigned int fields,
+                                                  int keep_min, int node_min, unsigned int chunk, DevCounters * ctr) {
+    extern __shared__ int s_stack[];
+    LdsStack<BLOCK> stack;
+    stack.attach(s_stack, threadIdx.x);
+    stack.cap = A.stack_lds_entries;
+    const unsigned int total = A.count;
+    const unsigned int lane = lane_id();
+    const float pad = query_pad(A);
+    unsigned int * head = A.work;
+
+    TravRay r;
+    trav_idle(r);
+    int ray = -1;                        // batch index of the lane's ray, -1 = idle
+    bool exhausted = false;              // wave-uniform: the batch has no more rays to hand out
+    TraceStats st;
+    st.nodes = st.tris = st.wnodes = st.wleaves = st.wtris = st.wrefills = st.wrays = st.max_sp = st.culled = 0;
+
+    unsigned int chunk_next = 0, chunk_end = 0;      // wave-uniform: rays reserved for this wave, not yet handed out
+    for (;;) {
+        // ---- refill idle lanes from the wave's reserved chunk (as k_trace); a ray that is a miss by definition is written at once
+        const unsigned long long idle = __ballot(ray < 0);
+        if (idle != 0ull && !(exhausted && chunk_next == chunk_end)) {
+            if (chunk_next == chunk_end) {
+                unsigned int base = 0;
+                if (lane == 0) base = atomicAdd(head, chunk);
+                base = (unsigned int)__shfl((int)base, 0);
+                if (base >= total) {
+                    exhausted = true;
+                } else {
+                    chunk_next = base;
+                    chunk_end = base + chunk < total ? base + chunk : total;
+                }
+            }
+            const unsigned int avail = chunk_end - chunk_next;
+            if (COUNT && avail && lane == 0) st.wrefills++;
+            if (avail) {
+                const unsigned int prefix = __builtin_amdgcn_mbcnt_hi((unsigned int)(idle >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)idle, 0u));
+                const unsigned int n_idle = (unsigned int)__popcll(idle);
+                const unsigned int take = n_idle < avail ? n_idle : avail;
+                if (ray < 0 && prefix < take) {
+                    const unsigned int idx = chunk_next + prefix;
+                    f3 ob, d;
+                    const bool valid = query_ray(A, idx, ob, d);
+                    if (valid && (MODE == QUERY_CLOSEST ? query_replays(A, ob, d) : query_far(A, ob))) {
+                        A.slow[atomicAdd(A.work + 1, 1u)] = idx;                    // query_replays / query_any_unculled
+                    } else if (valid) {
+                        trav_init(r, ob, d, MODE == QUERY_OCCLUDED ? TRACE_ANY : TRACE_CLOSEST, pad, stack);
+                        if (MODE == QUERY_OCCLUDED && A.tmax) r.best.t = A.tmax[idx];
+                        ray = (int)idx;
+                    } else {
+                        HitRec miss;
+                        miss.t = 3.402823466e+38f; miss.v = miss.w = 0.0f; miss.tri = -1;
+                        query_emit<MODE>(sc, A, leaf_map, fields, idx, ob, d, miss);
+                    }
+                }
+                chunk_next += take;
+            }
+        }
+        if (__ballot(ray >= 0) == 0ull) {
+            if (exhausted && chunk_next == chunk_end) break;
+            continue;                    // every ray of the refill was a miss by definition: refill again
+        }
+
+        // ---- traverse until fewer than `leave_below` lanes of the wave are still busy (k_trace's loop)
+        const int leave_below = (exhausted && chunk_next == chunk_end) ? 1 : keep_min;
+        while (ray >= 0) {
+            const int walkers = __popcll(__ballot(trav_walking(r)));
+            const int nmin = node_min < (walkers >> 1) ? node_min : (walkers >> 1);
+            while (trav_walking(r)) {
+                trav_node_step<LdsStack<BLOCK>, COUNT>(sc, r, stack, st, pad);
+                if (__popcll(__ballot(trav_walking(r))) < nmin) break;
+            }
+            bool fin = trav_done(r);
+            if (!fin && !trav_walking(r)) fin = trav_leaf<LdsStack<BLOCK>, COUNT>(sc, r, stack, st);
+            if (fin) {
+                if (trav_needs_slow_path(r, stack)) A.slow[atomicAdd(A.work + 1, 1u)] = (unsigned int)ray;
+                else query_emit<MODE>(sc, A, leaf_map, fields, (unsigned int)ray, r.o, r.d, r.best);   // r.o: the biased origin
+                ray = -1;
+                break;
+            }
+            if (__popcll(__ballot(true)) < leave_below) break;
+        }
+    }
+    if (COUNT) {
+        atomicAdd(&ctr->node_visits, (unsigned long long)st.nodes);
+        atomicAdd(&ctr->tri_tests, (unsigned long long)st.tris);
+        atomicAdd(&ctr->wave_node_steps, (unsigned long long)st.wnodes);
+        atomicAdd(&ctr->wave_leaf_steps, (unsigned long long)st.wleaves);
+        atomicAdd(&ctr->wave_tri_steps, (unsigned long long)st.wtris);
+        atomicAdd(&ctr->wave_refills, (unsigned long long)st.wrefills);
+        atomicMax(&ctr->max_sp, (unsigned long long)st.max_sp);
+    }
+}
+
+// Any hit below tmax on a stack that cannot overflow (trace_ray's walk with the best hit started at tmax).
+template <class STK, bool COUNT>
+PRT_D HitRec query_any_below(const DevScene & sc, f3 o, f3 d, float tmax, float pad, const STK & stk, TraceStats & st) {
+    TravRay r;
+    trav_init(r, o, d, TRACE_ANY, pad, stk);
+    r.best.t = tmax;
+    for (;;) {
+        while (trav_walking(r)) trav_node_step<STK, COUNT>(sc, r, stk, st, pad);
+        if (trav_done(r)) break;
+        if (trav_leaf<STK, COUNT>(sc, r, stk, st)) break;                   // found its occluder
+    }
+    return r.best;
+}
+
+// The walk's leaf in r: its triangle range, and the step past it (the two traversals keep a visited leaf differently).
+#if defined(PRT_BVH8)
+PRT_D void query_leaf_range(const TravRay & r, unsigned int & first, unsigned int & count) { trav_leaf_range(r, first, count); }
+template <class STK> PRT_D void query_leaf_next(TravRay & r, const STK &) { trav_leaf_consume(r); }
+#else
+PRT_D void query_leaf_range(const TravRay & r, unsigned int & first, unsigned int & count) {
+    const unsigned int leaf = (unsigned int)~r.node;
+    first = leaf >> 2;
+    count = (leaf & 3u) + 1u;
+}
+template <class STK> PRT_D void query_leaf_next(TravRay & r, const STK & stk) { trav_pop(r, stk); }
+#endif
+
+// OCCLUDED for an origin far from the scene (query_far): there the triangle test's t carries a rounding error (ap = o - a is
+// large and cancels in Dot(ap, n)) that can exceed the box pad, so a box culled against tmax could hold a triangle whose
+// computed t is below tmax.  This walk culls boxes by geometry only and applies the rule itself to every triangle the ray's
+// line meets: IntersectRayTriangle against FLT_MAX and t < tmax.
+template <class STK, bool COUNT>
+PRT_D HitRec query_any_unculled(const DevScene & sc, f3 o, f3 d, float tmax, float pad, const STK & stk, TraceStats & st) {
+    TravRay r;
+    trav_init(r, o, d, TRACE_ANY, pad, stk);
+    r.best.t = __uint_as_float(0x7F800000u);
+    const f3 qp = o - (o + d);                                              // raytracer.cpp:88-89
+    HitRec h;
+    h.t = 3.402823466e+38f; h.v = h.w = 0.0f; h.tri = -1;
+    for (;;) {
+        while (trav_walking(r)) trav_node_step<STK, COUNT>(sc, r, stk, st, pad);
+        if (trav_done(r)) break;
+        unsigned int first, count;
+        query_leaf_range(r, first, count);
+        for (unsigned int i = 0; i < count; ++i) {
+            const float4 * tp = sc.tris + 3 * (size_t)(first + i);
+            const float4 r0 = tp[0], r1 = tp[1], r2 = tp[2];
+            float t, dd, v, w;
+            if (COUNT) st.tris++;
+            if (!tri_geom(o, qp, mk3(r0.x, r0.y, r0.z), mk3(r0.w, r1.x, r1.y), mk3(r1.z, r1.w, r2.x), mk3(r2.y, r2.z, r2.w), t, dd, v, w)) continue;
+            if (t > 3.402823466e+38f * dd) continue;                        // raytracer.cpp:104 against FLT_MAX
+            const float th = t * (1.0f / dd);
+            if (th < tmax) { h.t = th; h.tri = (int)(first + i); return h; }
+        }
+        query_leaf_next(r, stk);
+    }
+    return h;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Slow path of k_query (as k_trace_exact is k_trace's): a small fixed grid that reads the list length on the device.
+template <int MODE, bool COUNT>
+__global__ __launch_bounds__(256) void k_query_exact(DevScene sc, QueryArgs A, const uint2 * leaf_map, unsigned int fields,
+                                                     DevCounters * ctr) {
+    const unsigned int gid = blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned int n_slow = A.work[1];
+    const float pad = query_pad(A);
+    TraceStats st;
+    st.nodes = st.tris = st.wnodes = st.wleaves = st.wtris = st.wrefills = st.wrays = st.max_sp = st.culled = 0;
+    GlobalStack slow;
+    slow.attach(A.exact_stack, gid, A.exact_stack_stride);
+    for (unsigned int i = gid; i < n_slow; i += gridDim.x * blockDim.x) {
+        const unsigned int idx = A.slow[i];
+        f3 ob, d;
+        (void)query_ray(A, idx, ob, d);                                     // listed rays are valid
+        HitRec h;
+        if (MODE == QUERY_OCCLUDED && query_far(A, ob))
+            h = query_any_unculled<GlobalStack, COUNT>(sc, ob, d, A.tmax ? A.tmax[idx] : 3.402823466e+38f, pad, slow, st);
+        else if (MODE == QUERY_OCCLUDED)
+            h = query_any_below<GlobalStack, COUNT>(sc, ob, d, A.tmax ? A.tmax[idx] : 3.402823466e+38f, pad, slow, st);
+        else if (query_replays(A, ob, d))
+            h = resolve_near_ties<GlobalStack, COUNT>(sc, ob, d, pad, 3.402823466e+38f, slow, st);      // bound = inf: every candidate
+        else
+            h = trace_ray<GlobalStack, COUNT>(sc, ob, d, TRACE_CLOSEST, pad, slow, st);
+        query_emit<MODE>(sc, A, leaf_map, fields, idx, ob, d, h);
+    }
+    if (COUNT) {
+        atomicAdd(&ctr->node_visits, (unsigned long long)st.nodes);
+        atomicAdd(&ctr->tri_tests, (unsigned long long)st.tris);
+    }
+}
+
+}  // namespace prt

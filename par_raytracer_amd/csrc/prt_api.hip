@@ -39,6 +39,7 @@
 #endif
 #include "bvh_lbvh.h"
 #include "kernels_debug.h"
+#include "kernels_query.h"
 
 using namespace prt;
 
@@ -192,6 +193,17 @@ struct prt_ctx {
     int reserved_cus = 0;
     unsigned int stack_bound = 0;
     DevBuf<int> stack_spill;
+    // ray queries (prt_trace_rays, kernels_query.h).  The upload keeps the builder's leaf order and the groups; the first query
+    // after it builds the leaf -> (group, vertex0) table from them (not in prt_scene_info.device_bytes: a render-only user pays
+    // no device memory for it), and the next upload frees it.
+    std::vector<uint32_t> q_tri_order;    // leaf slot -> input triangle
+    std::vector<prt_group> q_groups;
+    DevBuf<uint2> q_leaf_map;             // leaf slot -> (group, vertex0)
+    DevBuf<unsigned int> q_work;          // fetch head, slow-list length, origin extent (QueryArgs::work)
+    DevBuf<unsigned int> q_slow;          // rays handed to k_query_exact
+    DevBuf<int> q_exact_stack;
+    DevBuf<float> q_io;                   // host entry point: the batch and the requested fields on the device
+    DevBuf<unsigned char> q_occ;
 };
 
 namespace {
@@ -1339,6 +1351,137 @@ int render_pixels(prt_ctx * ctx, const prt_camera * cam_in, const prt_params * p
     return -7;
 }
 
+// ---- ray queries (prt_trace_rays, kernels_query.h) ---------------------------------------------------------------------------
+
+template <int MODE, bool COUNT>
+int launch_query(prt_ctx * ctx, const QueryArgs & A, const uint2 * leaf_map, unsigned int fields) {
+    constexpr int BLOCK = 256;
+    const size_t lds = stack_dwords(A.stack_lds_entries, BLOCK) * sizeof(int);
+    // persistent grid of resident blocks, chunks and lane-refill thresholds as the wavefront pipeline's k_trace
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_query<BLOCK, MODE, COUNT>, BLOCK, lds) != hipSuccess || per_cu < 1) per_cu = 2;
+    per_cu = std::min(per_cu, 8);
+    const PrtOptions & opt = ctx->opt;
+    if (opt.trace_blocks_per_cu >= 0) per_cu = std::max(1, std::min(per_cu, (int)opt.trace_blocks_per_cu));
+    int keep_min = 40, node_min = 32;
+    if (opt.keep_min >= 0) keep_min = std::max(1, std::min(64, (int)opt.keep_min));
+    if (opt.node_min >= 0) node_min = std::max(0, std::min(64, (int)opt.node_min));
+    unsigned int chunk_min = 128;
+    if (opt.chunk_min >= 0) chunk_min = (unsigned int)std::max(64ll, std::min(512ll, opt.chunk_min));
+    const unsigned int grid = std::max(1u, std::min((unsigned int)per_cu * (unsigned int)ctx->cu_count, (A.count + BLOCK - 1) / BLOCK));
+    unsigned int chunk = A.count / (grid * (BLOCK / 64) * 8u);
+    chunk = std::max(chunk_min, std::min(512u, (chunk / 64u) * 64u));
+    hipLaunchKernelGGL((k_query<BLOCK, MODE, COUNT>), dim3(grid), dim3(BLOCK), lds, ctx->stream, ctx->scene, A, leaf_map, fields,
+                       keep_min, node_min, chunk, ctx->counters.p);
+    HIP_TRY(ctx, hipGetLastError());
+    constexpr unsigned int SLOW_BLOCKS = 64;               // A.exact_stack holds SLOW_BLOCKS * 256 columns
+    hipLaunchKernelGGL((k_query_exact<MODE, COUNT>), dim3(SLOW_BLOCKS), dim3(256), 0, ctx->stream, ctx->scene, A, leaf_map, fields, ctx->counters.p);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+// One batch on the device: A's rays and outputs are device pointers; pad_max < 0 asks k_query_pad for the origins' extent.
+// Synchronous (returns after the context's stream has drained).
+int run_query(prt_ctx * ctx, int mode, QueryArgs A, unsigned int fields, bool count_visits, prt_counters * counters) {
+    // the leaf -> (group, vertex0) table, built on the first query after an upload
+    if (!ctx->q_leaf_map.p) {
+        const uint32_t n_tris = ctx->scene.tri_count;
+        if (ctx->q_tri_order.size() != n_tris) { ctx->error = "prt_trace_rays: the scene's leaf order is not available"; return -2; }
+        std::vector<uint2> of_input(n_tris), map((size_t)n_tris + 1, make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu));
+        for (uint32_t g = 0; g < (uint32_t)ctx->q_groups.size(); ++g) {
+            const prt_group & pg = ctx->q_groups[g];
+            for (uint32_t k = 0; k < pg.index_count / 3; ++k) of_input[pg.first_index / 3 + k] = make_uint2(g, 3u * k);   // IntersectRayMesh's vertex0 = i
+        }
+        for (uint32_t slot = 0; slot < n_tris; ++slot) map[slot] = of_input[ctx->q_tri_order[slot]];
+        HIP_TRY(ctx, ctx->q_leaf_map.upload(map));
+        HIP_TRY(ctx, hipDeviceSynchronize());              // the upload went through the null stream
+    }
+    hipStream_t stream = ctx->stream;
+    ctx->scene.tie_widen_max = (unsigned int)std::max(0ll, std::min(64ll, ctx->opt.tie_widen_max));
+    // LDS stack column as the render pipelines size it; k_query_exact's fixed grid gets full-height global columns
+    unsigned int stack_cap = STACK_LDS_CAP_DEFAULT;
+    if (ctx->opt.stack_cap >= 0) stack_cap = (unsigned int)std::max(2ll, std::min(40ll, ctx->opt.stack_cap));
+    A.stack_lds_entries = std::min(ctx->stack_bound, stack_cap);
+    const size_t exact_lanes = 64 * 256;
+    HIP_TRY(ctx, ctx->q_exact_stack.ensure(stack_dwords(std::max(ctx->stack_bound, 4u), exact_lanes)));
+    A.exact_stack = ctx->q_exact_stack.p;
+    A.exact_stack_stride = (unsigned int)exact_lanes;
+    HIP_TRY(ctx, ctx->q_work.ensure(4));
+    HIP_TRY(ctx, ctx->q_slow.ensure(A.count));
+    HIP_TRY(ctx, ctx->counters.ensure(1));
+    A.work = ctx->q_work.p;
+    A.slow = ctx->q_slow.p;
+    A.replay_beyond = 64.0f * ctx->scene_abs_max;
+    const bool device_pad = A.pad_max < 0.0f;
+    if (device_pad) A.pad_max = ctx->scene_abs_max;
+
+    HIP_TRY(ctx, hipMemsetAsync(ctx->counters.p, 0, sizeof(DevCounters), stream));
+    HIP_TRY(ctx, hipMemsetAsync(A.work, 0, 4 * sizeof(unsigned int), stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev[0], stream));
+    if (device_pad) {
+        hipLaunchKernelGGL(k_query_pad, dim3(std::min(1024u, (A.count + 255) / 256)), dim3(256), 0, stream, A);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev[2], stream));
+    int rc = mode == PRT_QUERY_OCCLUDED ? (count_visits ? launch_query<QUERY_OCCLUDED, true>(ctx, A, ctx->q_leaf_map.p, fields)
+                                                        : launch_query<QUERY_OCCLUDED, false>(ctx, A, ctx->q_leaf_map.p, fields))
+                                        : (count_visits ? launch_query<QUERY_CLOSEST, true>(ctx, A, ctx->q_leaf_map.p, fields)
+                                                        : launch_query<QUERY_CLOSEST, false>(ctx, A, ctx->q_leaf_map.p, fields));
+    if (rc) return rc;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev[3], stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->host_counters, ctx->counters.p, sizeof(DevCounters), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev[1], stream));
+    HIP_TRY(ctx, hipEventSynchronize(ctx->ev[1]));
+    const DevCounters h = *ctx->host_counters;
+    if (h.near_tie_unresolved) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "prt_trace_rays: %llu near-tied hits could not be resolved within %lld widenings of the candidate set",
+                 (unsigned long long)h.near_tie_unresolved, ctx->opt.tie_widen_max);
+        ctx->error = msg;
+        return -8;
+    }
+    if (ctx->opt.debug_util && h.wave_node_steps)
+        fprintf(stderr, "[prt] k_query: node loop %.1f%% of lanes (%llu wave steps), triangle tests %.1f%% (%llu wave steps, %llu leaf visits), %llu refills\n",
+                100.0 * (double)h.node_visits / (64.0 * (double)h.wave_node_steps), (unsigned long long)h.wave_node_steps,
+                100.0 * (double)h.tri_tests / (64.0 * (double)h.wave_tri_steps), (unsigned long long)h.wave_tri_steps,
+                (unsigned long long)h.wave_leaf_steps, (unsigned long long)h.wave_refills);
+    if (counters) {
+        float ms = 0.0f, tms = 0.0f;
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+        HIP_TRY(ctx, hipEventElapsedTime(&tms, ctx->ev[2], ctx->ev[3]));
+        memset(counters, 0, sizeof(*counters));
+        counters->ray_count = A.count;                     // one TraceRay call per ray
+        counters->node_visits = h.node_visits;
+        counters->tri_tests = h.tri_tests;
+        counters->render_ms = ms;
+        counters->trace_kernel_ms = tms;
+        counters->trace_kernel_launches = 2;
+        counters->pipeline = 0;
+    }
+    return 0;
+}
+
+unsigned int query_fields(int mode, const prt_hit_buffers * o) {
+    if (!o) return 0u;
+    if (mode == PRT_QUERY_OCCLUDED) return o->occluded ? (unsigned int)QF_OCCLUDED : 0u;
+    return (o->t ? QF_T : 0) | (o->bw ? QF_BW : 0) | (o->vertex0 ? QF_VERTEX0 : 0) | (o->group ? QF_GROUP : 0) |
+           (o->position ? QF_POSITION : 0) | (o->normal ? QF_NORMAL : 0);
+}
+
+// The checks both entry points share; 1 = nothing to trace (count 0: counters zeroed), 0 = go on, < 0 = error.
+int query_check(prt_ctx * ctx, int mode, const prt_ray_batch * b, prt_counters * counters) {
+    if (!ctx) return -1;
+    if (mode != PRT_QUERY_CLOSEST && mode != PRT_QUERY_OCCLUDED) { ctx->error = "prt_trace_rays: unknown mode"; return -1; }
+    if (!b) { ctx->error = "prt_trace_rays: null batch"; return -1; }
+    if (b->count && (!b->origins || !b->directions)) { ctx->error = "prt_trace_rays: null origins or directions"; return -1; }
+    if (!ctx->has_scene) { ctx->error = "prt_trace_rays: no scene uploaded"; return -2; }
+    if (b->count == 0) {
+        if (counters) memset(counters, 0, sizeof(*counters));
+        return 1;
+    }
+    return 0;
+}
+
 }  // namespace
 
 // =============================================================================================================
@@ -1480,6 +1623,7 @@ void prt_destroy(prt_ctx * ctx) {
    
     ctx->textures.release(); ctx->texels.release(); ctx->srgb_lut.release(); ctx->tri_uv.release(); ctx->tri_tan.release();
     ctx->ref_spheres.release();
+    ctx->q_leaf_map.release(); ctx->q_work.release(); ctx->q_slow.release(); ctx->q_exact_stack.release(); ctx->q_io.release(); ctx->q_occ.release();
     for (int c = 0; c < PRT_MAX_CHAINS; ++c) {
         prt_ctx::ChainWs & w = ctx->chain[c];
         w.f4.release(); w.rng.release(); w.counts.release(); w.overflow.release(); w.slow_stack.release();
@@ -1528,6 +1672,9 @@ int prt_upload_scene(prt_ctx * ctx, const prt_scene_desc * s) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->has_scene = false;
+    ctx->q_leaf_map.release();
+    ctx->q_tri_order.clear();
+    ctx->q_groups.clear();
     const uint32_t n_tris = s->index_count / 3;
     if (n_tris >= (1u << 26)) { ctx->error = "prt_upload_scene: 2^26 triangles or more (the traversal addresses nodes and triangles by 32-bit byte offsets)"; return -1; }
 
@@ -1824,6 +1971,8 @@ int prt_upload_scene(prt_ctx * ctx, const prt_scene_desc * s) {
                         (textured ? ctx->textures.bytes() + ctx->texels.bytes() + ctx->srgb_lut.bytes() + ctx->tri_uv.bytes() : 0) +
                         (bumped ? ctx->tri_tan.bytes() : 0) + (ref_spheres.empty() ? 0 : ctx->ref_spheres.bytes());
     info.bvh_build_ms = build_ms;
+    ctx->q_tri_order.swap(bvh.tri_order);
+    ctx->q_groups.assign(s->groups, s->groups + s->group_count);
     HIP_TRY(ctx, hipDeviceSynchronize());      // uploads went through the null stream; renders use the context's non-blocking streams
     ctx->has_scene = true;
     ctx->scene_epoch++;
@@ -1921,6 +2070,82 @@ int prt_render_pixel_list(prt_ctx * ctx, const prt_camera * cam, const prt_param
     if (n_pixels) HIP_TRY(ctx, hipMemcpy(rgba_out, ctx->frame_out.p, (size_t)n_pixels * sizeof(float4), hipMemcpyDeviceToHost));
     return 0;
     PRT_API_CATCH_RC(ctx, "prt_render_pixel_list")
+}
+
+int prt_trace_rays_device(prt_ctx * ctx, int mode, const prt_ray_batch * batch, const prt_hit_buffers * hits, uint32_t flags,
+                          prt_counters * counters) {
+    PRT_API_TRY
+    const int chk = query_check(ctx, mode, batch, counters);
+    if (chk) return chk > 0 ? 0 : chk;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    QueryArgs A;
+    memset(&A, 0, sizeof(A));
+    A.origins = batch->origins; A.dirs = batch->directions; A.tmax = mode == PRT_QUERY_OCCLUDED ? batch->tmax : nullptr;
+    A.count = batch->count; A.ray_bias = batch->ray_bias;
+    if (hits) {
+        A.t = hits->t; A.bw = hits->bw; A.vertex0 = hits->vertex0; A.group = hits->group;
+        A.position = hits->position; A.normal = hits->normal; A.occluded = hits->occluded;
+    }
+    A.pad_max = -1.0f;                                     // the origins' extent is reduced on the device (k_query_pad)
+    return run_query(ctx, mode, A, query_fields(mode, hits), (flags & PRT_FLAG_COUNT_VISITS) != 0, counters);
+    PRT_API_CATCH_RC(ctx, "prt_trace_rays_device")
+}
+
+int prt_trace_rays(prt_ctx * ctx, int mode, const prt_ray_batch * batch, const prt_hit_buffers * hits, uint32_t flags,
+                   prt_counters * counters) {
+    PRT_API_TRY
+    const int chk = query_check(ctx, mode, batch, counters);
+    if (chk) return chk > 0 ? 0 : chk;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t n = batch->count;
+    const bool occ = mode == PRT_QUERY_OCCLUDED;
+    const unsigned int fields = query_fields(mode, hits);
+    // device copies: origins, directions, tmax, then the requested fields (float-sized words; occluded in its own bytes)
+    const bool has_tmax = occ && batch->tmax;
+    const size_t f_in = 6 * n + (has_tmax ? n : 0);
+    const size_t f_out = ((fields & QF_T) ? n : 0) + ((fields & QF_BW) ? 3 * n : 0) + ((fields & QF_VERTEX0) ? n : 0) +
+                         ((fields & QF_GROUP) ? n : 0) + ((fields & QF_POSITION) ? 3 * n : 0) + ((fields & QF_NORMAL) ? 3 * n : 0);
+    HIP_TRY(ctx, ctx->q_io.ensure(f_in + f_out));
+    if (fields & QF_OCCLUDED) HIP_TRY(ctx, ctx->q_occ.ensure(n));
+    float * p = ctx->q_io.p;
+    QueryArgs A;
+    memset(&A, 0, sizeof(A));
+    A.origins = p; p += 3 * n;
+    A.dirs = p; p += 3 * n;
+    if (has_tmax) { A.tmax = p; p += n; }
+    if (fields & QF_T) { A.t = p; p += n; }
+    if (fields & QF_BW) { A.bw = p; p += 3 * n; }
+    if (fields & QF_VERTEX0) { A.vertex0 = reinterpret_cast<unsigned int *>(p); p += n; }
+    if (fields & QF_GROUP) { A.group = reinterpret_cast<int *>(p); p += n; }
+    if (fields & QF_POSITION) { A.position = p; p += 3 * n; }
+    if (fields & QF_NORMAL) { A.normal = p; p += 3 * n; }
+    if (fields & QF_OCCLUDED) A.occluded = ctx->q_occ.p;
+    A.count = batch->count; A.ray_bias = batch->ray_bias;
+    // the box pad from the origins' extent, on the host (the same rule as k_query_pad)
+    float extent = ctx->scene_abs_max;
+    for (size_t i = 0; i < n; ++i) {
+        const f3 o = ld3(batch->origins + 3 * i), d = ld3(batch->directions + 3 * i), ob = o + d * batch->ray_bias;
+        const bool ok = std::isfinite(o.x) && std::isfinite(o.y) && std::isfinite(o.z) && std::isfinite(d.x) && std::isfinite(d.y) &&
+                        std::isfinite(d.z) && std::isfinite(ob.x) && std::isfinite(ob.y) && std::isfinite(ob.z);
+        if (ok) extent = std::max(extent, std::max(std::max(fabsf(ob.x), fabsf(ob.y)), fabsf(ob.z)));
+    }
+    A.pad_max = extent;
+    hipStream_t stream = ctx->stream;
+    HIP_TRY(ctx, hipMemcpyAsync(const_cast<float *>(A.origins), batch->origins, 12 * n, hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, hipMemcpyAsync(const_cast<float *>(A.dirs), batch->directions, 12 * n, hipMemcpyHostToDevice, stream));
+    if (has_tmax) HIP_TRY(ctx, hipMemcpyAsync(const_cast<float *>(A.tmax), batch->tmax, 4 * n, hipMemcpyHostToDevice, stream));
+    int rc = run_query(ctx, mode, A, fields, (flags & PRT_FLAG_COUNT_VISITS) != 0, counters);
+    if (rc) return rc;
+    if (fields & QF_T) HIP_TRY(ctx, hipMemcpyAsync(hits->t, A.t, 4 * n, hipMemcpyDeviceToHost, stream));
+    if (fields & QF_BW) HIP_TRY(ctx, hipMemcpyAsync(hits->bw, A.bw, 12 * n, hipMemcpyDeviceToHost, stream));
+    if (fields & QF_VERTEX0) HIP_TRY(ctx, hipMemcpyAsync(hits->vertex0, A.vertex0, 4 * n, hipMemcpyDeviceToHost, stream));
+    if (fields & QF_GROUP) HIP_TRY(ctx, hipMemcpyAsync(hits->group, A.group, 4 * n, hipMemcpyDeviceToHost, stream));
+    if (fields & QF_POSITION) HIP_TRY(ctx, hipMemcpyAsync(hits->position, A.position, 12 * n, hipMemcpyDeviceToHost, stream));
+    if (fields & QF_NORMAL) HIP_TRY(ctx, hipMemcpyAsync(hits->normal, A.normal, 12 * n, hipMemcpyDeviceToHost, stream));
+    if (fields & QF_OCCLUDED) HIP_TRY(ctx, hipMemcpyAsync(hits->occluded, A.occluded, n, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    return 0;
+    PRT_API_CATCH_RC(ctx, "prt_trace_rays")
 }
 
 int prt_debug_device_kat(prt_ctx * ctx, int kind, const void * in, size_t in_bytes, void * out, size_t out_bytes, uint32_t n,
