@@ -154,9 +154,9 @@ typedef struct prt_params {
  * POOL is not at least 3 % faster - worth it for many frames of one configuration, not for a single one.  Adaptive
  * sampling always runs on POOL.  All pipelines produce the same image (tests/test_gpu_parity.py); prt_counters.pipeline
  * reports which ran. */
-/* The shipped library has the two production pipelines, WAVEFRONT and POOL.  MEGAKERNEL (round 1's first version, which keeps
- * the reference's float association exactly) and PERSISTENT (a measured negative result) exist only in a library built with
- * -DPRT_EXPERIMENTAL (make hip-experimental); elsewhere asking for them is an error. */
+/* The library has two pipelines, WAVEFRONT and POOL.  MEGAKERNEL (1: round 1's first version, which kept the reference's float
+ * association exactly) and PERSISTENT (3: a measured negative result) are reserved values of removed pipelines: asking for
+ * them is an error. */
 enum { PRT_PIPELINE_DEFAULT = 0, PRT_PIPELINE_MEGAKERNEL = 1, PRT_PIPELINE_WAVEFRONT = 2, PRT_PIPELINE_PERSISTENT = 3,
        PRT_PIPELINE_POOL = 4, PRT_PIPELINE_MASK = 0xFF };
 /* OR-ed into prt_params.pipeline: also count BVH node visits and triangle tests (costs a few percent;
@@ -199,8 +199,8 @@ int prt_abi_version(void);
  * Returns 0, or -1 (unknown name, value that does not parse, RESERVE_CUS after creation). */
 int prt_set_option(prt_ctx * ctx, const char * name, const char * value);
 
-/* How the library was built: PRT_BUILD_EXPERIMENTAL - the MEGAKERNEL / PERSISTENT pipelines are present;
- * PRT_BUILD_BVH4 - the 4-wide sorted BVH traversal (the default build; clear in a -DPRT_BVH8 library, which traverses the
+/* How the library was built: PRT_BUILD_EXPERIMENTAL - reserved, never set (it marked a library with the MEGAKERNEL /
+ * PERSISTENT pipelines); PRT_BUILD_BVH4 - the 4-wide sorted BVH traversal (the default build; clear in a -DPRT_BVH8 library, which traverses the
  * 8-wide compressed tree instead: same results). */
 enum { PRT_BUILD_EXPERIMENTAL = 1, PRT_BUILD_BVH4 = 2 };
 int prt_build_flags(void);

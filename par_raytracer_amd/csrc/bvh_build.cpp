@@ -510,7 +510,7 @@ void finish_bvh4q_impl(Builder & b, uint32_t n_tris, Bvh4Result * out) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// 8-wide, quantised, octant-ordered (layout: bvh_build.h Bvh8Result)
+// 8-wide, quantised, children sorted along an ordering axis (layout: bvh_build.h Bvh8Result)
 // ---------------------------------------------------------------------------------------------------------
 void finish_bvh8q_impl(Builder & b, uint32_t n_tris, Bvh8Result * out);
 void finish_bvh8q(Builder & b, uint32_t n_tris, Bvh8Result * out) {
@@ -521,14 +521,12 @@ void finish_bvh8q(Builder & b, uint32_t n_tris, Bvh8Result * out) {
 void finish_bvh8q_impl(Builder & b, uint32_t n_tris, Bvh8Result * out) {
     auto is_leaf = [&](uint32_t t) { return b.pool[t].left < 0; };
     enum : uint32_t { EMPTY = 0xFFFFFFFFu };
-    struct Wide8 { uint32_t slot[8]; uint32_t axis = 0; };  // TmpNode index per slot, EMPTY for none; (experiment) the ordering axis
+    struct Wide8 { uint32_t slot[8]; uint32_t axis = 0; };  // TmpNode index per slot, EMPTY for none; the ordering axis
 
-    // ---- collapse (below), then give every child a slot: slot s stands for the
-    // octant direction ((s & 1) ? +x : -x, (s & 2) ? +y : -y, (s & 4) ? +z : -z) as seen from the node's centre, and a ray
-    // whose direction signs are o = (dx < 0) | (dy < 0) << 1 | (dz < 0) << 2 visits the hit slots in ascending order of
-    // (s XOR o): the child on the side the ray comes from first, on every axis.  Children are matched to slots greedily by
-    // how far their centres lie in the slot's direction (Ylitie et al. 2017, section 3.2, solve it with an auction; the
-    // greedy matching is within a few per cent of it and this runs 150,000 times per upload).
+    // ---- collapse (below), then give every child a slot: children in ascending order of their centres along the node's
+    // ordering axis (by default the one on which the centres spread most); a ray takes the hit slots in ascending or descending
+    // order by the sign of its direction on that axis (dev_trace8.h).  (The slot-per-octant order of Ylitie et al. 2017,
+    // section 3.2, measured 1.7 % more node visits: profiles/r03_ab_bvh8.txt.)
     // The collapse itself is the small dynamic programme of Ylitie et al. (section 3.1) over the binary tree, leaves fixed:
     //   F(m, k) = least total area of wide nodes below binary node m if m may occupy up to k slots of its parent
     //   F(m, 1) = area(m) + min over i of F(left, i) + F(right, 8 - i)          (m becomes a wide node; 0 for a leaf)
@@ -605,81 +603,47 @@ void finish_bvh8q_impl(Builder & b, uint32_t n_tris, Bvh8Result * out) {
                 kids[n++] = (uint32_t)b.pool[t].right;
             }
         }
-        Box u;
-        u.reset();
-        for (uint32_t k = 0; k < n; ++k) u.grow(b.pool[kids[k]].box);
-        float cost[8][8];
-        for (uint32_t k = 0; k < n; ++k) {
-            const Box & cb = b.pool[kids[k]].box;
-            float rel[3];
-            for (int a = 0; a < 3; ++a) rel[a] = (0.5f * cb.lo[a] + 0.5f * cb.hi[a]) - (0.5f * u.lo[a] + 0.5f * u.hi[a]);
-            for (uint32_t s = 0; s < 8; ++s)
-                cost[k][s] = ((s & 1u) ? rel[0] : -rel[0]) + ((s & 2u) ? rel[1] : -rel[1]) + ((s & 4u) ? rel[2] : -rel[2]);
-        }
         Wide8 w;
         for (uint32_t s = 0; s < 8; ++s) w.slot[s] = EMPTY;
-        if (b.opt.slot_order == 1) {
-            // experiment: children in ascending order of their centres along the axis on which the centres spread most; a ray
-            // takes the hit slots in ascending or descending order by the sign of its direction on that axis (axis in w.axis)
-            float lo[3] = { FLT_MAX, FLT_MAX, FLT_MAX }, hi[3] = { -FLT_MAX, -FLT_MAX, -FLT_MAX };
-            float c[8][3];
-            for (uint32_t k = 0; k < n; ++k)
-                for (int a = 0; a < 3; ++a) {
-                    c[k][a] = 0.5f * b.pool[kids[k]].box.lo[a] + 0.5f * b.pool[kids[k]].box.hi[a];
-                    lo[a] = std::min(lo[a], c[k][a]); hi[a] = std::max(hi[a], c[k][a]);
-                }
-            int axis = 0;
-            for (int a = 1; a < 3; ++a) if (hi[a] - lo[a] > hi[axis] - lo[axis]) axis = a;
-            if (b.opt.axis_rule == 1) {
-                // experiment: the longest axis of the node's box
-                Box u2; u2.reset();
-                for (uint32_t k = 0; k < n; ++k) u2.grow(b.pool[kids[k]].box);
-                axis = 0;
-                for (int a = 1; a < 3; ++a) if (u2.hi[a] - u2.lo[a] > u2.hi[axis] - u2.lo[axis]) axis = a;
-            } else if (b.opt.axis_rule == 2) {
-                // experiment: the axis along which the children's boxes, sorted by centre, overlap least (sum over all pairs of
-                // the overlap of their intervals, relative to the node's extent on that axis)
-                float best = FLT_MAX;
-                for (int a = 0; a < 3; ++a) {
-                    float ext = 0.0f, lo_a = FLT_MAX, hi_a = -FLT_MAX;
-                    for (uint32_t k = 0; k < n; ++k) { lo_a = std::min(lo_a, b.pool[kids[k]].box.lo[a]); hi_a = std::max(hi_a, b.pool[kids[k]].box.hi[a]); }
-                    ext = hi_a - lo_a;
-                    if (!(ext > 0.0f)) continue;
-                    float ov = 0.0f;
-                    for (uint32_t i = 0; i < n; ++i)
-                        for (uint32_t j = i + 1; j < n; ++j) {
-                            const Box & bi = b.pool[kids[i]].box, & bj = b.pool[kids[j]].box;
-                            const float o = std::min(bi.hi[a], bj.hi[a]) - std::max(bi.lo[a], bj.lo[a]);
-                            if (o > 0.0f) ov += o / ext;
-                        }
-                    if (ov < best) { best = ov; axis = a; }
-                }
+        float lo[3] = { FLT_MAX, FLT_MAX, FLT_MAX }, hi[3] = { -FLT_MAX, -FLT_MAX, -FLT_MAX };
+        float c[8][3];
+        for (uint32_t k = 0; k < n; ++k)
+            for (int a = 0; a < 3; ++a) {
+                c[k][a] = 0.5f * b.pool[kids[k]].box.lo[a] + 0.5f * b.pool[kids[k]].box.hi[a];
+                lo[a] = std::min(lo[a], c[k][a]); hi[a] = std::max(hi[a], c[k][a]);
             }
-            uint32_t order[8];
-            for (uint32_t k = 0; k < n; ++k) order[k] = k;
-            std::sort(order, order + n, [&](uint32_t x, uint32_t y) { return c[x][axis] < c[y][axis]; });
-            for (uint32_t k = 0; k < n; ++k) w.slot[k] = kids[order[k]];
-            w.axis = (uint32_t)axis;
-            return w;
+        int axis = 0;
+        for (int a = 1; a < 3; ++a) if (hi[a] - lo[a] > hi[axis] - lo[axis]) axis = a;
+        if (b.opt.axis_rule == 1) {
+            // experiment: the longest axis of the node's box
+            Box u2; u2.reset();
+            for (uint32_t k = 0; k < n; ++k) u2.grow(b.pool[kids[k]].box);
+            axis = 0;
+            for (int a = 1; a < 3; ++a) if (u2.hi[a] - u2.lo[a] > u2.hi[axis] - u2.lo[axis]) axis = a;
+        } else if (b.opt.axis_rule == 2) {
+            // experiment: the axis along which the children's boxes, sorted by centre, overlap least (sum over all pairs of
+            // the overlap of their intervals, relative to the node's extent on that axis)
+            float best = FLT_MAX;
+            for (int a = 0; a < 3; ++a) {
+                float ext = 0.0f, lo_a = FLT_MAX, hi_a = -FLT_MAX;
+                for (uint32_t k = 0; k < n; ++k) { lo_a = std::min(lo_a, b.pool[kids[k]].box.lo[a]); hi_a = std::max(hi_a, b.pool[kids[k]].box.hi[a]); }
+                ext = hi_a - lo_a;
+                if (!(ext > 0.0f)) continue;
+                float ov = 0.0f;
+                for (uint32_t i = 0; i < n; ++i)
+                    for (uint32_t j = i + 1; j < n; ++j) {
+                        const Box & bi = b.pool[kids[i]].box, & bj = b.pool[kids[j]].box;
+                        const float o = std::min(bi.hi[a], bj.hi[a]) - std::max(bi.lo[a], bj.lo[a]);
+                        if (o > 0.0f) ov += o / ext;
+                    }
+                if (ov < best) { best = ov; axis = a; }
+            }
         }
-        bool placed[8] = { false, false, false, false, false, false, false, false };
-        for (uint32_t round = 0; round < n; ++round) {
-            int bk = -1, bs = -1;
-            float bc = -FLT_MAX;
-            for (uint32_t k = 0; k < n; ++k) {
-                if (placed[k]) continue;
-                for (uint32_t s = 0; s < 8; ++s) {
-                    if (w.slot[s] != EMPTY) continue;
-                    if (cost[k][s] > bc) { bc = cost[k][s]; bk = (int)k; bs = (int)s; }
-                }
-            }
-            if (bk < 0) {                                   // NaN / inf boxes: any free slot will do
-                for (uint32_t k = 0; k < n && bk < 0; ++k) if (!placed[k]) bk = (int)k;
-                for (uint32_t s = 0; s < 8 && bs < 0; ++s) if (w.slot[s] == EMPTY) bs = (int)s;
-            }
-            placed[bk] = true;
-            w.slot[bs] = kids[bk];
-        }
+        uint32_t order[8];
+        for (uint32_t k = 0; k < n; ++k) order[k] = k;
+        std::sort(order, order + n, [&](uint32_t x, uint32_t y) { return c[x][axis] < c[y][axis]; });
+        for (uint32_t k = 0; k < n; ++k) w.slot[k] = kids[order[k]];
+        w.axis = (uint32_t)axis;
         return w;
     };
 

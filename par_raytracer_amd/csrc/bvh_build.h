@@ -44,15 +44,16 @@ void build_bvh4q_from_radix_tree(uint32_t n_tris, uint32_t leaf_max, const int32
                                  const uint32_t * sorted_ids, Bvh4Result * out, const BvhBuildOptions * opt = nullptr);
 
 // 8-wide compressed BVH: 80 B per node (5 x dwordx4), child boxes quantised to 8 bits per plane on the node's own
-// power-of-two grid, children assigned to slots so that (slot XOR ray octant) ascending is a front-to-back visiting order
-// (Ylitie, Karras, Laine 2017: no per-step sort), children addressed implicitly (internal children consecutive from
-// child_base, leaf triangles consecutive from tri_base, both in slot order).  Layout (dwords; dev_trace8.h reads it):
+// power-of-two grid, children in slot order sorted along the node's ordering axis, so that a ray visits them front to back in
+// ascending or descending slot order by its direction's sign on that axis (no per-step sort), children addressed implicitly
+// (internal children consecutive from child_base, leaf triangles consecutive from tri_base, both in slot order).  Layout
+// (dwords; dev_trace8.h reads it):
 //    0-2   origin xyz (float: lo corner of the union of the children)
 //    3     2^e_x as float bits (bits 23-30) | imask (bits 0-7: slot holds an internal node) | lmask << 8 (slot holds a leaf)
 //    4     child_base: node index of the first internal child
 //    5     tri_base: leaf-order index of the first triangle of the first leaf slot
 //    6     2^e_y as float bits | c0 (bits 0-7) | c1 << 8: a leaf slot holds 1 + c0 + 2 c1 triangles (1..4)
-//    7     2^e_z as float bits
+//    7     2^e_z as float bits | the ordering axis (bits 0-1)
 //    8-9   lo x of slots 0-3, 4-7 (one byte per slot)     10-11 lo y     12-13 lo z
 //    14-15 hi x                                            16-17 hi y     18-19 hi z
 // An empty slot has lo = 255 > hi = 0 on every axis and is in neither mask.

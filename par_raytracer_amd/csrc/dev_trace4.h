@@ -12,10 +12,8 @@ namespace prt {
 struct TravRay {
     f3 o, d;                          // origin ALREADY biased by direction * ray_bias (raytracer.cpp:163), direction
     float ix, iy, iz;                 // 1 / direction, components clamped away from 0
-    float pnx, pny, pnz;              // (o +- pad) / direction for the plane the ray ENTERS through on each axis
-#if defined(PRT_BVH4_SIX_PLANE_OFFSETS)
-    float pfx, pfy, pfz;              // ... and for the plane it LEAVES through (pad always widens the box)
-#endif                                // (default: the exit side's offset is the entry side's plus 2 pad |1 / d|, formed per step - three registers fewer)
+    float pnx, pny, pnz;              // (o +- pad) / direction for the plane the ray ENTERS through on each axis; the plane it
+                                      // leaves through is 2 pad |1 / direction| further on (pad always widens the box)
     HitRec best;
     int node, sp, kind;               // kind: TRACE_CLOSEST / TRACE_ANY
 };
@@ -128,11 +126,6 @@ PRT_D void trav_init(TravRay & r, f3 o, f3 d, int kind, float pad, const STK & s
     r.pnx = (dx < 0.0f ? o.x - pad : o.x + pad) * r.ix;
     r.pny = (dy < 0.0f ? o.y - pad : o.y + pad) * r.iy;
     r.pnz = (dz < 0.0f ? o.z - pad : o.z + pad) * r.iz;
-#if defined(PRT_BVH4_SIX_PLANE_OFFSETS)
-    r.pfx = (dx < 0.0f ? o.x + pad : o.x - pad) * r.ix;
-    r.pfy = (dy < 0.0f ? o.y + pad : o.y - pad) * r.iy;
-    r.pfz = (dz < 0.0f ? o.z + pad : o.z - pad) * r.iz;
-#endif
     r.best.t = 3.402823466e+38f;
     r.best.v = r.best.w = 0.0f;
     r.best.tri = -1;
@@ -140,32 +133,6 @@ PRT_D void trav_init(TravRay & r, f3 o, f3 d, int kind, float pad, const STK & s
     stk.push(0, TRAV_SENTINEL);
     r.sp = 1;
     r.node = 0;
-}
-
-// A ray's traversal registers as dwords, and its stack column copied from another lane's: what a wave needs to take over a ray
-// another wave of its workgroup was tracing (kernels_pool.h: rays handed over at the end of a round).  Field k at dst[k * stride].
-#if defined(PRT_BVH4_SIX_PLANE_OFFSETS)
-#error "trav_save_regs / trav_restore_regs cover the default ray state (three plane offsets)"
-#endif
-enum { TRAV_STATE_DWORDS = 19 };
-PRT_D void trav_save_regs(const TravRay & r, float * dst, unsigned int stride) {
-    const float f[TRAV_STATE_DWORDS] = { r.o.x, r.o.y, r.o.z, r.d.x, r.d.y, r.d.z, r.ix, r.iy, r.iz, r.pnx, r.pny, r.pnz,
-                                         r.best.t, r.best.v, r.best.w, as_f(r.best.tri), as_f(r.node), as_f(r.sp), as_f(r.kind) };
-#pragma unroll
-    for (int k = 0; k < TRAV_STATE_DWORDS; ++k) dst[(size_t)k * stride] = f[k];
-}
-PRT_D void trav_restore_regs(TravRay & r, const float * src, unsigned int stride) {
-    float f[TRAV_STATE_DWORDS];
-#pragma unroll
-    for (int k = 0; k < TRAV_STATE_DWORDS; ++k) f[k] = src[(size_t)k * stride];
-    r.o = mk3(f[0], f[1], f[2]); r.d = mk3(f[3], f[4], f[5]);
-    r.ix = f[6]; r.iy = f[7]; r.iz = f[8]; r.pnx = f[9]; r.pny = f[10]; r.pnz = f[11];
-    r.best.t = f[12]; r.best.v = f[13]; r.best.w = f[14]; r.best.tri = as_i(f[15]);
-    r.node = as_i(f[16]); r.sp = as_i(f[17]); r.kind = as_i(f[18]);
-}
-template <class STK>
-PRT_D void trav_copy_stack(const STK & dst, const STK & src, int sp) {
-    for (int e = 0; e < sp; ++e) dst.push(e, src.pop(e));
 }
 
 PRT_D void cswap(float & ka, float & kb, int & la, int & lb) {
@@ -180,39 +147,14 @@ PRT_D void cswap(float & ka, float & kb, int & la, int & lb) {
 //   plane = origin + q * 2^e  =>  t = (plane - o -+ pad) / d = q * (2^e / d) + (origin / d - (o +- pad) / d)
 // so after 3 scale products and 6 FMAs per node every plane costs one byte->float convert and one FMA.
 // The slab test may use FMA: it only has to be conservative, and the boxes are widened by `pad`.
-// Experiment PRT_TOP_LDS = n (round 4, the north star's "BVH nodes staged through LDS" on the production kernel): the first n
-// nodes of the breadth-first array - the top levels every ray walks - live in a workgroup LDS table `top` and a step at one of
-// them reads LDS instead of the vector L1.  Measured in profiles/r04_ab_top_levels_in_lds.txt; not in the shipped build.
-#if defined(PRT_TOP_LDS)
-enum { TRAV_TOP_LDS_NODES = PRT_TOP_LDS };
-#else
-enum { TRAV_TOP_LDS_NODES = 0 };
-#endif
-
+// (The top levels of the tree staged in LDS, round 4: no gain, profiles/r04_experiments.txt section 1.)
 template <class STK, bool COUNT>
-PRT_D void trav_node_step(const DevScene & sc, TravRay & r, const STK & stk, TraceStats & st, float pad, const uint4 * top = nullptr) {
+PRT_D void trav_node_step(const DevScene & sc, TravRay & r, const STK & stk, TraceStats & st, float pad) {
     // 32-bit byte offset from the (scalar) array base: the loads take the SGPR-base + VGPR-offset form and no 64-bit address is
     // built per lane (-0.7 % frame time; upload caps the scene at 2^26 triangles, so nodes * 64 and triangles * 48 fit)
     const uint4 * np = reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(sc.nodes) + ((unsigned int)r.node << 6));
-    uint4 w0, w1, w2, w3;
-    if (TRAV_TOP_LDS_NODES > 0 && top && r.node < (int)TRAV_TOP_LDS_NODES) {
-        const uint4 * tp = top + 4 * r.node;
-        w0 = tp[0]; w1 = tp[1]; w2 = tp[2]; w3 = tp[3];
-    } else {
-        w0 = np[0]; w1 = np[1]; w2 = np[2]; w3 = np[3];
-    }
+    const uint4 w0 = np[0], w1 = np[1], w2 = np[2], w3 = np[3];
     if (COUNT) { st.nodes++; if (first_active_lane()) st.wnodes++; if ((unsigned int)r.sp > st.max_sp) st.max_sp = (unsigned int)r.sp; }
-#ifdef PRT_PROBE_EXTRA_LOAD
-    // sensitivity probe (tools/ab_probe.sh): one more divergent vector-memory instruction per node step
-    { unsigned int e; asm volatile("global_load_dword %0, %1, off offset:32\n\ts_waitcnt vmcnt(0)" : "=v"(e) : "v"(np) : "memory"); }
-#endif
-#ifdef PRT_PROBE_EXTRA_VALU
-    // sensitivity probe: PRT_PROBE_EXTRA_VALU more vector ALU instructions per node step, on a value the step needs
-    { unsigned int x = w0.w;
-#pragma unroll
-      for (int i = 0; i < PRT_PROBE_EXTRA_VALU; ++i) asm volatile("v_mov_b32 %0, %0" : "+v"(x));
-      const_cast<uint4 &>(w0).w = x; }
-#endif
     const float kx = __uint_as_float(w0.w) * r.ix;
     const float ky = __uint_as_float(w3.z) * r.iy;
     const float kz = __uint_as_float(w3.w) * r.iz;
@@ -220,17 +162,11 @@ PRT_D void trav_node_step(const DevScene & sc, TravRay & r, const STK & stk, Tra
     // entry / exit parameter of the node origin on each axis; the ray's direction signs pick, per axis, which
     // quantised plane set (lo or hi bytes) is the entry side - no per-plane min/max, and an empty child slot
     // (lo = 255 > hi = 0 on every axis) can never satisfy entry <= exit.
-#if defined(PRT_BVH4_SIX_PLANE_OFFSETS)
-    const float cnx = __builtin_fmaf(ox, r.ix, -r.pnx), cfx = __builtin_fmaf(ox, r.ix, -r.pfx);
-    const float cny = __builtin_fmaf(oy, r.iy, -r.pny), cfy = __builtin_fmaf(oy, r.iy, -r.pfy);
-    const float cnz = __builtin_fmaf(oz, r.iz, -r.pnz), cfz = __builtin_fmaf(oz, r.iz, -r.pfz);
-#else
-    // (o -+ pad) / d on the exit side = the entry side's value + 2 pad |1 / d|: same six FMAs, three ray registers fewer
+    // (o -+ pad) / d on the exit side = the entry side's value + 2 pad |1 / d|: six FMAs, no exit-side registers in the ray
     const float pad2 = pad + pad;
     const float cnx = __builtin_fmaf(ox, r.ix, -r.pnx), cfx = __builtin_fmaf(pad2, fabsf(r.ix), cnx);
     const float cny = __builtin_fmaf(oy, r.iy, -r.pny), cfy = __builtin_fmaf(pad2, fabsf(r.iy), cny);
     const float cnz = __builtin_fmaf(oz, r.iz, -r.pnz), cfz = __builtin_fmaf(pad2, fabsf(r.iz), cnz);
-#endif
     const bool sx = r.ix < 0.0f, sy = r.iy < 0.0f, sz = r.iz < 0.0f;
     const unsigned int qnx = sx ? w1.w : w1.x, qfx = sx ? w1.x : w1.w;
     const unsigned int qny = sy ? w2.x : w1.y, qfy = sy ? w1.y : w2.x;

@@ -10,8 +10,8 @@
 //   * no sort.  The builder stores a node's children in ascending order of their centres along the axis on which those centres
 //     spread most (2 bits per node); a ray visits the hit slots in ascending or descending slot order by the sign of its
 //     direction on that axis, so "which child next" is a find-first-bit on the 8-bit hit mask, not a 5-comparator network with
-//     30 selects.  (-DPRT_BVH8_OCTANT: the slot-per-octant order of Ylitie, Karras, Laine 2017, three conditional bit swaps
-//     per pick; measured 1.7 % more node visits and 0.9 % more triangle tests on the frame, profiles/r03_ab_bvh8.txt.)
+//     30 selects.  (The slot-per-octant order of Ylitie, Karras, Laine 2017 measured 1.7 % more node visits and 0.9 % more
+//     triangle tests on the frame, profiles/r03_ab_bvh8.txt.)
 //   * no links.  Internal children are consecutive from child_base and the triangles of the node's leaves consecutive from
 //     tri_base, both in slot order: a child's address is a base plus a population count, and the node is 5 dwordx4 loads
 //     for eight children where the 4-wide node is 4 loads for four;
@@ -31,14 +31,9 @@
 namespace prt {
 
 typedef int2 StackEntry;                 // (child_base, imask | unvisited hit slots << 8); the marker: (TRAV_SENTINEL | flags, 0)
+// Nodes are packed in the device array.  (One node per 128-byte cache line, so that no node straddles two lines - half of the
+// packed ones do - gained nothing: profiles/r03_ab_bvh8.txt item 7.)
 enum { STACK_ENTRY_INTS = 2, BVH_NODE_BYTES = 80, STACK_LDS_CAP_DEFAULT = 13 };
-// distance between nodes in the device array: 80 = packed.  (Experiment -DPRT_BVH8_STRIDE=128: one node per 128-byte cache line,
-// so that no node straddles two lines - half of the packed ones do; no gain: profiles/r03_ab_bvh8.txt item 7.)
-#ifndef PRT_BVH8_STRIDE
-#define PRT_BVH8_STRIDE 80
-#endif
-enum { BVH_NODE_STRIDE = PRT_BVH8_STRIDE };
-enum { TRAV_TOP_LDS_NODES = 0 };          // the top-levels-in-LDS experiment exists for the 4-wide tree only (dev_trace4.h)
 
 // Per-lane traversal registers.  A ray can be suspended and resumed at any step boundary.
 struct TravRay {
@@ -123,29 +118,6 @@ PRT_D bool trav_at_leaf(const TravRay & r) { return (r.tbits & 0xFFu) != 0u; }
 PRT_D bool trav_walking(const TravRay & r) { return (r.tbits & 0xFFu) == 0u && r.node >= 0; }    // wants a node step
 PRT_D bool trav_done(const TravRay & r) { return (r.tbits & 0xFFu) == 0u && r.node < 0; }
 
-// A ray's traversal registers as dwords, and its stack column copied from another lane's (dev_trace4.h has the commentary).
-enum { TRAV_STATE_DWORDS = 21 };
-PRT_D void trav_save_regs(const TravRay & r, float * dst, unsigned int stride) {
-    const float f[TRAV_STATE_DWORDS] = { r.o.x, r.o.y, r.o.z, r.d.x, r.d.y, r.d.z, r.ix, r.iy, r.iz, r.pnx, r.pny, r.pnz,
-                                         r.best.t, r.best.v, r.best.w, as_f(r.best.tri), as_f(r.node), as_f((int)r.tbase), as_f((int)r.tbits),
-                                         as_f(r.sp), as_f(r.kind) };
-#pragma unroll
-    for (int k = 0; k < TRAV_STATE_DWORDS; ++k) dst[(size_t)k * stride] = f[k];
-}
-PRT_D void trav_restore_regs(TravRay & r, const float * src, unsigned int stride) {
-    float f[TRAV_STATE_DWORDS];
-#pragma unroll
-    for (int k = 0; k < TRAV_STATE_DWORDS; ++k) f[k] = src[(size_t)k * stride];
-    r.o = mk3(f[0], f[1], f[2]); r.d = mk3(f[3], f[4], f[5]);
-    r.ix = f[6]; r.iy = f[7]; r.iz = f[8]; r.pnx = f[9]; r.pny = f[10]; r.pnz = f[11];
-    r.best.t = f[12]; r.best.v = f[13]; r.best.w = f[14]; r.best.tri = as_i(f[15]);
-    r.node = as_i(f[16]); r.tbase = (unsigned int)as_i(f[17]); r.tbits = (unsigned int)as_i(f[18]); r.sp = as_i(f[19]); r.kind = as_i(f[20]);
-}
-template <class STK>
-PRT_D void trav_copy_stack(const STK & dst, const STK & src, int sp) {
-    for (int e = 0; e < sp; ++e) dst.put(e, src.get(e));
-}
-
 // After a traversal ended: what its marker says.  0 for a ray that ended on an any-hit occluder (a found occluder is final
 // whatever happened before).
 template <class STK> PRT_D int trav_end_flags(const TravRay & r, const STK & stk) {
@@ -187,37 +159,17 @@ PRT_D void trav_init(TravRay & r, f3 o, f3 d, int kind, float pad, const STK & s
     r.tbits = 0u;
 }
 
-// Of the hit slots `rest` (non-zero), the one a ray of octant `oct` visits first: smallest (slot XOR oct).
-// Bit j of the mask moves to bit (j XOR oct) - three conditional swaps of neighbours, pairs, halves - and the lowest set bit wins.
-PRT_D unsigned int trav_pick_slot(unsigned int rest, unsigned int oct) {
-    unsigned int p = rest;
-    const unsigned int s1 = ((p & 0x55u) << 1) | ((p >> 1) & 0x55u);
-    p = (oct & 1u) ? s1 : p;
-    const unsigned int s2 = ((p & 0x33u) << 2) | ((p >> 2) & 0x33u);
-    p = (oct & 2u) ? s2 : p;
-    const unsigned int s4 = ((p & 0x0Fu) << 4) | ((p >> 4) & 0x0Fu);
-    p = (oct & 4u) ? s4 : p;
-    return (unsigned int)(__ffs((int)p) - 1) ^ oct;
-}
-
 // One 8-wide node: fetch 80 B, dequantise + slab-test eight child boxes, note the hit leaf slots for the leaf phase, descend
-// into the first hit internal child in octant order and leave the others, as one entry, on the stack - or, if no internal
+// into the first hit internal child in the ray's slot order and leave the others, as one entry, on the stack - or, if no internal
 // child was hit, take the next child from the entry on top of the stack.
 //   plane = origin + q * 2^e  =>  t = (plane - o -+ pad) / d = q * (2^e / d) + (origin / d - (o +- pad) / d)
 // The slab test may use FMA: it only has to be conservative, and the boxes are widened by `pad`.
 template <class STK, bool COUNT>
-PRT_D void trav_node_step(const DevScene & sc, TravRay & r, const STK & stk, TraceStats & st, float pad, const uint4 * /*top: dev_trace4.h's PRT_TOP_LDS experiment*/ = nullptr) {
+PRT_D void trav_node_step(const DevScene & sc, TravRay & r, const STK & stk, TraceStats & st, float pad) {
     // 32-bit byte offset from the (scalar) array base (upload caps the scene at 2^26 triangles)
-    const uint4 * np = reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(sc.nodes) + (unsigned int)r.node * (unsigned int)BVH_NODE_STRIDE);
+    const uint4 * np = reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(sc.nodes) + (unsigned int)r.node * (unsigned int)BVH_NODE_BYTES);
     const uint4 q0 = np[0], q1 = np[1], q2 = np[2], q3 = np[3], q4 = np[4];
     if (COUNT) { st.nodes++; if (first_active_lane()) st.wnodes++; if ((unsigned int)r.sp > st.max_sp) st.max_sp = (unsigned int)r.sp; }
-#if defined(PRT_PROBE_EXTRA_VALU) && defined(__HIP_DEVICE_COMPILE__)
-    // sensitivity probe (tools/ab_probe.sh): PRT_PROBE_EXTRA_VALU more vector ALU instructions per node step, on a value it needs
-    { unsigned int x = q0.w;
-#pragma unroll
-      for (int i = 0; i < PRT_PROBE_EXTRA_VALU; ++i) asm volatile("v_mov_b32 %0, %0" : "+v"(x));
-      const_cast<uint4 &>(q0).w = x; }
-#endif
     const float kx = __uint_as_float(q0.w & 0x7F800000u) * r.ix;
     const float ky = __uint_as_float(q1.z & 0x7F800000u) * r.iy;
     const float kz = __uint_as_float(q1.w & 0x7F800000u) * r.iz;
@@ -244,7 +196,7 @@ PRT_D void trav_node_step(const DevScene & sc, TravRay & r, const STK & stk, Tra
         const float fz = __builtin_fmaf((float)((qfz[h] >> (8 * k)) & 0xFFu), kz, cfz);
         const float tmin = fmaxf(fmaxf(fmaxf(nx, ny), nz), 0.0f);
         const float tmax = fminf(fminf(fminf(fx, fy), fz), r.best.t);
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(PRT_BVH8_NO_ADDC)
+#if defined(__HIP_DEVICE_COMPILE__)
         // m = 2 m + (tmin <= tmax): the compare's lane mask goes straight into an add-with-carry, one instruction per child
         // where a select and an or would be two
         asm("v_cmp_le_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(m) : "v"(tmin), "v"(tmax) : "vcc");
@@ -258,11 +210,7 @@ PRT_D void trav_node_step(const DevScene & sc, TravRay & r, const STK & stk, Tra
     r.tbits = (m & ~imask) | (q0.w & 0xFF00u) | (q1.z << 16);
     // the next node: from this node's hit internal children, else from the group on top of the stack
     const unsigned int mi = m & imask;
-#if defined(PRT_BVH8_OCTANT)
-    unsigned int gbase = q1.x, gbits = imask | mi << 8;
-#else
     unsigned int gbase = q1.x, gbits = imask | mi << 8 | (q1.w & 3u) << 16;
-#endif
     int at = r.sp;                                      // where the group's remainder goes: a new entry, or back where it came from
     if (mi == 0u) {
         if (COUNT && r.best.tri >= 0 && (m & ~imask) == 0u) st.culled++;
@@ -276,15 +224,11 @@ PRT_D void trav_node_step(const DevScene & sc, TravRay & r, const STK & stk, Tra
         gbase = (unsigned int)e.x;
         gbits = (unsigned int)e.y;
     }
-#if defined(PRT_BVH8_OCTANT)
-    const unsigned int s = trav_pick_slot(gbits >> 8, ((unsigned int)r.kind >> 4) & 7u);
-#else
     // the slots of a node are sorted along its ordering axis (bits 16-17 of the group word): a ray takes the hit ones in
     // ascending or descending slot order by its direction sign on that axis
     const unsigned int rest8 = (gbits >> 8) & 0xFFu;
     const bool backwards = (((unsigned int)r.kind >> 4) >> ((gbits >> 16) & 3u)) & 1u;
     const unsigned int s = backwards ? 31u - (unsigned int)__clz((int)rest8) : (unsigned int)(__ffs((int)rest8) - 1);
-#endif
     r.node = (int)(gbase + (unsigned int)__popc(gbits & ((1u << s) - 1u) & 0xFFu));
     gbits &= ~(0x100u << s);
     if ((gbits >> 8) & 0xFFu) {

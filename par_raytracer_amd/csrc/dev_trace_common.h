@@ -1,6 +1,6 @@
 // dev_trace_common.h - TraceRay for the device, the parts every traversal shares: hit record, counters, the reference's
 // triangle test.  (The traversal itself: dev_trace4.h - 4-wide BVH, children sorted per step - or dev_trace8.h - 8-wide,
-// octant-ordered; dev_trace.h picks one.)
+// children ordered along one axis per node; dev_trace.h picks one.)
 //
 // Replaces TraceRay / IntersectRaySphere / IntersectRayMesh / IntersectRayTriangle
 // (raytracer.cpp:32-60, 82-232).  What must be preserved is the RESULT of the reference's traversal:

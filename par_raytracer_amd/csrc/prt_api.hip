@@ -25,18 +25,7 @@
 #include "dev_scene.h"
 #include "kernels_wave.h"
 #include "kernels_pool.h"
-#if defined(PRT_FLOW_EXPERIMENT)
-// round 4's round-free experiment (three tracer waves + one shading wave per workgroup): correct, and slower than the round-based
-// kernel because one shading wave per workgroup cannot keep up (profiles/r04_flow_kernel.txt); not in the shipped library
-#include "kernels_flow.h"
-#endif
 #include "kernels_resolve.h"
-#if defined(PRT_EXPERIMENTAL)
-// the round-1 megakernel (the exact-association cross-check) and the persistent single-launch experiment: not in the
-// shipped library; `make hip-experimental` builds a library that has them (tests/test_gpu_parity.py uses it when it is there)
-#include "kernels_mega.h"
-#include "kernels_persist.h"
-#endif
 #include "bvh_lbvh.h"
 #include "kernels_debug.h"
 #include "kernels_query.h"
@@ -48,12 +37,6 @@ using namespace prt;
 #endif
 #ifndef PRT_POOL_SHARED_DEFAULT
 #define PRT_POOL_SHARED_DEFAULT 1 // block-shared pools (kernels_pool.h) for fixed-spp renders when the option POOL_SHARED is not set
-#endif
-#ifndef PRT_POOL_EXCHANGE_DEFAULT
-#define PRT_POOL_EXCHANGE_DEFAULT 0   // block-shared pools: rays a wave hands over at the end of a round when the option POOL_EXCHANGE is not set (0: none)
-#endif
-#ifndef PRT_POOL_FLOW_DEFAULT
-#define PRT_POOL_FLOW_DEFAULT 0   // the pool pipeline without rounds (kernels_flow.h) for fixed-spp renders when the option POOL_FLOW is not set
 #endif
 #ifndef PRT_POOL_BLOCK
 #define PRT_POOL_BLOCK 256        // threads per workgroup of the fixed-spp pool kernel (experiments: 320, 640 with block-shared pools)
@@ -181,11 +164,6 @@ struct prt_ctx {
     DevCounters * host_counters = nullptr;                            // pinned: the render's counters arrive here on the context's stream
     DevBuf<unsigned int> pool_fin;        // adaptive mode: per-wave lists of pixels to finalise
     DevBuf<PoolArgs> pool_args;           // k_pool's arguments (read per phase from memory, kernels_pool.h)
-#if defined(PRT_FLOW_EXPERIMENT)
-    DevBuf<FlowArgs> flow_args;           // k_flow's (kernels_flow.h)
-    DevBuf<unsigned int> flow_u32;        // ... its slot id rings and free-slot stacks
-#endif
-    DevBuf<float> pool_xchg;                // block-shared pools: the rays waves hand to each other at the end of a round (PoolBuffers::xchg)
     DevBuf<unsigned long long> wave_times;  // DEBUG_UTIL + counting render: (start, counter dry, exit) wall clock of every wave of the fast kernel
     unsigned int wave_times_n = 0;
     DevBuf<float4> adapt_f4;              // adaptive mode: scratch [max_spp][n] + running sums [n] + final colours [n]
@@ -283,48 +261,6 @@ struct PixelSet {
     uint32_t block_rows, rank, nranks;         // interleaved row blocks otherwise
     const unsigned int * d_pixel_list;         // explicit list (device pointer) or NULL
 };
-
-#if defined(PRT_EXPERIMENTAL)
-template <int MAXLEV, bool RING>
-void launch_mega(prt_ctx * ctx, bool count, unsigned int grid, size_t lds, const DevCamera & cam, const DevParams & P,
-                 unsigned int n_samples) {
-    constexpr int BLOCK = 256;
-    if (count)
-        hipLaunchKernelGGL((k_render_mega<BLOCK, MAXLEV, RING, true>), dim3(grid), dim3(BLOCK), lds, ctx->stream, ctx->scene, cam, P,
-                           n_samples, ctx->sample_rgb.p, ctx->counters.p, ctx->ring_ws.p);
-    else
-        hipLaunchKernelGGL((k_render_mega<BLOCK, MAXLEV, RING, false>), dim3(grid), dim3(BLOCK), lds, ctx->stream, ctx->scene, cam, P,
-                           n_samples, ctx->sample_rgb.p, ctx->counters.p, ctx->ring_ws.p);
-}
-
-template <int MAXLEV, bool RING>
-int launch_persistent(prt_ctx * ctx, bool count, size_t lds, const DevCamera & cam, const DevParams & P, unsigned int n_samples,
-                      int keep_min, int node_min, int blocks_cap) {
-    constexpr int BLOCK = 256;
-    int per_cu = 0;
-    hipError_t oe = count ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_render_persistent<BLOCK, MAXLEV, RING, true>, BLOCK, lds)
-                          : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_render_persistent<BLOCK, MAXLEV, RING, false>, BLOCK, lds);
-    if (oe != hipSuccess || per_cu < 1) per_cu = 2;
-    per_cu = std::min(per_cu, blocks_cap);
-    const unsigned int max_blocks = (unsigned int)per_cu * (unsigned int)ctx->cu_count;
-    const unsigned int grid = std::max(1u, std::min(max_blocks, (n_samples + BLOCK - 1) / BLOCK));
-    // samples reserved per head atomic: whole waves, 64..512, ~1/16 of a wave's fair share
-    unsigned int chunk = n_samples / (grid * (BLOCK / 64) * 16u);
-    chunk = std::max(64u, std::min(512u, (chunk / 64u) * 64u));
-    if (RING) {
-        hipError_t e = ctx->ring_ws.ensure((size_t)16 * grid * BLOCK);
-        if (e != hipSuccess) { ctx->error = std::string("ring workspace: ") + hipGetErrorString(e); return -10; }
-    }
-    if (count)
-        hipLaunchKernelGGL((k_render_persistent<BLOCK, MAXLEV, RING, true>), dim3(grid), dim3(BLOCK), lds, ctx->stream, ctx->scene, cam, P,
-                           n_samples, ctx->sample_rgb.p, ctx->counters.p, ctx->ring_ws.p, ctx->wf_counts.p, keep_min, node_min, chunk);
-    else
-        hipLaunchKernelGGL((k_render_persistent<BLOCK, MAXLEV, RING, false>), dim3(grid), dim3(BLOCK), lds, ctx->stream, ctx->scene, cam, P,
-                           n_samples, ctx->sample_rgb.p, ctx->counters.p, ctx->ring_ws.p, ctx->wf_counts.p, keep_min, node_min, chunk);
-    return 0;
-}
-
-#endif  // PRT_EXPERIMENTAL
 
 // The wavefront pipeline (kernels_wave.h): raygen, then rounds of {persistent trace, shade} until no ray is
 // left.  Queue sizes come back to the host once per round (8 bytes, pinned): they size the next launches, end
@@ -587,13 +523,7 @@ int launch_pool(prt_ctx * ctx, bool count, const DevCamera & cam, DevParams P, u
     // most 15 draws per sample, opaque untextured scene: RINGMEM = 0) - the full C4 frame 1.5 - 2 % faster, its 1/2 .. 1/16
     // shards 1.5 - 3.5 % -; OFF for the adaptive mode, whose short rounds lose 11 % to the four waves waiting for each other at
     // every phase boundary, and for deep bounce trees (C5: 886 -> 949 ms; that variant spills 59 dwords shared, 31 private).
-    // (the round-free kernel, kernels_flow.h, has its own workgroup-level structure; its follow-up launches use wave-private pools)
-#if defined(PRT_FLOW_EXPERIMENT)
-    const bool flow = !ADAPT && BLOCK == 256 && !exact_only && (opt.pool_flow >= 0 ? opt.pool_flow != 0 : PRT_POOL_FLOW_DEFAULT != 0);
-#else
-    const bool flow = false;
-#endif
-    const bool shared = !flow && !exact_only && (opt.pool_shared >= 0 ? opt.pool_shared != 0 : (PRT_POOL_SHARED_DEFAULT != 0 && !ADAPT && !TEX && RINGMEM == 0));
+    const bool shared = !exact_only && (opt.pool_shared >= 0 ? opt.pool_shared != 0 : (PRT_POOL_SHARED_DEFAULT != 0 && !ADAPT && !TEX && RINGMEM == 0));
     hipError_t oe = exact_only ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pool<BLOCK, WAVES, LDSTAB, RING, false, TEX, ADAPT, RINGMEM, true, false>, BLOCK, lds)
                   : shared     ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pool<BLOCK, WAVES, LDSTAB, RING, false, TEX, ADAPT, RINGMEM, false, true>, BLOCK, lds)
                   : count      ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pool<BLOCK, WAVES, LDSTAB, RING, true, TEX, ADAPT, RINGMEM, false, false>, BLOCK, lds)
@@ -710,15 +640,6 @@ int launch_pool(prt_ctx * ctx, bool count, const DevCamera & cam, DevParams P, u
     // guided top-ups: adaptive mode by default (a pixel is a chain of up to max_spp samples: the pixels started last are the frame's tail)
     Q.guided = (unsigned int)std::max(0ll, std::min(64ll, opt.pool_guided >= 0 ? opt.pool_guided : (ADAPT ? 16ll : 0ll)));
     Q.guided_min = (unsigned int)std::max(1ll, std::min(512ll, opt.pool_guided_min >= 0 ? opt.pool_guided_min : 8ll));
-    Q.xchg = nullptr; Q.xchg_max = 0;
-    {
-        const long long xm = opt.pool_exchange >= 0 ? opt.pool_exchange : PRT_POOL_EXCHANGE_DEFAULT;
-        if (shared && xm > 0 && PRT_POOL_EXCHANGE_BUILD) {
-            Q.xchg_max = (unsigned int)std::min<long long>(xm, POOL_XCHG_MAX);
-            HIP_TRY(ctx, ctx->pool_xchg.ensure((size_t)units * (BLOCK / 64) * POOL_XCHG_FIELDS * Q.xchg_max));
-            Q.xchg = ctx->pool_xchg.p;
-        }
-    }
     Q.topup_max = topup_max == 0xFFFFFFFFu ? topup_max : topup_max * (shared ? (unsigned int)(BLOCK / 64) : 1u);
     Q.topup_min = ADAPT ? std::max(64u, cap / 2u) : std::max(64u, cap / 4u);
     if (opt.pool_topup >= 0) Q.topup_min = (unsigned int)std::max(1ll, std::min((long long)cap, opt.pool_topup * (shared ? BLOCK / 64 : 1)));   // the option counts per wave
@@ -739,62 +660,6 @@ int launch_pool(prt_ctx * ctx, bool count, const DevCamera & cam, DevParams P, u
     if (opt.node_frac >= 0) A.node_frac = std::max(0, std::min(8, (int)opt.node_frac));
     A.multi_light = multi_light;
     HIP_TRY(ctx, ctx->pool_args.ensure(2));
-#if defined(PRT_FLOW_EXPERIMENT)
-    if constexpr (!ADAPT && BLOCK == 256) {
-        if (flow) {
-            // ---- no rounds (kernels_flow.h): three tracer waves and a shading wave per workgroup, ray slots and rings instead of lists.
-            // The follow-up launches are the pool kernel's (their PoolArgs `A` as built above, wave-private layout over the same buffers).
-            int fper_cu = 0;
-            hipError_t foe = count ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&fper_cu, k_flow<BLOCK, WAVES, RING, true, TEX, RINGMEM>, BLOCK, lds)
-                                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&fper_cu, k_flow<BLOCK, WAVES, RING, false, TEX, RINGMEM>, BLOCK, lds);
-            if (foe != hipSuccess || fper_cu < 1) fper_cu = 1;
-            fper_cu = std::min(fper_cu, 8);
-            if (opt.pool_blocks_per_cu >= 0) fper_cu = std::max(1, std::min(fper_cu, (int)opt.pool_blocks_per_cu));
-            const unsigned int fgrid = std::max(1u, std::min((unsigned int)fper_cu * (unsigned int)ctx->cu_count, (n_samples + BLOCK - 1) / BLOCK));
-            auto pow2 = [](unsigned int v) { unsigned int p = 64; while (p < v) p <<= 1; return p; };
-            // samples in flight per workgroup: what the block's waves would hold in their pools
-            unsigned int fcap = (n_samples / (fgrid * (BLOCK / 64)) / 2u + 63u) / 64u * 64u;
-            fcap = std::max(64u, std::min(512u, fcap));
-            if (opt.pool_cap >= 0) fcap = (unsigned int)std::max(64ll, std::min(4096ll, opt.pool_cap / 64 * 64));
-            const unsigned int slots = fcap * (BLOCK / 64);
-            const unsigned int rc = pow2(slots), rd = pow2(slots), rs = pow2(std::max(1024u, 2u * slots * n_lights));
-            HIP_TRY(ctx, ctx->pool_f4.ensure(std::max((size_t)units * (7u * (size_t)cap + 3u * (size_t)scap), (size_t)fgrid * (4u * (size_t)slots + 3u * (size_t)rs))));
-            HIP_TRY(ctx, ctx->flow_u32.ensure((size_t)fgrid * ((size_t)rc + 3u * rd + slots)));
-            HIP_TRY(ctx, ctx->flow_args.ensure(1));
-            // (pool_f4 may have moved: the wave-private layout of the follow-up launches again)
-            A.Q.cq = ctx->pool_f4.p;
-            A.Q.hits = A.Q.cq + (size_t)units * 6u * cap;
-            A.Q.sq = A.Q.hits + (size_t)units * cap;
-            FlowArgs FA;
-            memset(&FA, 0, sizeof(FA));
-            FA.pool = A;
-            FA.pool.Q.cq = ctx->pool_f4.p;                                   // [blocks][3][slots]
-            FA.pool.Q.hits = FA.pool.Q.cq + (size_t)fgrid * 3u * slots;      // [blocks][slots]
-            FA.pool.Q.sq = FA.pool.Q.hits + (size_t)fgrid * slots;           // [blocks][3][rs]
-            FA.F.crq = ctx->flow_u32.p;
-            FA.F.done = FA.F.crq + (size_t)fgrid * rc;
-            FA.F.freelist = FA.F.done + (size_t)fgrid * 3u * rd;
-            FA.F.slots = slots;
-            FA.F.rc_mask = rc - 1u; FA.F.rd_mask = rd - 1u; FA.F.rs_mask = rs - 1u;
-            FA.F.topup_min = 64u;
-            FA.F.topup_max = 256u;
-            if (opt.pool_topup >= 0) FA.F.topup_min = (unsigned int)std::max(1ll, std::min((long long)slots, opt.pool_topup));
-            FA.F.low_water = 3u * 64u;
-            FA.F.error = &ctx->counters.p->flow_error;
-            if (opt.debug_util) fprintf(stderr, "[prt] k_flow<%d,%d>: %d blocks per CU, %u workgroups, %u slots each, rings %u / %u / %u\n", BLOCK, WAVES, fper_cu, fgrid, slots, rc, rd, rs);
-            hipLaunchKernelGGL(k_flow_store_args, dim3(1), dim3(64), 0, ctx->stream, FA, A, ctx->flow_args.p, ctx->pool_args.p, ctx->wf_counts.p, 16u, ctx->wf_counts.p + 3);
-            HIP_TRY(ctx, hipGetLastError());
-            if (count) hipLaunchKernelGGL((k_flow<BLOCK, WAVES, RING, true, TEX, RINGMEM>), dim3(fgrid), dim3(BLOCK), lds, ctx->stream, ctx->flow_args.p, ctx->counters.p);
-            else hipLaunchKernelGGL((k_flow<BLOCK, WAVES, RING, false, TEX, RINGMEM>), dim3(fgrid), dim3(BLOCK), lds, ctx->stream, ctx->flow_args.p, ctx->counters.p);
-            HIP_TRY(ctx, hipGetLastError());
-            if (count) hipLaunchKernelGGL(k_pool_parked_shadows<true>, dim3(POOL_PARKED_SHADOW_BLOCKS), dim3(256), 0, ctx->stream, ctx->pool_args.p, ctx->counters.p);
-            else hipLaunchKernelGGL(k_pool_parked_shadows<false>, dim3(POOL_PARKED_SHADOW_BLOCKS), dim3(256), 0, ctx->stream, ctx->pool_args.p, ctx->counters.p);
-            HIP_TRY(ctx, hipGetLastError());
-            return count ? launch_pool_kernel<BLOCK, WAVES, LDSTAB, RING, true, TEX, ADAPT, RINGMEM, true>(ctx, grid2, lds, ctx->pool_args.p + 1)
-                         : launch_pool_kernel<BLOCK, WAVES, LDSTAB, RING, false, TEX, ADAPT, RINGMEM, true>(ctx, grid2, lds, ctx->pool_args.p + 1);
-        }
-    }
-#endif
     // the adopting launch's units are waves whatever the fast kernel's were: a quarter of a shared pool's slots each, in the
     // same buffers (grid2 <= grid, so its waves' lists fit where the blocks' lists lie)
     hipLaunchKernelGGL(k_pool_store_args, dim3(1), dim3(64), 0, ctx->stream, A, ctx->pool_args.p, ctx->wf_counts.p, 16u,
@@ -821,23 +686,18 @@ int launch_pool(prt_ctx * ctx, bool count, const DevCamera & cam, DevParams P, u
                  : launch_pool_kernel<BLOCK, WAVES, LDSTAB, RING, false, TEX, ADAPT, RINGMEM, true>(ctx, grid2, lds, ctx->pool_args.p + 1);
 }
 
-template <bool FIXED>
-void launch_resolve_t(hipStream_t stream, const void * samples, float4 * out, unsigned int n_px, unsigned int spp, ResolveMap map) {
+// The fixed-spp resolve: the samples are the wavefront / pool pipelines' fixed-point accumulators (dev_scene.h Accum)
+void launch_resolve(hipStream_t stream, const void * samples, float4 * out, unsigned int n_px, unsigned int spp, ResolveMap map) {
     const unsigned int grid2 = (unsigned int)(((unsigned long long)n_px * spp + 255ull) / 256ull);
     switch (spp) {
-        case 2: hipLaunchKernelGGL((k_resolve_pow2<2, FIXED>), dim3(grid2), dim3(256), 0, stream, samples, out, n_px, map); break;
-        case 4: hipLaunchKernelGGL((k_resolve_pow2<4, FIXED>), dim3(grid2), dim3(256), 0, stream, samples, out, n_px, map); break;
-        case 8: hipLaunchKernelGGL((k_resolve_pow2<8, FIXED>), dim3(grid2), dim3(256), 0, stream, samples, out, n_px, map); break;
-        case 16: hipLaunchKernelGGL((k_resolve_pow2<16, FIXED>), dim3(grid2), dim3(256), 0, stream, samples, out, n_px, map); break;
-        case 32: hipLaunchKernelGGL((k_resolve_pow2<32, FIXED>), dim3(grid2), dim3(256), 0, stream, samples, out, n_px, map); break;
-        case 64: hipLaunchKernelGGL((k_resolve_pow2<64, FIXED>), dim3(grid2), dim3(256), 0, stream, samples, out, n_px, map); break;
-        default: hipLaunchKernelGGL(k_resolve<FIXED>, dim3((n_px + 255) / 256), dim3(256), 0, stream, samples, out, n_px, spp, map);
+        case 2: hipLaunchKernelGGL((k_resolve_pow2<2, true>), dim3(grid2), dim3(256), 0, stream, samples, out, n_px, map); break;
+        case 4: hipLaunchKernelGGL((k_resolve_pow2<4, true>), dim3(grid2), dim3(256), 0, stream, samples, out, n_px, map); break;
+        case 8: hipLaunchKernelGGL((k_resolve_pow2<8, true>), dim3(grid2), dim3(256), 0, stream, samples, out, n_px, map); break;
+        case 16: hipLaunchKernelGGL((k_resolve_pow2<16, true>), dim3(grid2), dim3(256), 0, stream, samples, out, n_px, map); break;
+        case 32: hipLaunchKernelGGL((k_resolve_pow2<32, true>), dim3(grid2), dim3(256), 0, stream, samples, out, n_px, map); break;
+        case 64: hipLaunchKernelGGL((k_resolve_pow2<64, true>), dim3(grid2), dim3(256), 0, stream, samples, out, n_px, map); break;
+        default: hipLaunchKernelGGL(k_resolve<true>, dim3((n_px + 255) / 256), dim3(256), 0, stream, samples, out, n_px, spp, map);
     }
-}
-// fixed: the samples are the wavefront / pool pipelines' fixed-point accumulators (dev_scene.h Accum), else float4 colours
-void launch_resolve(hipStream_t stream, const void * samples, bool fixed, float4 * out, unsigned int n_px, unsigned int spp, ResolveMap map) {
-    if (fixed) launch_resolve_t<true>(stream, samples, out, n_px, spp, map);
-    else launch_resolve_t<false>(stream, samples, out, n_px, spp, map);
 }
 
 // GPU radix-tree build + host collapse / quantise.  verts: 9 floats per triangle.
@@ -977,9 +837,6 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
     // the compact 2-register RNG only covers opaque scenes with <= 15 draws per sample; textured scenes always take the
     // general variant (an alpha map can make any hit translucent)
     const bool ring = adaptive || ctx->any_translucent || ctx->textured || max_rng_draws(P.bounce_depth, P.reflection_samples, P.spec_samples) > 15;
-#if defined(PRT_EXPERIMENTAL)
-    const int levels = (int)P.bounce_depth + 1;
-#endif
 
     unsigned int pipeline = params->pipeline & PRT_PIPELINE_MASK;
     if (adaptive) {
@@ -1042,17 +899,12 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
             }
         }
     }
-    if (pipeline != PRT_PIPELINE_MEGAKERNEL && pipeline != PRT_PIPELINE_WAVEFRONT && pipeline != PRT_PIPELINE_PERSISTENT && pipeline != PRT_PIPELINE_POOL) { ctx->error = "prt_render: unknown pipeline"; return -1; }
-#if !defined(PRT_EXPERIMENTAL)
     if (pipeline == PRT_PIPELINE_MEGAKERNEL || pipeline == PRT_PIPELINE_PERSISTENT) {
-        ctx->error = "prt_render: the experimental pipelines (MEGAKERNEL, PERSISTENT) are not built into this library (make hip-experimental)";
+        // reserved values (include/prt.h): round 1's megakernel and the persistent single-launch pipeline, measured and removed
+        ctx->error = "prt_render: the experimental pipelines (MEGAKERNEL, PERSISTENT) are not built into this library";
         return -1;
     }
-#endif
-    if (ctx->textured && (pipeline == PRT_PIPELINE_MEGAKERNEL || pipeline == PRT_PIPELINE_PERSISTENT)) {
-        ctx->error = "prt_render: textured scenes run on PRT_PIPELINE_WAVEFRONT / PRT_PIPELINE_POOL (or DEFAULT) only";
-        return -1;
-    }
+    if (pipeline != PRT_PIPELINE_WAVEFRONT && pipeline != PRT_PIPELINE_POOL) { ctx->error = "prt_render: unknown pipeline"; return -1; }
 
     // The pool kernel always runs its general-RNG variant: with the draw ring in memory it fits 96 VGPRs with 29 dwords
     // spilled and runs 5 waves per SIMD, where the 2-register RNG variant spills 105 (measured: 14.7 vs 15.3 ms per C4 frame
@@ -1068,11 +920,10 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
     unsigned int pass_pixels = px.n_pixels;
     {
         const unsigned long long lv = std::max(1u, P.bounce_depth), fr4 = ctx->textured ? 7 : ring_eff ? 5 : 4, nl = std::max(1u, ctx->scene.light_count);
-        unsigned long long per_sample = 32 + (ring && pipeline != PRT_PIPELINE_PERSISTENT ? 128 : 0);
+        unsigned long long per_sample = 32 + (ring ? 128 : 0);
         if (pipeline == PRT_PIPELINE_WAVEFRONT) per_sample += (lv * fr4 + 7 + 3 * nl) * 16 + (ring ? 32 : 16) + 4 * (1 + nl);
         if (pipeline == PRT_PIPELINE_POOL) per_sample += lv * fr4 * 16 + 32;
         if (adaptive) per_sample += ((unsigned long long)P.max_spp + 2) * 16;
-        if (pipeline == PRT_PIPELINE_MEGAKERNEL && ctx->stack_bound > 24) per_sample += 4ull * ctx->stack_bound;
         // A pass ends with a drain (the waves run dry one by one), so fewer, larger passes are faster - C5: 8 passes 1,046 - 1,076
         // ms, 4 passes 1,002, 3 passes 977 - 992 (profiles/r02_c5_pass_size.txt) - and 288 GB are there to be used: up to 192 M
         // samples and 160 GB of workspace per pass, but no more than 80 % of what the device has free plus what this context
@@ -1100,9 +951,9 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
     }
     const size_t n_samples64 = (size_t)pass_pixels * unit_spp;              // work items of the largest pass
     if (n_samples64 > 0x7FFFFFFFull) { ctx->error = "prt_render: spp too large for one pixel per pass"; return -1; }
-    HIP_TRY(ctx, ctx->sample_rgb.ensure(2 * n_samples64));      // float4 colours (megakernel, persistent) or 32-byte fixed-point accumulators
+    HIP_TRY(ctx, ctx->sample_rgb.ensure(2 * n_samples64));      // 32-byte fixed-point accumulators
     HIP_TRY(ctx, ctx->counters.ensure(1));
-    if (ring && pipeline != PRT_PIPELINE_PERSISTENT) HIP_TRY(ctx, ctx->ring_ws.ensure(n_samples64 * 16));
+    if (ring) HIP_TRY(ctx, ctx->ring_ws.ensure(n_samples64 * 16));
 
     // Traversal stack: LDS column of up to STACK_LDS_CAP entries per lane (occupancy); the rest of the worst-case bound
     // - 3 pushes per 4-wide level are possible, nothing real comes close - lives in a per-lane global column behind it
@@ -1114,30 +965,14 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
     const size_t lds = stack_dwords(stack_entries, BLOCK) * sizeof(int);
     P.stack_lds_entries = stack_entries;
     P.stack_spill = nullptr;
-    P.stack_spill_stride = 0;
-
-
-    {
-        const unsigned int spill_entries = ctx->stack_bound > stack_entries ? ctx->stack_bound - stack_entries : 0;
-        // one spill column per lane that may need it: every sample lane (megakernel), every persistent lane (persistent);
-        // the pool and wavefront pipelines size theirs where they know their grids (launch_pool, chain_setup)
-        const size_t spill_lanes = pipeline == PRT_PIPELINE_MEGAKERNEL ? ((n_samples64 + BLOCK - 1) / BLOCK) * BLOCK
-                                 : pipeline == PRT_PIPELINE_PERSISTENT ? (size_t)8 * (size_t)ctx->cu_count * BLOCK
-                                                                       : 0;                      // wavefront: per chain, see chain_setup
-        if (spill_entries && spill_lanes) {
-            if (spill_lanes >= (1ull << 32)) { ctx->error = "prt_render: too many lanes for the stack spill area"; return -1; }
-            HIP_TRY(ctx, ctx->stack_spill.ensure(stack_dwords(spill_entries, spill_lanes)));
-            P.stack_spill = ctx->stack_spill.p;
-            P.stack_spill_stride = (unsigned int)spill_lanes;
-        }
-    }
+    P.stack_spill_stride = 0;     // the pool and wavefront pipelines size their spill columns where they know their grids (launch_pool, chain_setup)
 
     HIP_TRY(ctx, hipMemsetAsync(ctx->counters.p, 0, sizeof(DevCounters), stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev[0], stream));
     unsigned int launches = 0;
     unsigned long long host_ray_count = 0;
     float trace_ms_accum = 0.0f;
-    const bool single_launch = pipeline != PRT_PIPELINE_WAVEFRONT;
+    const bool single_launch = pipeline == PRT_PIPELINE_POOL;
     for (unsigned int p0 = 0; p0 < px.n_pixels; p0 += pass_pixels) {
         const unsigned int n_px = std::min(pass_pixels, px.n_pixels - p0);
         const unsigned int n_samples = n_px * unit_spp;
@@ -1145,27 +980,6 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
         P.local_base = p0;
         if (single_launch) HIP_TRY(ctx, hipEventRecord(ctx->ev[2], stream));
         int rc = 0;
-#if defined(PRT_EXPERIMENTAL)
-        if (pipeline == PRT_PIPELINE_MEGAKERNEL) {
-            const unsigned int grid = (n_samples + BLOCK - 1) / BLOCK;
-            if (!ring && levels <= 3) launch_mega<3, false>(ctx, count_visits, grid, lds, cam, P, n_samples);
-            else if (levels <= 9) launch_mega<9, true>(ctx, count_visits, grid, lds, cam, P, n_samples);
-            else launch_mega<17, true>(ctx, count_visits, grid, lds, cam, P, n_samples);
-            launches += 1;
-        } else if (pipeline == PRT_PIPELINE_PERSISTENT) {
-            HIP_TRY(ctx, ctx->wf_counts.ensure(16));
-            HIP_TRY(ctx, hipMemsetAsync(ctx->wf_counts.p, 0, 16, stream));
-            int keep_min = 40, node_min = 32;
-            if (opt.keep_min >= 0) keep_min = std::max(1, std::min(64, (int)opt.keep_min));
-            if (opt.node_min >= 0) node_min = std::max(0, std::min(64, (int)opt.node_min));
-            int blocks_cap = 8;
-            if (opt.trace_blocks_per_cu >= 0) blocks_cap = std::max(1, std::min(8, (int)opt.trace_blocks_per_cu));
-            if (!ring && levels <= 3) rc = launch_persistent<3, false>(ctx, count_visits, lds, cam, P, n_samples, keep_min, node_min, blocks_cap);
-            else if (levels <= 9) rc = launch_persistent<9, true>(ctx, count_visits, lds, cam, P, n_samples, keep_min, node_min, blocks_cap);
-            else rc = launch_persistent<17, true>(ctx, count_visits, lds, cam, P, n_samples, keep_min, node_min, blocks_cap);
-            launches += 1;
-        } else
-#endif
         if (pipeline == PRT_PIPELINE_POOL) {
             // 256-thread blocks, the Hammersley direction table in global memory (staging it in LDS measured 17.04 vs 17.15 ms:
             // nothing).  Small blocks retire - and let the blocks of the next frame's kernel in - at a finer grain: with two
@@ -1186,9 +1000,6 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
             else
                 rc = ctx->textured ? launch_pool<256, 4, false, true, true, false>(ctx, count_visits, cam, P, n_samples, stack_entries)
                    : !ring ? launch_pool<PRT_POOL_BLOCK, PRT_POOL_WAVES, false, true, false, false, 0>(ctx, count_visits, cam, P, n_samples, stack_entries)
-#if defined(PRT_DEEP_OPAQUE_VARIANT)
-                   : opaque ? launch_pool<PRT_POOL_BLOCK, PRT_DEEP_WAVES, false, true, false, false, 2>(ctx, count_visits, cam, P, n_samples, stack_entries)
-#endif
                            : launch_pool<PRT_POOL_BLOCK, PRT_DEEP_WAVES, false, true, false, false, 1>(ctx, count_visits, cam, P, n_samples, stack_entries);
             launches += 1;
         } else {
@@ -1210,7 +1021,7 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
             hipLaunchKernelGGL(k_resolve<false>, dim3((n_px + 255) / 256), dim3(256), 0, stream,
                                ctx->adapt_f4.p + ((size_t)P.max_spp + 1u) * n_samples, d_out, n_px, 1u, rmap);
         else
-            launch_resolve(stream, ctx->sample_rgb.p, pipeline == PRT_PIPELINE_WAVEFRONT || pipeline == PRT_PIPELINE_POOL, d_out, n_px, P.spp, rmap);
+            launch_resolve(stream, ctx->sample_rgb.p, d_out, n_px, P.spp, rmap);
         HIP_TRY(ctx, hipGetLastError());
         if (single_launch && (counters || !last_pass)) {
             // the next pass reuses ev[2] / ev[3] (and the workspace is stream ordered anyway): take this pass's time now
@@ -1239,12 +1050,6 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
         ctx->pool_spark_cap = std::max<size_t>(ctx->pool_spark_cap, (size_t)h.park_over[1] + (size_t)h.park_over[1] / 2);
         *park_overflow = true;
         return 0;
-    }
-    if (h.flow_error) {
-        char msg[160];
-        snprintf(msg, sizeof(msg), "prt_render: a wait inside a pool kernel exceeded its watchdog (code 0x%x): the frame is incomplete", h.flow_error);
-        ctx->error = msg;
-        return -5;
     }
     if (h.near_tie_unresolved) {
         // resolve_near_ties ran out of widenings (dev_trace8.h): some hit among near-coincident candidates was decided over an
@@ -1289,11 +1094,6 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
                             "the steps before the list ran dry: %.1f%% of lane slots hold a ray\n",
                     100.0 * (double)h.drain_node_steps / (double)h.wave_node_steps, 100.0 * (double)h.drain_node_step_rays / (64.0 * (double)h.drain_node_steps),
                     100.0 * ((double)h.wave_node_step_rays - (double)h.drain_node_step_rays) / (64.0 * ((double)h.wave_node_steps - (double)h.drain_node_steps)));
-        if (opt.debug_util && h.flow_cycles[1] && h.flow_cycles[5])
-            fprintf(stderr, "[prt] k_flow: tracer waves wait for rays %.1f%% of their time; the shading wave tops up %.1f%%, shades %.1f%%, waits %.1f%% of its time; %llu shade batches of %.1f hits\n",
-                    100.0 * (double)h.flow_cycles[0] / (double)h.flow_cycles[1], 100.0 * (double)h.flow_cycles[2] / (double)h.flow_cycles[5],
-                    100.0 * (double)h.flow_cycles[3] / (double)h.flow_cycles[5], 100.0 * (double)h.flow_cycles[4] / (double)h.flow_cycles[5],
-                    (unsigned long long)h.flow_cycles[6], h.flow_cycles[6] ? (double)h.flow_cycles[7] / (double)h.flow_cycles[6] : 0.0);
         if (opt.debug_util && h.phase_cycles[3])
             fprintf(stderr, "[prt] k_pool wave time by phase: top-up %.1f%%, trace %.1f%%, shade %.1f%% of the main loop\n",
                     100.0 * (double)h.phase_cycles[0] / (double)h.phase_cycles[3], 100.0 * (double)h.phase_cycles[1] / (double)h.phase_cycles[3],
@@ -1511,10 +1311,7 @@ extern "C" {
 int prt_abi_version(void) { return PRT_ABI_VERSION; }
 
 int prt_build_flags(void) {
-    int f = 0;
-#if defined(PRT_EXPERIMENTAL)
-    f |= PRT_BUILD_EXPERIMENTAL;
-#endif
+    int f = 0;                            // (PRT_BUILD_EXPERIMENTAL is never set: include/prt.h)
 #if !defined(PRT_BVH8)
     f |= PRT_BUILD_BVH4;
 #endif
@@ -1550,11 +1347,6 @@ prt_ctx * prt_create(int device_id) {
     memset(&ctx->info, 0, sizeof(ctx->info));
     memset(&ctx->last_stats, 0, sizeof(ctx->last_stats));
     prt_options_from_env(ctx->opt);       // the environment is read here and nowhere else
-#if defined(PRT_BVH8_OCTANT)
-    ctx->opt.bvh.slot_order = 0;          // the traversal of this build expects one slot per octant (dev_trace8.h)
-#else
-    ctx->opt.bvh.slot_order = 1;          // ... slots sorted along the node's ordering axis
-#endif
     // PRT_RESERVE_CUS=k (multi-GPU callers): the context's streams are created with a CU mask that leaves k compute units to
     // others - the RCCL gather of the previous frame must not wait for a wave slot while this context's persistent kernels
     // hold every one of theirs (bench.py sets it for N > 1 with frames in flight).  The persistent grids are sized for the
@@ -1616,11 +1408,7 @@ void prt_destroy(prt_ctx * ctx) {
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     ctx->nodes.release(); ctx->tris.release(); ctx->shade.release(); ctx->diffuse_dirs.release(); ctx->spec_dirs.release();
     ctx->tri_rank.release(); ctx->materials.release(); ctx->lights.release();
-    ctx->sample_rgb.release(); ctx->frame_out.release(); ctx->counters.release(); ctx->ring_ws.release(); ctx->pixel_list.release(); ctx->wf_counts.release(); ctx->stack_spill.release(); ctx->pool_f4.release(); ctx->pool_park.release(); ctx->pool_fin.release(); ctx->pool_args.release(); ctx->adapt_f4.release(); ctx->wave_times.release(); ctx->pool_xchg.release();
-#if defined(PRT_FLOW_EXPERIMENT)
-    ctx->flow_args.release(); ctx->flow_u32.release();
-#endif
-   
+    ctx->sample_rgb.release(); ctx->frame_out.release(); ctx->counters.release(); ctx->ring_ws.release(); ctx->pixel_list.release(); ctx->wf_counts.release(); ctx->stack_spill.release(); ctx->pool_f4.release(); ctx->pool_park.release(); ctx->pool_fin.release(); ctx->pool_args.release(); ctx->adapt_f4.release(); ctx->wave_times.release();
     ctx->textures.release(); ctx->texels.release(); ctx->srgb_lut.release(); ctx->tri_uv.release(); ctx->tri_tan.release();
     ctx->ref_spheres.release();
     ctx->q_leaf_map.release(); ctx->q_work.release(); ctx->q_slow.release(); ctx->q_exact_stack.release(); ctx->q_io.release(); ctx->q_occ.release();
@@ -1907,14 +1695,8 @@ int prt_upload_scene(prt_ctx * ctx, const prt_scene_desc * s) {
     std::vector<float4> ddirs(1024);
     for (uint32_t i = 0; i < 1024; ++i) ddirs[i] = diffuse_tangent_dir(i);
 
-#if defined(PRT_BVH8) && PRT_BVH8_STRIDE != 80
-    std::vector<float4> nodes4((size_t)bvh.node_count * (BVH_NODE_STRIDE / 16), make_float4(0, 0, 0, 0));
-    for (uint32_t ni = 0; ni < bvh.node_count; ++ni)
-        memcpy(reinterpret_cast<char *>(nodes4.data()) + (size_t)ni * BVH_NODE_STRIDE, &bvh.nodes[(size_t)ni * BVH8_NODE_DWORDS], BVH8_NODE_DWORDS * 4);
-#else
     std::vector<float4> nodes4(bvh.nodes.size() / 4);
     memcpy(nodes4.data(), bvh.nodes.data(), bvh.nodes.size() * sizeof(uint32_t));
-#endif
     ctx->stack_bound = bvh.stack_bound;
 
     HIP_TRY(ctx, ctx->nodes.upload(nodes4));
@@ -2350,11 +2132,6 @@ int prt_debug_check_bvh(const prt_scene_desc * s, uint64_t * out) {
         for (int c = 0; c < 3; ++c) memcpy(&verts[(size_t)t * 9 + 3 * c], s->positions + 3 * (size_t)s->idx_positions[3 * t + c], 12);
     PrtOptions opt;
     prt_options_from_env(opt);                  // the test-suite selects the collapse rule through the environment
-#if defined(PRT_BVH8_OCTANT)
-    opt.bvh.slot_order = 0;
-#else
-    opt.bvh.slot_order = 1;
-#endif
     BvhWide bvh;
     PRT_BUILD_WIDE(verts.data(), n_tris, BVH_LEAF_MAX, 4, &bvh, 1.0f, &opt.bvh);
     if (validate_bvh_links(bvh, n_tris)) return -9;          // what prt_upload_scene checks before it uploads a tree

@@ -33,22 +33,7 @@ def _render_fixture(gpu_renderer_factory, name, pipeline=0):
     return g, img, ctr
 
 
-ALL_PIPELINES = {"megakernel": 1, "wavefront": 2, "persistent": 3, "pool": 4}
-
-
-def _built_pipelines():
-    """The shipped library has the two production pipelines; a -DPRT_EXPERIMENTAL build (make hip-experimental, selected with
-    PRT_HIP_LIB=libprt_hip_experimental.so) also has round 1's megakernel - the exact-association cross-check - and the
-    persistent experiment, and then every test below runs on all four."""
-    from par_raytracer_amd import capi
-    try:
-        experimental = bool(capi.hip_lib().prt_build_flags() & capi.BUILD_EXPERIMENTAL)
-    except Exception:
-        experimental = False
-    return dict(ALL_PIPELINES) if experimental else {"wavefront": 2, "pool": 4}
-
-
-PIPELINES = _built_pipelines()
+PIPELINES = {"wavefront": 2, "pool": 4}
 
 
 @pytest.mark.parametrize("pipeline", sorted(PIPELINES))
@@ -185,12 +170,14 @@ def test_textured_scene_shards_passes_and_pipelines_agree(gpu_renderer_factory, 
 
 
 def test_textured_scene_is_refused_by_the_experimental_pipelines(gpu_renderer_factory):
+    from par_raytracer_amd import capi
     g = load_golden("gallery_160x120")
     r = gpu_renderer_factory(str(g["scene"]), 0)
-    cam, p = camera_and_params(g, ALL_PIPELINES["megakernel"])
-    # a library with the experimental pipelines refuses the scene; the shipped one refuses the pipeline
-    with pytest.raises(RuntimeError, match="textured scenes run on|not built into this library"):
-        r.render(cam, p, 16, 16)
+    # MEGAKERNEL (1) and PERSISTENT (3) are reserved values of removed pipelines: the library refuses them
+    for pipeline in (capi.PIPELINE_MEGAKERNEL, capi.PIPELINE_PERSISTENT):
+        cam, p = camera_and_params(g, pipeline)
+        with pytest.raises(RuntimeError, match="not built into this library"):
+            r.render(cam, p, 16, 16)
 
 
 @pytest.mark.parametrize("name", ["c2_cornell_128", "terrain64_d3"])

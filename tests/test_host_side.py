@@ -95,7 +95,7 @@ def test_error_paths_without_a_gpu_or_scene():
     assert lib.prt_multi_render(None, None, None, 1, 1, None, None) == -1
     lib.prt_multi_destroy(None)
     assert lib.prt_set_option(None, b"STACK_CAP", b"2") == -1
-    assert lib.prt_build_flags() & ~(capi.BUILD_EXPERIMENTAL | capi.BUILD_BVH4) == 0
+    assert lib.prt_build_flags() & ~capi.BUILD_BVH4 == 0
     # the two-deep form of the n-device handle
     assert lib.prt_multi_depth(None) == 0
     assert lib.prt_multi_submit(None, None, None, 1, 1, None, None) == -1

@@ -2,7 +2,7 @@
 one lane at a time (tests/trace_host_harness.cpp).  For thousands of rays over a scene with doubled and coplanar triangles the
 hit trace_ray() returns - through the BVH the library builds and, where hits are near-tied, through resolve_near_ties() - must be
 the hit of the reference's own sequential filter over every triangle in visit order (raytracer.cpp:104, 149, 208-220), bit for
-bit; any-hit rays must agree on occluded / unoccluded.  All three traversal flavours the sources can be built as."""
+bit; any-hit rays must agree on occluded / unoccluded.  Both traversal flavours the sources can be built as."""
 import os
 import subprocess
 
@@ -11,10 +11,10 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.mark.parametrize("flavour", ["bvh8", "bvh8_octant", "bvh4"])
+@pytest.mark.parametrize("flavour", ["bvh8", "bvh4"])
 def test_device_traversal_equals_the_references_filter_on_the_host(flavour, tmp_path):
     exe = str(tmp_path / ("trace_host_" + flavour))
-    flags = {"bvh4": [], "bvh8": ["-DPRT_BVH8"], "bvh8_octant": ["-DPRT_BVH8", "-DPRT_BVH8_OCTANT"]}[flavour]
+    flags = {"bvh4": [], "bvh8": ["-DPRT_BVH8"]}[flavour]
     cmd = ["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-pthread", "-I" + os.path.join(ROOT, "tests", "hip_shim"),
            "-I" + os.path.join(ROOT, "par_raytracer_amd", "csrc")] + flags + [
            os.path.join(ROOT, "tests", "trace_host_harness.cpp"), os.path.join(ROOT, "par_raytracer_amd", "csrc", "bvh_build.cpp"), "-o", exe]

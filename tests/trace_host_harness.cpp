@@ -2,7 +2,7 @@
 // tests/hip_shim and run one lane at a time against a brute-force restatement of the reference's hit filter.
 //
 // What it checks, with no GPU: that trace_ray() over the BVH the library builds (4-wide sorted by default; -DPRT_BVH8: 8-wide, slots sorted along one
-// axis, or one per octant with -DPRT_BVH8_OCTANT) returns, for every ray, exactly the hit the reference's sequential filter returns over ALL triangles
+// axis) returns, for every ray, exactly the hit the reference's sequential filter returns over ALL triangles
 // in visit order (raytracer.cpp:104, 149, 208-220) - t, barycentrics and triangle bit for bit, near ties included - and
 // that any-hit rays agree on occluded / not occluded.  Scene: a wavy height field plus floating, doubled and coplanar
 // triangles.  Built and run by tests/test_trace_host.py.
@@ -56,9 +56,6 @@ int main(int argc, char ** argv) {
 #else
     Bvh8Result bvh;
     BvhBuildOptions bopt;
-#if defined(PRT_BVH8_OCTANT)
-    bopt.slot_order = 0;
-#endif
     build_bvh8q(verts.data(), n_tris, 4, 2, &bvh, 1.0f, &bopt);
 #endif
     // device records, as prt_upload_scene lays them out

@@ -1,6 +1,6 @@
 // bvh_price.cpp - prices a BVH layout on the CPU before it is built into the kernels: node visits, triangle tests and stack
-// depth per ray for the 4-wide quantised BVH (sorted children, csrc/dev_trace.h) and the 8-wide octant-ordered one
-// (csrc/dev_trace8.h), on the same rays.  Host only; links csrc/bvh_build.cpp.
+// depth per ray for the 4-wide quantised BVH (sorted children, csrc/dev_trace4.h) and the 8-wide one with its children sorted
+// along one axis per node (csrc/dev_trace8.h), on the same rays.  Host only; links csrc/bvh_build.cpp.
 //
 //   g++ -O2 -std=c++17 -pthread -Ipar_raytracer_amd/csrc tools/bvh_price.cpp par_raytracer_amd/csrc/bvh_build.cpp -o /tmp/bvh_price
 //   python3 tools/bvh_price_scene.py terrain_1m /tmp/terrain.bin && /tmp/bvh_price /tmp/terrain.bin
@@ -112,83 +112,14 @@ static Hit trace4(const Bvh4Result & bvh, const Ray & r, Stats & st) {
     return best;
 }
 
-// ---- 8-wide: csrc/dev_trace8.h
-static Hit trace8(const Bvh8Result & bvh, const Ray & r, Stats & st, bool ordered) {
-    Hit best;
-    struct Group { uint32_t base, imask, rest; };
-    std::vector<Group> stack;
-    int64_t cur = 0;
-    const double inv[3] = { 1.0 / (std::fabs(r.d.x) < 1e-30 ? 1e-30 : r.d.x), 1.0 / (std::fabs(r.d.y) < 1e-30 ? 1e-30 : r.d.y), 1.0 / (std::fabs(r.d.z) < 1e-30 ? 1e-30 : r.d.z) };
-    const double o[3] = { r.o.x, r.o.y, r.o.z };
-    const uint32_t oct = ordered ? ((r.d.x < 0) | (r.d.y < 0) << 1 | (r.d.z < 0) << 2) : 0u;
-    auto pick = [&](uint32_t rest) {                       // the slot of `rest` with the smallest (slot XOR octant)
-        uint32_t bs = 0, bk = 99;
-        for (uint32_t s = 0; s < 8; ++s) if ((rest >> s & 1u) && (s ^ oct) < bk) { bk = s ^ oct; bs = s; }
-        return bs;
-    };
-    st.rays++;
-    for (;;) {
-        st.nodes++;
-        const uint32_t * d = &bvh.nodes[(size_t)cur * BVH8_NODE_DWORDS];
-        const double org[3] = { bits_f(d[0]), bits_f(d[1]), bits_f(d[2]) };
-        const double sc[3] = { bits_f(d[3] & 0x7F800000u), bits_f(d[6] & 0x7F800000u), bits_f(d[7] & 0x7F800000u) };
-        const uint32_t imask = d[3] & 0xFF, lmask = d[3] >> 8 & 0xFF, c0 = d[6] & 0xFF, c1 = d[6] >> 8 & 0xFF;
-        uint32_t m = 0;
-        for (uint32_t s = 0; s < 8; ++s) {
-            double tmin = 0.0, tmax = best.t;
-            bool empty = false;
-            for (int a = 0; a < 3; ++a) {
-                const uint32_t qlo = d[8 + 2 * a + (s >> 2)] >> (8 * (s & 3)) & 0xFF, qhi = d[14 + 2 * a + (s >> 2)] >> (8 * (s & 3)) & 0xFF;
-                if (qlo > qhi) { empty = true; break; }
-                double t0 = (org[a] + qlo * sc[a] - o[a]) * inv[a], t1 = (org[a] + qhi * sc[a] - o[a]) * inv[a];
-                if (t0 > t1) std::swap(t0, t1);
-                tmin = std::max(tmin, t0);
-                tmax = std::min(tmax, t1);
-            }
-            if (!empty && tmin <= tmax) m |= 1u << s;
-        }
-        // leaves of this node first, in slot order
-        uint32_t L = m & lmask;
-        while (L) {
-            const uint32_t s = (uint32_t)__builtin_ctz(L), below = (1u << s) - 1u;
-            L &= L - 1;
-            const uint32_t off = __builtin_popcount(lmask & below) + __builtin_popcount(c0 & below) + 2 * __builtin_popcount(c1 & below);
-            const uint32_t cnt = 1 + (c0 >> s & 1) + 2 * (c1 >> s & 1);
-            for (uint32_t i = 0; i < cnt; ++i) {
-                const uint32_t slot = d[5] + off + i;
-                if (slot >= bvh.tri_order.size()) continue;
-                st.tris++;
-                const double t = tri_hit(r, bvh.tri_order[slot]);
-                if (t >= 0 && t < best.t) { best.t = t; best.tri = (int)slot; if (r.any) return best; }
-            }
-        }
-        Group g{ d[4], imask, m & imask };
-        bool from_stack = false;
-        if (!g.rest) {
-            if (stack.empty()) break;
-            g = stack.back();
-            from_stack = true;
-        }
-        const uint32_t s = pick(g.rest);
-        cur = g.base + __builtin_popcount(g.imask & ((1u << s) - 1u));
-        g.rest &= ~(1u << s);
-        if (from_stack) { if (g.rest) stack.back() = g; else stack.pop_back(); }
-        else if (g.rest) stack.push_back(g);
-        st.max_sp = std::max<uint64_t>(st.max_sp, stack.size() + 1);
-    }
-    return best;
-}
-
-
-// ---- 8-wide, hit slots (leaves and internal children alike) visited in one order: mode 0 = (slot XOR octant) ascending,
-// mode 1 = entry distance ascending (what a per-step sort would give: the bound on what any ordering can do)
+// ---- 8-wide, hit slots (leaves and internal children alike) visited in one order: mode 1 = entry distance ascending (what a
+// per-step sort would give: the bound on what any ordering can do), mode 2 = slot order along the node's axis (csrc/dev_trace8.h)
 static Hit trace8u(const Bvh8Result & bvh, const Ray & r, Stats & st, int mode) {
     Hit best;
     struct Group { const uint32_t * d; uint32_t rest; double key[8]; };
     std::vector<Group> stack;
     const double inv[3] = { 1.0 / (std::fabs(r.d.x) < 1e-30 ? 1e-30 : r.d.x), 1.0 / (std::fabs(r.d.y) < 1e-30 ? 1e-30 : r.d.y), 1.0 / (std::fabs(r.d.z) < 1e-30 ? 1e-30 : r.d.z) };
     const double o[3] = { r.o.x, r.o.y, r.o.z };
-    const uint32_t oct = (r.d.x < 0) | (r.d.y < 0) << 1 | (r.d.z < 0) << 2;
     st.rays++;
     auto visit = [&](int64_t cur) {
         st.nodes++;
@@ -209,7 +140,7 @@ static Hit trace8u(const Bvh8Result & bvh, const Ray & r, Stats & st, int mode) 
                 tmin = std::max(tmin, t0);
                 tmax = std::min(tmax, t1);
             }
-            g.key[s] = mode == 1 ? tmin : mode == 2 ? ((&r.d.x)[d[7] & 3u] >= 0 ? (double)s : (double)(7 - s)) : (double)(s ^ oct);
+            g.key[s] = mode == 1 ? tmin : ((&r.d.x)[d[7] & 3u] >= 0 ? (double)s : (double)(7 - s));
             if (!empty && tmin <= tmax) g.rest |= 1u << s;
         }
         return g;
@@ -266,17 +197,13 @@ int main(int argc, char ** argv) {
     const int lattice = argc > 2 ? atoi(argv[2]) : 4;
 
     Bvh4Result b4;
-    Bvh8Result b8, b8a;
+    Bvh8Result b8;
     const uint32_t leaf_max = getenv("PRICE_LEAF_MAX") ? (uint32_t)atoi(getenv("PRICE_LEAF_MAX")) : 4u;
     build_bvh4q(g_verts.data(), n_tris, 4, 8, &b4);
-    BvhBuildOptions oct_opt;
-    oct_opt.slot_order = 0;
-    build_bvh8q(g_verts.data(), n_tris, leaf_max, 8, &b8, 1.0f, &oct_opt);
     BvhBuildOptions axis_opt;
-    axis_opt.slot_order = 1;
     if (getenv("PRICE_WIDTH")) axis_opt.width = atoi(getenv("PRICE_WIDTH"));
     if (getenv("PRICE_AXIS_RULE")) axis_opt.axis_rule = atoi(getenv("PRICE_AXIS_RULE"));
-    build_bvh8q(g_verts.data(), n_tris, leaf_max, 8, &b8a, 1.0f, &axis_opt);
+    build_bvh8q(g_verts.data(), n_tris, leaf_max, 8, &b8, 1.0f, &axis_opt);
 
     // camera (main.cpp:145-177)
     const int W = 1920, H = 1080;
@@ -285,17 +212,14 @@ int main(int argc, char ** argv) {
     const V3 right = norm(cross(fwd, V3{ 0, 1, 0 })), up = norm(cross(right, fwd));
     const V3 light = norm(V3{ 1, -1.5, 0.25 }) * -1.0;
 
-    Stats s4[3], s8[3], s8u[3], s8o[3], s8d[3], s8a[3];            // primary, shadow, bounce
+    Stats s4[3], s8d[3], s8a[3];            // primary, shadow, bounce
     uint64_t mismatches = 0;
     uint64_t rng = 0x9E3779B97F4A7C15ull;
     auto rnd = [&]() { rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17; return (double)(rng >> 11) / 9007199254740992.0; };
     auto trace_all = [&](const Ray & r, int cls) {
         const Hit h4 = trace4(b4, r, s4[cls]);
-        const Hit h8 = trace8(b8, r, s8[cls], true);
-        trace8(b8, r, s8u[cls], false);
-        trace8u(b8, r, s8o[cls], 0);
+        const Hit h8 = trace8u(b8, r, s8a[cls], 2);
         trace8u(b8, r, s8d[cls], 1);
-        trace8u(b8a, r, s8a[cls], 2);
         if (r.any ? (h4.tri < 0) != (h8.tri < 0) : (h4.tri < 0) != (h8.tri < 0) || (h4.tri >= 0 && std::fabs(h4.t - h8.t) > 1e-9 * std::max(1.0, h4.t))) mismatches++;
         return h8;
     };
@@ -327,28 +251,19 @@ int main(int argc, char ** argv) {
     for (int k = 0; k < 3; ++k) {
         printf("-- %s rays: %llu\n", cls[k], (unsigned long long)s4[k].rays);
         report("4-wide, sorted children (64 B)", s4[k], b4.node_count, 64, b4.max_depth);
-        report("8-wide, octant order (80 B)", s8[k], b8.node_count, 80, b8.max_depth);
-        report("8-wide, slot order (no octant)", s8u[k], b8.node_count, 80, b8.max_depth);
-        report("8-wide, one octant order, leaves too", s8o[k], b8.node_count, 80, b8.max_depth);
+        report("8-wide, one axis per node (80 B)", s8a[k], b8.node_count, 80, b8.max_depth);
         report("8-wide, sorted by entry distance", s8d[k], b8.node_count, 80, b8.max_depth);
-        report("8-wide, one axis per node", s8a[k], b8a.node_count, 80, b8a.max_depth);
     }
-    Stats t4, t8, t8u, t8o, t8d, t8a;
+    Stats t4, t8d, t8a;
     for (int k = 0; k < 3; ++k) {
         t4.rays += s4[k].rays; t4.nodes += s4[k].nodes; t4.tris += s4[k].tris; t4.max_sp = std::max(t4.max_sp, s4[k].max_sp);
-        t8.rays += s8[k].rays; t8.nodes += s8[k].nodes; t8.tris += s8[k].tris; t8.max_sp = std::max(t8.max_sp, s8[k].max_sp);
-        t8u.rays += s8u[k].rays; t8u.nodes += s8u[k].nodes; t8u.tris += s8u[k].tris; t8u.max_sp = std::max(t8u.max_sp, s8u[k].max_sp);
-        t8o.rays += s8o[k].rays; t8o.nodes += s8o[k].nodes; t8o.tris += s8o[k].tris; t8o.max_sp = std::max(t8o.max_sp, s8o[k].max_sp);
         t8a.rays += s8a[k].rays; t8a.nodes += s8a[k].nodes; t8a.tris += s8a[k].tris; t8a.max_sp = std::max(t8a.max_sp, s8a[k].max_sp);
         t8d.rays += s8d[k].rays; t8d.nodes += s8d[k].nodes; t8d.tris += s8d[k].tris; t8d.max_sp = std::max(t8d.max_sp, s8d[k].max_sp);
     }
     printf("-- all rays: %llu\n", (unsigned long long)t4.rays);
     report("4-wide, sorted children (64 B)", t4, b4.node_count, 64, b4.max_depth);
-    report("8-wide, octant order (80 B)", t8, b8.node_count, 80, b8.max_depth);
-    report("8-wide, slot order (no octant)", t8u, b8.node_count, 80, b8.max_depth);
-    report("8-wide, one octant order, leaves too", t8o, b8.node_count, 80, b8.max_depth);
+    report("8-wide, one axis per node (80 B)", t8a, b8.node_count, 80, b8.max_depth);
     report("8-wide, sorted by entry distance", t8d, b8.node_count, 80, b8.max_depth);
-    report("8-wide, one axis per node", t8a, b8a.node_count, 80, b8a.max_depth);
     printf("hit / miss or distance mismatches between the two trees: %llu\n", (unsigned long long)mismatches);
     return mismatches ? 1 : 0;
 }
