@@ -357,6 +357,46 @@ typedef struct prt_render_stats {
 } prt_render_stats;
 int prt_get_render_stats(const prt_ctx * ctx, prt_render_stats * stats);
 
+/* Where the pool pipeline's kernel (k_pool) spends its instructions: for every region of the kernel, how often a wave ran it
+ * and with how many active lanes, in the context's last render call made with PRT_FLAG_COUNT_VISITS (0 everywhere after any
+ * other render, and for the wavefront pipeline).  out[2 * r] = wave-level executions of region r, out[2 * r + 1] = lanes active
+ * in them, summed; the first min(n, 2 * PRT_REGION_COUNT) words are written.  Returns the number of words a full table has.
+ * tools/valu_budget.py joins the table with the kernel's static instruction counts per region. */
+enum {
+    PRT_REGION_ROUND = 0,            /* passes of a wave's main loop (top up, trace, shade) */
+    PRT_REGION_TOPUP,                /* top-ups that took samples from the counter */
+    PRT_REGION_TOPUP_PASS,           /* ... and the passes of their camera-ray loop (64 samples each) */
+    PRT_REGION_TRACE_OUTER,          /* trace phase: passes of the outer loop (refill test, then the walk) */
+    PRT_REGION_REFILL,               /* ... refill blocks; lanes = lanes that got a ray (wave_refills of prt_render_stats also counts
+                                      * the refills that found a block-shared list already handed out) */
+    PRT_REGION_WALK_PASS,            /* ... passes of the walk loop (a run of node steps, then a leaf or a finished ray) */
+    PRT_REGION_NODE_STEP,            /* = wave_node_steps; lanes = node_visits */
+    PRT_REGION_NODE_DESCEND,         /* node steps in which a lane descended into a child (it may push up to three others) */
+    PRT_REGION_NODE_POP,             /* node steps in which a lane hit no child and popped */
+    PRT_REGION_NODE_PUSH,            /* pushes of a node step, each counted once per wave (the 4-wide step has up to three) */
+    PRT_REGION_LEAF,                 /* = wave_leaf_visits */
+    PRT_REGION_TRI,                  /* = wave_tri_steps; lanes = tri_tests */
+    PRT_REGION_FINISH,               /* finish blocks: a ray's result is written */
+    PRT_REGION_PARK,                 /* ... of which: a ray is handed to the slow launches */
+    PRT_REGION_SHADE_PASS,           /* shade phase: passes of 64 list entries; lanes = entries shaded (hits and misses) */
+    PRT_REGION_SHADE_HIT,            /* ... the hit branch; lanes sum to shaded_hits */
+    PRT_REGION_SHADE_MISS,           /* ... the miss branch */
+    PRT_REGION_RADIANCE_STORE,       /* ... the sample's radiance record written back */
+    PRT_REGION_SHADOW_BLOCK,         /* ... the light block, per light */
+    PRT_REGION_SHADOW_EMIT,          /* ... light blocks that appended a shadow ray; lanes = shadow rays appended */
+    PRT_REGION_WALK_LOOP,            /* bounce walk: passes of its loop */
+    PRT_REGION_WALK_NEXT_CHILD,      /* ... step "next child" */
+    PRT_REGION_WALK_ENTER,           /* ... step "enter" */
+    PRT_REGION_WALK_RETURN_UP,       /* ... step "return up" */
+    PRT_REGION_FRAME_SAVE,           /* ... a parent frame parked in memory */
+    PRT_REGION_FRAME_LOAD,           /* ... and resumed */
+    PRT_REGION_WALK_CHILD_RAY,       /* after the walk: the surviving child's direction and throughput */
+    PRT_REGION_OUTPUTS,              /* RNG state written back; lanes = samples that go on */
+    PRT_REGION_WAVE,                 /* waves of the launch (kernel entry and exit) */
+    PRT_REGION_COUNT
+};
+int prt_get_region_stats(const prt_ctx * ctx, uint64_t * out, uint32_t n);
+
 /* Host-only self check of the acceleration structure prt_upload_scene builds (runs without a GPU; the
  * CPU test-suite calls it): every triangle inside every ancestor's de-quantised box, every triangle in
  * exactly one leaf, links in range.  out[6] = { violations, nodes, depth, stack bound, leaves, triangle refs }. */

@@ -243,6 +243,15 @@ class Renderer:
         self._check(self._lib.prt_get_render_stats(self._ctx, C.byref(st)), "prt_get_render_stats")
         return st
 
+    def region_stats(self) -> dict:
+        """k_pool's region table of the last render made with FLAG_COUNT_VISITS: {region: (wave-level executions, active lanes)}."""
+        n = 2 * len(capi.REGION_NAMES)
+        out = (C.c_uint64 * n)()
+        got = self._lib.prt_get_region_stats(self._ctx, out, n)
+        if got != n:
+            raise RuntimeError("prt_get_region_stats: the library has %d words, capi.REGION_NAMES %d" % (got, n))
+        return {name: (int(out[2 * k]), int(out[2 * k + 1])) for k, name in enumerate(capi.REGION_NAMES)}
+
     def render(self, cam: PrtCamera, params: PrtParams, width: int, height: int, start_idx: int = 0,
                end_idx: Optional[int] = None) -> Tuple[np.ndarray, PrtCounters]:
         if end_idx is None:

@@ -116,7 +116,12 @@ PRT_SYMBOLS = ["prt_create", "prt_destroy", "prt_last_error", "prt_abi_version",
                "prt_render_device", "prt_shard_rows", "prt_render_shard_device", "prt_render_shard", "prt_render_pixel_list", "prt_get_scene_info", "prt_get_render_stats", "prt_debug_check_bvh", "prt_debug_check_bvh_lbvh", "prt_debug_device_kat",
                "prt_multi_create", "prt_multi_destroy", "prt_multi_last_error", "prt_multi_device_count", "prt_multi_context",
                "prt_multi_upload_scene", "prt_multi_render", "prt_multi_depth", "prt_multi_submit", "prt_multi_wait", "prt_debug_throw",
-               "prt_trace_rays", "prt_trace_rays_device"]
+               "prt_trace_rays", "prt_trace_rays_device", "prt_get_region_stats"]
+# PRT_REGION_* of include/prt.h, in index order (tests/test_host_side.py's header check keeps the symbol list in step; the
+# region test compares this list with the header's enum)
+REGION_NAMES = ["round", "topup", "topup_pass", "trace_outer", "refill", "walk_pass", "node_step", "node_descend", "node_pop", "node_push", "leaf",
+                "tri", "finish", "park", "shade_pass", "shade_hit", "shade_miss", "radiance_store", "shadow_block", "shadow_emit", "walk_loop",
+                "walk_next_child", "walk_enter", "walk_return_up", "frame_save", "frame_load", "walk_child_ray", "outputs", "wave"]
 PRT_HOST_SYMBOLS = ["prt_host_load_obj", "prt_host_free_scene", "prt_host_scene_desc", "prt_host_scene_hierarchy_seconds",
                     "prt_host_scene_parse_seconds", "prt_host_last_error", "prt_host_make_camera",
                     "prt_host_default_params", "prt_host_render", "prt_host_render_error", "prt_host_write_image", "prt_host_tonemap",
@@ -168,6 +173,8 @@ def hip_lib() -> C.CDLL:
                                               C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(PrtCounters)]
         lib.prt_get_scene_info.argtypes = [C.c_void_p, C.POINTER(PrtSceneInfo)]
         lib.prt_get_render_stats.argtypes = [C.c_void_p, C.POINTER(PrtRenderStats)]
+        if hasattr(lib, "prt_get_region_stats"):       # (absent from a PRT_HIP_LIB build of an earlier commit, in an A/B run against it)
+            lib.prt_get_region_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32]
         lib.prt_debug_check_bvh.argtypes = [C.POINTER(PrtSceneDesc), C.POINTER(C.c_uint64)]
         lib.prt_debug_check_bvh_lbvh.argtypes = [C.c_void_p, C.POINTER(PrtSceneDesc), C.POINTER(C.c_uint64)]
         lib.prt_debug_device_kat.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32,

@@ -31,6 +31,7 @@
 //              transcendental ever feeds a direction); spec_dirs [material][spec_samples] likewise.
 #pragma once
 
+#include "../../include/prt.h"
 #include "dev_math.h"
 
 namespace prt {
@@ -191,6 +192,9 @@ struct DevCounters {          // device-side accumulators (atomics, one add per 
     // adaptive mode: stopping-rule verdicts whose variance lay within 0.1 % of the threshold (k_pool's finalise step): the only
     // verdicts the device's last bits could turn against the reference's
     unsigned long long variance_close_calls;
+    // k_pool, COUNT builds: (wave-level executions, active lanes) of every region of the kernel, by PRT_REGION_* of include/prt.h
+    // (the node step, leaf visit and triangle test rows are filled by the host from the counters above)
+    unsigned long long region[2 * PRT_REGION_COUNT];
 };
 
 // Per-sample radiance accumulator of the wavefront and pool pipelines: 2^-32 fixed point in 64-bit integers.  A sample's

@@ -193,12 +193,18 @@ PRT_D void trav_node_step(const DevScene & sc, TravRay & r, const STK & stk, Tra
     cswap(key[1], key[3], link[1], link[3]);
     cswap(key[1], key[2], link[1], link[2]);
     if (key[0] < inf) {
+        if (COUNT && first_active_lane()) st.wdescend++;
+        if (COUNT) {
+            const unsigned long long p3 = __ballot(key[3] < inf), p2 = __ballot(key[2] < inf), p1 = __ballot(key[1] < inf);
+            if (first_active_lane()) st.wpush += (unsigned int)(p3 != 0ull) + (unsigned int)(p2 != 0ull) + (unsigned int)(p1 != 0ull);
+        }
         if (key[3] < inf) trav_push(r, stk, link[3]);
         if (key[2] < inf) trav_push(r, stk, link[2]);
         if (key[1] < inf) trav_push(r, stk, link[1]);
         r.node = link[0];
     } else {
         if (COUNT && r.best.tri >= 0) st.culled++;
+        if (COUNT && first_active_lane()) st.wpop++;
         trav_pop(r, stk);
     }
 }

@@ -212,6 +212,11 @@ PRT_D void trav_node_step(const DevScene & sc, TravRay & r, const STK & stk, Tra
     const unsigned int mi = m & imask;
     unsigned int gbase = q1.x, gbits = imask | mi << 8 | (q1.w & 3u) << 16;
     int at = r.sp;                                      // where the group's remainder goes: a new entry, or back where it came from
+    if (COUNT) {
+        // wave-level steps with a lane that goes down into a child / that takes its next node from the stack
+        const unsigned long long down = __ballot(mi != 0u), all = __ballot(true);
+        if (first_active_lane()) { st.wdescend += down != 0ull; st.wpop += down != all; }
+    }
     if (mi == 0u) {
         if (COUNT && r.best.tri >= 0 && (m & ~imask) == 0u) st.culled++;
         at = r.sp - 1;
@@ -231,6 +236,10 @@ PRT_D void trav_node_step(const DevScene & sc, TravRay & r, const STK & stk, Tra
     const unsigned int s = backwards ? 31u - (unsigned int)__clz((int)rest8) : (unsigned int)(__ffs((int)rest8) - 1);
     r.node = (int)(gbase + (unsigned int)__popc(gbits & ((1u << s) - 1u) & 0xFFu));
     gbits &= ~(0x100u << s);
+    if (COUNT) {
+        const unsigned long long pushing = __ballot(((gbits >> 8) & 0xFFu) != 0u);
+        if (first_active_lane()) st.wpush += pushing != 0ull;
+    }
     if ((gbits >> 8) & 0xFFu) {
         if (stk.put(at, make_int2((int)gbase, (int)gbits))) r.sp = at + 1;
         else { stk.flag(TRAV_FLAG_OVERFLOW); r.sp = at; }

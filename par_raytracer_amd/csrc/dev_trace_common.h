@@ -40,11 +40,32 @@ struct TraceStats {
     unsigned int wnodes, wleaves, wtris, wrefills;   // counted by the first active lane only (wave-level steps)
     unsigned int wrays;                              // k_pool: lanes that held a ray, summed over the wave-level node steps
     unsigned int max_sp, culled;                     // deepest stack use; popped nodes whose entry distance was already beyond the hit
+    unsigned int wdescend = 0, wpop = 0, wpush = 0;  // wave-level node steps in which a lane went down into a child / took its next node from the stack; wave-level pushes
 };
 
 PRT_D bool first_active_lane() {
     const unsigned long long m = __ballot(true);
     return (int)(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u))) == (__ffsll((long long)m) - 1);
+}
+
+// k_pool, COUNT builds: how often each region of the kernel ran.  A region has two words in a workgroup's LDS table `rg`:
+// [2 * which] wave-level executions, [2 * which + 1] the lanes that were active in them.  Called from INSIDE the region (by
+// the lanes that run it).  `which` is a PRT_REGION_* of include/prt.h; the shipped kernels compile none of it.
+// (The table's pointer carries its address space: the adds are LDS atomics, not flat ones that test the address at run time.)
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef __attribute__((address_space(3))) unsigned int * RegionTable;
+#else
+typedef unsigned int * RegionTable;
+#endif
+template <bool COUNT>
+PRT_D void region_count(RegionTable rg, int which) {
+    if (COUNT) {
+        const unsigned long long m = __ballot(true);
+        if (first_active_lane()) {
+            __hip_atomic_fetch_add(rg + 2 * which, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_add(rg + 2 * which + 1, (unsigned int)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+    }
 }
 
 PRT_D float as_f(int v) { return __int_as_float(v); }

@@ -81,7 +81,7 @@ struct PoolBuffers {
 // Emitter of k_pool: appends to the unit's lists, slots by rank among the appending lanes.  Per-wave pools (SHARED = false):
 // the fill counts are wave-uniform registers.  Block-shared pools: they are LDS words that every wave of the block adds to -
 // one ds_add_rtn per wave and call, the lanes' slots follow from the returned base and the ballot rank as before.
-template <bool ADAPT, bool SHARED>
+template <bool ADAPT, bool SHARED, bool COUNT>
 struct PoolEmit {
     enum { KEEPS_RNG = ADAPT ? 1 : 0 };      // adaptive mode: the pixel's next sample continues the RNG stream of the one that ended
     float4 * co, * cd, * ct;     // next closest list
@@ -90,6 +90,8 @@ struct PoolEmit {
     unsigned int m_c, m_s, m_f;  // wave-uniform fill counts (SHARED: unused, the counts are s_cnt[0..2])
     unsigned int * s_cnt;        // SHARED: LDS, [0] closest [1] shadow [2] finalise entries of the lists being filled
     unsigned int m_elided;       // wave-uniform: shadow rays counted, not traced (their radiance-if-unoccluded is zero)
+    RegionTable rg;              // COUNT: the workgroup's region table (LDS), see region_count
+    PRT_D void region(int which) const { region_count<COUNT>(rg, which); }
     // first slot of this wave's `n` new entries of list `which` (0 closest, 1 shadow, 2 finalise); called wave-converged
     PRT_D unsigned int reserve(int which, unsigned int n) {
         if (SHARED) {
@@ -247,6 +249,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
     __shared__ DevLight s_lights[LDS_LIGHTS];
     __shared__ unsigned long long s_red[2];
     __shared__ unsigned int s_ctl[SHARED ? PCTL_WORDS : 1];
+    __shared__ unsigned int s_rg[COUNT ? 2 * PRT_REGION_COUNT : 1];      // COUNT: (executions, lanes) per region, see region_count
     {
         const PoolArgs A0 = pool_args(args);
         const DevScene & sc = A0.sc;
@@ -264,6 +267,8 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
     }
     if (threadIdx.x < 2) s_red[threadIdx.x] = 0ull;
     if (SHARED && threadIdx.x < (unsigned int)PCTL_WORDS) s_ctl[threadIdx.x] = 0u;
+    if (COUNT) for (unsigned int k = threadIdx.x; k < 2u * PRT_REGION_COUNT; k += BLOCK) s_rg[k] = 0u;
+    const RegionTable rg = (RegionTable)s_rg;
     __syncthreads();
 
     const unsigned int slot_id = blockIdx.x * BLOCK + threadIdx.x;
@@ -310,8 +315,10 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
     const unsigned long long ph_begin = COUNT ? __builtin_readcyclecounter() : 0ull;
     const unsigned long long wt_begin = COUNT ? wall_clock64() : 0ull;
     unsigned long long wt_dry = 0ull;
+    region_count<COUNT>(rg, PRT_REGION_WAVE);
     for (;;) {
         const unsigned long long ph_t0 = COUNT ? __builtin_readcyclecounter() : 0ull;
+        region_count<COUNT>(rg, PRT_REGION_ROUND);
         // ---- top up: fresh samples into the free closest-hit slots ------------------------------------------
         if (!fetch_done) {
           const PoolArgs A = pool_args(args);
@@ -403,7 +410,9 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
                 unsigned int cnt = B.n_samples - base;
                 if (cnt <= want) fetch_done = true; else cnt = want;
                 const DevCamera cam = A.cam;
+                region_count<COUNT>(rg, PRT_REGION_TOPUP);
                 for (unsigned int k = ulane; k < cnt; k += ULANES) {
+                    region_count<COUNT>(rg, PRT_REGION_TOPUP_PASS);
                     const unsigned int sid = base + k;
                     const unsigned int gsid = B.sample_base + sid;
                     SampleState S;
@@ -457,6 +466,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
             unsigned int next = 0;                                         // wave-uniform: rays handed out so far (SHARED: where this wave's last refill began)
             bool dry = total == 0u;                                        // wave-uniform: the list has no ray left to hand out
             for (;;) {
+                region_count<COUNT>(rg, PRT_REGION_TRACE_OUTER);
                 const unsigned long long idle = __ballot(ray < 0);
                 if (idle != 0ull && !dry) {
                     if (COUNT && lane == 0) st.wrefills++;
@@ -472,6 +482,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
                     const unsigned int avail = total - next;
                     const unsigned int take = n_idle < avail ? n_idle : avail;
                     if (ray < 0 && prefix < take) {
+                        region_count<COUNT>(rg, PRT_REGION_REFILL);
                         const unsigned int idx = next + prefix;
                         float4 ro, rd;
                         int kind;
@@ -506,6 +517,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
                 if (__ballot(ray >= 0) == 0ull) break;
 
                 while (ray >= 0) {
+                    region_count<COUNT>(rg, PRT_REGION_WALK_PASS);
                     const int walkers = __popcll(__ballot(trav_walking(r)));
                     const int wfrac = (walkers * node_frac) >> 3;
                     const int nmin = node_min < wfrac ? node_min : wfrac;
@@ -518,10 +530,12 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
                     bool fin = trav_done(r);
                     if (!fin && !trav_walking(r)) fin = trav_leaf<Stack, COUNT>(sc, r, stack, st);
                     if (fin) {
+                        region_count<COUNT>(rg, PRT_REGION_FINISH);
                         if (EXACT && trav_wants_resolve(r, stack)) r.best = resolve_near_ties<Stack, COUNT>(sc, r.o, r.d, P.box_pad, r.best.t, stack, st);
                         if (!EXACT && trav_needs_slow_path(r, stack)) {
                             // rare: the hit has company within a few ulp and the reference's visit order decides, or a push did
                             // not fit the LDS column (dev_trace.h).  Not here: the ray is parked for the launches that follow.
+                            region_count<COUNT>(rg, PRT_REGION_PARK);
                             if (ADAPT && (unsigned int)ray < n_c && ((unsigned int)as_i(cd[ray].w) >> 8 & POOL_SPEC_PENDING_BIT)) {
                                 // a speculative camera ray (see the end of the shade phase) is not worth parking: call it off; the
                                 // finalise step notices and starts the sample again, in the open
@@ -582,7 +596,8 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
             tb.materials = sc.material_count <= (unsigned int)LDS_MATS ? s_mats : sc.materials;
             tb.lights = sc.light_count <= (unsigned int)LDS_LIGHTS ? s_lights : sc.lights;
             const int nxt = cur ^ 1;
-            PoolEmit<ADAPT, SHARED> emit;
+            PoolEmit<ADAPT, SHARED, COUNT> emit;
+            emit.rg = rg;
             emit.co = cq_base + (size_t)nxt * 3u * cap;
             emit.cd = emit.co + cap;
             emit.ct = emit.cd + cap;
@@ -770,6 +785,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
                     rays -= (unsigned long long)__popcll(__ballot(cancelled));
                 }
                 unsigned int shaded = 0;
+                if (live && !parked && !cancelled) region_count<COUNT>(rg, PRT_REGION_SHADE_PASS);
                 // the frame under construction lives in this lane's (idle) traversal stack column
                 shade_entry_lds<RING, TEX, BLOCK, RINGMEM>(sc, P, B, tb, live && !parked && !cancelled, s, level, pending, ray_o, ray_d, T, hit, emit, shaded, stack.frame_col());
                 shaded_w += (unsigned int)__popcll(__ballot(shaded != 0));
@@ -864,6 +880,10 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
         atomicMax(&ctr->max_sp, (unsigned long long)st.max_sp);
         atomicAdd(&ctr->culled, (unsigned long long)st.culled);
         atomicAdd(&ctr->wave_node_step_rays, (unsigned long long)st.wrays);
+        atomicAdd(&ctr->region[2 * PRT_REGION_NODE_DESCEND], (unsigned long long)st.wdescend);
+        atomicAdd(&ctr->region[2 * PRT_REGION_NODE_POP], (unsigned long long)st.wpop);
+        atomicAdd(&ctr->region[2 * PRT_REGION_NODE_PUSH], (unsigned long long)st.wpush);
+        for (unsigned int k = threadIdx.x; k < 2u * PRT_REGION_COUNT; k += BLOCK) if (s_rg[k]) atomicAdd(&ctr->region[k], (unsigned long long)s_rg[k]);
         if (dry_steps) { atomicAdd(&ctr->drain_node_steps, dry_steps); atomicAdd(&ctr->drain_node_step_rays, dry_rays); }
         if (lane == 0) {
             atomicAdd(&ctr->phase_cycles[0], ph_topup);

@@ -469,10 +469,12 @@ PRT_D void shade_entry_on(const DevScene & sc, const DevParams & P, const WaveBu
     DevMaterial mat = tb.materials[0];
     if (live) {
         if (hit.tri < 0) {                                                         // raytracer.cpp:573-575
+            emit.region(PRT_REGION_SHADE_MISS);
             add = add + T * P.background;
             mode = M_RETURN_UP;
         } else {
             shaded = 1;
+            emit.region(PRT_REGION_SHADE_HIT);
             const f3 ob = ray_o + ray_d * P.ray_bias;                               // raytracer.cpp:163
             const f3 pos = ob + ray_d * hit.t;                                      // raytracer.cpp:121
             const float4 * sp = sc.shade + 4 * (size_t)hit.tri;
@@ -558,7 +560,10 @@ PRT_D void shade_entry_on(const DevScene & sc, const DevParams & P, const WaveBu
     }
 
     // everything this invocation adds to the sample is known now (the bounce walk below adds nothing): write the record back
-    if (live && (fresh || add.x != 0.0f || add.y != 0.0f || add.z != 0.0f)) accum_store_owner(B.accum + s, acc_x, acc_y, acc_z, add);
+    if (live && (fresh || add.x != 0.0f || add.y != 0.0f || add.z != 0.0f)) {
+        emit.region(PRT_REGION_RADIANCE_STORE);
+        accum_store_owner(B.accum + s, acc_x, acc_y, acc_z, add);
+    }
 
     // ---- shadow rays of this hit (raytracer.cpp:507-511, 378-411): radiance-if-unoccluded rides with the ray
     for (unsigned int li = 0; li < sc.light_count; ++li) {
@@ -566,6 +571,7 @@ PRT_D void shade_entry_on(const DevScene & sc, const DevParams & P, const WaveBu
         float dist_sq = -1.0f;
         int kind = WF_KIND_SHADOW_ANY;
         if (want_shadow) {
+            emit.region(PRT_REGION_SHADOW_BLOCK);
             const DevLight L = tb.lights[li];
             f3 light_color = mk3(L.color[0], L.color[1], L.color[2]);
             f3 light_vector;
@@ -592,6 +598,7 @@ PRT_D void shade_entry_on(const DevScene & sc, const DevParams & P, const WaveBu
         // and counts it, :161); here it is COUNTED (ray_count stays the reference's) and not traced.
         const bool dead = want_shadow && P.elide_dead_shadow_rays && contrib.x == 0.0f && contrib.y == 0.0f && contrib.z == 0.0f;
         emit.elided(dead);
+        if (want_shadow && !dead) emit.region(PRT_REGION_SHADOW_EMIT);
         emit.shadow(want_shadow && !dead, s, so, sd, contrib, kind == WF_KIND_SHADOW_DIST ? dist_sq : -(float)(li + 1u), kind);
     }
 
@@ -599,12 +606,19 @@ PRT_D void shade_entry_on(const DevScene & sc, const DevParams & P, const WaveBu
     // The three steps follow each other in ONE pass of the loop (not one step per pass): a lane's own sequence of steps is
     // the same, but the lanes of a wave, each at its own step, no longer pay for the union of all three on every pass -
     // spawning a child and entering it, or retiring a frame and resuming its parent, take one pass instead of two.
+    // What the loop decides about a child is only WHETHER it flies: which lobe, which direction sample (the draws happen here,
+    // in the reference's order) and the survival draw.  Half of the children die at that draw, and a wave repeats the loop until
+    // its last lane has a survivor or runs out of frames - four passes per shade pass on a C4 frame.  So the child's direction
+    // and throughput (tangent_to_world: two normalisations, a cross product) are computed ONCE, behind the loop, for the child
+    // that flies, from the frame that spawned it (still in f: nothing touches a frame between its child's entry and the end of
+    // the walk) - the same operations on the same operands, for one child in two.
+    int spawn = -1;          // the last child spawned: lobe (0 diffuse, 1 specular) << 30 | its direction sample (index into the diffuse table / the material's specular set); -1: none, or an alpha continuation (its ray is made in the loop)
     while (mode != M_DONE) {
+        emit.region(PRT_REGION_WALK_LOOP);
         if (mode == M_NEXT_CHILD) {                       // frame f at `level` spawns its next child, if any
+            emit.region(PRT_REGION_WALK_NEXT_CHILD);
             const int iters = depth - level;
-            const DevMaterial fm = tb.materials[f.mat];
-            const f3 own = TRANS && f.alpha < 1.0f ? f.T_in * f.alpha : f.T_in;
-            // which child comes next (cheap), then ONE copy of the expensive direction code for both lobes
+            // which child comes next
             int kind = -1;                                                          // 0 diffuse, 1 specular, 2 alpha continuation
             if (f.stage == WF_STAGE_REFL) {                                         // raytracer.cpp:516-526
                 if (iters > 0 && (unsigned int)f.idx < P.reflection_samples) kind = 0;
@@ -619,26 +633,14 @@ PRT_D void shade_entry_on(const DevScene & sc, const DevParams & P, const WaveBu
                 if (TRANS && f.alpha < 1.0f) kind = 2;
             }
             const bool spawned = kind >= 0;
+            spawn = -1;
             if (kind == 2) {
                 next_o = f.hit_pos + f.ray_d * P.ray_bias * 2.0f;
                 next_d = f.ray_d;
                 next_T = f.T_in * (1.0f - f.alpha);
             } else if (kind >= 0) {
-                float4 ts;
-                if (kind == 0) {
-                    const unsigned int series_i = (unsigned int)(rng_next<RING>(rng, ring, ring_stride) % 1024ull);
-                    ts = tb.diffuse[series_i];
-                } else {
-                    ts = sc.spec_dirs[(size_t)f.mat * sc.spec_samples + (unsigned int)f.idx];
-                }
-                next_d = tangent_to_world(f.hit_n, mk3(ts.x, ts.y, ts.z));
-                const float cw = kind == 0 ? ref_max(0.0f, dot3(f.hit_n, next_d)) : ref_max(0.0f, dot3(next_d, f.ray_d * -1.0f));
-                // the frame's colours: carried in the frame for textured scenes, else re-read from the material table
-                const f3 fkd = TEX ? f.kd : mk3(fm.diffuse[0], fm.diffuse[1], fm.diffuse[2]);
-                const f3 fks = TEX ? f.ks : mk3(fm.specular[0], fm.specular[1], fm.specular[2]);
-                const f3 lobe = kind == 0 ? fkd * f.w_diffuse : fks;
-                next_T = own * (lobe * cw);
-                next_o = f.hit_p;
+                if (kind == 0) spawn = (int)(rng_next<RING>(rng, ring, ring_stride) % 1024ull);
+                else spawn = 1 << 30 | f.idx;
                 f.idx++;
                 // look ahead: if this was the frame's last child, retire the frame now so it is neither parked
                 // (64 B written, 64 B read back later) nor revisited
@@ -656,12 +658,14 @@ PRT_D void shade_entry_on(const DevScene & sc, const DevParams & P, const WaveBu
             }
         }
         if (mode == M_ENTER) {                     // TraceRayColor entry (raytracer.cpp:415-420) for (next_*, next_level)
+            emit.region(PRT_REGION_WALK_ENTER);
             const int iters = depth - next_level;
             bool dead = iters < 0;
             if (!dead && next_level != 0) dead = rng_float01<RING>(rng, ring, ring_stride) < 0.5f;
             if (!dead) {
                 // the child flies: park its parent frame if that still has children to spawn afterwards
                 if (f_held && f.stage != WF_STAGE_DONE) {
+                    emit.region(PRT_REGION_FRAME_SAVE);
                     wframe_save<POS, TEX>(B, level, s, f);
                     pending |= 1u << level;
                 }
@@ -674,11 +678,13 @@ PRT_D void shade_entry_on(const DevScene & sc, const DevParams & P, const WaveBu
             }
         }
         if (mode == M_RETURN_UP) {                        // resume the deepest parked frame
+            emit.region(PRT_REGION_WALK_RETURN_UP);
             if (pending == 0u) {
                 mode = M_DONE;
             } else {
                 level = 31 - __clz((int)pending);
                 pending &= ~(1u << level);
+                emit.region(PRT_REGION_FRAME_LOAD);
                 wframe_load<POS, TEX>(B, level, s, f);
                 mode = M_NEXT_CHILD;
             }
@@ -689,9 +695,29 @@ PRT_D void shade_entry_on(const DevScene & sc, const DevParams & P, const WaveBu
     // the RNG state goes back to memory for the sample's next shade event; a sample that has no ray left (every level returned)
     // will never draw again - except in adaptive mode, where the pixel's next sample continues the stream (Emit::KEEPS_RNG)
     if (live && (emit_closest || Emit::KEEPS_RNG)) {
+        emit.region(PRT_REGION_OUTPUTS);
         B.rng[s] = make_ulonglong2(rng.chain, rng.prev);
         if (RING && RM) B.rng_aux[s] = make_ulonglong2(rng.seed0, (u64)rng.k);
     }
+    // ---- the child that flies: its ray, from the frame that spawned it ------------------------------------
+    if (emit_closest && spawn >= 0) {
+        emit.region(PRT_REGION_WALK_CHILD_RAY);
+        const int spawn_kind = spawn >> 30;
+        const unsigned int spawn_sel = (unsigned int)spawn & 0x3FFFFFFFu;
+        const DevMaterial fm = tb.materials[f.mat];
+        const f3 own = TRANS && f.alpha < 1.0f ? f.T_in * f.alpha : f.T_in;
+        const float4 ts = spawn_kind == 0 ? tb.diffuse[spawn_sel] : sc.spec_dirs[(size_t)f.mat * sc.spec_samples + spawn_sel];
+        next_d = tangent_to_world(f.hit_n, mk3(ts.x, ts.y, ts.z));
+        const float cw = spawn_kind == 0 ? ref_max(0.0f, dot3(f.hit_n, next_d)) : ref_max(0.0f, dot3(next_d, f.ray_d * -1.0f));
+        // the frame's colours: carried in the frame for textured scenes, else re-read from the material table
+        const f3 fkd = TEX ? f.kd : mk3(fm.diffuse[0], fm.diffuse[1], fm.diffuse[2]);
+        const f3 fks = TEX ? f.ks : mk3(fm.specular[0], fm.specular[1], fm.specular[2]);
+        const f3 lobe = spawn_kind == 0 ? fkd * f.w_diffuse : fks;
+        next_T = own * (lobe * cw);
+        next_o = f.hit_p;
+    }
+
+    // ---- append the next ray
     emit.closest(emit_closest, s, next_o, next_d, next_T, next_level, pending, live && !emit_closest);
 }
 
@@ -717,6 +743,7 @@ PRT_D void shade_entry_lds(const DevScene & sc, const DevParams & P, const WaveB
 template <int BLOCK>
 struct QueueEmit {
     enum { KEEPS_RNG = 0 };           // fixed spp: a sample that has ended never draws again
+    PRT_D void region(int) const {}   // (k_pool's COUNT builds count shade_entry_on's regions through their emitter)
     const WaveBuffers & B;
     int nxt;
     unsigned int * s_cnt;

@@ -159,6 +159,7 @@ struct prt_ctx {
     DevBuf<unsigned int> wf_counts;       // persistent / pool pipelines' sample counter
     DevBuf<float4> pool_f4;               // pool pipeline: the waves' private ray lists
     prt_render_stats last_stats;          // of the last render call (prt_get_render_stats)
+    uint64_t last_regions[2 * PRT_REGION_COUNT] = {};      // ... and its region table (prt_get_region_stats)
     DevBuf<float4> pool_park;             // pool pipeline: rays parked for the slow launches (kernels_pool.h PoolBuffers::park)
     size_t pool_park_cap = 1u << 18, pool_spark_cap = 1u << 18;     // entries; enlarged when a frame needed more (render_pixels)
     DevCounters * host_counters = nullptr;                            // pinned: the render's counters arrive here on the context's stream
@@ -1072,6 +1073,14 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
             rs.elided_shadow_rays = h.elided_shadow_rays;
             rs.variance_close_calls = h.variance_close_calls;
             rs.stack_lds_entries = stack_entries; rs.stack_bound = ctx->stack_bound;
+            // k_pool's COUNT variants fill the table; the steps that have counters of their own are copied into their rows
+            uint64_t * const rg = ctx->last_regions;
+            for (int k = 0; k < 2 * PRT_REGION_COUNT; ++k) rg[k] = pipeline == PRT_PIPELINE_POOL ? h.region[k] : 0;
+            if (pipeline == PRT_PIPELINE_POOL && h.region[2 * PRT_REGION_WAVE]) {
+                rg[2 * PRT_REGION_NODE_STEP] = h.wave_node_steps; rg[2 * PRT_REGION_NODE_STEP + 1] = h.node_visits;
+                rg[2 * PRT_REGION_LEAF] = h.wave_leaf_steps;
+                rg[2 * PRT_REGION_TRI] = h.wave_tri_steps; rg[2 * PRT_REGION_TRI + 1] = h.tri_tests;
+            }
         }
         float ms = 0.0f;
         const float trace_ms = trace_ms_accum;
@@ -1450,6 +1459,14 @@ int prt_get_render_stats(const prt_ctx * ctx, prt_render_stats * stats) {
     *stats = ctx->last_stats;
     return 0;
     PRT_API_CATCH_RC(nullptr, "prt_get_render_stats")
+}
+
+int prt_get_region_stats(const prt_ctx * ctx, uint64_t * out, uint32_t n) {
+    PRT_API_TRY
+    if (!ctx || (!out && n)) return -1;
+    for (uint32_t k = 0; k < n && k < 2u * PRT_REGION_COUNT; ++k) out[k] = ctx->last_regions[k];
+    return 2 * PRT_REGION_COUNT;
+    PRT_API_CATCH_RC(nullptr, "prt_get_region_stats")
 }
 
 int prt_upload_scene(prt_ctx * ctx, const prt_scene_desc * s) {
