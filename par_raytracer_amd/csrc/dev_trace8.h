@@ -114,7 +114,6 @@ struct GlobalStack {
 
 // The states of a lane's ray, as the kernels' loops ask for them
 PRT_D void trav_idle(TravRay & r) { r.node = TRAV_SENTINEL; r.tbits = 0u; r.tbase = 0u; r.sp = 0; r.kind = 0; }      // no ray
-PRT_D bool trav_at_leaf(const TravRay & r) { return (r.tbits & 0xFFu) != 0u; }
 PRT_D bool trav_walking(const TravRay & r) { return (r.tbits & 0xFFu) == 0u && r.node >= 0; }    // wants a node step
 PRT_D bool trav_done(const TravRay & r) { return (r.tbits & 0xFFu) == 0u && r.node < 0; }
 
@@ -260,6 +259,8 @@ PRT_D void trav_leaf_range(const TravRay & r, unsigned int & first, unsigned int
 }
 PRT_D void trav_leaf_consume(TravRay & r) { r.tbits &= r.tbits - 1u; }     // the lowest set bit is a pending slot (bits 0-7)
 
+template <class STK> PRT_D void trav_leaf_next(TravRay & r, const STK &) { trav_leaf_consume(r); }
+
 // The lowest pending leaf slot: test its triangles.  Returns true when an any-hit ray found its hit.
 template <class STK, bool COUNT>
 PRT_D bool trav_leaf(const DevScene & sc, TravRay & r, const STK & stk, TraceStats & st) {
@@ -292,101 +293,6 @@ PRT_D bool trav_leaf(const DevScene & sc, TravRay & r, const STK & stk, TraceSta
     }
     trav_leaf_consume(r);
     return false;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Near ties: the reference's answer for a ray whose closest hit has company within a few ulp.
-//
-// The reference keeps `best` (FLT_MAX at first) and offers it every triangle in ITS visit order - sphere tree depth first,
-// c1 before c0, groups in leaf order, triangles in index order (raytracer.cpp:136, 208-209); a triangle replaces best iff
-// !(t > best * d) and t / d < best (:104, :149, :220).  Far from best both comparisons say the same; within an ulp or two
-// they need not, so which of several near-coincident hits survives depends on the order.  What cannot depend on it:
-// let N be the candidates with t <= bound, where no candidate lies in the "moat" (bound, bound * (1 + 2^-20)].  Then
-//   - every member of N beats any best that is not in N on both comparisons with room to spare, so the first member the
-//     reference meets is accepted whatever came before it;
-//   - from then on best <= bound, and nothing outside N can pass `t / d < best`.
-// Hence the reference's final hit is its own filter run over N alone, in its visit order, from FLT_MAX.  That is what this
-// function does: N's members are fetched one by one in visit order (tri_rank) - each fetch a traversal bounded by `bound`,
-// no storage needed - and put through tri_test_ref.  If the moat turns out to be occupied the bound is widened and the
-// replay starts over; after sc.tie_widen_max widenings the replay is finished over the set as it stands and the event is
-// counted (DevScene::near_tie_unresolved: the render call then fails - it has never been seen to happen).
-// The reference also skips a whole GROUP whose bounding sphere it enters later than its best hit so far
-// (raytracer.cpp:176-181): RefSphereWalk (dev_trace_common.h) replays that on the uploaded sphere tree.
-template <class STK, bool COUNT>
-PRT_D HitRec resolve_near_ties(const DevScene & sc, f3 o, f3 d, float pad, float min_t, const STK & stk, TraceStats & st) {
-    TravRay r;
-    HitRec result;
-    result.t = 3.402823466e+38f; result.v = result.w = 0.0f; result.tri = -1;
-    const f3 qp = o - (o + d);
-    float bound = min_t * PRT_TIE_NEAR;
-    for (unsigned int widen = 0; ; ++widen) {
-        const bool last = widen >= sc.tie_widen_max;
-        const float moat = bound * 1.00000095367431640625f;          // 1 + 2^-20
-        bool occupied = false;
-        float best = 3.402823466e+38f;                              // the reference's best_hit.t, replayed
-        result.tri = -1;
-        unsigned int next_rank = 0;                                 // candidates of rank >= next_rank are still to come
-        RefSphereWalk walk;
-        walk.reset();
-        for (;;) {
-            // the member of N with the smallest rank >= next_rank
-            unsigned int c_rank = 0xFFFFFFFFu;
-            int c_tri = -1;
-            trav_init(r, o, d, TRACE_CLOSEST, pad, stk);
-            r.best.t = moat;                                        // the boxes are culled against the moat's far side
-            for (;;) {
-                while (trav_walking(r)) trav_node_step<STK, COUNT>(sc, r, stk, st, pad);
-                if (trav_done(r)) break;
-                unsigned int first, count;
-                trav_leaf_range(r, first, count);
-                for (unsigned int i = 0; i < count; ++i) {
-                    const unsigned int ti = first + i;
-                    const float4 * tp = sc.tris + 3 * (size_t)ti;
-                    const float4 r0 = tp[0], r1 = tp[1], r2 = tp[2];
-                    float t, dd, v, w;
-                    if (!tri_geom(o, qp, mk3(r0.x, r0.y, r0.z), mk3(r0.w, r1.x, r1.y), mk3(r1.z, r1.w, r2.x), mk3(r2.y, r2.z, r2.w), t, dd, v, w)) continue;
-                    const float th = t * (1.0f / dd);
-                    if (th > bound) { if (th <= moat) occupied = true; continue; }
-                    const unsigned int rk = sc.tri_rank[ti];
-                    if (rk >= next_rank && rk < c_rank) { c_rank = rk; c_tri = (int)ti; }
-                }
-                trav_leaf_consume(r);
-            }
-            if (c_tri < 0 || (occupied && !last)) break;
-            const float4 * tp = sc.tris + 3 * (size_t)c_tri;
-            const float4 r0 = tp[0], r1 = tp[1], r2 = tp[2];
-            float t, v, w;
-            if (walk.offers(sc, o, d, c_rank, best) &&
-                tri_test_ref(o, qp, mk3(r0.x, r0.y, r0.z), mk3(r0.w, r1.x, r1.y), mk3(r1.z, r1.w, r2.x), mk3(r2.y, r2.z, r2.w), best, t, v, w)) {
-                best = t;
-                result.t = t; result.v = v; result.w = w; result.tri = c_tri;
-            }
-            next_rank = c_rank + 1u;
-        }
-        if (!occupied) break;
-        if (last) {                                                 // gave up widening: the replay ran over the set as it stood
-            if (sc.near_tie_unresolved) atomicAdd(sc.near_tie_unresolved, 1ull);
-            break;
-        }
-        bound = moat * PRT_TIE_NEAR;                                // take the moat's occupants in and try again
-    }
-    return result;
-}
-
-// Whole-ray traversal, "while-while" (Aila & Laine): every lane first walks internal nodes until it holds a leaf (or runs out
-// of work), and only then does the wave run the triangle code.  Near ties are decided on the spot: this is the form for the
-// slow paths and the experimental kernels, on a stack that cannot overflow.
-template <class STK, bool COUNT>
-PRT_D HitRec trace_ray(const DevScene & sc, f3 o, f3 d, int kind, float pad, const STK & stk, TraceStats & st) {
-    TravRay r;
-    trav_init(r, o, d, kind, pad, stk);
-    for (;;) {
-        while (trav_walking(r)) trav_node_step<STK, COUNT>(sc, r, stk, st, pad);
-        if (trav_done(r)) break;
-        if (trav_leaf<STK, COUNT>(sc, r, stk, st)) return r.best;           // any-hit ray: found its occluder
-    }
-    if (trav_wants_resolve(r, stk)) return resolve_near_ties<STK, COUNT>(sc, o, d, pad, r.best.t, stk, st);
-    return r.best;
 }
 
 }  // namespace prt

@@ -36,10 +36,10 @@ struct HitRec {
 enum { TRACE_CLOSEST = 0, TRACE_ANY = 1 };
 
 struct TraceStats {
-    unsigned int nodes, tris;
-    unsigned int wnodes, wleaves, wtris, wrefills;   // counted by the first active lane only (wave-level steps)
-    unsigned int wrays;                              // k_pool: lanes that held a ray, summed over the wave-level node steps
-    unsigned int max_sp, culled;                     // deepest stack use; popped nodes whose entry distance was already beyond the hit
+    unsigned int nodes = 0, tris = 0;
+    unsigned int wnodes = 0, wleaves = 0, wtris = 0, wrefills = 0;   // counted by the first active lane only (wave-level steps)
+    unsigned int wrays = 0;                          // k_pool: lanes that held a ray, summed over the wave-level node steps
+    unsigned int max_sp = 0, culled = 0;             // deepest stack use; popped nodes whose entry distance was already beyond the hit
     unsigned int wdescend = 0, wpop = 0, wpush = 0;  // wave-level node steps in which a lane went down into a child / took its next node from the stack; wave-level pushes
 };
 

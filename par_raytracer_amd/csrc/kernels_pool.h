@@ -295,7 +295,6 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
     unsigned int shaded_w = 0;                 // wave-uniform
     unsigned int elided_w = 0;                 // wave-uniform: shadow rays counted, not traced
     TraceStats st;
-    st.nodes = st.tris = st.wnodes = st.wleaves = st.wtris = st.wrefills = st.wrays = st.max_sp = st.culled = 0;
 
 // this wave's lists, from the arguments as re-read in the current phase
 #define PRT_POOL_LISTS(A)                                                                              \
@@ -494,7 +493,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
                             const unsigned int j = idx - n_c;
                             ro = sq_o[j];
                             payload = sq_c[j];
-                            if (payload.w < 0.0f) {          // directional light: the direction is a per-light constant
+                            if (payload.w < 0.0f) {          // shadow_entry_dir (kernels_wave.h), spelled out: the helper changes this kernel's code
                                 const DevLight & L = lights[(unsigned int)(-payload.w) - 1u];
                                 const f3 lv = mk3(L.facing[0], L.facing[1], L.facing[2]) * -1.0f;   // raytracer.cpp:240
                                 rd = make_float4(lv.x, lv.y, lv.z, 0.0f);
@@ -566,7 +565,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
                         } else if ((unsigned int)ray < n_c) {
                             hits[ray] = make_float4(r.best.t, r.best.v, r.best.w, as_f(r.best.tri));
                         } else {
-                            // shadow ray: add the precomputed radiance when unoccluded (k_trace has the commentary)
+                            // shadow ray: add the precomputed radiance when unoccluded.  shadow_lit (kernels_wave.h), spelled out likewise
                             const bool lit = r.best.tri < 0 || (payload.w >= 0.0f && r.best.t * r.best.t <= payload.w);
                             if (lit) {
                                 accum_add(B.accum + sample, mk3(payload.x, payload.y, payload.z));
@@ -871,13 +870,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
         if (s_red[1]) atomicAdd(&ctr->shaded_hits, s_red[1]);
     }
     if (COUNT) {
-        atomicAdd(&ctr->node_visits, (unsigned long long)st.nodes);
-        atomicAdd(&ctr->tri_tests, (unsigned long long)st.tris);
-        atomicAdd(&ctr->wave_node_steps, (unsigned long long)st.wnodes);
-        atomicAdd(&ctr->wave_leaf_steps, (unsigned long long)st.wleaves);
-        atomicAdd(&ctr->wave_tri_steps, (unsigned long long)st.wtris);
-        atomicAdd(&ctr->wave_refills, (unsigned long long)st.wrefills);
-        atomicMax(&ctr->max_sp, (unsigned long long)st.max_sp);
+        trace_stats_flush<true>(ctr, st);
         atomicAdd(&ctr->culled, (unsigned long long)st.culled);
         atomicAdd(&ctr->wave_node_step_rays, (unsigned long long)st.wrays);
         atomicAdd(&ctr->region[2 * PRT_REGION_NODE_DESCEND], (unsigned long long)st.wdescend);
@@ -927,7 +920,6 @@ __global__ __launch_bounds__(256) void k_pool_parked_shadows(const PoolArgs * ar
         if (A.Q.park_count[1] > A.Q.spark_cap) atomicMax(&ctr->park_over[1], (unsigned long long)A.Q.park_count[1]);
     }
     TraceStats st;
-    st.nodes = st.tris = st.wnodes = st.wleaves = st.wtris = st.wrefills = st.wrays = st.max_sp = st.culled = 0;
     GlobalStack slow;
     slow.attach(P.exact_stack, gid, P.exact_stack_stride);
     for (unsigned int i = gid; i < n; i += gridDim.x * blockDim.x) {
@@ -936,13 +928,9 @@ __global__ __launch_bounds__(256) void k_pool_parked_shadows(const PoolArgs * ar
         const f3 d = mk3(rd.x, rd.y, rd.z);
         const f3 ob = mk3(ro.x, ro.y, ro.z) + d * P.ray_bias;                   // raytracer.cpp:163
         const HitRec h = trace_ray<GlobalStack, COUNT>(sc, ob, d, pay.w < 0.0f ? TRACE_ANY : TRACE_CLOSEST, P.box_pad, slow, st);
-        const bool lit = h.tri < 0 || (pay.w >= 0.0f && h.t * h.t <= pay.w);
-        if (lit) accum_add(A.B.accum + sample, mk3(pay.x, pay.y, pay.z));
+        if (shadow_lit(h, pay.w)) accum_add(A.B.accum + sample, mk3(pay.x, pay.y, pay.z));
     }
-    if (COUNT) {
-        atomicAdd(&ctr->node_visits, (unsigned long long)st.nodes);
-        atomicAdd(&ctr->tri_tests, (unsigned long long)st.tris);
-    }
+    if (COUNT) trace_stats_flush<false>(ctr, st);
 }
 
 }  // namespace prt

@@ -144,7 +144,6 @@ __global__ __launch_bounds__(BLOCK, 6) void k_query(DevScene sc, QueryArgs A, co
     int ray = -1;                        // batch index of the lane's ray, -1 = idle
     bool exhausted = false;              // wave-uniform: the batch has no more rays to hand out
     TraceStats st;
-    st.nodes = st.tris = st.wnodes = st.wleaves = st.wtris = st.wrefills = st.wrays = st.max_sp = st.culled = 0;
 
     unsigned int chunk_next = 0, chunk_end = 0;      // wave-uniform: rays reserved for this wave, not yet handed out
     for (;;) {
@@ -212,15 +211,7 @@ __global__ __launch_bounds__(BLOCK, 6) void k_query(DevScene sc, QueryArgs A, co
             if (__popcll(__ballot(true)) < leave_below) break;
         }
     }
-    if (COUNT) {
-        atomicAdd(&ctr->node_visits, (unsigned long long)st.nodes);
-        atomicAdd(&ctr->tri_tests, (unsigned long long)st.tris);
-        atomicAdd(&ctr->wave_node_steps, (unsigned long long)st.wnodes);
-        atomicAdd(&ctr->wave_leaf_steps, (unsigned long long)st.wleaves);
-        atomicAdd(&ctr->wave_tri_steps, (unsigned long long)st.wtris);
-        atomicAdd(&ctr->wave_refills, (unsigned long long)st.wrefills);
-        atomicMax(&ctr->max_sp, (unsigned long long)st.max_sp);
-    }
+    if (COUNT) trace_stats_flush<true>(ctr, st);
 }
 
 // Any hit below tmax on a stack that cannot overflow (trace_ray's walk with the best hit started at tmax).
@@ -236,19 +227,6 @@ PRT_D HitRec query_any_below(const DevScene & sc, f3 o, f3 d, float tmax, float 
     }
     return r.best;
 }
-
-// The walk's leaf in r: its triangle range, and the step past it (the two traversals keep a visited leaf differently).
-#if defined(PRT_BVH8)
-PRT_D void query_leaf_range(const TravRay & r, unsigned int & first, unsigned int & count) { trav_leaf_range(r, first, count); }
-template <class STK> PRT_D void query_leaf_next(TravRay & r, const STK &) { trav_leaf_consume(r); }
-#else
-PRT_D void query_leaf_range(const TravRay & r, unsigned int & first, unsigned int & count) {
-    const unsigned int leaf = (unsigned int)~r.node;
-    first = leaf >> 2;
-    count = (leaf & 3u) + 1u;
-}
-template <class STK> PRT_D void query_leaf_next(TravRay & r, const STK & stk) { trav_pop(r, stk); }
-#endif
 
 // OCCLUDED for an origin far from the scene (query_far): there the triangle test's t carries a rounding error (ap = o - a is
 // large and cancels in Dot(ap, n)) that can exceed the box pad, so a box culled against tmax could hold a triangle whose
@@ -266,7 +244,7 @@ PRT_D HitRec query_any_unculled(const DevScene & sc, f3 o, f3 d, float tmax, flo
         while (trav_walking(r)) trav_node_step<STK, COUNT>(sc, r, stk, st, pad);
         if (trav_done(r)) break;
         unsigned int first, count;
-        query_leaf_range(r, first, count);
+        trav_leaf_range(r, first, count);
         for (unsigned int i = 0; i < count; ++i) {
             const float4 * tp = sc.tris + 3 * (size_t)(first + i);
             const float4 r0 = tp[0], r1 = tp[1], r2 = tp[2];
@@ -277,7 +255,7 @@ PRT_D HitRec query_any_unculled(const DevScene & sc, f3 o, f3 d, float tmax, flo
             const float th = t * (1.0f / dd);
             if (th < tmax) { h.t = th; h.tri = (int)(first + i); return h; }
         }
-        query_leaf_next(r, stk);
+        trav_leaf_next(r, stk);
     }
     return h;
 }
@@ -291,7 +269,6 @@ __global__ __launch_bounds__(256) void k_query_exact(DevScene sc, QueryArgs A, c
     const unsigned int n_slow = A.work[1];
     const float pad = query_pad(A);
     TraceStats st;
-    st.nodes = st.tris = st.wnodes = st.wleaves = st.wtris = st.wrefills = st.wrays = st.max_sp = st.culled = 0;
     GlobalStack slow;
     slow.attach(A.exact_stack, gid, A.exact_stack_stride);
     for (unsigned int i = gid; i < n_slow; i += gridDim.x * blockDim.x) {
@@ -309,10 +286,7 @@ __global__ __launch_bounds__(256) void k_query_exact(DevScene sc, QueryArgs A, c
             h = trace_ray<GlobalStack, COUNT>(sc, ob, d, TRACE_CLOSEST, pad, slow, st);
         query_emit<MODE>(sc, A, leaf_map, fields, idx, ob, d, h);
     }
-    if (COUNT) {
-        atomicAdd(&ctr->node_visits, (unsigned long long)st.nodes);
-        atomicAdd(&ctr->tri_tests, (unsigned long long)st.tris);
-    }
+    if (COUNT) trace_stats_flush<false>(ctr, st);
 }
 
 }  // namespace prt

@@ -101,6 +101,37 @@ PRT_D unsigned int block_append(unsigned int * counter, bool pred, unsigned int 
     return slot;
 }
 
+// A shadow list entry's direction and kind: a directional light's direction is a per-light constant (payload.w < 0: light
+// number -w - 1, raytracer.cpp:240), a point light's travels with the ray.
+PRT_D float4 shadow_entry_dir(const DevLight * lights, float4 payload, const float4 * sq_d, unsigned int j, int & kind) {
+    if (payload.w < 0.0f) {
+        const DevLight & L = lights[(unsigned int)(-payload.w) - 1u];
+        const f3 lv = mk3(L.facing[0], L.facing[1], L.facing[2]) * -1.0f;
+        kind = WF_KIND_SHADOW_ANY;
+        return make_float4(lv.x, lv.y, lv.z, 0.0f);
+    }
+    kind = WF_KIND_SHADOW_DIST;
+    return sq_d[j];
+}
+// A shadow ray's verdict.  w < 0: directional light (boolean only, raytracer.cpp:385); otherwise the point light's inverted
+// distance test against w = distance^2 (:396)
+PRT_D bool shadow_lit(const HitRec & h, float w) { return h.tri < 0 || (w >= 0.0f && h.t * h.t <= w); }
+
+// A kernel's TraceStats into the context's counters.  FULL: the persistent kernels' wave-level counters too; else what the
+// slow kernels count.  (culled and k_pool's own counters stay with the kernels that report them.)
+template <bool FULL>
+PRT_D void trace_stats_flush(DevCounters * ctr, const TraceStats & st) {
+    atomicAdd(&ctr->node_visits, (unsigned long long)st.nodes);
+    atomicAdd(&ctr->tri_tests, (unsigned long long)st.tris);
+    if (FULL) {
+        atomicAdd(&ctr->wave_node_steps, (unsigned long long)st.wnodes);
+        atomicAdd(&ctr->wave_leaf_steps, (unsigned long long)st.wleaves);
+        atomicAdd(&ctr->wave_tri_steps, (unsigned long long)st.wtris);
+        atomicAdd(&ctr->wave_refills, (unsigned long long)st.wrefills);
+        atomicMax(&ctr->max_sp, (unsigned long long)st.max_sp);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------
 template <bool RING>
 __global__ __launch_bounds__(256) void k_raygen(DevCamera cam, DevParams P, WaveBuffers B) {
@@ -143,7 +174,6 @@ __global__ __launch_bounds__(BLOCK, 6) void k_trace(DevScene sc, DevParams P, Wa
     int sample = 0;
     bool exhausted = false;              // wave-uniform: the queue has no more rays to hand out
     TraceStats st;
-    st.nodes = st.tris = st.wnodes = st.wleaves = st.wtris = st.wrefills = st.wrays = st.max_sp = st.culled = 0;
 
     unsigned int chunk_next = 0, chunk_end = 0;      // wave-uniform: rays reserved for this wave, not yet handed out
     for (;;) {
@@ -180,15 +210,7 @@ __global__ __launch_bounds__(BLOCK, 6) void k_trace(DevScene sc, DevParams P, Wa
                         const unsigned int j = idx - n_closest;
                         ro = B.sq_o[j];
                         payload = B.sq_c[j];
-                        if (payload.w < 0.0f) {          // directional light: the direction is a per-light constant
-                            const DevLight & L = sc.lights[(unsigned int)(-payload.w) - 1u];
-                            const f3 lv = mk3(L.facing[0], L.facing[1], L.facing[2]) * -1.0f;   // raytracer.cpp:240
-                            rd = make_float4(lv.x, lv.y, lv.z, 0.0f);
-                            kind = WF_KIND_SHADOW_ANY;
-                        } else {
-                            rd = B.sq_d[j];
-                            kind = WF_KIND_SHADOW_DIST;
-                        }
+                        rd = shadow_entry_dir(sc.lights, payload, B.sq_d, j, kind);
                     }
                     sample = as_i(ro.w);
                     const f3 d = mk3(rd.x, rd.y, rd.z);
@@ -224,12 +246,8 @@ __global__ __launch_bounds__(BLOCK, 6) void k_trace(DevScene sc, DevParams P, Wa
                 } else if ((unsigned int)ray < n_closest) {
                     B.hits[ray] = make_float4(r.best.t, r.best.v, r.best.w, as_f(r.best.tri));
                 } else {
-                    // shadow ray: add the precomputed radiance when unoccluded.  payload.w < 0: directional light
-                    // (boolean only, raytracer.cpp:385); otherwise the point light's inverted distance test (:396)
-                    const bool lit = r.best.tri < 0 || (payload.w >= 0.0f && r.best.t * r.best.t <= payload.w);
-                    if (lit) {
-                        accum_add(B.accum + sample, mk3(payload.x, payload.y, payload.z));
-                    }
+                    // shadow ray: add the precomputed radiance when unoccluded
+                    if (shadow_lit(r.best, payload.w)) accum_add(B.accum + sample, mk3(payload.x, payload.y, payload.z));
                 }
                 ray = -1;
                 break;
@@ -238,13 +256,7 @@ __global__ __launch_bounds__(BLOCK, 6) void k_trace(DevScene sc, DevParams P, Wa
         }
     }
     if (COUNT) {
-        atomicAdd(&ctr->node_visits, (unsigned long long)st.nodes);
-        atomicAdd(&ctr->tri_tests, (unsigned long long)st.tris);
-        atomicAdd(&ctr->wave_node_steps, (unsigned long long)st.wnodes);
-        atomicAdd(&ctr->wave_leaf_steps, (unsigned long long)st.wleaves);
-        atomicAdd(&ctr->wave_tri_steps, (unsigned long long)st.wtris);
-        atomicAdd(&ctr->wave_refills, (unsigned long long)st.wrefills);
-        atomicMax(&ctr->max_sp, (unsigned long long)st.max_sp);
+        trace_stats_flush<true>(ctr, st);
         atomicAdd(&ctr->culled, (unsigned long long)st.culled);
     }
 }
@@ -260,7 +272,6 @@ __global__ __launch_bounds__(256) void k_trace_exact(DevScene sc, DevParams P, W
     const unsigned int gid = blockIdx.x * blockDim.x + threadIdx.x;
     const unsigned int n_overflow = B.counts[3];
     TraceStats st;
-    st.nodes = st.tris = st.wnodes = st.wleaves = st.wtris = st.wrefills = st.wrays = st.max_sp = st.culled = 0;
     GlobalStack slow;
     slow.attach(P.exact_stack, gid, P.exact_stack_stride);
     for (unsigned int i = gid; i < n_overflow; i += gridDim.x * blockDim.x) {
@@ -275,15 +286,7 @@ __global__ __launch_bounds__(256) void k_trace_exact(DevScene sc, DevParams P, W
             const unsigned int j = idx - n_closest;
             ro = B.sq_o[j];
             payload = B.sq_c[j];
-            if (payload.w < 0.0f) {
-                const DevLight & L = sc.lights[(unsigned int)(-payload.w) - 1u];
-                const f3 lv = mk3(L.facing[0], L.facing[1], L.facing[2]) * -1.0f;
-                rd = make_float4(lv.x, lv.y, lv.z, 0.0f);
-                kind = WF_KIND_SHADOW_ANY;
-            } else {
-                rd = B.sq_d[j];
-                kind = WF_KIND_SHADOW_DIST;
-            }
+            rd = shadow_entry_dir(sc.lights, payload, B.sq_d, j, kind);
         }
         const int sample = as_i(ro.w);
         const f3 d = mk3(rd.x, rd.y, rd.z);
@@ -292,17 +295,10 @@ __global__ __launch_bounds__(256) void k_trace_exact(DevScene sc, DevParams P, W
         if (idx < n_closest) {
             B.hits[idx] = make_float4(best.t, best.v, best.w, as_f(best.tri));
         } else {
-            const float dist_sq = kind == WF_KIND_SHADOW_ANY ? -1.0f : payload.w;
-            const bool lit = best.tri < 0 || (dist_sq >= 0.0f && best.t * best.t <= dist_sq);
-            if (lit) {
-                accum_add(B.accum + sample, mk3(payload.x, payload.y, payload.z));
-            }
+            if (shadow_lit(best, payload.w)) accum_add(B.accum + sample, mk3(payload.x, payload.y, payload.z));
         }
     }
-    if (COUNT) {
-        atomicAdd(&ctr->node_visits, (unsigned long long)st.nodes);
-        atomicAdd(&ctr->tri_tests, (unsigned long long)st.tris);
-    }
+    if (COUNT) trace_stats_flush<false>(ctr, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------

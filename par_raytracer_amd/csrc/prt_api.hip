@@ -1053,7 +1053,7 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
         return 0;
     }
     if (h.near_tie_unresolved) {
-        // resolve_near_ties ran out of widenings (dev_trace8.h): some hit among near-coincident candidates was decided over an
+        // resolve_near_ties ran out of widenings (dev_trace.h): some hit among near-coincident candidates was decided over an
         // incomplete candidate set.  Never seen on real geometry; reported, not hidden.
         char msg[160];
         snprintf(msg, sizeof(msg), "prt_render: %llu near-tied hits could not be resolved within %lld widenings of the candidate set",

@@ -1,6 +1,6 @@
 """The option libraries in the driver's GPU suite.
 
-`make hip-bvh8` builds libprt_hip_bvh8.so: the same ABI over the 8-wide compressed BVH (csrc/dev_trace8.h, 415 lines that the
+`make hip-bvh8` builds libprt_hip_bvh8.so: the same ABI over the 8-wide compressed BVH (csrc/dev_trace8.h, 298 lines that the
 default library does not contain).  The suite loads one library per process (PRT_HIP_LIB, par_raytracer_amd/capi.py), so the
 variant runs in a CHILD process: three of the reference's golden fixtures - the Cornell box, the coincident-geometry scene
 with two lights (near ties decided by the reference's visit order) and the headline 1M-triangle frame - on both production

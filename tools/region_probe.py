@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""One C4 frame (terrain_1m, 1920x1080, 8 spp, depth 2, pool pipeline) with the library PRT_HIP_LIB names: frame times, ray
-count, shaded hits and a hash of the frame's words - one process per library and round gives the interleaved A/B protocol of
-profiles/r05_valu_budget.txt section 3 - and, with --regions, the region table of a COUNT render of the same frame as JSON for
-tools/valu_budget.py --regions.
+"""One C4 frame (terrain_1m, 1920x1080, 8 spp, depth 2; pool pipeline, or --pipeline wavefront, whose traversal kernel is k_trace)
+with the library PRT_HIP_LIB names: frame times, ray count, shaded hits and a hash of the frame's words - one process per library
+and round gives the interleaved A/B protocol of profiles/r05_valu_budget.txt section 3 - and, with --regions (pool only), the
+region table of a COUNT render of the same frame as JSON for tools/valu_budget.py --regions.
 
-    python tools/region_probe.py [--frames N] [--regions OUT.json] [--tag NAME]
+    python tools/region_probe.py [--pipeline pool|wavefront] [--frames N] [--regions OUT.json] [--tag NAME]
 """
 import hashlib, json, os, sys, tempfile
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -18,6 +18,9 @@ def arg(name, default):
 
 frames = int(arg("--frames", "15"))
 out = arg("--regions", None)
+pipeline = {"pool": capi.PIPELINE_POOL, "wavefront": capi.PIPELINE_WAVEFRONT}[arg("--pipeline", "pool")]
+if out and pipeline != capi.PIPELINE_POOL:
+    sys.exit("--regions: the region table is k_pool's")
 tag = arg("--tag", os.environ.get("PRT_HIP_LIB", "libprt_hip.so"))
 s = scenes.make_scene("terrain_1m"); d = tempfile.mkdtemp(); scenes.write_obj(s, d, "scene.obj")
 hs = api.HostScene(d, "scene.obj", 0, s.camera_position)
@@ -32,7 +35,7 @@ def sha(t):
     return hashlib.sha1(t.cpu().numpy().view(np.uint32).tobytes()).hexdigest()[:16]
 
 
-p = api.default_params(8, 1234, pipeline=capi.PIPELINE_POOL)
+p = api.default_params(8, 1234, pipeline=pipeline)
 r.render_device(cam, p, w, h, 0, w * h, buf.data_ptr(), True)          # warm-up
 ms = []
 for _ in range(frames):

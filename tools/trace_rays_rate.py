@@ -9,7 +9,7 @@
 2. Incoherent rays: origins at the first hits of (1), cosine-distributed directions about the hit normal from a host RNG,
    CLOSEST and OCCLUDED.
 3. A 64 k-ray batch (the first rays of (2)): fixed overhead.
-Median of --reps calls each (after one warm-up call).  Mrays/s = rays / trace_kernel_ms and rays / render_ms (the whole call).
+Median of --reps calls each (after one warm-up call); the line before each result gives the kernels' min and median, for A/B runs.  Mrays/s = rays / trace_kernel_ms and rays / render_ms (the whole call).
 """
 from __future__ import annotations
 
@@ -47,6 +47,7 @@ def timed(fn, reps):
     runs = [fn() for _ in range(reps)]
     ker = float(np.median([c.trace_kernel_ms for c in runs]))
     call = float(np.median([c.render_ms for c in runs]))
+    print("    [kernels min %.3f median %.3f ms over %d calls]" % (min(c.trace_kernel_ms for c in runs), ker, reps))
     return runs[-1], ker, call
 
 
