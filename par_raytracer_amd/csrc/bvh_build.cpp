@@ -1,4 +1,5 @@
-// bvh_build.cpp - binned surface-area-heuristic BVH2 builder (host, multi-threaded over subtrees).
+// bvh_build.cpp - host BVH builder: a binned surface-area-heuristic binary tree (multi-threaded over subtrees), or a radix
+// tree built elsewhere, collapsed to 4 or 8 children per node and quantised (one back end, finish_wide).
 #include "bvh_build.h"
 #include "prt_options.h"
 
@@ -10,6 +11,7 @@
 #include <cstring>
 #include <chrono>
 #include <cstdio>
+#include <stdexcept>
 #include <thread>
 
 namespace prt {
@@ -212,106 +214,10 @@ struct Builder {
     }
 };
 
-inline float int_bits(int32_t v) {
-    float f;
-    memcpy(&f, &v, 4);
-    return f;
-}
-
-}  // namespace
-
-void build_bvh2(const float * verts, uint32_t n_tris, uint32_t leaf_max, uint32_t threads, BvhResult * out) {
-    *out = BvhResult();
-    if (leaf_max < 1) leaf_max = 1;
-    if (leaf_max > 4) leaf_max = 4;
-    Builder b;
-    b.leaf_max = leaf_max;
-    b.prims.resize(n_tris);
-    Box scene;
-    scene.reset();
-    for (uint32_t i = 0; i < n_tris; ++i) {
-        Prim & p = b.prims[i];
-        p.box.reset();
-        p.box.grow(verts + 9 * (size_t)i);
-        p.box.grow(verts + 9 * (size_t)i + 3);
-        p.box.grow(verts + 9 * (size_t)i + 6);
-        for (int a = 0; a < 3; ++a) p.c[a] = 0.5f * p.box.lo[a] + 0.5f * p.box.hi[a];
-        p.id = i;
-        scene.grow(p.box);
-    }
-    for (int a = 0; a < 3; ++a) { out->scene_lo[a] = n_tris ? scene.lo[a] : 0.0f; out->scene_hi[a] = n_tris ? scene.hi[a] : 0.0f; }
-
-    b.pool.resize(n_tris ? 2 * (size_t)n_tris : 1);
-    b.next_node = 1;
-    b.max_depth = 0;
-    b.threads_free = (int)(threads > 1 ? threads - 1 : 0);
-    if (n_tris) b.build(0, 0, n_tris, 0);
-
-    out->tri_order.resize(n_tris);
-    for (uint32_t i = 0; i < n_tris; ++i) out->tri_order[i] = b.prims[i].id;
-    out->max_depth = b.max_depth.load() + 1;
-
-    // --- emit the device layout.  Internal nodes are numbered in DFS preorder (node 0 = root, a left child
-    // directly follows its parent).  Leaves live only as links.  The root is always an internal node: a scene
-    // of <= leaf_max triangles becomes a root whose two links name the same leaf (testing a triangle twice
-    // cannot change a closest hit: equal t and equal rank never replace), and an empty scene a root over one
-    // all-zero dummy triangle, which the test always rejects (d = 0).
-    auto leaf_link = [&](const TmpNode & n) -> int32_t { return ~(int32_t)((n.first << 2) | (n.count - 1)); };
-    auto emit = [&](uint32_t slot, const Box & b0, int32_t l0, const Box & b1, int32_t l1) {
-        float * n = &out->nodes[16 * (size_t)slot];
-        n[0] = b0.lo[0]; n[1] = b0.hi[0]; n[2] = b0.lo[1]; n[3] = b0.hi[1];
-        n[4] = b1.lo[0]; n[5] = b1.hi[0]; n[6] = b1.lo[1]; n[7] = b1.hi[1];
-        n[8] = b0.lo[2]; n[9] = b0.hi[2]; n[10] = b1.lo[2]; n[11] = b1.hi[2];
-        n[12] = int_bits(l0); n[13] = int_bits(l1); n[14] = 0.0f; n[15] = 0.0f;
-    };
-
-    if (n_tris == 0 || b.pool[0].left < 0) {
-        out->nodes.assign(16, 0.0f);
-        out->node_count = 1;
-        Box zero = { { 0, 0, 0 }, { 0, 0, 0 } };
-        if (n_tris == 0) emit(0, zero, ~0, zero, ~0);
-        else emit(0, b.pool[0].box, leaf_link(b.pool[0]), b.pool[0].box, leaf_link(b.pool[0]));
-        out->max_depth = 1;
-        return;
-    }
-
-    // count internal nodes, assign preorder slots
-    std::vector<int32_t> slot_of(b.next_node.load(), -1);
-    std::vector<uint32_t> stack;
-    uint32_t n_internal = 0;
-    stack.push_back(0);
-    while (!stack.empty()) {
-        uint32_t t = stack.back();
-        stack.pop_back();
-        const TmpNode & n = b.pool[t];
-        if (n.left < 0) continue;
-        slot_of[t] = (int32_t)n_internal++;
-        stack.push_back((uint32_t)n.right);
-        stack.push_back((uint32_t)n.left);
-    }
-    out->node_count = n_internal;
-    out->nodes.assign(16 * (size_t)n_internal, 0.0f);
-    for (uint32_t t = 0; t < slot_of.size(); ++t) {
-        if (slot_of[t] < 0) continue;
-        const TmpNode & n = b.pool[t];
-        const TmpNode & l = b.pool[n.left];
-        const TmpNode & r = b.pool[n.right];
-        int32_t ll = l.left < 0 ? leaf_link(l) : slot_of[n.left];
-        int32_t rl = r.left < 0 ? leaf_link(r) : slot_of[n.right];
-        emit((uint32_t)slot_of[t], l.box, ll, r.box, rl);
-    }
-}
-
 
 // ---------------------------------------------------------------------------------------------------------
-// 4-wide, quantised
+// Back end: binary tree (b.pool, root 0; leaves carry [first, first + count) of b.prims) -> wide quantised nodes
 // ---------------------------------------------------------------------------------------------------------
-namespace {
-
-struct Wide {
-    uint32_t tmp[4];        // TmpNode indices of the children
-    uint32_t n;
-};
 
 inline uint32_t float_bits(float f) {
     uint32_t u;
@@ -319,240 +225,44 @@ inline uint32_t float_bits(float f) {
     return u;
 }
 
-}  // namespace
-
-namespace {
-
-// Shared back end: TmpNode tree (b.pool, root 0; leaves carry [first, first + count) of b.prims) -> 4-wide quantised nodes.
-void finish_bvh4q_impl(Builder & b, uint32_t n_tris, Bvh4Result * out);
-void finish_bvh4q(Builder & b, uint32_t n_tris, Bvh4Result * out) {
-    const auto t0 = std::chrono::steady_clock::now();
-    finish_bvh4q_impl(b, n_tris, out);
-    if (b.opt.debug) fprintf(stderr, "[prt] BVH back end (collapse to 4-wide, quantise, reorder): %.1f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-}
-void finish_bvh4q_impl(Builder & b, uint32_t n_tris, Bvh4Result * out) {
-    out->tri_order.resize(n_tris);
-    for (uint32_t i = 0; i < n_tris; ++i) out->tri_order[i] = b.prims[i].id;
-
-    auto is_leaf = [&](uint32_t t) { return b.pool[t].left < 0; };
-    auto leaf_link = [&](uint32_t t) -> int32_t { return ~(int32_t)((b.pool[t].first << 2) | (b.pool[t].count - 1)); };
-
-    // ---- collapse: each wide node adopts up to 4 binary-tree descendants.
-    // Every visit of a wide node costs the same (all four boxes are tested), and under the surface-area heuristic a
-    // node is visited in proportion to the area of its box, so the best collapse of a given binary tree is the one
-    // with the smallest total area of wide nodes (the leaves stay what they are).  That optimum is a small dynamic
-    // programme over the binary tree (Ylitie, Karras, Laine 2017, section 3.1, here for width 4 and fixed leaves):
-    //   F(m, k) = least area needed below binary node m if it may occupy up to k child slots of its parent
-    //   F(m, 1) = area(m) + min over i of F(left, i) + F(right, 4 - i)          (m becomes a wide node; 0 for a leaf)
-    //   F(m, k) = min(F(m, k - 1), min over i of F(left, i) + F(right, k - i))  (m is dissolved into its parent)
-    // Measured on MI355X: 18-20 % fewer wide nodes, but only 1-2 % fewer node visits per frame and 2.5 % MORE triangle
-    // tests on C4 (the rays of a terrain seen from above are far from the uniform distribution the heuristic assumes):
-    // frame time unchanged within noise.  So the default stays the first version - open the child with the largest box
-    // until four are there - and the BVH_COLLAPSE=dp option selects this one.
-    struct Item { uint32_t tmp; uint32_t slot; uint32_t depth; };
-    std::vector<Wide> wide;
-    std::vector<Item> work;
-    const bool greedy = b.opt.collapse != 1;                 // 4-wide default: greedy
-    const uint32_t n_tmp = b.next_node.load();
-    struct Dp { float f[3]; uint8_t root_split, split[2]; };   // f[k-1] = F(m, k); split: i of the best distribution, 0 = "use k - 1"
+// Collapse: each wide node adopts up to W binary-tree descendants.
+// Every visit of a wide node costs the same (all W boxes are tested), and under the surface-area heuristic a node is
+// visited in proportion to the area of its box, so the best collapse of a given binary tree is the one with the smallest
+// total area of wide nodes (the leaves stay what they are).  That optimum is a small dynamic programme over the binary
+// tree (Ylitie, Karras, Laine 2017, section 3.1, here with fixed leaves):
+//   F(m, k) = least area needed below binary node m if it may occupy up to k child slots of its parent
+//   F(m, 1) = area(m) + min over i of F(left, i) + F(right, W - i)          (m becomes a wide node; 0 for a leaf)
+//   F(m, k) = min(F(m, k - 1), min over i of F(left, i) + F(right, k - i))  (m is dissolved into its parent)
+// The other rule is greedy: open the child with the largest box until W are there.
+// 4-wide, measured on MI355X: the programme gives 18-20 % fewer wide nodes, but only 1-2 % fewer node visits per frame
+// and 2.5 % MORE triangle tests on C4 (the rays of a terrain seen from above are far from the uniform distribution the
+// heuristic assumes): frame time unchanged within noise.  So the 4-wide default stays greedy.  8-wide: the greedy rule
+// leaves the tree of the 1M-triangle terrain at 3.6 children per node; the programme fills it (tools/bvh_price.cpp) and
+// is the default.  The option BVH_COLLAPSE = greedy / dp selects either for both.
+struct Collapse {
+    struct Dp { float f[7]; uint8_t root_split, split[6]; };   // f[k-1] = F(m, k); split[k-2]: i of the best distribution, 0 = "use k - 1"
+    const std::vector<TmpNode> & pool;
+    const int W;                                             // children per node, <= 8
+    const bool greedy;
     std::vector<Dp> dp;
-    if (!greedy) {
-        dp.resize(n_tmp);
+
+    bool is_leaf(uint32_t t) const { return pool[t].left < 0; }
+
+    Collapse(const Builder & b, int W_, bool greedy_) : pool(b.pool), W(W_), greedy(greedy_) {
+        if (greedy) return;
+        const uint32_t n_tmp = b.next_node.load();
+        dp.resize(n_tmp);                                    // all zero, which is what a leaf keeps: F = 0, nothing to decide
         for (uint32_t t = n_tmp; t-- > 0;) {                  // children are allocated after their parent: bottom-up
+            if (is_leaf(t)) continue;
             Dp & d = dp[t];
-            if (is_leaf(t)) { d.f[0] = d.f[1] = d.f[2] = 0.0f; d.root_split = 0; d.split[0] = d.split[1] = 0; continue; }
-            const Dp & l = dp[(uint32_t)b.pool[t].left], & r = dp[(uint32_t)b.pool[t].right];
-            float best = FLT_MAX;
-            for (int i = 1; i <= 3; ++i) {
-                const float c = l.f[i - 1] + r.f[3 - i];
-                if (c < best) { best = c; d.root_split = (uint8_t)i; }
-            }
-            d.f[0] = b.pool[t].box.half_area() + best;
-            for (int k = 2; k <= 3; ++k) {
-                float bk = d.f[k - 2];
-                uint8_t sk = 0;
-                for (int i = 1; i < k; ++i) {
-                    const float c = l.f[i - 1] + r.f[k - i - 1];
-                    if (c < bk) { bk = c; sk = (uint8_t)i; }
-                }
-                d.f[k - 1] = bk;
-                d.split[k - 2] = sk;
-            }
-        }
-    }
-    auto make_wide = [&](uint32_t root_tmp) -> Wide {
-        Wide w;
-        w.n = 0;
-        if (is_leaf(root_tmp)) { w.tmp[w.n++] = root_tmp; return w; }
-        if (!greedy) {
-            // unfold the stored decisions: (node, slots it may occupy)
-            struct Todo { uint32_t t; int k; };
-            Todo stack[8];
-            int sp = 0;
-            const int i0 = dp[root_tmp].root_split;
-            stack[sp++] = Todo{ (uint32_t)b.pool[root_tmp].right, 4 - i0 };
-            stack[sp++] = Todo{ (uint32_t)b.pool[root_tmp].left, i0 };
-            while (sp > 0) {
-                Todo cur = stack[--sp];
-                while (cur.k > 1 && !is_leaf(cur.t) && dp[cur.t].split[cur.k - 2] == 0) cur.k--;      // "use k - 1 slots"
-                if (cur.k == 1 || is_leaf(cur.t)) { w.tmp[w.n++] = cur.t; continue; }
-                const int i = dp[cur.t].split[cur.k - 2];
-                stack[sp++] = Todo{ (uint32_t)b.pool[cur.t].right, cur.k - i };
-                stack[sp++] = Todo{ (uint32_t)b.pool[cur.t].left, i };
-            }
-            // largest box first: the slot order is the visiting order of equal keys
-            for (uint32_t i = 1; i < w.n; ++i)
-                for (uint32_t j = i; j > 0 && b.pool[w.tmp[j]].box.half_area() > b.pool[w.tmp[j - 1]].box.half_area(); --j)
-                    std::swap(w.tmp[j], w.tmp[j - 1]);
-            return w;
-        }
-        w.tmp[w.n++] = (uint32_t)b.pool[root_tmp].left;
-        w.tmp[w.n++] = (uint32_t)b.pool[root_tmp].right;
-        while (w.n < 4) {
-            int best = -1;
-            float best_area = -1.0f;
-            for (uint32_t k = 0; k < w.n; ++k) {
-                if (is_leaf(w.tmp[k])) continue;
-                float a = b.pool[w.tmp[k]].box.half_area();
-                if (a > best_area) { best_area = a; best = (int)k; }
-            }
-            if (best < 0) break;
-            uint32_t t = w.tmp[best];
-            w.tmp[best] = (uint32_t)b.pool[t].left;
-            w.tmp[w.n++] = (uint32_t)b.pool[t].right;
-        }
-        return w;
-    };
-
-    // BFS numbering: the top of the tree is contiguous (cache / LDS friendly), children of a node are adjacent
-    std::vector<uint32_t> depth_of;
-    work.push_back(Item{ 0u, 0u, 1u });
-    wide.push_back(make_wide(0));
-    depth_of.push_back(1);
-    std::vector<int32_t> links;           // 4 per wide node
-    links.assign(4, 0);
-    uint32_t max_depth = 1;
-    for (size_t head = 0; head < work.size(); ++head) {
-        const Item it = work[head];
-        const Wide w = wide[it.slot];
-        for (uint32_t k = 0; k < 4; ++k) {
-            int32_t link;
-            if (k >= w.n) {
-                link = ~(int32_t)(n_tris << 2);               // empty slot: a 1-triangle leaf naming the all-zero dummy record
-                                                             // the uploader appends at slot n_tris (always rejected: d = 0)
-            } else if (is_leaf(w.tmp[k])) {
-                link = leaf_link(w.tmp[k]);
-            } else {
-                uint32_t slot = (uint32_t)wide.size();
-                wide.push_back(make_wide(w.tmp[k]));
-                links.resize(links.size() + 4, 0);
-                work.push_back(Item{ w.tmp[k], slot, it.depth + 1 });
-                if (it.depth + 1 > max_depth) max_depth = it.depth + 1;
-                link = (int32_t)slot;
-            }
-            links[(size_t)it.slot * 4 + k] = link;
-        }
-    }
-
-    // ---- quantise
-    const uint32_t n_nodes = (uint32_t)wide.size();
-    out->nodes.assign((size_t)n_nodes * 16, 0u);
-    for (uint32_t s = 0; s < n_nodes; ++s) {
-        const Wide & w = wide[s];
-        Box u;
-        u.reset();
-        for (uint32_t k = 0; k < w.n; ++k) u.grow(b.pool[w.tmp[k]].box);
-        uint32_t * d = &out->nodes[(size_t)s * 16];
-        uint32_t ebyte[3];
-        double scale[3];
-        for (int a = 0; a < 3; ++a) {
-            double ext = (double)u.hi[a] - (double)u.lo[a];
-            int e = -100;
-            if (ext > 0.0) {
-                e = (int)std::ceil(std::log2(ext / 255.0));
-                while (std::ldexp(255.0, e) < ext) ++e;
-                if (e < -100) e = -100;
-            }
-            if (e > 100) e = 100;
-            ebyte[a] = (uint32_t)(e + 127);
-            scale[a] = std::ldexp(1.0, e);
-            d[a] = float_bits(u.lo[a]);
-        }
-        // the grid steps 2^e as ready-made floats (the exponent byte in place): the traversal multiplies, it does not decode
-        d[3] = ebyte[0] << 23;
-        d[14] = ebyte[1] << 23;
-        d[15] = ebyte[2] << 23;
-        for (uint32_t k = 0; k < 4; ++k) {
-            uint32_t qlo[3] = { 255, 255, 255 }, qhi[3] = { 0, 0, 0 };      // empty slot: inverted (and masked by its link)
-            if (k < w.n) {
-                const Box & cb = b.pool[w.tmp[k]].box;
-                for (int a = 0; a < 3; ++a) {
-                    double lo = std::floor(((double)cb.lo[a] - (double)u.lo[a]) / scale[a]);
-                    double hi = std::ceil(((double)cb.hi[a] - (double)u.lo[a]) / scale[a]);
-                    if (lo < 0.0) lo = 0.0;
-                    if (lo > 255.0) lo = 255.0;
-                    if (hi < 0.0) hi = 0.0;
-                    if (hi > 255.0) hi = 255.0;
-                    qlo[a] = (uint32_t)lo;
-                    qhi[a] = (uint32_t)hi;
-                }
-            }
-            for (int a = 0; a < 3; ++a) {
-                d[4 + a] |= qlo[a] << (8 * k);
-                d[7 + a] |= qhi[a] << (8 * k);
-            }
-            d[10 + k] = (uint32_t)links[(size_t)s * 4 + k];
-        }
-    }
-    out->node_count = n_nodes;
-    out->max_depth = max_depth;
-    out->stack_bound = 3 * max_depth + 2;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// 8-wide, quantised, children sorted along an ordering axis (layout: bvh_build.h Bvh8Result)
-// ---------------------------------------------------------------------------------------------------------
-void finish_bvh8q_impl(Builder & b, uint32_t n_tris, Bvh8Result * out);
-void finish_bvh8q(Builder & b, uint32_t n_tris, Bvh8Result * out) {
-    const auto t0 = std::chrono::steady_clock::now();
-    finish_bvh8q_impl(b, n_tris, out);
-    if (b.opt.debug) fprintf(stderr, "[prt] BVH back end (collapse to 8-wide, slot assignment, quantise, reorder): %.1f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-}
-void finish_bvh8q_impl(Builder & b, uint32_t n_tris, Bvh8Result * out) {
-    auto is_leaf = [&](uint32_t t) { return b.pool[t].left < 0; };
-    enum : uint32_t { EMPTY = 0xFFFFFFFFu };
-    struct Wide8 { uint32_t slot[8]; uint32_t axis = 0; };  // TmpNode index per slot, EMPTY for none; the ordering axis
-
-    // ---- collapse (below), then give every child a slot: children in ascending order of their centres along the node's
-    // ordering axis (by default the one on which the centres spread most); a ray takes the hit slots in ascending or descending
-    // order by the sign of its direction on that axis (dev_trace8.h).  (The slot-per-octant order of Ylitie et al. 2017,
-    // section 3.2, measured 1.7 % more node visits: profiles/r03_ab_bvh8.txt.)
-    // The collapse itself is the small dynamic programme of Ylitie et al. (section 3.1) over the binary tree, leaves fixed:
-    //   F(m, k) = least total area of wide nodes below binary node m if m may occupy up to k slots of its parent
-    //   F(m, 1) = area(m) + min over i of F(left, i) + F(right, 8 - i)          (m becomes a wide node; 0 for a leaf)
-    //   F(m, k) = min(F(m, k - 1), min over i of F(left, i) + F(right, k - i))  (m is dissolved into its parent)
-    // Every visit of a wide node costs the same (all eight boxes are tested) and a node is visited in proportion to its
-    // area.  The greedy rule of the 4-wide back end (open the largest child until the node is full) leaves the 8-wide
-    // tree of the 1M-triangle terrain at 3.6 children per node; the programme fills it (tools/bvh_price.cpp).
-    // The option BVH_COLLAPSE=greedy selects the greedy rule.
-    const bool greedy = b.opt.collapse == 0;                 // 8-wide default: the dynamic programme
-    const int W = b.opt.width >= 2 && b.opt.width <= 8 ? (int)b.opt.width : 8;      // children per node (experiments: 6)
-    const uint32_t n_tmp = b.next_node.load();
-    struct Dp8 { float f[7]; uint8_t root_split, split[6]; };   // f[k-1] = F(m, k); split[k-2]: i of the best distribution, 0 = "use k - 1"
-    std::vector<Dp8> dp;
-    if (!greedy) {
-        dp.resize(n_tmp);
-        for (uint32_t t = n_tmp; t-- > 0;) {                  // children are allocated after their parent: bottom-up
-            Dp8 & d = dp[t];
-            if (is_leaf(t)) { memset(&d, 0, sizeof(d)); continue; }
-            const Dp8 & l = dp[(uint32_t)b.pool[t].left], & r = dp[(uint32_t)b.pool[t].right];
+            const Dp & l = dp[(uint32_t)pool[t].left], & r = dp[(uint32_t)pool[t].right];
             float best = FLT_MAX;
             d.root_split = 1;
             for (int i = 1; i <= W - 1; ++i) {
                 const float c = l.f[i - 1] + r.f[W - 1 - i];
                 if (c < best) { best = c; d.root_split = (uint8_t)i; }
             }
-            d.f[0] = b.pool[t].box.half_area() + best;
+            d.f[0] = pool[t].box.half_area() + best;
             for (int k = 2; k <= W - 1; ++k) {
                 float bk = d.f[k - 2];
                 uint8_t sk = 0;
@@ -565,132 +275,104 @@ void finish_bvh8q_impl(Builder & b, uint32_t n_tris, Bvh8Result * out) {
             }
         }
     }
-    auto make_wide = [&](uint32_t root_tmp) -> Wide8 {
-        uint32_t kids[8];
+
+    // The binary-tree nodes the wide node rooted at `root` adopts, into kids[0 .. n); returns n.
+    uint32_t adopt(uint32_t root, uint32_t * kids) const {
         uint32_t n = 0;
-        if (is_leaf(root_tmp)) {
-            kids[n++] = root_tmp;
-        } else if (!greedy) {
+        if (is_leaf(root)) { kids[n++] = root; return n; }
+        if (!greedy) {
             // unfold the stored decisions: (node, slots it may occupy)
             struct Todo { uint32_t t; int k; };
             Todo stack[16];
             int sp = 0;
-            const int i0 = dp[root_tmp].root_split;
-            stack[sp++] = Todo{ (uint32_t)b.pool[root_tmp].right, W - i0 };
-            stack[sp++] = Todo{ (uint32_t)b.pool[root_tmp].left, i0 };
+            const int i0 = dp[root].root_split;
+            stack[sp++] = Todo{ (uint32_t)pool[root].right, W - i0 };
+            stack[sp++] = Todo{ (uint32_t)pool[root].left, i0 };
             while (sp > 0) {
                 Todo cur = stack[--sp];
                 while (cur.k > 1 && !is_leaf(cur.t) && dp[cur.t].split[cur.k - 2] == 0) cur.k--;      // "use k - 1 slots"
                 if (cur.k == 1 || is_leaf(cur.t)) { kids[n++] = cur.t; continue; }
                 const int i = dp[cur.t].split[cur.k - 2];
-                stack[sp++] = Todo{ (uint32_t)b.pool[cur.t].right, cur.k - i };
-                stack[sp++] = Todo{ (uint32_t)b.pool[cur.t].left, i };
+                stack[sp++] = Todo{ (uint32_t)pool[cur.t].right, cur.k - i };
+                stack[sp++] = Todo{ (uint32_t)pool[cur.t].left, i };
             }
-        } else {
-            kids[n++] = (uint32_t)b.pool[root_tmp].left;
-            kids[n++] = (uint32_t)b.pool[root_tmp].right;
-            while (n < (uint32_t)W) {
-                int best = -1;
-                float best_area = -1.0f;
-                for (uint32_t k = 0; k < n; ++k) {
-                    if (is_leaf(kids[k])) continue;
-                    const float a = b.pool[kids[k]].box.half_area();
-                    if (a > best_area) { best_area = a; best = (int)k; }
-                }
-                if (best < 0) break;
-                const uint32_t t = kids[best];
-                kids[best] = (uint32_t)b.pool[t].left;
-                kids[n++] = (uint32_t)b.pool[t].right;
-            }
+            return n;
         }
-        Wide8 w;
-        for (uint32_t s = 0; s < 8; ++s) w.slot[s] = EMPTY;
-        float lo[3] = { FLT_MAX, FLT_MAX, FLT_MAX }, hi[3] = { -FLT_MAX, -FLT_MAX, -FLT_MAX };
-        float c[8][3];
-        for (uint32_t k = 0; k < n; ++k)
-            for (int a = 0; a < 3; ++a) {
-                c[k][a] = 0.5f * b.pool[kids[k]].box.lo[a] + 0.5f * b.pool[kids[k]].box.hi[a];
-                lo[a] = std::min(lo[a], c[k][a]); hi[a] = std::max(hi[a], c[k][a]);
+        kids[n++] = (uint32_t)pool[root].left;
+        kids[n++] = (uint32_t)pool[root].right;
+        while (n < (uint32_t)W) {
+            int best = -1;
+            float best_area = -1.0f;
+            for (uint32_t k = 0; k < n; ++k) {
+                if (is_leaf(kids[k])) continue;
+                const float a = pool[kids[k]].box.half_area();
+                if (a > best_area) { best_area = a; best = (int)k; }
             }
-        int axis = 0;
-        for (int a = 1; a < 3; ++a) if (hi[a] - lo[a] > hi[axis] - lo[axis]) axis = a;
-        if (b.opt.axis_rule == 1) {
-            // experiment: the longest axis of the node's box
-            Box u2; u2.reset();
-            for (uint32_t k = 0; k < n; ++k) u2.grow(b.pool[kids[k]].box);
-            axis = 0;
-            for (int a = 1; a < 3; ++a) if (u2.hi[a] - u2.lo[a] > u2.hi[axis] - u2.lo[axis]) axis = a;
-        } else if (b.opt.axis_rule == 2) {
-            // experiment: the axis along which the children's boxes, sorted by centre, overlap least (sum over all pairs of
-            // the overlap of their intervals, relative to the node's extent on that axis)
-            float best = FLT_MAX;
-            for (int a = 0; a < 3; ++a) {
-                float ext = 0.0f, lo_a = FLT_MAX, hi_a = -FLT_MAX;
-                for (uint32_t k = 0; k < n; ++k) { lo_a = std::min(lo_a, b.pool[kids[k]].box.lo[a]); hi_a = std::max(hi_a, b.pool[kids[k]].box.hi[a]); }
-                ext = hi_a - lo_a;
-                if (!(ext > 0.0f)) continue;
-                float ov = 0.0f;
-                for (uint32_t i = 0; i < n; ++i)
-                    for (uint32_t j = i + 1; j < n; ++j) {
-                        const Box & bi = b.pool[kids[i]].box, & bj = b.pool[kids[j]].box;
-                        const float o = std::min(bi.hi[a], bj.hi[a]) - std::max(bi.lo[a], bj.lo[a]);
-                        if (o > 0.0f) ov += o / ext;
-                    }
-                if (ov < best) { best = ov; axis = a; }
-            }
+            if (best < 0) break;
+            const uint32_t t = kids[best];
+            kids[best] = (uint32_t)pool[t].left;
+            kids[n++] = (uint32_t)pool[t].right;
         }
-        uint32_t order[8];
-        for (uint32_t k = 0; k < n; ++k) order[k] = k;
-        std::sort(order, order + n, [&](uint32_t x, uint32_t y) { return c[x][axis] < c[y][axis]; });
-        for (uint32_t k = 0; k < n; ++k) w.slot[k] = kids[order[k]];
-        w.axis = (uint32_t)axis;
-        return w;
-    };
+        return n;
+    }
+};
 
-    // ---- number the nodes breadth-first - the internal children of a node get consecutive indices in slot order - and lay
-    // the triangles out so that the leaves of a node are consecutive in slot order too: a child is then addressed by the
-    // node's base index plus the number of like children in lower slots, and the node needs no links.
-    struct Item { uint32_t tmp, depth; };
-    std::vector<Wide8> wide;
-    std::vector<Item> work;
-    std::vector<uint32_t> child_base, tri_base;
-    out->tri_order.clear();
-    out->tri_order.reserve(n_tris);
-    work.push_back(Item{ 0u, 1u });
-    uint32_t max_depth = 1;
-    for (size_t head = 0; head < work.size(); ++head) {
-        const Item it = work[head];
-        const Wide8 w = make_wide(it.tmp);
-        wide.push_back(w);
-        child_base.push_back((uint32_t)work.size());
-        tri_base.push_back((uint32_t)out->tri_order.size());
-        for (uint32_t s = 0; s < 8; ++s) {
-            const uint32_t t = w.slot[s];
-            if (t == EMPTY) continue;
-            if (is_leaf(t)) {
-                // (an empty scene's root leaf names the all-zero dummy record the uploader appends at slot n_tris = 0)
-                for (uint32_t i = 0; i < b.pool[t].count && b.pool[t].first + i < n_tris; ++i)
-                    out->tri_order.push_back(b.prims[b.pool[t].first + i].id);
-            } else {
-                work.push_back(Item{ t, it.depth + 1 });
-                if (it.depth + 1 > max_depth) max_depth = it.depth + 1;
-            }
+// 8-wide slot order: the children in ascending order of their centres along the node's ordering axis (by default the one
+// on which the centres spread most); a ray takes the hit slots in ascending or descending order by the sign of its
+// direction on that axis (dev_trace8.h).  (The slot-per-octant order of Ylitie et al. 2017, section 3.2, measured 1.7 %
+// more node visits: profiles/r03_ab_bvh8.txt.)  Sorts kids[0 .. n) and returns the axis.
+uint32_t sort_along_axis(const Builder & b, uint32_t * kids, uint32_t n) {
+    float lo[3] = { FLT_MAX, FLT_MAX, FLT_MAX }, hi[3] = { -FLT_MAX, -FLT_MAX, -FLT_MAX };
+    float c[8][3];
+    for (uint32_t k = 0; k < n; ++k)
+        for (int a = 0; a < 3; ++a) {
+            c[k][a] = 0.5f * b.pool[kids[k]].box.lo[a] + 0.5f * b.pool[kids[k]].box.hi[a];
+            lo[a] = std::min(lo[a], c[k][a]); hi[a] = std::max(hi[a], c[k][a]);
+        }
+    int axis = 0;
+    for (int a = 1; a < 3; ++a) if (hi[a] - lo[a] > hi[axis] - lo[axis]) axis = a;
+    if (b.opt.axis_rule == 1) {
+        // experiment: the longest axis of the node's box
+        Box u2; u2.reset();
+        for (uint32_t k = 0; k < n; ++k) u2.grow(b.pool[kids[k]].box);
+        axis = 0;
+        for (int a = 1; a < 3; ++a) if (u2.hi[a] - u2.lo[a] > u2.hi[axis] - u2.lo[axis]) axis = a;
+    } else if (b.opt.axis_rule == 2) {
+        // experiment: the axis along which the children's boxes, sorted by centre, overlap least (sum over all pairs of
+        // the overlap of their intervals, relative to the node's extent on that axis)
+        float best = FLT_MAX;
+        for (int a = 0; a < 3; ++a) {
+            float ext = 0.0f, lo_a = FLT_MAX, hi_a = -FLT_MAX;
+            for (uint32_t k = 0; k < n; ++k) { lo_a = std::min(lo_a, b.pool[kids[k]].box.lo[a]); hi_a = std::max(hi_a, b.pool[kids[k]].box.hi[a]); }
+            ext = hi_a - lo_a;
+            if (!(ext > 0.0f)) continue;
+            float ov = 0.0f;
+            for (uint32_t i = 0; i < n; ++i)
+                for (uint32_t j = i + 1; j < n; ++j) {
+                    const Box & bi = b.pool[kids[i]].box, & bj = b.pool[kids[j]].box;
+                    const float o = std::min(bi.hi[a], bj.hi[a]) - std::max(bi.lo[a], bj.lo[a]);
+                    if (o > 0.0f) ov += o / ext;
+                }
+            if (ov < best) { best = ov; axis = a; }
         }
     }
+    uint32_t order[8], sorted[8];
+    for (uint32_t k = 0; k < n; ++k) order[k] = k;
+    std::sort(order, order + n, [&](uint32_t x, uint32_t y) { return c[x][axis] < c[y][axis]; });
+    for (uint32_t k = 0; k < n; ++k) sorted[k] = kids[order[k]];
+    for (uint32_t k = 0; k < n; ++k) kids[k] = sorted[k];
+    return (uint32_t)axis;
+}
 
-    // ---- quantise
-    const uint32_t n_nodes = (uint32_t)wide.size();
-    out->nodes.assign((size_t)n_nodes * BVH8_NODE_DWORDS, 0u);
-    for (uint32_t ni = 0; ni < n_nodes; ++ni) {
-        const Wide8 & w = wide[ni];
-        Box u;
-        u.reset();
-        for (uint32_t s = 0; s < 8; ++s) if (w.slot[s] != EMPTY) u.grow(b.pool[w.slot[s]].box);
-        uint32_t * d = &out->nodes[(size_t)ni * BVH8_NODE_DWORDS];
-        uint32_t ebyte[3];
-        double scale[3];
+// A node's power-of-two grid: origin at the lo corner of the union box `u` of its children, step 2^e per axis with e the
+// smallest exponent for which 255 steps span the box.
+struct Grid {
+    float org[3];
+    uint32_t ebyte[3];        // e + 127: the exponent byte of the float 2^e (the traversal multiplies, it does not decode)
+    double scale[3];          // 2^e
+    explicit Grid(const Box & u) {
         for (int a = 0; a < 3; ++a) {
-            double ext = (double)u.hi[a] - (double)u.lo[a];
+            const double ext = (double)u.hi[a] - (double)u.lo[a];
             int e = -100;
             if (ext > 0.0) {
                 e = (int)std::ceil(std::log2(ext / 255.0));
@@ -698,54 +380,142 @@ void finish_bvh8q_impl(Builder & b, uint32_t n_tris, Bvh8Result * out) {
                 if (e < -100) e = -100;
             }
             if (e > 100) e = 100;
+            org[a] = u.lo[a];
             ebyte[a] = (uint32_t)(e + 127);
             scale[a] = std::ldexp(1.0, e);
-            d[a] = float_bits(u.lo[a]);
         }
-        uint32_t imask = 0, lmask = 0, c0 = 0, c1 = 0;
-        for (uint32_t s = 0; s < 8; ++s) {
+    }
+    // A child's box rounded OUTWARD onto the grid.
+    void round_out(const Box & cb, uint32_t * qlo, uint32_t * qhi) const {
+        for (int a = 0; a < 3; ++a) {
+            double lo = std::floor(((double)cb.lo[a] - (double)org[a]) / scale[a]);
+            double hi = std::ceil(((double)cb.hi[a] - (double)org[a]) / scale[a]);
+            if (lo < 0.0) lo = 0.0;
+            if (lo > 255.0) lo = 255.0;
+            if (hi < 0.0) hi = 0.0;
+            if (hi > 255.0) hi = 255.0;
+            qlo[a] = (uint32_t)lo;
+            qhi[a] = (uint32_t)hi;
+        }
+    }
+};
+
+// What differs between the widths is stated here, once each: the default collapse rule, the order of a node's children,
+// the order of the triangles, how a node names its children and how its bytes are packed, and the stack bound.
+void finish_wide(Builder & b, uint32_t n_tris, int width, BvhWide * out) {
+    if (width != 4 && width != 8) throw std::invalid_argument("build_bvh_wide: width must be 4 or 8");
+    const auto t0 = std::chrono::steady_clock::now();
+    const bool eight = width == 8;
+    const bool greedy = eight ? b.opt.collapse == 0 : b.opt.collapse != 1;
+    const int W = eight && b.opt.width >= 2 && b.opt.width <= 8 ? (int)b.opt.width : width;   // children per node (experiments: 6 of 8)
+    const Collapse collapse(b, W, greedy);
+    auto is_leaf = [&](uint32_t t) { return b.pool[t].left < 0; };
+
+    // ---- number the nodes breadth-first: the top of the tree is contiguous (cache / LDS friendly) and the internal
+    // children of a node get consecutive indices in slot order.  4-wide: the triangles stay in the binary tree's leaf
+    // order and every slot carries a link.  8-wide: the triangles are laid out so that the leaves of a node are
+    // consecutive in slot order too; a child is then addressed by the node's base index plus the number of like children
+    // in lower slots, and the node needs no links.
+    struct WideNode { uint32_t kid[8], n, axis, child_base, tri_base; };   // kid: TmpNode indices, slots n.. are empty
+    struct Item { uint32_t tmp, depth; };
+    std::vector<WideNode> wide;
+    std::vector<Item> work;
+    out->tri_order.clear();
+    out->tri_order.reserve(n_tris);
+    if (!eight) for (uint32_t i = 0; i < n_tris; ++i) out->tri_order.push_back(b.prims[i].id);
+    work.push_back(Item{ 0u, 1u });
+    uint32_t max_depth = 1;
+    for (size_t head = 0; head < work.size(); ++head) {
+        const Item it = work[head];
+        WideNode w;
+        w.n = collapse.adopt(it.tmp, w.kid);
+        w.axis = 0;
+        if (eight) {
+            w.axis = sort_along_axis(b, w.kid, w.n);
+        } else if (!greedy) {
+            // largest box first: the slot order is the visiting order of equal keys
+            for (uint32_t i = 1; i < w.n; ++i)
+                for (uint32_t j = i; j > 0 && b.pool[w.kid[j]].box.half_area() > b.pool[w.kid[j - 1]].box.half_area(); --j)
+                    std::swap(w.kid[j], w.kid[j - 1]);
+        }
+        w.child_base = (uint32_t)work.size();
+        w.tri_base = (uint32_t)out->tri_order.size();
+        for (uint32_t s = 0; s < w.n; ++s) {
+            const uint32_t t = w.kid[s];
+            if (!is_leaf(t)) {
+                work.push_back(Item{ t, it.depth + 1 });
+                if (it.depth + 1 > max_depth) max_depth = it.depth + 1;
+            } else if (eight) {
+                // (an empty scene's root leaf names the all-zero dummy record the uploader appends at slot n_tris = 0)
+                for (uint32_t i = 0; i < b.pool[t].count && b.pool[t].first + i < n_tris; ++i)
+                    out->tri_order.push_back(b.prims[b.pool[t].first + i].id);
+            }
+        }
+        wide.push_back(w);
+    }
+
+    // ---- quantise and pack
+    const uint32_t n_nodes = (uint32_t)wide.size();
+    out->node_dwords = eight ? BVH8_NODE_DWORDS : BVH4_NODE_DWORDS;
+    out->nodes.assign((size_t)n_nodes * out->node_dwords, 0u);
+    for (uint32_t ni = 0; ni < n_nodes; ++ni) {
+        const WideNode & w = wide[ni];
+        Box u;
+        u.reset();
+        for (uint32_t s = 0; s < w.n; ++s) u.grow(b.pool[w.kid[s]].box);
+        const Grid g(u);
+        uint32_t * d = &out->nodes[(size_t)ni * out->node_dwords];
+        for (int a = 0; a < 3; ++a) d[a] = float_bits(g.org[a]);
+        uint32_t imask = 0, lmask = 0, c0 = 0, c1 = 0, next_child = w.child_base;
+        for (uint32_t s = 0; s < (uint32_t)width; ++s) {
             uint32_t qlo[3] = { 255, 255, 255 }, qhi[3] = { 0, 0, 0 };      // empty slot: inverted, can never be hit
-            const uint32_t t = w.slot[s];
-            if (t != EMPTY) {
-                const Box & cb = b.pool[t].box;
-                for (int a = 0; a < 3; ++a) {
-                    double lo = std::floor(((double)cb.lo[a] - (double)u.lo[a]) / scale[a]);
-                    double hi = std::ceil(((double)cb.hi[a] - (double)u.lo[a]) / scale[a]);
-                    if (lo < 0.0) lo = 0.0;
-                    if (lo > 255.0) lo = 255.0;
-                    if (hi < 0.0) hi = 0.0;
-                    if (hi > 255.0) hi = 255.0;
-                    qlo[a] = (uint32_t)lo;
-                    qhi[a] = (uint32_t)hi;
-                }
-                if (is_leaf(t)) {
-                    const uint32_t extra = b.pool[t].count - 1u;             // 0..3
+            const bool used = s < w.n, leaf = used && is_leaf(w.kid[s]);
+            if (used) g.round_out(b.pool[w.kid[s]].box, qlo, qhi);
+            if (eight) {
+                if (leaf) {
+                    const uint32_t extra = b.pool[w.kid[s]].count - 1u;          // 0..3
                     lmask |= 1u << s;
                     c0 |= (extra & 1u) << s;
                     c1 |= (extra >> 1) << s;
-                } else {
+                } else if (used) {
                     imask |= 1u << s;
                 }
-            }
-            for (int a = 0; a < 3; ++a) {
-                d[8 + 2 * a + (s >> 2)] |= qlo[a] << (8 * (s & 3u));
-                d[14 + 2 * a + (s >> 2)] |= qhi[a] << (8 * (s & 3u));
+                for (int a = 0; a < 3; ++a) {
+                    d[8 + 2 * a + (s >> 2)] |= qlo[a] << (8 * (s & 3u));
+                    d[14 + 2 * a + (s >> 2)] |= qhi[a] << (8 * (s & 3u));
+                }
+            } else {
+                for (int a = 0; a < 3; ++a) {
+                    d[4 + a] |= qlo[a] << (8 * s);
+                    d[7 + a] |= qhi[a] << (8 * s);
+                }
+                // an empty slot is also masked by its link: a 1-triangle leaf naming the all-zero dummy record the uploader
+                // appends at slot n_tris (always rejected: d = 0)
+                if (!used) d[10 + s] = (uint32_t)~(int32_t)(n_tris << 2);
+                else if (leaf) d[10 + s] = (uint32_t)~(int32_t)((b.pool[w.kid[s]].first << 2) | (b.pool[w.kid[s]].count - 1));
+                else d[10 + s] = next_child++;
             }
         }
-        d[3] = ebyte[0] << 23 | imask | lmask << 8;
-        d[4] = child_base[ni];
-        d[5] = tri_base[ni];
-        d[6] = ebyte[1] << 23 | c0 | c1 << 8;
-        d[7] = ebyte[2] << 23 | w.axis;
+        // the grid steps 2^e as ready-made floats (the exponent byte in place)
+        if (eight) {
+            d[3] = g.ebyte[0] << 23 | imask | lmask << 8;
+            d[4] = w.child_base;
+            d[5] = w.tri_base;
+            d[6] = g.ebyte[1] << 23 | c0 | c1 << 8;
+            d[7] = g.ebyte[2] << 23 | w.axis;
+        } else {
+            d[3] = g.ebyte[0] << 23;
+            d[14] = g.ebyte[1] << 23;
+            d[15] = g.ebyte[2] << 23;
+        }
     }
     out->node_count = n_nodes;
     out->max_depth = max_depth;
-    out->stack_bound = max_depth + 2;       // one group of unvisited siblings per level, the bottom marker, one to spare
+    // 4-wide: 3 unvisited siblings per level + the sentinel; 8-wide: one group of unvisited siblings per level, the bottom
+    // marker, one to spare
+    out->stack_bound = eight ? max_depth + 2 : 3 * max_depth + 2;
+    if (b.opt.debug) fprintf(stderr, "[prt] BVH back end (collapse to %d-wide, quantise, reorder): %.1f ms\n", width, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
 }
-
-}  // namespace
-
-namespace {
 
 // Front end shared by the 4- and 8-wide builds: binned-SAH binary tree over the triangles into b.pool (root 0).
 void build_sah_binary(Builder & b, const float * verts, uint32_t n_tris, uint32_t leaf_max, uint32_t threads, float trav_cost,
@@ -789,20 +559,13 @@ void build_sah_binary(Builder & b, const float * verts, uint32_t n_tris, uint32_
 
 }  // namespace
 
-void build_bvh4q(const float * verts, uint32_t n_tris, uint32_t leaf_max, uint32_t threads, Bvh4Result * out, float trav_cost, const BvhBuildOptions * opt) {
-    *out = Bvh4Result();
+void build_bvh_wide(int width, const float * verts, uint32_t n_tris, uint32_t leaf_max, uint32_t threads, BvhWide * out, float trav_cost,
+                    const BvhBuildOptions * opt) {
+    *out = BvhWide();
     Builder b;
     b.configure(opt);
     build_sah_binary(b, verts, n_tris, leaf_max, threads, trav_cost, out->scene_lo, out->scene_hi);
-    finish_bvh4q(b, n_tris, out);
-}
-
-void build_bvh8q(const float * verts, uint32_t n_tris, uint32_t leaf_max, uint32_t threads, Bvh8Result * out, float trav_cost, const BvhBuildOptions * opt) {
-    *out = Bvh8Result();
-    Builder b;
-    b.configure(opt);
-    build_sah_binary(b, verts, n_tris, leaf_max, threads, trav_cost, out->scene_lo, out->scene_hi);
-    finish_bvh8q(b, n_tris, out);
+    finish_wide(b, n_tris, width, out);
 }
 
 // Back end for a tree built elsewhere (the GPU LBVH builder, bvh_lbvh.hip): a binary radix tree over the triangles in
@@ -989,24 +752,14 @@ void radix_tree_to_binary(Builder & b, uint32_t n_tris, uint32_t leaf_max, const
 }
 }  // namespace
 
-void build_bvh4q_from_radix_tree(uint32_t n_tris, uint32_t leaf_max, const int32_t * left, const int32_t * right,
-                                 const uint32_t * first, const uint32_t * last, const float * node_box, const float * leaf_box,
-                                 const uint32_t * sorted_ids, Bvh4Result * out, const BvhBuildOptions * opt) {
-    *out = Bvh4Result();
+void build_bvh_wide_from_radix_tree(int width, uint32_t n_tris, uint32_t leaf_max, const int32_t * left, const int32_t * right,
+                                    const uint32_t * first, const uint32_t * last, const float * node_box, const float * leaf_box,
+                                    const uint32_t * sorted_ids, BvhWide * out, const BvhBuildOptions * opt) {
+    *out = BvhWide();
     Builder b;
     b.configure(opt);
     radix_tree_to_binary(b, n_tris, leaf_max, left, right, first, last, node_box, leaf_box, sorted_ids, out->scene_lo, out->scene_hi);
-    finish_bvh4q(b, n_tris, out);
-}
-
-void build_bvh8q_from_radix_tree(uint32_t n_tris, uint32_t leaf_max, const int32_t * left, const int32_t * right,
-                                 const uint32_t * first, const uint32_t * last, const float * node_box, const float * leaf_box,
-                                 const uint32_t * sorted_ids, Bvh8Result * out, const BvhBuildOptions * opt) {
-    *out = Bvh8Result();
-    Builder b;
-    b.configure(opt);
-    radix_tree_to_binary(b, n_tris, leaf_max, left, right, first, last, node_box, leaf_box, sorted_ids, out->scene_lo, out->scene_hi);
-    finish_bvh8q(b, n_tris, out);
+    finish_wide(b, n_tris, width, out);
 }
 
 }  // namespace prt

@@ -1,9 +1,11 @@
-// bvh_build.h - host-side per-triangle BVH2 builder for the HIP traversal kernels.
+// bvh_build.h - host-side per-triangle BVH builder and checker for the HIP traversal kernels.
 //
 // The reference's acceleration structure is a sphere tree over whole OBJ groups with brute force inside
 // each leaf (bsphere.cpp:379-444, raytracer.cpp:136-154).  Its RESULT is the exact closest front-facing
 // hit over all triangles, so any conservative structure gives the same answer; the
-// device uses a binned-SAH binary BVH with <= 4 triangles per leaf.
+// device uses a binned-SAH binary tree with <= 4 triangles per leaf, collapsed to 4 or 8 children per node
+// with the child boxes quantised to 8 bits per plane.  The node layouts are written in bvh_build.cpp (finish_wide),
+// decoded on the host in bvh_check.cpp (decode4 / decode8) and traversed in dev_trace4.h / dev_trace8.h.
 #pragma once
 
 #include <cstdint>
@@ -13,35 +15,23 @@ namespace prt { struct BvhBuildOptions; }     // prt_options.h: bins, sweep, col
 
 namespace prt {
 
-struct BvhResult {
-    std::vector<float> nodes;          // 16 floats (64 B) per internal node, layout in dev_scene.h
+// A wide quantised BVH of either width.  Every child box is rounded OUTWARD onto its node's own 2^e grid, so the tree
+// stays conservative.
+struct BvhWide {
+    std::vector<uint32_t> nodes;       // node_dwords per node
     std::vector<uint32_t> tri_order;   // tri_order[i] = input triangle stored at leaf-order slot i
+    uint32_t node_dwords = 0;          // BVH4_NODE_DWORDS or BVH8_NODE_DWORDS: which layout `nodes` holds
     uint32_t node_count = 0;
-    uint32_t max_depth = 0;            // deepest leaf; bounds the traversal stack
+    uint32_t max_depth = 0;            // in wide nodes
+    uint32_t stack_bound = 0;          // entries a traversal can ever hold (4-wide: 3 per level + sentinel; 8-wide: one group per
+                                       // level + the marker)
     float scene_lo[3] = { 0, 0, 0 }, scene_hi[3] = { 0, 0, 0 };
 };
+enum { BVH4_NODE_DWORDS = 16, BVH8_NODE_DWORDS = 20 };
 
-// verts: 9 floats per triangle (a, b, c).  leaf_max <= 4 (2 bits in the leaf link).
-void build_bvh2(const float * verts, uint32_t n_tris, uint32_t leaf_max, uint32_t threads, BvhResult * out);
-
-// 4-wide BVH with child boxes quantised to 8 bits per plane relative to the node's own box: 64 B per node
-// (layout in dev_scene.h).  Built by collapsing the binned-SAH binary tree (largest-area child first) and
-// rounding every child box OUTWARD onto the node's 2^e grid, so it stays conservative.
-struct Bvh4Result {
-    std::vector<uint32_t> nodes;       // 16 dwords (64 B) per node
-    std::vector<uint32_t> tri_order;
-    uint32_t node_count = 0;
-    uint32_t max_depth = 0;            // in 4-wide nodes
-    uint32_t stack_bound = 0;          // entries a traversal can ever hold: 3 per level + sentinel
-    float scene_lo[3] = { 0, 0, 0 }, scene_hi[3] = { 0, 0, 0 };
-};
-void build_bvh4q(const float * verts, uint32_t n_tris, uint32_t leaf_max, uint32_t threads, Bvh4Result * out, float trav_cost = 1.0f,
-                 const BvhBuildOptions * opt = nullptr);
-
-// The same 4-wide quantised result from a binary radix tree built elsewhere (GPU LBVH, bvh_lbvh.h); see bvh_build.cpp.
-void build_bvh4q_from_radix_tree(uint32_t n_tris, uint32_t leaf_max, const int32_t * left, const int32_t * right,
-                                 const uint32_t * first, const uint32_t * last, const float * node_box, const float * leaf_box,
-                                 const uint32_t * sorted_ids, Bvh4Result * out, const BvhBuildOptions * opt = nullptr);
+// 4-wide: 64 B per node (layout in dev_scene.h), explicit links, tri_order in the binary tree's leaf order, an empty
+// slot linked to the all-zero dummy record the uploader appends at slot n_tris.  Collapsed largest-area child first.
+typedef BvhWide Bvh4Result;
 
 // 8-wide compressed BVH: 80 B per node (5 x dwordx4), child boxes quantised to 8 bits per plane on the node's own
 // power-of-two grid, children in slot order sorted along the node's ordering axis, so that a ray visits them front to back in
@@ -57,19 +47,24 @@ void build_bvh4q_from_radix_tree(uint32_t n_tris, uint32_t leaf_max, const int32
 //    8-9   lo x of slots 0-3, 4-7 (one byte per slot)     10-11 lo y     12-13 lo z
 //    14-15 hi x                                            16-17 hi y     18-19 hi z
 // An empty slot has lo = 255 > hi = 0 on every axis and is in neither mask.
-struct Bvh8Result {
-    std::vector<uint32_t> nodes;       // 20 dwords (80 B) per node
-    std::vector<uint32_t> tri_order;   // tri_order[i] = input triangle stored at leaf-order slot i
-    uint32_t node_count = 0;
-    uint32_t max_depth = 0;            // in 8-wide nodes
-    uint32_t stack_bound = 0;          // entries a traversal can ever hold: one group per level + the marker
-    float scene_lo[3] = { 0, 0, 0 }, scene_hi[3] = { 0, 0, 0 };
-};
-enum { BVH8_NODE_DWORDS = 20 };
-void build_bvh8q(const float * verts, uint32_t n_tris, uint32_t leaf_max, uint32_t threads, Bvh8Result * out, float trav_cost = 1.0f,
-                 const BvhBuildOptions * opt = nullptr);
-void build_bvh8q_from_radix_tree(uint32_t n_tris, uint32_t leaf_max, const int32_t * left, const int32_t * right,
-                                 const uint32_t * first, const uint32_t * last, const float * node_box, const float * leaf_box,
-                                 const uint32_t * sorted_ids, Bvh8Result * out, const BvhBuildOptions * opt = nullptr);
+typedef BvhWide Bvh8Result;
+
+// width: 4 or 8 children per node.  verts: 9 floats per triangle (a, b, c).  leaf_max <= 4 (2 bits in the leaf link).
+void build_bvh_wide(int width, const float * verts, uint32_t n_tris, uint32_t leaf_max, uint32_t threads, BvhWide * out,
+                    float trav_cost = 1.0f, const BvhBuildOptions * opt = nullptr);
+
+// The same result from a binary radix tree built elsewhere (GPU LBVH, bvh_lbvh.h); see bvh_build.cpp.
+void build_bvh_wide_from_radix_tree(int width, uint32_t n_tris, uint32_t leaf_max, const int32_t * left, const int32_t * right,
+                                    const uint32_t * first, const uint32_t * last, const float * node_box, const float * leaf_box,
+                                    const uint32_t * sorted_ids, BvhWide * out, const BvhBuildOptions * opt = nullptr);
+
+// bvh_check.cpp.  Every address the traversal kernels will form from the tree, checked on the host before the tree is
+// uploaded: a message naming the first node link or triangle range outside the arrays, or NULL.  O(nodes), links only.
+const char * validate_bvh_links(const BvhWide & bvh, uint32_t n_tris);
+
+// bvh_check.cpp.  The full geometric check: every triangle lies inside the de-quantised box of every ancestor and is
+// referenced by exactly one leaf, and the layout's own invariants hold.  out[0] = violations, out[1] = nodes,
+// out[2] = depth, out[3] = stack bound, out[4] = leaves, out[5] = triangles referenced.
+void check_bvh_wide(const float * verts, uint32_t n_tris, const BvhWide & bvh, uint64_t * out);
 
 }  // namespace prt

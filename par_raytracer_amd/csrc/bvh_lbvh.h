@@ -4,9 +4,9 @@
 // this is the fast alternative for scenes that change between frames: Morton codes of the triangle centroids (21 bits per
 // axis), a device radix sort, Karras' parallel radix-tree construction (one lane per internal node, longest common
 // prefix of neighbouring keys, ties broken by position) and a bottom-up box fit (one lane per triangle climbs while it
-// is the second child to arrive).  The tree comes back to the host, where the same collapse-to-4-wide / quantise back
-// end as the SAH builder turns it into the 64 B nodes the traversal kernels read (bvh_build.cpp
-// build_bvh4q_from_radix_tree).  Any conservative tree gives the same image; this one is built ~10x
+// is the second child to arrive).  The tree comes back to the host, where the same collapse / quantise back end as the
+// SAH builder turns it into the wide nodes the traversal kernels read (bvh_build.cpp
+// build_bvh_wide_from_radix_tree).  Any conservative tree gives the same image; this one is built ~10x
 // faster and traverses slower (§6).
 #pragma once
 
@@ -20,7 +20,7 @@
 
 namespace prt {
 
-struct LbvhTree {                        // host copies of the device result, see build_bvh4q_from_radix_tree
+struct LbvhTree {                        // host copies of the device result, see build_bvh_wide_from_radix_tree
     std::vector<int32_t> left, right;
     std::vector<uint32_t> first, last;
     std::vector<float> node_box, leaf_box;

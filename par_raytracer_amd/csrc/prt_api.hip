@@ -50,15 +50,7 @@ using namespace prt;
 
 // The acceleration structure the library is built with (dev_trace.h): the 4-wide sorted tree, or -DPRT_BVH8 the 8-wide one
 // of round 3.
-#if !defined(PRT_BVH8)
-typedef Bvh4Result BvhWide;
-#define PRT_BUILD_WIDE build_bvh4q
-#define PRT_BUILD_WIDE_FROM_RADIX build_bvh4q_from_radix_tree
-#else
-typedef Bvh8Result BvhWide;
-#define PRT_BUILD_WIDE build_bvh8q
-#define PRT_BUILD_WIDE_FROM_RADIX build_bvh8q_from_radix_tree
-#endif
+enum { BVH_WIDTH = BVH_NODE_BYTES == 4 * BVH8_NODE_DWORDS ? 8 : 4 };
 
 namespace {
 
@@ -713,48 +705,10 @@ int build_bvh_lbvh(prt_ctx * ctx, const float * verts, uint32_t n_tris, uint32_t
     LbvhTree tree;
     double device_ms = 0.0;
     HIP_TRY(ctx, build_lbvh_tree(verts, n_tris, lo, hi, ctx->stream, &tree, &device_ms));
-    PRT_BUILD_WIDE_FROM_RADIX(n_tris, leaf_max, tree.left.data(), tree.right.data(), tree.first.data(), tree.last.data(),
-                              tree.node_box.data(), tree.leaf_box.data(), tree.sorted_ids.data(), bvh, &ctx->opt.bvh);
+    build_bvh_wide_from_radix_tree(BVH_WIDTH, n_tris, leaf_max, tree.left.data(), tree.right.data(), tree.first.data(), tree.last.data(),
+                                   tree.node_box.data(), tree.leaf_box.data(), tree.sorted_ids.data(), bvh, &ctx->opt.bvh);
     if (ctx->opt.debug_util) fprintf(stderr, "[prt] LBVH: %u triangles, radix tree on the device in %.2f ms\n", n_tris, device_ms);
     return 0;
-}
-
-// Every address the traversal kernels will form from the tree is checked HERE, on the host, before the tree is uploaded: a
-// node link or a triangle range outside the arrays would be a wild read on the device - which the runtime reports by
-// aborting the process (the round-3 abort) - and is an upload error instead.  O(nodes), links only;
-// prt_debug_check_bvh is the full geometric check.
-const char * validate_bvh_links(const Bvh4Result & bvh, uint32_t n_tris) {
-    if (bvh.node_count == 0 || bvh.nodes.size() != (size_t)bvh.node_count * 16) return "4-wide BVH: node array size does not match the node count";
-    if (bvh.tri_order.size() != n_tris) return "4-wide BVH: triangle order does not cover the triangles";
-    for (uint32_t ni = 0; ni < bvh.node_count; ++ni)
-        for (int k = 0; k < 4; ++k) {
-            const int32_t link = (int32_t)bvh.nodes[(size_t)ni * 16 + 10 + k];
-            if (link >= 0) {
-                if ((uint32_t)link >= bvh.node_count || (uint32_t)link <= ni) return "4-wide BVH: child link out of range (children follow their parent in breadth-first order)";
-            } else {
-                const uint32_t leaf = (uint32_t)~link, first = leaf >> 2, cnt = (leaf & 3u) + 1u;
-                // an empty slot points at the all-zero dummy record behind the last triangle
-                if (first > n_tris || (first < n_tris && first + cnt > n_tris)) return "4-wide BVH: leaf triangle range out of range";
-            }
-        }
-    return nullptr;
-}
-const char * validate_bvh_links(const Bvh8Result & bvh, uint32_t n_tris) {
-    if (bvh.node_count == 0 || bvh.nodes.size() != (size_t)bvh.node_count * BVH8_NODE_DWORDS) return "8-wide BVH: node array size does not match the node count";
-    if (bvh.tri_order.size() != n_tris) return "8-wide BVH: triangle order does not cover the triangles";
-    for (uint32_t ni = 0; ni < bvh.node_count; ++ni) {
-        const uint32_t * d = &bvh.nodes[(size_t)ni * BVH8_NODE_DWORDS];
-        const uint32_t imask = d[3] & 0xFFu, lmask = d[3] >> 8 & 0xFFu, c0 = d[6] & 0xFFu, c1 = d[6] >> 8 & 0xFFu;
-        if (imask & lmask) return "8-wide BVH: a slot is both an internal node and a leaf";
-        uint32_t n_child = 0, n_leaf_tris = 0;
-        for (uint32_t sl = 0; sl < 8; ++sl) {
-            n_child += imask >> sl & 1u;
-            if (lmask >> sl & 1u) n_leaf_tris += 1u + (c0 >> sl & 1u) + 2u * (c1 >> sl & 1u);
-        }
-        if (n_child && ((uint64_t)d[4] + n_child > bvh.node_count || d[4] <= ni)) return "8-wide BVH: child range out of range";
-        if (n_leaf_tris && (uint64_t)d[5] + n_leaf_tris > (uint64_t)n_tris + (n_tris == 0 ? 1u : 0u)) return "8-wide BVH: leaf triangle range out of range";
-    }
-    return nullptr;
 }
 
 int render_pixels(prt_ctx * ctx, const prt_camera * cam_in, const prt_params * params, uint32_t width, uint32_t height,
@@ -1541,9 +1495,10 @@ int prt_upload_scene(prt_ctx * ctx, const prt_scene_desc * s) {
         int rc = build_bvh_lbvh(ctx, verts.data(), n_tris, leaf_max, &bvh);
         if (rc) return rc;
     } else {
-        PRT_BUILD_WIDE(verts.data(), n_tris, leaf_max, std::min(hw, 16u), &bvh, trav_cost, &ctx->opt.bvh);
+        build_bvh_wide(BVH_WIDTH, verts.data(), n_tris, leaf_max, std::min(hw, 16u), &bvh, trav_cost, &ctx->opt.bvh);
     }
     double build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    // every address the traversal kernels will form from the tree is checked on the host before the tree is uploaded (bvh_check.cpp)
     if (const char * bad = validate_bvh_links(bvh, n_tris)) { ctx->error = std::string("prt_upload_scene: the builder produced a broken tree - ") + bad; return -9; }
 
     // ---- reference visit rank: leaves of the sphere tree in the order TraceRay pops them (c1 first)
@@ -1986,160 +1941,9 @@ int prt_debug_device_kat(prt_ctx * ctx, int kind, const void * in, size_t in_byt
     PRT_API_CATCH_RC(ctx, "prt_debug_device_kat")
 }
 
-// Host-only self check of the acceleration structure (no GPU needed; used by the CPU test-suite): builds the
-// quantised 4-wide BVH for `scene` exactly as prt_upload_scene does and verifies that every triangle lies
-// inside the de-quantised box of every ancestor, that every triangle is referenced by exactly one leaf and
-// that links are in range.  out[0] = violations, out[1] = nodes, out[2] = depth, out[3] = stack bound,
-// out[4] = leaves, out[5] = triangles referenced.
-static int check_bvh4q(const std::vector<float> & verts, uint32_t n_tris, const Bvh4Result & bvh, uint64_t * out) {
-    uint64_t violations = 0, leaves = 0, refs = 0;
-    std::vector<uint8_t> seen(std::max(1u, n_tris), 0);
-    struct Item { uint32_t node; float lo[3], hi[3]; };
-    std::vector<Item> stack;
-    Item root;
-    root.node = 0;
-    for (int a = 0; a < 3; ++a) { root.lo[a] = -3.0e38f; root.hi[a] = 3.0e38f; }
-    stack.push_back(root);
-    while (!stack.empty()) {
-        Item it = stack.back();
-        stack.pop_back();
-        if (it.node >= bvh.node_count) { violations++; continue; }
-        const uint32_t * d = &bvh.nodes[(size_t)it.node * 16];
-        float org[3], scale[3];
-        const int scale_dword[3] = { 3, 14, 15 };
-        for (int a = 0; a < 3; ++a) {
-            memcpy(&org[a], &d[a], 4);
-            memcpy(&scale[a], &d[scale_dword[a]], 4);
-            if ((d[scale_dword[a]] & 0x807FFFFFu) != 0u || d[scale_dword[a]] == 0u) violations++;      // a positive power of two
-        }
-        uint32_t count = 0;                                  // children come first; an empty slot has inverted planes on every axis
-        while (count < 4 && !(((d[4] >> (8 * count)) & 0xFFu) == 255u && ((d[7] >> (8 * count)) & 0xFFu) == 0u)) ++count;
-        if (count < 1) violations++;
-        for (uint32_t k = 0; k < 4; ++k) {
-            Item ch;
-            if (k >= count) {
-                // empty slot: inverted box on every axis and a link to the dummy leaf
-                const int32_t el = (int32_t)d[10 + k];
-                if (el >= 0 || ((uint32_t)~el >> 2) != n_tris) violations++;
-                for (int a = 0; a < 3; ++a) if (((d[4 + a] >> (8 * k)) & 0xFFu) != 255u || ((d[7 + a] >> (8 * k)) & 0xFFu) != 0u) violations++;
-                continue;
-            }
-            for (int a = 0; a < 3; ++a) {
-                ch.lo[a] = std::max(it.lo[a], org[a] + (float)((d[4 + a] >> (8 * k)) & 0xFFu) * scale[a]);
-                ch.hi[a] = std::min(it.hi[a], org[a] + (float)((d[7 + a] >> (8 * k)) & 0xFFu) * scale[a]);
-            }
-            const int32_t link = (int32_t)d[10 + k];
-            if (link >= 0) {
-                ch.node = (uint32_t)link;
-                stack.push_back(ch);
-            } else {
-                const uint32_t leaf = (uint32_t)~link, first = leaf >> 2, cnt = (leaf & 3u) + 1u;
-                leaves++;
-                for (uint32_t i = 0; i < cnt; ++i) {
-                    const uint32_t slot = first + i;
-                    if (slot == n_tris) continue;                       // the dummy triangle of an empty slot
-                    if (slot > n_tris) { violations++; continue; }
-                    refs++;
-                    if (seen[slot]++) violations++;
-                    const uint32_t t = bvh.tri_order[slot];
-                    for (int c = 0; c < 3; ++c)
-                        for (int a = 0; a < 3; ++a) {
-                            const float v = verts[(size_t)t * 9 + 3 * c + a];
-                            // de-quantised planes may round by an ulp of the coordinate; the kernels widen every box
-                            // by 2^-16 of the scene extent, far more than that
-                            const float tol = 4.0f * 1.1920929e-7f * std::max(1.0f, fabsf(v));
-                            if (v < ch.lo[a] - tol || v > ch.hi[a] + tol) violations++;
-                        }
-                }
-            }
-        }
-    }
-    for (uint32_t t = 0; t < n_tris; ++t) if (!seen[t]) violations++;
-    out[0] = violations; out[1] = bvh.node_count; out[2] = bvh.max_depth; out[3] = bvh.stack_bound; out[4] = leaves; out[5] = refs;
-    return 0;
-}
-
-// The same for the 8-wide tree (bvh_build.h Bvh8Result): masks disjoint, empty slots inverted, scales positive powers of two,
-// implicit child / triangle addresses in range, every triangle inside every ancestor's box and in exactly one leaf.
-static int check_bvh8q(const std::vector<float> & verts, uint32_t n_tris, const Bvh8Result & bvh, uint64_t * out) {
-    uint64_t violations = 0, leaves = 0, refs = 0;
-    std::vector<uint8_t> seen(std::max(1u, n_tris), 0);
-    std::vector<uint8_t> node_seen(std::max(1u, bvh.node_count), 0);
-    struct Item { uint32_t node; float lo[3], hi[3]; };
-    std::vector<Item> stack;
-    Item root;
-    root.node = 0;
-    for (int a = 0; a < 3; ++a) { root.lo[a] = -3.0e38f; root.hi[a] = 3.0e38f; }
-    stack.push_back(root);
-    while (!stack.empty()) {
-        Item it = stack.back();
-        stack.pop_back();
-        if (it.node >= bvh.node_count) { violations++; continue; }
-        if (node_seen[it.node]++) { violations++; continue; }
-        const uint32_t * d = &bvh.nodes[(size_t)it.node * BVH8_NODE_DWORDS];
-        float org[3], scale[3];
-        const int scale_dword[3] = { 3, 6, 7 };
-        for (int a = 0; a < 3; ++a) {
-            memcpy(&org[a], &d[a], 4);
-            const uint32_t sb = d[scale_dword[a]] & 0x7F800000u;
-            memcpy(&scale[a], &sb, 4);
-            if (sb == 0u || (d[scale_dword[a]] & 0x80000000u)) violations++;      // a positive power of two
-        }
-        const uint32_t imask = d[3] & 0xFFu, lmask = d[3] >> 8 & 0xFFu, c0 = d[6] & 0xFFu, c1 = d[6] >> 8 & 0xFFu;
-        if (imask & lmask) violations++;
-        if ((c0 | c1) & ~lmask) violations++;
-        if (!(imask | lmask)) violations++;
-        uint32_t next_child = d[4], next_tri = d[5];
-        for (uint32_t sl = 0; sl < 8; ++sl) {
-            uint32_t qlo[3], qhi[3];
-            for (int a = 0; a < 3; ++a) {
-                qlo[a] = d[8 + 2 * a + (sl >> 2)] >> (8 * (sl & 3u)) & 0xFFu;
-                qhi[a] = d[14 + 2 * a + (sl >> 2)] >> (8 * (sl & 3u)) & 0xFFu;
-            }
-            if (!((imask | lmask) >> sl & 1u)) {
-                for (int a = 0; a < 3; ++a) if (qlo[a] != 255u || qhi[a] != 0u) violations++;
-                continue;
-            }
-            Item ch;
-            for (int a = 0; a < 3; ++a) {
-                ch.lo[a] = std::max(it.lo[a], org[a] + (float)qlo[a] * scale[a]);
-                ch.hi[a] = std::min(it.hi[a], org[a] + (float)qhi[a] * scale[a]);
-            }
-            if (imask >> sl & 1u) {
-                ch.node = next_child++;
-                stack.push_back(ch);
-            } else {
-                const uint32_t cnt = 1u + (c0 >> sl & 1u) + 2u * (c1 >> sl & 1u);
-                leaves++;
-                for (uint32_t i = 0; i < cnt; ++i) {
-                    const uint32_t slot = next_tri++;
-                    if (slot == n_tris && n_tris == 0) continue;        // the dummy triangle of an empty scene
-                    if (slot >= n_tris) { violations++; continue; }
-                    refs++;
-                    if (seen[slot]++) violations++;
-                    const uint32_t t = bvh.tri_order[slot];
-                    for (int c = 0; c < 3; ++c)
-                        for (int a = 0; a < 3; ++a) {
-                            const float v = verts[(size_t)t * 9 + 3 * c + a];
-                            const float tol = 4.0f * 1.1920929e-7f * std::max(1.0f, fabsf(v));
-                            if (v < ch.lo[a] - tol || v > ch.hi[a] + tol) violations++;
-                        }
-                }
-            }
-        }
-    }
-    for (uint32_t t = 0; t < n_tris; ++t) if (!seen[t]) violations++;
-    for (uint32_t n = 0; n < bvh.node_count; ++n) if (!node_seen[n]) violations++;
-    out[0] = violations; out[1] = bvh.node_count; out[2] = bvh.max_depth; out[3] = bvh.stack_bound; out[4] = leaves; out[5] = refs;
-    return 0;
-}
-
-#if !defined(PRT_BVH8)
-static int check_bvh_wide(const std::vector<float> & verts, uint32_t n_tris, const BvhWide & bvh, uint64_t * out) { return check_bvh4q(verts, n_tris, bvh, out); }
-#else
-static int check_bvh_wide(const std::vector<float> & verts, uint32_t n_tris, const BvhWide & bvh, uint64_t * out) { return check_bvh8q(verts, n_tris, bvh, out); }
-#endif
-
+// Host-only self check of the acceleration structure (no GPU needed; used by the CPU test-suite): builds the wide BVH for
+// `scene` exactly as prt_upload_scene does and runs the link validation and the geometric check of bvh_check.cpp on it
+// (out[0..5]: bvh_build.h check_bvh_wide).
 int prt_debug_check_bvh(const prt_scene_desc * s, uint64_t * out) {
     PRT_API_TRY
     if (!s || !out || s->index_count % 3) return -1;
@@ -2150,9 +1954,10 @@ int prt_debug_check_bvh(const prt_scene_desc * s, uint64_t * out) {
     PrtOptions opt;
     prt_options_from_env(opt);                  // the test-suite selects the collapse rule through the environment
     BvhWide bvh;
-    PRT_BUILD_WIDE(verts.data(), n_tris, BVH_LEAF_MAX, 4, &bvh, 1.0f, &opt.bvh);
+    build_bvh_wide(BVH_WIDTH, verts.data(), n_tris, BVH_LEAF_MAX, 4, &bvh, 1.0f, &opt.bvh);
     if (validate_bvh_links(bvh, n_tris)) return -9;          // what prt_upload_scene checks before it uploads a tree
-    return check_bvh_wide(verts, n_tris, bvh, out);
+    check_bvh_wide(verts.data(), n_tris, bvh, out);
+    return 0;
     PRT_API_CATCH_RC(nullptr, "prt_debug_check_bvh")
 }
 
@@ -2169,7 +1974,8 @@ int prt_debug_check_bvh_lbvh(prt_ctx * ctx, const prt_scene_desc * s, uint64_t *
     int rc = build_bvh_lbvh(ctx, verts.data(), n_tris, BVH_LEAF_MAX, &bvh);
     if (rc) return rc;
     if (const char * bad = validate_bvh_links(bvh, n_tris)) { ctx->error = bad; return -9; }
-    return check_bvh_wide(verts, n_tris, bvh, out);
+    check_bvh_wide(verts.data(), n_tris, bvh, out);
+    return 0;
     PRT_API_CATCH_RC(ctx, "prt_debug_check_bvh_lbvh")
 }
 

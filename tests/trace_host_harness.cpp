@@ -5,7 +5,7 @@
 // axis) returns, for every ray, exactly the hit the reference's sequential filter returns over ALL triangles
 // in visit order (raytracer.cpp:104, 149, 208-220) - t, barycentrics and triangle bit for bit, near ties included - and
 // that any-hit rays agree on occluded / not occluded.  Scene: a wavy height field plus floating, doubled and coplanar
-// triangles.  Built and run by tests/test_trace_host.py.
+// triangles (harness_scene.h).  Built and run by tests/test_trace_host.py.
 //
 //   g++ -O1 -std=c++17 -ffp-contract=off -Itests/hip_shim -Ipar_raytracer_amd/csrc tests/trace_host_harness.cpp \
 //       par_raytracer_amd/csrc/bvh_build.cpp -pthread -o /tmp/trace_host && /tmp/trace_host
@@ -16,47 +16,22 @@
 #include "dev_trace.h"
 #include "bvh_build.h"
 #include "prt_options.h"
+#include "harness_scene.h"
 
 using namespace prt;
-
-static uint64_t g_rng = 0x243F6A8885A308D3ull;
-static double rnd() { g_rng ^= g_rng << 13; g_rng ^= g_rng >> 7; g_rng ^= g_rng << 17; return (double)(g_rng >> 11) / 9007199254740992.0; }
 
 int main(int argc, char ** argv) {
     const int grid = argc > 1 ? atoi(argv[1]) : 48;
     const int n_rays = argc > 2 ? atoi(argv[2]) : 20000;
-    std::vector<float> verts;
-    auto tri = [&](float ax, float ay, float az, float bx, float by, float bz, float cx, float cy, float cz) {
-        const float v[9] = { ax, ay, az, bx, by, bz, cx, cy, cz };
-        verts.insert(verts.end(), v, v + 9);
-    };
-    auto height = [](float x, float z) { return 0.35f * sinf(x * 0.9f) * cosf(z * 0.7f) + 0.1f * sinf(x * 3.1f + z * 2.3f); };
-    for (int i = 0; i < grid; ++i)
-        for (int j = 0; j < grid; ++j) {
-            const float x0 = i * 0.25f - grid * 0.125f, x1 = x0 + 0.25f, z0 = j * 0.25f - grid * 0.125f, z1 = z0 + 0.25f;
-            tri(x0, height(x0, z0), z0, x0, height(x0, z1), z1, x1, height(x1, z0), z0);            // counter-clockwise seen from +y
-            tri(x1, height(x1, z0), z0, x0, height(x0, z1), z1, x1, height(x1, z1), z1);
-        }
-    for (int k = 0; k < 300; ++k) {                          // floating triangles, some of them twice (coincident copies)
-        const float cx = (float)(rnd() * 8 - 4), cy = (float)(rnd() * 2 + 0.3), cz = (float)(rnd() * 8 - 4);
-        float p[9];
-        for (int q = 0; q < 9; ++q) p[q] = (float)(rnd() - 0.5) * 0.8f;
-        tri(cx + p[0], cy + p[1], cz + p[2], cx + p[3], cy + p[4], cz + p[5], cx + p[6], cy + p[7], cz + p[8]);
-        if (k % 5 == 0) tri(cx + p[0], cy + p[1], cz + p[2], cx + p[3], cy + p[4], cz + p[5], cx + p[6], cy + p[7], cz + p[8]);
-    }
-    for (int k = 0; k < 40; ++k) {                           // coplanar overlapping patches at y = 1.5 (decals)
-        const float cx = (float)(rnd() * 6 - 3), cz = (float)(rnd() * 6 - 3), s = (float)(rnd() * 0.8 + 0.2);
-        tri(cx, 1.5f, cz, cx, 1.5f, cz + s, cx + s, 1.5f, cz);
-    }
+    const std::vector<float> verts = harness_scene(grid);
     const uint32_t n_tris = (uint32_t)(verts.size() / 9);
 
+    BvhWide bvh;
 #if !defined(PRT_BVH8)
-    Bvh4Result bvh;
-    build_bvh4q(verts.data(), n_tris, 4, 2, &bvh);
+    build_bvh_wide(4, verts.data(), n_tris, 4, 2, &bvh);
 #else
-    Bvh8Result bvh;
     BvhBuildOptions bopt;
-    build_bvh8q(verts.data(), n_tris, 4, 2, &bvh, 1.0f, &bopt);
+    build_bvh_wide(8, verts.data(), n_tris, 4, 2, &bvh, 1.0f, &bopt);
 #endif
     // device records, as prt_upload_scene lays them out
     std::vector<float4> tris((size_t)(n_tris + 1) * 3, make_float4(0, 0, 0, 0));

@@ -199,11 +199,11 @@ int main(int argc, char ** argv) {
     Bvh4Result b4;
     Bvh8Result b8;
     const uint32_t leaf_max = getenv("PRICE_LEAF_MAX") ? (uint32_t)atoi(getenv("PRICE_LEAF_MAX")) : 4u;
-    build_bvh4q(g_verts.data(), n_tris, 4, 8, &b4);
+    build_bvh_wide(4, g_verts.data(), n_tris, 4, 8, &b4);
     BvhBuildOptions axis_opt;
     if (getenv("PRICE_WIDTH")) axis_opt.width = atoi(getenv("PRICE_WIDTH"));
     if (getenv("PRICE_AXIS_RULE")) axis_opt.axis_rule = atoi(getenv("PRICE_AXIS_RULE"));
-    build_bvh8q(g_verts.data(), n_tris, leaf_max, 8, &b8, 1.0f, &axis_opt);
+    build_bvh_wide(8, g_verts.data(), n_tris, leaf_max, 8, &b8, 1.0f, &axis_opt);
 
     // camera (main.cpp:145-177)
     const int W = 1920, H = 1080;
