@@ -292,6 +292,50 @@ int prt_trace_rays(prt_ctx * ctx, int mode, const prt_ray_batch * batch, const p
 int prt_trace_rays_device(prt_ctx * ctx, int mode, const prt_ray_batch * batch, const prt_hit_buffers * hits, uint32_t flags,
                           prt_counters * counters);
 
+/* ---- geometry updates: the uploaded scene's vertices move, the tree is refitted on the device ---------------------------
+ * For a caller that moves a mesh between frames or batches of queries (an animation, an optimisation loop over vertex
+ * positions).  The tree keeps its topology; the triangle records are rewritten from the new positions and every node's boxes
+ * are refitted bottom-up, one small kernel launch per tree level (csrc/kernels_refit.h; no lane waits for another workgroup).
+ * THE CONTRACT: after a successful update every render and every query of the context gives the bits prt_upload_scene would
+ * give, on the same context with the same options, for a prt_scene_desc that equals the uploaded one except for the fields
+ * passed here - any conservative tree gives the same image, and near ties are decided by the reference's visit ranks, not by the
+ * tree (DESIGN.md sections 2-3, 4.8).  Only the tree's quality may differ: node_visits and tri_tests are exempt from the
+ * equality; ray_count, shaded_hits, every pixel and every hit field are not.
+ *   positions      the new positions; position_count must equal the uploaded scene's (the index buffers stay the upload's, as do
+ *                  groups, materials, textures, lights and texture coordinates)
+ *   normals        NULL = keep the uploaded ones; else normal_count must equal the upload's
+ *   tangents       NULL = keep; else one per normal of the upload (with or without new normals); only read when the scene has
+ *                  bump maps
+ *   spheres, sphere_group, sphere_count
+ *                  HOST pointers in both entry points: the reference's hierarchy of the MOVED scene, or NULL / 0.  NULL means
+ *                  what it means at upload - visit ranks in input order, no spheres for the near-tie resolution; the spheres of
+ *                  the old geometry are never kept (they would not bound the moved groups).  A tree that cannot be walked falls
+ *                  back to input order, as at upload.
+ * prt_update_info: device_ms = the device time of the update (coordinate check, records, every level, the rank upload), levels
+ * = tree levels = refit launches, node_count, abs_max = the largest |coordinate| of a referenced position (it feeds the box pad).
+ * Stream contract of prt_render_device: the call returns after the context's stream has drained; for the device entry point the
+ * caller's work on positions / normals / tangents must have finished before the call.
+ * Errors: -1 NULL update or positions, a count that differs from the upload's, or a referenced coordinate that is not finite or
+ * not below 1e18 (the upload's rule) - found BEFORE anything of the scene is modified on the device: the scene then renders
+ * exactly as before the call; -2 no scene uploaded; -10 a HIP call failed - after the first write the context drops to "no
+ * scene" rather than render half-moved arrays.  A scene of 0 triangles is a successful no-op.
+ * The first update after an upload builds a leaf -> vertex indices table on the device (24 B per triangle, plus 24 B per node of
+ * scratch boxes; not in prt_scene_info.device_bytes; freed by the next upload).
+ * Out of scope: a change of topology (index buffers, groups: upload again); re-clustering a tree that large moves have degraded
+ * - the results stay exact, node_visits grows, and the caller uploads again when it says so -; texture coordinates. */
+typedef struct prt_geometry_update {
+    const float * positions;  uint32_t position_count;   /* xyz; count must equal the uploaded scene's */
+    const float * normals;    uint32_t normal_count;     /* optional (NULL = keep); count must equal the upload's */
+    const float * tangents;                              /* optional, per normal; only read when the scene has bump maps */
+    const prt_bsphere * spheres; const int32_t * sphere_group; uint32_t sphere_count;  /* HOST, always: the reference's
+                                 hierarchy of the MOVED scene, or NULL / 0 */
+} prt_geometry_update;
+typedef struct prt_update_info { double device_ms; uint32_t levels; uint32_t node_count; float abs_max; } prt_update_info;
+/* positions / normals / tangents are HOST arrays; info may be NULL. */
+int prt_update_geometry(prt_ctx * ctx, const prt_geometry_update * update, prt_update_info * info);
+/* positions / normals / tangents are DEVICE pointers on the context's device (hipMalloc'ed or torch tensors' data_ptr). */
+int prt_update_geometry_device(prt_ctx * ctx, const prt_geometry_update * update, prt_update_info * info);
+
 /* ---- several devices behind one handle --------------------------------------------------------------------------------
  * SURVEY.md 8(b)'s prt_create(const int * device_ids, int n_dev): what the host mirror's Render() uses for n GPUs, in place
  * of the reference's one-rank-per-core partition + MPI_Gather (main.cpp:311-347).  The scene is replicated (as every MPI rank
@@ -320,6 +364,8 @@ int prt_multi_device_count(const prt_multi * m);
 int prt_multi_depth(const prt_multi * m);                         /* frames that can be in flight at once */
 prt_ctx * prt_multi_context(prt_multi * m, int i);
 int prt_multi_upload_scene(prt_multi * m, const prt_scene_desc * scene);   /* not while a frame is in flight */
+/* prt_update_geometry (host arrays) on every device of the handle; PRT_ERR_IN_FLIGHT while a frame is in flight. */
+int prt_multi_update_geometry(prt_multi * m, const prt_geometry_update * update);
 int prt_multi_render(prt_multi * m, const prt_camera * cam, const prt_params * params, uint32_t width, uint32_t height,
                      float * rgba_out, prt_counters * counters);
 int prt_multi_submit(prt_multi * m, const prt_camera * cam, const prt_params * params, uint32_t width, uint32_t height,
@@ -404,6 +450,10 @@ int prt_debug_check_bvh(const prt_scene_desc * scene, uint64_t * out);
 /* The same check on the tree of the GPU LBVH builder (option BVH_BUILDER=lbvh at upload: radix tree built on the
  * device, bvh_lbvh.h; an alternative for scenes that change every frame - ~10x faster to build, slower to traverse). */
 int prt_debug_check_bvh_lbvh(prt_ctx * ctx, const prt_scene_desc * scene, uint64_t * out);
+/* The same check on the tree as it lies on the context's device NOW - after any number of prt_update_geometry calls -
+ * against the un-indexed triangles of moved_scene (its positions and idx_positions; the triangle count must be the uploaded
+ * scene's): the GPU test-suite's geometric proof that a refitted tree is conservative. */
+int prt_debug_check_refit(prt_ctx * ctx, const prt_scene_desc * moved_scene, uint64_t * out);
 
 /* Device known-answer hook (GPU test-suite): runs one device function of the hot path on `n` caller-supplied
  * records (host pointers) and returns its outputs, so tests can compare them bit for bit with the reference's.

@@ -11,7 +11,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 from . import capi
-from .capi import PrtCamera, PrtCounters, PrtParams, PrtSceneDesc, PrtSceneInfo
+from .capi import PrtCamera, PrtCounters, PrtParams, PrtSceneDesc, PrtSceneInfo, PrtUpdateInfo
 
 
 class HostScene:
@@ -399,6 +399,76 @@ class Renderer:
                     "prt_trace_rays_device" if is_torch else "prt_trace_rays")
         out["counters"] = counters
         return out
+
+    def update_geometry(self, positions, normals=None, tangents=None, spheres=None, sphere_group=None) -> PrtUpdateInfo:
+        """Move the uploaded scene's vertices in place and refit the tree on the device (prt_update_geometry, include/prt.h):
+        afterwards renders and queries give the bits a fresh upload of the moved scene would.
+
+        positions (and optionally normals, tangents): float32 (n, 3) or flat, contiguous, with the uploaded scene's counts - numpy
+        arrays (host entry point) or torch tensors on this context's device (device entry point).  spheres, sphere_group: the
+        reference's hierarchy of the MOVED scene as HOST data - the raw prt_bsphere bytes and int32 groups of api.desc_arrays(),
+        or ctypes pointers with a count as (pointer, count) - or None (ranks in input order, as an upload without spheres)."""
+        is_torch = type(positions).__module__.split(".")[0] == "torch"
+        keep = []
+        if is_torch:
+            import torch
+
+            def conv(x, what):
+                if x is None:
+                    return None, 0
+                if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or not x.is_contiguous():
+                    raise ValueError("%s must be a contiguous float32 torch tensor" % what)
+                if x.device.type != "cuda" or (x.device.index or 0) != self.device_id:
+                    raise ValueError("%s must live on this context's device (cuda:%d)" % (what, self.device_id))
+                if x.numel() % 3:
+                    raise ValueError("%s has %d floats, not a multiple of 3" % (what, x.numel()))
+                keep.append(x)
+                return x.data_ptr(), x.numel() // 3
+            # the library's stream is not ordered against torch's: whatever torch still has queued on the inputs must be done
+            torch.cuda.current_stream(positions.device).synchronize()
+            entry, name = self._lib.prt_update_geometry_device, "prt_update_geometry_device"
+        else:
+            def conv(x, what):
+                if x is None:
+                    return None, 0
+                a = np.asarray(x)
+                if a.dtype != np.float32 or not a.flags["C_CONTIGUOUS"]:
+                    raise ValueError("%s must be a contiguous float32 array" % what)
+                if a.size % 3:
+                    raise ValueError("%s has %d floats, not a multiple of 3" % (what, a.size))
+                keep.append(a)
+                return a.ctypes.data, a.size // 3
+            entry, name = self._lib.prt_update_geometry, "prt_update_geometry"
+        u = capi.PrtGeometryUpdate()
+        u.positions, u.position_count = conv(positions, "positions")
+        u.normals, u.normal_count = conv(normals, "normals")
+        u.tangents, n_tan = conv(tangents, "tangents")
+        if tangents is not None and normals is not None and n_tan != u.normal_count:
+            raise ValueError("tangents come one per normal")
+        if spheres is not None and sphere_group is not None:
+            if isinstance(spheres, tuple):
+                (sp, count), sg = spheres, sphere_group
+                u.spheres, u.sphere_group, u.sphere_count = sp, sg, int(count)
+            else:
+                sp = np.ascontiguousarray(np.asarray(spheres)).view(np.uint8).reshape(-1)
+                sg = np.ascontiguousarray(np.asarray(sphere_group), dtype=np.int32).reshape(-1)
+                if sp.size != sg.size * C.sizeof(capi.PrtBSphere):
+                    raise ValueError("spheres holds %d bytes for %d sphere groups" % (sp.size, sg.size))
+                keep += [sp, sg]
+                if sg.size:
+                    u.spheres = sp.ctypes.data_as(C.POINTER(capi.PrtBSphere))
+                    u.sphere_group = sg.ctypes.data_as(C.POINTER(C.c_int32))
+                    u.sphere_count = sg.size
+        info = PrtUpdateInfo()
+        self._check(entry(self._ctx, C.byref(u), C.byref(info)), name)
+        return info
+
+    def check_refit(self, moved_scene) -> dict:
+        """prt_debug_check_refit: the geometric BVH check on the tree as it lies on the device now, against moved_scene's triangles."""
+        desc = moved_scene.desc if isinstance(moved_scene, (HostScene, FlatDesc)) else moved_scene
+        out = (C.c_uint64 * 6)()
+        self._check(self._lib.prt_debug_check_refit(self._ctx, desc, out), "prt_debug_check_refit")
+        return dict(zip(("violations", "nodes", "depth", "stack_bound", "leaves", "refs"), (int(v) for v in out)))
 
     def close(self):
         if self._ctx:

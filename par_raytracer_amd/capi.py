@@ -105,6 +105,19 @@ class PrtHitBuffers(C.Structure):
                 ("position", C.c_void_p), ("normal", C.c_void_p), ("occluded", C.c_void_p)]
 
 
+class PrtGeometryUpdate(C.Structure):
+    _fields_ = [("positions", C.c_void_p), ("position_count", C.c_uint32), ("normals", C.c_void_p), ("normal_count", C.c_uint32),
+                ("tangents", C.c_void_p), ("spheres", C.POINTER(PrtBSphere)), ("sphere_group", C.POINTER(C.c_int32)),
+                ("sphere_count", C.c_uint32)]
+
+
+class PrtUpdateInfo(C.Structure):
+    _fields_ = [("device_ms", C.c_double), ("levels", C.c_uint32), ("node_count", C.c_uint32), ("abs_max", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 QUERY_CLOSEST, QUERY_OCCLUDED = 0, 1
 PIPELINE_DEFAULT, PIPELINE_MEGAKERNEL, PIPELINE_WAVEFRONT, PIPELINE_PERSISTENT, PIPELINE_POOL = 0, 1, 2, 3, 4
 FLAG_COUNT_VISITS = 0x100
@@ -116,7 +129,8 @@ PRT_SYMBOLS = ["prt_create", "prt_destroy", "prt_last_error", "prt_abi_version",
                "prt_render_device", "prt_shard_rows", "prt_render_shard_device", "prt_render_shard", "prt_render_pixel_list", "prt_get_scene_info", "prt_get_render_stats", "prt_debug_check_bvh", "prt_debug_check_bvh_lbvh", "prt_debug_device_kat",
                "prt_multi_create", "prt_multi_destroy", "prt_multi_last_error", "prt_multi_device_count", "prt_multi_context",
                "prt_multi_upload_scene", "prt_multi_render", "prt_multi_depth", "prt_multi_submit", "prt_multi_wait", "prt_debug_throw",
-               "prt_trace_rays", "prt_trace_rays_device", "prt_get_region_stats"]
+               "prt_trace_rays", "prt_trace_rays_device", "prt_get_region_stats",
+               "prt_update_geometry", "prt_update_geometry_device", "prt_multi_update_geometry", "prt_debug_check_refit"]
 # PRT_REGION_* of include/prt.h, in index order (tests/test_host_side.py's header check keeps the symbol list in step; the
 # region test compares this list with the header's enum)
 REGION_NAMES = ["round", "topup", "topup_pass", "trace_outer", "refill", "walk_pass", "node_step", "node_descend", "node_pop", "node_push", "leaf",
@@ -198,6 +212,11 @@ def hip_lib() -> C.CDLL:
         lib.prt_trace_rays.argtypes = [C.c_void_p, C.c_int, C.POINTER(PrtRayBatch), C.POINTER(PrtHitBuffers), C.c_uint32,
                                        C.POINTER(PrtCounters)]
         lib.prt_trace_rays_device.argtypes = lib.prt_trace_rays.argtypes
+        if hasattr(lib, "prt_update_geometry"):        # (absent from a PRT_HIP_LIB build of an earlier commit: tools/refit_rate.py)
+            lib.prt_update_geometry.argtypes = [C.c_void_p, C.POINTER(PrtGeometryUpdate), C.POINTER(PrtUpdateInfo)]
+            lib.prt_update_geometry_device.argtypes = lib.prt_update_geometry.argtypes
+            lib.prt_multi_update_geometry.argtypes = [C.c_void_p, C.POINTER(PrtGeometryUpdate)]
+            lib.prt_debug_check_refit.argtypes = [C.c_void_p, C.POINTER(PrtSceneDesc), C.POINTER(C.c_uint64)]
         _hip = lib
     return _hip
 

@@ -29,6 +29,7 @@
 #include "bvh_lbvh.h"
 #include "kernels_debug.h"
 #include "kernels_query.h"
+#include "kernels_refit.h"
 
 using namespace prt;
 
@@ -175,6 +176,18 @@ struct prt_ctx {
     DevBuf<int> q_exact_stack;
     DevBuf<float> q_io;                   // host entry point: the batch and the requested fields on the device
     DevBuf<unsigned char> q_occ;
+    // geometry updates (prt_update_geometry, kernels_refit.h).  The upload keeps, on the host, the index buffers and the first
+    // node of every tree level; the first update builds the leaf slot -> vertex indices table from them (24 B per triangle; like
+    // q_leaf_map not in prt_scene_info.device_bytes, freed by the next upload).  The table and the scratch boxes are reused by
+    // later updates.
+    std::vector<uint32_t> rf_idx_positions, rf_idx_normals;
+    std::vector<unsigned int> rf_level_first;   // levels + 1 entries; empty: the tree is not level-ordered (never, for finish_wide's)
+    uint32_t rf_position_count = 0, rf_normal_count = 0;
+    bool rf_bumped = false;
+    DevBuf<unsigned int> rf_table;        // leaf slot -> three position indices, three normal indices
+    DevBuf<RefitBox> rf_boxes;            // every node's exact float box
+    DevBuf<unsigned int> rf_bounds;       // k_refit_bounds' two words
+    DevBuf<float> rf_in;                  // host entry point: positions, normals, tangents on the device
 };
 
 namespace {
@@ -1269,6 +1282,192 @@ int api_exception(std::string * err, const char * where) noexcept {
 #define PRT_API_CATCH_PTR(where) } catch (...) { (void)api_exception(&g_create_error, where); return nullptr; }
 #define PRT_API_CATCH_VOID } catch (...) {}
 
+// =============================================================================================================
+// Shared by prt_upload_scene and prt_update_geometry.
+namespace {
+
+// The reference's visit rank of every input triangle - the leaves of its sphere tree in the order TraceRay pops them (c1
+// first), ascending index inside a group - and the tree as the device's near-tie resolution reads it (RefSphereWalk).  Without
+// a usable tree (none given, a cycle, a group named twice, triangles left over): input order, and no spheres.
+void reference_ranks(const prt_group * groups, uint32_t group_count, const prt_bsphere * spheres, const int32_t * sphere_group,
+                     uint32_t sphere_count, uint32_t n_tris, std::vector<uint32_t> & rank_of_input, std::vector<float4> & ref_spheres) {
+    rank_of_input.assign(n_tris, 0u);
+    ref_spheres.clear();
+    std::vector<uint32_t> group_base(group_count, 0);
+    bool ranked = false;
+    if (spheres && sphere_group && sphere_count) {
+        std::vector<uint32_t> stack(1, 0u);
+        std::vector<uint8_t> seen(group_count, 0);
+        std::vector<uint32_t> first_rank(sphere_count, 0), pop_order(sphere_count, 0);
+        std::vector<uint8_t> popped(sphere_count, 0);
+        uint32_t next = 0, visited = 0;
+        bool ok = true;
+        while (!stack.empty() && ok) {
+            uint32_t i = stack.back();
+            stack.pop_back();
+            if (i >= sphere_count || ++visited > 2 * sphere_count || popped[i]) { ok = false; break; }
+            popped[i] = 1;
+            pop_order[i] = visited - 1;
+            first_rank[i] = next;                         // the first triangle the reference meets below this sphere
+            const prt_bsphere & bs = spheres[i];
+            if (bs.c0 && bs.c1) {
+                stack.push_back(bs.c0);
+                stack.push_back(bs.c1);
+            } else {
+                int32_t g = sphere_group[i];
+                if (g < 0 || (uint32_t)g >= group_count || seen[g]) { ok = false; break; }
+                seen[g] = 1;
+                group_base[g] = next;
+                next += groups[g].index_count / 3;
+            }
+        }
+        ranked = ok && next == n_tris;
+        if (ranked) {
+            ref_spheres.resize(2 * (size_t)sphere_count, make_float4(0, 0, 0, 0));
+            for (uint32_t i = 0; i < sphere_count; ++i) {
+                const prt_bsphere & bs = spheres[i];
+                ref_spheres[2 * (size_t)i] = make_float4(bs.center[0], bs.center[1], bs.center[2], bs.radius);
+                const bool inner = bs.c0 && bs.c1 && popped[i];
+                const uint32_t w[4] = { inner ? bs.c0 : 0u, inner ? bs.c1 : 0u, inner ? first_rank[bs.c0] : 0u, pop_order[i] };
+                float4 f;
+                memcpy(&f, w, 16);
+                ref_spheres[2 * (size_t)i + 1] = f;
+            }
+        }
+    }
+    if (ranked) {
+        for (uint32_t g = 0; g < group_count; ++g) {
+            uint32_t first = groups[g].first_index / 3, cnt = groups[g].index_count / 3;
+            for (uint32_t k = 0; k < cnt; ++k) rank_of_input[first + k] = group_base[g] + k;
+        }
+    } else {
+        for (uint32_t t = 0; t < n_tris; ++t) rank_of_input[t] = t;
+    }
+}
+
+// prt_update_geometry / prt_update_geometry_device: `device` says where positions / normals / tangents live.  Everything that
+// can refuse the update - the arguments, the coordinates (k_refit_bounds) - comes before the first write to the scene's
+// arrays; a HIP failure after it leaves the context without a scene rather than with half-moved arrays.
+int update_geometry(prt_ctx * ctx, const prt_geometry_update * u, prt_update_info * info, bool device) {
+    if (!ctx) return -1;
+    if (info) memset(info, 0, sizeof(*info));
+    if (!u || !u->positions) { ctx->error = "prt_update_geometry: null update or null positions"; return -1; }
+    if (!ctx->has_scene) { ctx->error = "prt_update_geometry: upload a scene first"; return -2; }
+    if (u->position_count != ctx->rf_position_count) { ctx->error = "prt_update_geometry: position_count differs from the uploaded scene's"; return -1; }
+    if (u->normals && u->normal_count != ctx->rf_normal_count) { ctx->error = "prt_update_geometry: normal_count differs from the uploaded scene's"; return -1; }
+    const uint32_t n_tris = ctx->scene.tri_count, n_nodes = ctx->scene.node_count;
+    const uint32_t levels = ctx->rf_level_first.empty() ? 0u : (uint32_t)ctx->rf_level_first.size() - 1u;
+    if (info) { info->levels = levels; info->node_count = n_nodes; info->abs_max = ctx->scene_abs_max; }
+    if (n_tris == 0) return 0;                                    // nothing references a position: nothing moves
+    if (!levels || ctx->q_tri_order.size() != n_tris || ctx->rf_idx_positions.size() != 3 * (size_t)n_tris) {
+        ctx->error = "prt_update_geometry: the uploaded tree is not level-ordered and cannot be refitted (upload the moved scene instead)";
+        return -9;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+
+    // ---- host work that can fail, first: the reference's ranks for the moved scene's sphere tree
+    std::vector<uint32_t> rank_of_input;
+    std::vector<float4> ref_spheres;
+    reference_ranks(ctx->q_groups.data(), (uint32_t)ctx->q_groups.size(), u->spheres, u->sphere_group, u->sphere_count, n_tris, rank_of_input, ref_spheres);
+    std::vector<unsigned int> rank((size_t)n_tris + 1, 0u);
+    for (uint32_t slot = 0; slot < n_tris; ++slot) rank[slot] = rank_of_input[ctx->q_tri_order[slot]];
+
+    // ---- the update's own device arrays (not the scene's): table, scratch boxes, the two words of k_refit_bounds, inputs
+    if (!ctx->rf_table.p) {
+        std::vector<unsigned int> table((size_t)n_tris * REFIT_TABLE_WORDS);
+        for (uint32_t slot = 0; slot < n_tris; ++slot) {
+            const uint32_t t = ctx->q_tri_order[slot];
+            for (uint32_t c = 0; c < 3; ++c) {
+                table[(size_t)slot * REFIT_TABLE_WORDS + c] = ctx->rf_idx_positions[3 * (size_t)t + c];
+                table[(size_t)slot * REFIT_TABLE_WORDS + 3 + c] = ctx->rf_idx_normals[3 * (size_t)t + c];
+            }
+        }
+        hipError_t e = ctx->rf_table.upload(table);
+        if (e != hipSuccess) { ctx->rf_table.release(); ctx->error = std::string("prt_update_geometry: table upload: ") + hipGetErrorString(e); return -10; }
+    }
+    HIP_TRY(ctx, ctx->rf_boxes.ensure(n_nodes));
+    HIP_TRY(ctx, ctx->rf_bounds.ensure(2));
+    const bool with_tangents = u->tangents && ctx->rf_bumped && ctx->tri_tan.p;      // one per normal of the upload
+    RefitArgs A;
+    memset(&A, 0, sizeof(A));
+    A.positions = u->positions;
+    A.normals = u->normals;
+    A.tangents = with_tangents ? u->tangents : nullptr;
+    if (!device) {
+        const size_t np = 3 * (size_t)u->position_count, nn = u->normals ? 3 * (size_t)u->normal_count : 0;
+        const size_t nt = with_tangents ? 3 * (size_t)ctx->rf_normal_count : 0;
+        HIP_TRY(ctx, ctx->rf_in.ensure(np + nn + nt));
+        float * p = ctx->rf_in.p;
+        HIP_TRY(ctx, hipMemcpyAsync(p, u->positions, np * sizeof(float), hipMemcpyHostToDevice, stream));
+        A.positions = p; p += np;
+        if (nn) { HIP_TRY(ctx, hipMemcpyAsync(p, u->normals, nn * sizeof(float), hipMemcpyHostToDevice, stream)); A.normals = p; p += nn; }
+        if (nt) { HIP_TRY(ctx, hipMemcpyAsync(p, u->tangents, nt * sizeof(float), hipMemcpyHostToDevice, stream)); A.tangents = p; }
+    }
+    A.table = ctx->rf_table.p;
+    A.n_tris = n_tris;
+    A.node_count = n_nodes;
+    A.nodes = ctx->nodes.p; A.tris = ctx->tris.p; A.shade = ctx->shade.p;
+    A.tri_tan = with_tangents ? ctx->tri_tan.p : nullptr;
+    A.boxes = ctx->rf_boxes.p;
+    A.bounds = ctx->rf_bounds.p;
+
+    // ---- the coordinates, before anything of the scene is written
+    HIP_TRY(ctx, hipEventRecord(ctx->ev[0], stream));
+    HIP_TRY(ctx, hipMemsetAsync(A.bounds, 0, 2 * sizeof(unsigned int), stream));
+    {
+        const unsigned int want = (3u * n_tris + 255u) / 256u;
+        const unsigned int grid = std::max(1u, std::min(want, (unsigned int)std::max(1, ctx->cu_count) * 8u));
+        hipLaunchKernelGGL(k_refit_bounds, dim3(grid), dim3(256), 0, stream, A);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    unsigned int bounds[2] = { 0u, 0u };
+    HIP_TRY(ctx, hipMemcpyAsync(bounds, A.bounds, sizeof(bounds), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    if (bounds[1]) { ctx->error = "prt_update_geometry: vertex coordinate is not finite or exceeds 1e18"; return -1; }
+    float abs_max;
+    memcpy(&abs_max, &bounds[0], 4);
+
+    // ---- from here on the scene's arrays change: a failure leaves the context without a scene
+#define REFIT_TRY(call)                                                                                      \
+    do {                                                                                                     \
+        hipError_t e_ = (call);                                                                              \
+        if (e_ != hipSuccess) {                                                                              \
+            ctx->error = std::string(#call) + ": " + hipGetErrorString(e_);                                  \
+            ctx->has_scene = false;                                                                          \
+            return -10;                                                                                      \
+        }                                                                                                    \
+    } while (0)
+    const bool had_spheres = ctx->scene.ref_spheres != nullptr;
+    const size_t old_sphere_bytes = had_spheres ? ctx->ref_spheres.bytes() : 0;
+    hipLaunchKernelGGL(k_refit_records, dim3((n_tris + 255u) / 256u), dim3(256), 0, stream, A);
+    REFIT_TRY(hipGetLastError());
+    for (uint32_t l = levels; l-- > 0;) {                         // deepest level first; the stream is the only ordering
+        const unsigned int first = ctx->rf_level_first[l], count = ctx->rf_level_first[l + 1] - first;
+        hipLaunchKernelGGL(k_refit_level<BVH_WIDTH>, dim3((count + 63u) / 64u), dim3(64), 0, stream, A, first, count);
+        REFIT_TRY(hipGetLastError());
+    }
+    REFIT_TRY(hipMemcpyAsync(ctx->tri_rank.p, rank.data(), rank.size() * sizeof(unsigned int), hipMemcpyHostToDevice, stream));
+    if (!ref_spheres.empty()) {
+        REFIT_TRY(ctx->ref_spheres.ensure(ref_spheres.size()));
+        REFIT_TRY(hipMemcpyAsync(ctx->ref_spheres.p, ref_spheres.data(), ref_spheres.size() * sizeof(float4), hipMemcpyHostToDevice, stream));
+    }
+    REFIT_TRY(hipEventRecord(ctx->ev[1], stream));
+    REFIT_TRY(hipStreamSynchronize(stream));
+    float ms = 0.0f;
+    REFIT_TRY(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+#undef REFIT_TRY
+    ctx->scene.ref_spheres = ref_spheres.empty() ? nullptr : ctx->ref_spheres.p;      // spheres of the old geometry are never kept
+    ctx->info.device_bytes = ctx->info.device_bytes - old_sphere_bytes + (ref_spheres.empty() ? 0 : ctx->ref_spheres.bytes());
+    ctx->scene_abs_max = abs_max;
+    ctx->tuned.clear();                                           // a refitted tree may change which pipeline wins a try-out
+    if (info) { info->device_ms = ms; info->abs_max = abs_max; }
+    return 0;
+}
+
+}  // namespace
+
 extern "C" {
 
 int prt_abi_version(void) { return PRT_ABI_VERSION; }
@@ -1375,6 +1574,7 @@ void prt_destroy(prt_ctx * ctx) {
     ctx->textures.release(); ctx->texels.release(); ctx->srgb_lut.release(); ctx->tri_uv.release(); ctx->tri_tan.release();
     ctx->ref_spheres.release();
     ctx->q_leaf_map.release(); ctx->q_work.release(); ctx->q_slow.release(); ctx->q_exact_stack.release(); ctx->q_io.release(); ctx->q_occ.release();
+    ctx->rf_table.release(); ctx->rf_boxes.release(); ctx->rf_bounds.release(); ctx->rf_in.release();
     for (int c = 0; c < PRT_MAX_CHAINS; ++c) {
         prt_ctx::ChainWs & w = ctx->chain[c];
         w.f4.release(); w.rng.release(); w.counts.release(); w.overflow.release(); w.slow_stack.release();
@@ -1434,6 +1634,10 @@ int prt_upload_scene(prt_ctx * ctx, const prt_scene_desc * s) {
     ctx->q_leaf_map.release();
     ctx->q_tri_order.clear();
     ctx->q_groups.clear();
+    ctx->rf_table.release();
+    ctx->rf_idx_positions.clear();
+    ctx->rf_idx_normals.clear();
+    ctx->rf_level_first.clear();
     const uint32_t n_tris = s->index_count / 3;
     if (n_tris >= (1u << 26)) { ctx->error = "prt_upload_scene: 2^26 triangles or more (the traversal addresses nodes and triangles by 32-bit byte offsets)"; return -1; }
 
@@ -1502,60 +1706,9 @@ int prt_upload_scene(prt_ctx * ctx, const prt_scene_desc * s) {
     if (const char * bad = validate_bvh_links(bvh, n_tris)) { ctx->error = std::string("prt_upload_scene: the builder produced a broken tree - ") + bad; return -9; }
 
     // ---- reference visit rank: leaves of the sphere tree in the order TraceRay pops them (c1 first)
-    std::vector<uint32_t> rank_of_input(n_tris);
+    std::vector<uint32_t> rank_of_input;
     std::vector<float4> ref_spheres;                          // (centre, radius) (c0, c1, first rank of c0's triangles, pop order)
-    {
-        std::vector<uint32_t> group_base(s->group_count, 0);
-        bool ranked = false;
-        if (s->spheres && s->sphere_group && s->sphere_count) {
-            std::vector<uint32_t> stack(1, 0u);
-            std::vector<uint8_t> seen(s->group_count, 0);
-            std::vector<uint32_t> first_rank(s->sphere_count, 0), pop_order(s->sphere_count, 0);
-            std::vector<uint8_t> popped(s->sphere_count, 0);
-            uint32_t next = 0, visited = 0;
-            bool ok = true;
-            while (!stack.empty() && ok) {
-                uint32_t i = stack.back();
-                stack.pop_back();
-                if (i >= s->sphere_count || ++visited > 2 * s->sphere_count || popped[i]) { ok = false; break; }
-                popped[i] = 1;
-                pop_order[i] = visited - 1;
-                first_rank[i] = next;                         // the first triangle the reference meets below this sphere
-                const prt_bsphere & bs = s->spheres[i];
-                if (bs.c0 && bs.c1) {
-                    stack.push_back(bs.c0);
-                    stack.push_back(bs.c1);
-                } else {
-                    int32_t g = s->sphere_group[i];
-                    if (g < 0 || (uint32_t)g >= s->group_count || seen[g]) { ok = false; break; }
-                    seen[g] = 1;
-                    group_base[g] = next;
-                    next += s->groups[g].index_count / 3;
-                }
-            }
-            ranked = ok && next == n_tris;
-            if (ranked) {
-                ref_spheres.resize(2 * (size_t)s->sphere_count, make_float4(0, 0, 0, 0));
-                for (uint32_t i = 0; i < s->sphere_count; ++i) {
-                    const prt_bsphere & bs = s->spheres[i];
-                    ref_spheres[2 * (size_t)i] = make_float4(bs.center[0], bs.center[1], bs.center[2], bs.radius);
-                    const bool inner = bs.c0 && bs.c1 && popped[i];
-                    const uint32_t w[4] = { inner ? bs.c0 : 0u, inner ? bs.c1 : 0u, inner ? first_rank[bs.c0] : 0u, pop_order[i] };
-                    float4 f;
-                    memcpy(&f, w, 16);
-                    ref_spheres[2 * (size_t)i + 1] = f;
-                }
-            }
-        }
-        if (ranked) {
-            for (uint32_t g = 0; g < s->group_count; ++g) {
-                uint32_t first = s->groups[g].first_index / 3, cnt = s->groups[g].index_count / 3;
-                for (uint32_t k = 0; k < cnt; ++k) rank_of_input[first + k] = group_base[g] + k;
-            }
-        } else {
-            for (uint32_t t = 0; t < n_tris; ++t) rank_of_input[t] = t;
-        }
-    }
+    reference_ranks(s->groups, s->group_count, s->spheres, s->sphere_group, s->sphere_count, n_tris, rank_of_input, ref_spheres);
 
     // ---- device records in BVH leaf order
     const uint32_t n_rec = n_tris + 1;                              // + the all-zero dummy triangle empty BVH slots point at
@@ -1727,6 +1880,13 @@ int prt_upload_scene(prt_ctx * ctx, const prt_scene_desc * s) {
     info.bvh_build_ms = build_ms;
     ctx->q_tri_order.swap(bvh.tri_order);
     ctx->q_groups.assign(s->groups, s->groups + s->group_count);
+    // what a later prt_update_geometry needs (host memory only)
+    ctx->rf_idx_positions.assign(s->idx_positions, s->idx_positions + s->index_count);
+    ctx->rf_idx_normals.assign(s->idx_normals, s->idx_normals + s->index_count);
+    ctx->rf_position_count = s->position_count;
+    ctx->rf_normal_count = s->normal_count;
+    ctx->rf_bumped = bumped;
+    if (!refit_level_table<BVH_WIDTH>(bvh.nodes.data(), bvh.node_count, &ctx->rf_level_first)) ctx->rf_level_first.clear();
     HIP_TRY(ctx, hipDeviceSynchronize());      // uploads went through the null stream; renders use the context's non-blocking streams
     ctx->has_scene = true;
     ctx->scene_epoch++;
@@ -1900,6 +2060,48 @@ int prt_trace_rays(prt_ctx * ctx, int mode, const prt_ray_batch * batch, const p
     HIP_TRY(ctx, hipStreamSynchronize(stream));
     return 0;
     PRT_API_CATCH_RC(ctx, "prt_trace_rays")
+}
+
+int prt_update_geometry(prt_ctx * ctx, const prt_geometry_update * update, prt_update_info * info) {
+    PRT_API_TRY
+    return update_geometry(ctx, update, info, false);
+    PRT_API_CATCH_RC(ctx, "prt_update_geometry")
+}
+
+int prt_update_geometry_device(prt_ctx * ctx, const prt_geometry_update * update, prt_update_info * info) {
+    PRT_API_TRY
+    return update_geometry(ctx, update, info, true);
+    PRT_API_CATCH_RC(ctx, "prt_update_geometry_device")
+}
+
+// The geometric check of bvh_check.cpp on the tree as it lies on the device NOW (after any number of updates), against the
+// un-indexed triangles of `s`: the GPU suite's proof that a refitted tree is conservative (out[0..5]: bvh_build.h).
+int prt_debug_check_refit(prt_ctx * ctx, const prt_scene_desc * s, uint64_t * out) {
+    PRT_API_TRY
+    if (!ctx) return -1;
+    if (!s || !out || s->index_count % 3) { ctx->error = "prt_debug_check_refit: null scene or output"; return -1; }
+    if (!ctx->has_scene) { ctx->error = "prt_debug_check_refit: upload a scene first"; return -2; }
+    const uint32_t n_tris = s->index_count / 3;
+    if (n_tris != ctx->scene.tri_count || ctx->q_tri_order.size() != n_tris) { ctx->error = "prt_debug_check_refit: the scene's triangle count differs from the uploaded scene's"; return -1; }
+    for (uint32_t i = 0; i < s->index_count; ++i)
+        if (s->idx_positions[i] >= s->position_count) { ctx->error = "prt_debug_check_refit: vertex index out of range"; return -1; }
+    std::vector<float> verts((size_t)n_tris * 9);
+    for (uint32_t t = 0; t < n_tris; ++t)
+        for (int c = 0; c < 3; ++c) memcpy(&verts[(size_t)t * 9 + 3 * c], s->positions + 3 * (size_t)s->idx_positions[3 * t + c], 12);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    BvhWide bvh;
+    bvh.node_dwords = BVH_WIDTH == 8 ? BVH8_NODE_DWORDS : BVH4_NODE_DWORDS;
+    bvh.node_count = ctx->scene.node_count;
+    bvh.max_depth = ctx->info.bvh_max_depth;
+    bvh.stack_bound = ctx->stack_bound;
+    bvh.nodes.resize((size_t)bvh.node_count * bvh.node_dwords);
+    bvh.tri_order = ctx->q_tri_order;
+    HIP_TRY(ctx, hipMemcpy(bvh.nodes.data(), ctx->nodes.p, bvh.nodes.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (const char * bad = validate_bvh_links(bvh, n_tris)) { ctx->error = std::string("prt_debug_check_refit: ") + bad; return -9; }
+    check_bvh_wide(verts.data(), n_tris, bvh, out);
+    return 0;
+    PRT_API_CATCH_RC(ctx, "prt_debug_check_refit")
 }
 
 int prt_debug_device_kat(prt_ctx * ctx, int kind, const void * in, size_t in_bytes, void * out, size_t out_bytes, uint32_t n,
@@ -2232,6 +2434,37 @@ int prt_multi_upload_scene(prt_multi * m, const prt_scene_desc * scene) {
         }
     return 0;
     PRT_API_CATCH_RC_MULTI(m, "prt_multi_upload_scene")
+}
+
+int prt_multi_update_geometry(prt_multi * m, const prt_geometry_update * update) {
+    PRT_API_TRY
+    if (!m) return -1;
+    {
+        std::lock_guard<std::mutex> lk(m->mu);
+        for (MultiLane & L : m->lane)
+            if (L.busy) { m->error = "prt_multi_update_geometry: a frame is still in flight (prt_multi_wait it first)"; return PRT_ERR_IN_FLIGHT; }
+    }
+    // no lane is busy: every render call has returned with its stream drained.  Lane 0's contexts own the scene arrays ...
+    int rc = 0;
+    for (size_t g = 0; g < m->devices.size() && !rc; ++g) {
+        rc = prt_update_geometry(m->lane[0].ctx[g], update, nullptr);
+        if (rc) m->error = prt_last_error(m->lane[0].ctx[g]);
+    }
+    // ... and the other lanes' contexts share them, with copies of what describes them: those follow (also after a failure:
+    // a context that lost its scene takes its clones' with it)
+    for (size_t f = 1; f < m->lane.size(); ++f)
+        for (size_t g = 0; g < m->devices.size(); ++g) {
+            prt_ctx * src = m->lane[0].ctx[g], * c = m->lane[f].ctx[g];
+            if (!src || !c) continue;
+            c->ref_spheres.borrow(src->ref_spheres);              // the update may have allocated or enlarged it
+            c->scene.ref_spheres = src->scene.ref_spheres;
+            c->scene_abs_max = src->scene_abs_max;
+            c->info = src->info;
+            c->has_scene = src->has_scene;
+            c->tuned.clear();
+        }
+    return rc;
+    PRT_API_CATCH_RC_MULTI(m, "prt_multi_update_geometry")
 }
 
 #define MULTI_TRY(m, call)                                                                                   \
