@@ -336,6 +336,50 @@ int prt_update_geometry(prt_ctx * ctx, const prt_geometry_update * update, prt_u
 /* positions / normals / tangents are DEVICE pointers on the context's device (hipMalloc'ed or torch tensors' data_ptr). */
 int prt_update_geometry_device(prt_ctx * ctx, const prt_geometry_update * update, prt_update_info * info);
 
+/* ---- gradients of closest-hit queries: how t, bw, position and normal change with the vertices and with the rays --------------
+ * Closes the optimisation loop over vertex positions: prt_update_geometry moves the mesh, prt_trace_rays queries it, and this call
+ * turns the gradients of a loss with respect to the queries' outputs into gradients with respect to the vertex positions, the
+ * origins and the directions.  What is differentiated is the real-valued function behind the forward query on the triangle
+ * (a, b, c) it REPORTED (group, vertex0 -> corners idx_positions[first_index + vertex0 + 0..2]):
+ *     ob = o + d * ray_bias   ab = b - a   ac = c - a   n = cross(ab, ac)   qp = -d   dd = dot(qp, n)   ap = ob - a   e = cross(qp, ap)
+ *     t = dot(ap, n) / dd     v = dot(ac, e) / dd     w = -dot(ab, e) / dd     bw = (1 - v - w, v, w)
+ *     position = ob + d * t   normal = n / |n|
+ * for any length of d.  The gradient is that of this smooth function; a change of visibility (a ray that slides off a silhouette
+ * onto another triangle) is not modelled: there is no edge sampling.
+ *   batch          the forward call's rays and ray_bias; tmax is ignored
+ *   group, vertex0 the forward call's hit references, count each.  group < 0 is a miss and contributes nothing.
+ *   positions      the vertex positions the forward query saw - the uploaded ones, or those last given to prt_update_geometry;
+ *                  position_count must equal the upload's
+ *   gout           dL/dt (count), dL/dbw, dL/dposition, dL/dnormal (count x 3); a NULL array, or gout NULL, means zero
+ *   gin            where the results go; a NULL array is not computed.  positions: position_count x 3, summed over the rays,
+ *                  OVERWRITTEN (not accumulated into); origins, directions: count x 3.
+ * A ray is SKIPPED - zeros in origins / directions, nothing added to positions - when the named triangle does not face it
+ * (dd <= 0) or any of its 15 gradient components is not finite (a grazing hit that overflows, a NaN vertex or ray, a NaN in gout).
+ * Determinism: the vertex gradient is a sum over rays.  Every contribution is rounded once to a multiple of 2^unit_exponent and
+ * added as a 64-bit integer, so the result is the same bits for every order of the rays, every launch shape and every run;
+ * unit_exponent = E + L - 62 with 2^(E-1) <= max_contribution < 2^E and L the smallest integer with 3 * count <= 2^L: the sum cannot
+ * overflow, and the rounding per contribution is at most 2^(L-63) of max_contribution.
+ * prt_grad_info: device_ms = the call's device time (scan, scatter, resolve); hit_rays = rays that contributed, skipped_rays = hits
+ * that were skipped (misses are in neither); max_contribution = the largest |component| a ray added to a vertex (0 when none did,
+ * and unit_exponent is then 0).
+ * Errors: -1 NULL batch; NULL origins, directions, group, vertex0 or positions with count > 0; a position_count that differs from
+ * the upload's; a hit reference the scene does not have (group >= group_count, vertex0 not a multiple of 3, vertex0 + 2 >= the
+ * group's index_count) - found BEFORE any output is written; -2 no scene; -10 a HIP call failed.  count == 0 zeroes gin->positions
+ * (if wanted) and returns 0.  Stream contract of prt_render_device.  The call reads nothing of the tree and leaves the scene, the
+ * render stats and the counters alone; the first call after an upload copies the position index buffer and the groups' runs to
+ * the device and allocates 24 B per position (not in prt_scene_info.device_bytes; freed by the next upload). */
+typedef struct prt_hit_grads   { const float * t; const float * bw; const float * position; const float * normal; } prt_hit_grads;
+typedef struct prt_query_grads { float * positions; float * origins; float * directions; } prt_query_grads;
+typedef struct prt_grad_info   { double device_ms; uint32_t hit_rays, skipped_rays; int32_t unit_exponent; float max_contribution; } prt_grad_info;
+/* Host pointers (batch arrays, group, vertex0, positions, gout's and gin's arrays); info may be NULL. */
+int prt_trace_rays_backward(prt_ctx * ctx, const prt_ray_batch * batch, const int32_t * group, const uint32_t * vertex0,
+                            const float * positions, uint32_t position_count, const prt_hit_grads * gout,
+                            const prt_query_grads * gin, prt_grad_info * info);
+/* The same with device pointers on the context's device (hipMalloc'ed or torch tensors' data_ptr). */
+int prt_trace_rays_backward_device(prt_ctx * ctx, const prt_ray_batch * batch, const int32_t * group, const uint32_t * vertex0,
+                                   const float * positions, uint32_t position_count, const prt_hit_grads * gout,
+                                   const prt_query_grads * gin, prt_grad_info * info);
+
 /* ---- several devices behind one handle --------------------------------------------------------------------------------
  * SURVEY.md 8(b)'s prt_create(const int * device_ids, int n_dev): what the host mirror's Render() uses for n GPUs, in place
  * of the reference's one-rank-per-core partition + MPI_Gather (main.cpp:311-347).  The scene is replicated (as every MPI rank

@@ -11,7 +11,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 from . import capi
-from .capi import PrtCamera, PrtCounters, PrtParams, PrtSceneDesc, PrtSceneInfo, PrtUpdateInfo
+from .capi import PrtCamera, PrtCounters, PrtParams, PrtSceneDesc, PrtGradInfo, PrtSceneInfo, PrtUpdateInfo
 
 
 class HostScene:
@@ -398,6 +398,75 @@ class Renderer:
         self._check(entry(self._ctx, m, C.byref(batch), C.byref(hb), flags, C.byref(counters)),
                     "prt_trace_rays_device" if is_torch else "prt_trace_rays")
         out["counters"] = counters
+        return out
+
+    GRAD_NAMES = ("positions", "origins", "directions")
+
+    def trace_rays_backward(self, origins, directions, group, vertex0, positions, *, ray_bias: float = 0.0, grad_t=None, grad_bw=None,
+                            grad_position=None, grad_normal=None, want: Sequence[str] = ("positions", "origins", "directions")) -> dict:
+        """Gradients of a closest-hit query (prt_trace_rays_backward, include/prt.h): from dL/dt, dL/dbw, dL/dposition, dL/dnormal
+        of n rays (None = zero) to dL/dpositions (summed over the rays; the same bits for every order of the rays), dL/dorigins and
+        dL/ddirections - whichever `want` names.
+
+        origins, directions, ray_bias, group, vertex0: the forward trace_rays call's inputs and hit references (vertex0 uint32, or
+        int32 holding the same bits); positions: float32 (P, 3), the vertices that call saw.  numpy arrays go to the host entry
+        point, torch tensors on this context's device to the device entry point.  Returns {name: array} plus "info" (PrtGradInfo)."""
+        for w in want:
+            if w not in self.GRAD_NAMES:
+                raise ValueError("unknown gradient %r" % (w,))
+        is_torch = type(origins).__module__.split(".")[0] == "torch"
+        if is_torch:
+            import torch
+
+            def check(x, what, shape, dtypes=(torch.float32,)):
+                if not isinstance(x, torch.Tensor) or x.dtype not in dtypes or not x.is_contiguous():
+                    raise ValueError("%s must be a contiguous %s torch tensor" % (what, " or ".join(str(d) for d in dtypes)))
+                if x.device.type != "cuda" or (x.device.index or 0) != self.device_id:
+                    raise ValueError("%s must live on this context's device (cuda:%d)" % (what, self.device_id))
+                if tuple(x.shape) != shape:
+                    raise ValueError("%s has shape %s, not %s" % (what, tuple(x.shape), shape))
+                return x
+            ints = (torch.int32,)
+            empty = lambda shape: torch.empty(shape, dtype=torch.float32, device=origins.device)     # noqa: E731
+            ptr = lambda x: x.data_ptr() if x is not None else None                                 # noqa: E731
+            entry, name = self._lib.prt_trace_rays_backward_device, "prt_trace_rays_backward_device"
+        else:
+            def check(x, what, shape, dtypes=(np.float32,)):
+                a = np.asarray(x)
+                if a.dtype not in dtypes or not a.flags["C_CONTIGUOUS"]:
+                    raise ValueError("%s must be a contiguous %s array" % (what, " or ".join(np.dtype(d).name for d in dtypes)))
+                if a.shape != shape:
+                    raise ValueError("%s has shape %s, not %s" % (what, a.shape, shape))
+                return a
+            ints = (np.int32, np.uint32)
+            empty = lambda shape: np.empty(shape, dtype=np.float32)                                  # noqa: E731
+            ptr = lambda x: x.ctypes.data if x is not None else None                                 # noqa: E731
+            entry, name = self._lib.prt_trace_rays_backward, "prt_trace_rays_backward"
+        if getattr(origins, "ndim", 0) != 2:
+            raise ValueError("origins must have shape (n, 3)")
+        n = int(origins.shape[0])
+        if getattr(positions, "ndim", 0) != 2:
+            raise ValueError("positions must have shape (P, 3)")
+        n_pos = int(positions.shape[0])
+        origins = check(origins, "origins", (n, 3))
+        directions = check(directions, "directions", (n, 3))
+        group = check(group, "group", (n,), ints[:1])
+        vertex0 = check(vertex0, "vertex0", (n,), ints)
+        positions = check(positions, "positions", (n_pos, 3))
+        gouts = [None if g is None else check(g, what, shape) for g, what, shape in
+                 ((grad_t, "grad_t", (n,)), (grad_bw, "grad_bw", (n, 3)), (grad_position, "grad_position", (n, 3)),
+                  (grad_normal, "grad_normal", (n, 3)))]
+        out = {w: empty((n_pos, 3) if w == "positions" else (n, 3)) for w in want}
+        if is_torch:
+            # the library's stream is not ordered against torch's: whatever torch still has queued on the inputs must be done
+            torch.cuda.current_stream(origins.device).synchronize()
+        batch = capi.PrtRayBatch(ptr(origins), ptr(directions), None, n, float(ray_bias))
+        go = capi.PrtHitGrads(*[ptr(g) for g in gouts])
+        gi = capi.PrtQueryGrads(*[ptr(out.get(w)) for w in self.GRAD_NAMES])
+        info = PrtGradInfo()
+        self._check(entry(self._ctx, C.byref(batch), ptr(group), ptr(vertex0), ptr(positions), n_pos, C.byref(go), C.byref(gi),
+                          C.byref(info)), name)
+        out["info"] = info
         return out
 
     def update_geometry(self, positions, normals=None, tangents=None, spheres=None, sphere_group=None) -> PrtUpdateInfo:

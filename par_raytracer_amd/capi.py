@@ -118,6 +118,22 @@ class PrtUpdateInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class PrtHitGrads(C.Structure):
+    _fields_ = [("t", C.c_void_p), ("bw", C.c_void_p), ("position", C.c_void_p), ("normal", C.c_void_p)]
+
+
+class PrtQueryGrads(C.Structure):
+    _fields_ = [("positions", C.c_void_p), ("origins", C.c_void_p), ("directions", C.c_void_p)]
+
+
+class PrtGradInfo(C.Structure):
+    _fields_ = [("device_ms", C.c_double), ("hit_rays", C.c_uint32), ("skipped_rays", C.c_uint32), ("unit_exponent", C.c_int32),
+                ("max_contribution", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 QUERY_CLOSEST, QUERY_OCCLUDED = 0, 1
 PIPELINE_DEFAULT, PIPELINE_MEGAKERNEL, PIPELINE_WAVEFRONT, PIPELINE_PERSISTENT, PIPELINE_POOL = 0, 1, 2, 3, 4
 FLAG_COUNT_VISITS = 0x100
@@ -130,7 +146,8 @@ PRT_SYMBOLS = ["prt_create", "prt_destroy", "prt_last_error", "prt_abi_version",
                "prt_multi_create", "prt_multi_destroy", "prt_multi_last_error", "prt_multi_device_count", "prt_multi_context",
                "prt_multi_upload_scene", "prt_multi_render", "prt_multi_depth", "prt_multi_submit", "prt_multi_wait", "prt_debug_throw",
                "prt_trace_rays", "prt_trace_rays_device", "prt_get_region_stats",
-               "prt_update_geometry", "prt_update_geometry_device", "prt_multi_update_geometry", "prt_debug_check_refit"]
+               "prt_update_geometry", "prt_update_geometry_device", "prt_multi_update_geometry", "prt_debug_check_refit",
+               "prt_trace_rays_backward", "prt_trace_rays_backward_device"]
 # PRT_REGION_* of include/prt.h, in index order (tests/test_host_side.py's header check keeps the symbol list in step; the
 # region test compares this list with the header's enum)
 REGION_NAMES = ["round", "topup", "topup_pass", "trace_outer", "refill", "walk_pass", "node_step", "node_descend", "node_pop", "node_push", "leaf",
@@ -217,6 +234,10 @@ def hip_lib() -> C.CDLL:
             lib.prt_update_geometry_device.argtypes = lib.prt_update_geometry.argtypes
             lib.prt_multi_update_geometry.argtypes = [C.c_void_p, C.POINTER(PrtGeometryUpdate)]
             lib.prt_debug_check_refit.argtypes = [C.c_void_p, C.POINTER(PrtSceneDesc), C.POINTER(C.c_uint64)]
+        if hasattr(lib, "prt_trace_rays_backward"):    # (absent from a PRT_HIP_LIB build of an earlier commit)
+            lib.prt_trace_rays_backward.argtypes = [C.c_void_p, C.POINTER(PrtRayBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                    C.POINTER(PrtHitGrads), C.POINTER(PrtQueryGrads), C.POINTER(PrtGradInfo)]
+            lib.prt_trace_rays_backward_device.argtypes = lib.prt_trace_rays_backward.argtypes
         _hip = lib
     return _hip
 

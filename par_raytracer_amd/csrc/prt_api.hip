@@ -30,6 +30,7 @@
 #include "kernels_debug.h"
 #include "kernels_query.h"
 #include "kernels_refit.h"
+#include "kernels_query_grad.h"
 
 using namespace prt;
 
@@ -41,6 +42,9 @@ using namespace prt;
 #endif
 #ifndef PRT_POOL_BLOCK
 #define PRT_POOL_BLOCK 256        // threads per workgroup of the fixed-spp pool kernel (experiments: 320, 640 with block-shared pools)
+#endif
+#ifndef PRT_QGRAD_MERGE_DEFAULT
+#define PRT_QGRAD_MERGE_DEFAULT 1 // prt_trace_rays_backward: lanes of a wave on one triangle merge their adds (same bits either way)
 #endif
 #ifndef PRT_DEEP_WAVES
 #define PRT_DEEP_WAVES PRT_POOL_WAVES   // waves per SIMD of the fixed-spp kernel for bounce trees of more than 15 draws (C5)
@@ -188,6 +192,14 @@ struct prt_ctx {
     DevBuf<RefitBox> rf_boxes;            // every node's exact float box
     DevBuf<unsigned int> rf_bounds;       // k_refit_bounds' two words
     DevBuf<float> rf_in;                  // host entry point: positions, normals, tangents on the device
+    // query gradients (prt_trace_rays_backward, kernels_query_grad.h).  Built by the first call after an upload from what the
+    // upload kept on the host (rf_idx_positions, q_groups); like q_leaf_map not in prt_scene_info.device_bytes, reused by later
+    // calls, freed by the next upload.
+    DevBuf<unsigned int> qg_idx;          // the position index buffer
+    DevBuf<unsigned int> qg_runs;         // (first_index, index_count) per group
+    DevBuf<long long> qg_acc;             // position_count x 3 fixed-point accumulators
+    DevBuf<unsigned int> qg_words;        // k_qgrad_scan's control words
+    DevBuf<float> qg_io;                  // host entry point: the inputs and the requested gradients on the device
 };
 
 namespace {
@@ -1466,6 +1478,132 @@ int update_geometry(prt_ctx * ctx, const prt_geometry_update * u, prt_update_inf
     return 0;
 }
 
+// prt_trace_rays_backward / prt_trace_rays_backward_device: `device` says where the caller's arrays live.  Nothing of the tree is
+// read and nothing of the scene, the render stats or the counters is written.  k_qgrad_scan validates every hit reference before
+// the first write to an output of the caller's.
+int query_backward(prt_ctx * ctx, const prt_ray_batch * b, const int32_t * group, const uint32_t * vertex0, const float * positions,
+                   uint32_t position_count, const prt_hit_grads * gout, const prt_query_grads * gin, prt_grad_info * info, bool device) {
+    if (!ctx) return -1;
+    if (info) memset(info, 0, sizeof(*info));
+    if (!b) { ctx->error = "prt_trace_rays_backward: null batch"; return -1; }
+    if (b->count && (!b->origins || !b->directions || !group || !vertex0 || !positions)) {
+        ctx->error = "prt_trace_rays_backward: null origins, directions, group, vertex0 or positions";
+        return -1;
+    }
+    if (!ctx->has_scene) { ctx->error = "prt_trace_rays_backward: no scene uploaded"; return -2; }
+    if (position_count != ctx->rf_position_count) { ctx->error = "prt_trace_rays_backward: position_count differs from the uploaded scene's"; return -1; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    const size_t n = b->count, np = 3 * (size_t)position_count;
+    float * want_p = gin ? gin->positions : nullptr, * want_o = gin ? gin->origins : nullptr, * want_d = gin ? gin->directions : nullptr;
+    if (n == 0) {                                                 // no ray: the vertex gradient is zero
+        if (want_p && np) {
+            if (device) { HIP_TRY(ctx, hipMemsetAsync(want_p, 0, np * sizeof(float), stream)); HIP_TRY(ctx, hipStreamSynchronize(stream)); }
+            else memset(want_p, 0, np * sizeof(float));
+        }
+        return 0;
+    }
+    if (ctx->rf_idx_positions.size() != 3 * (size_t)ctx->scene.tri_count) { ctx->error = "prt_trace_rays_backward: the scene's index buffer is not available"; return -2; }
+    // ---- the call's own device data, built on the first call after an upload
+    if (!ctx->qg_idx.p || !ctx->qg_runs.p) {
+        std::vector<unsigned int> runs(2 * ctx->q_groups.size());
+        for (size_t g = 0; g < ctx->q_groups.size(); ++g) { runs[2 * g] = ctx->q_groups[g].first_index; runs[2 * g + 1] = ctx->q_groups[g].index_count; }
+        HIP_TRY(ctx, ctx->qg_idx.upload(ctx->rf_idx_positions));
+        HIP_TRY(ctx, ctx->qg_runs.upload(runs));
+        HIP_TRY(ctx, hipDeviceSynchronize());                     // the uploads went through the null stream
+    }
+    HIP_TRY(ctx, ctx->qg_words.ensure(QGRAD_WORDS));
+    if (want_p) HIP_TRY(ctx, ctx->qg_acc.ensure(np));
+    QGradArgs A;
+    memset(&A, 0, sizeof(A));
+    A.origins = b->origins; A.dirs = b->directions; A.group = group; A.vertex0 = vertex0; A.positions = positions;
+    if (gout) { A.g_t = gout->t; A.g_bw = gout->bw; A.g_pos = gout->position; A.g_nrm = gout->normal; }
+    A.g_origins = want_o; A.g_dirs = want_d; A.g_positions = want_p;
+    if (!device) {                                                // inputs, then the requested gradients, in one slab of 4-byte words
+        const size_t f_in = 8 * n + np + (A.g_t ? n : 0) + (A.g_bw ? 3 * n : 0) + (A.g_pos ? 3 * n : 0) + (A.g_nrm ? 3 * n : 0);
+        const size_t f_out = (want_o ? 3 * n : 0) + (want_d ? 3 * n : 0) + (want_p ? np : 0);
+        HIP_TRY(ctx, ctx->qg_io.ensure(f_in + f_out));
+        float * p = ctx->qg_io.p;
+        auto in = [&](const void * src, size_t words) -> float * {
+            float * at = p;
+            p += words;
+            return hipMemcpyAsync(at, src, words * 4, hipMemcpyHostToDevice, stream) == hipSuccess ? at : nullptr;
+        };
+        bool ok = true;
+        ok = (A.origins = in(b->origins, 3 * n)) && ok;
+        ok = (A.dirs = in(b->directions, 3 * n)) && ok;
+        ok = (A.group = reinterpret_cast<const int *>(in(group, n))) && ok;
+        ok = (A.vertex0 = reinterpret_cast<const unsigned int *>(in(vertex0, n))) && ok;
+        ok = (A.positions = in(positions, np)) && ok;
+        if (A.g_t) ok = (A.g_t = in(gout->t, n)) && ok;
+        if (A.g_bw) ok = (A.g_bw = in(gout->bw, 3 * n)) && ok;
+        if (A.g_pos) ok = (A.g_pos = in(gout->position, 3 * n)) && ok;
+        if (A.g_nrm) ok = (A.g_nrm = in(gout->normal, 3 * n)) && ok;
+        if (!ok) { ctx->error = "prt_trace_rays_backward: copying the inputs to the device failed"; return -10; }
+        if (want_o) { A.g_origins = p; p += 3 * n; }
+        if (want_d) { A.g_dirs = p; p += 3 * n; }
+        if (want_p) { A.g_positions = p; p += np; }
+    }
+    A.idx_positions = ctx->qg_idx.p;
+    A.group_runs = ctx->qg_runs.p;
+    A.words = ctx->qg_words.p;
+    A.count = b->count; A.group_count = (unsigned int)ctx->q_groups.size(); A.position_count = position_count;
+    A.ray_bias = b->ray_bias;
+
+    // ---- the references and the batch's largest contribution, before any output is written
+    const unsigned int grid = std::max(1u, std::min((b->count + 255u) / 256u, (unsigned int)std::max(1, ctx->cu_count) * 8u));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev[0], stream));
+    HIP_TRY(ctx, hipMemsetAsync(A.words, 0, QGRAD_WORDS * sizeof(unsigned int), stream));
+    hipLaunchKernelGGL(k_qgrad_scan, dim3(grid), dim3(256), 0, stream, A);
+    HIP_TRY(ctx, hipGetLastError());
+    unsigned int words[QGRAD_WORDS] = { 0u, 0u, 0u, 0u };
+    HIP_TRY(ctx, hipMemcpyAsync(words, A.words, sizeof(words), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    if (words[QGRAD_W_INVALID]) {
+        char msg[200];
+        snprintf(msg, sizeof(msg), "prt_trace_rays_backward: %u rays name a triangle the scene does not have (group out of range, vertex0 not a "
+                 "multiple of 3 or past its group's run)", words[QGRAD_W_INVALID]);
+        ctx->error = msg;
+        return -1;
+    }
+    float m;
+    memcpy(&m, &words[QGRAD_W_MAX], 4);
+    const bool adds = want_p && words[QGRAD_W_HIT] && m > 0.0f;   // else the vertex gradient is zero
+    A.unit_exponent = m > 0.0f ? qgrad_unit_exponent(m, b->count) : 0;
+    A.acc = adds ? ctx->qg_acc.p : nullptr;
+    if (adds) HIP_TRY(ctx, hipMemsetAsync(A.acc, 0, np * sizeof(long long), stream));
+    if (adds || want_o || want_d) {
+        if (ctx->opt.qgrad_merge < 0 ? PRT_QGRAD_MERGE_DEFAULT != 0 : ctx->opt.qgrad_merge != 0)
+            hipLaunchKernelGGL(k_qgrad_scatter<true>, dim3(grid), dim3(256), 0, stream, A);
+        else
+            hipLaunchKernelGGL(k_qgrad_scatter<false>, dim3(grid), dim3(256), 0, stream, A);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    if (adds) {
+        hipLaunchKernelGGL(k_qgrad_resolve, dim3((unsigned int)((np + 255) / 256)), dim3(256), 0, stream, A);
+        HIP_TRY(ctx, hipGetLastError());
+    } else if (want_p && np) {
+        HIP_TRY(ctx, hipMemsetAsync(A.g_positions, 0, np * sizeof(float), stream));
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev[1], stream));
+    if (!device) {
+        if (want_o) HIP_TRY(ctx, hipMemcpyAsync(want_o, A.g_origins, 12 * n, hipMemcpyDeviceToHost, stream));
+        if (want_d) HIP_TRY(ctx, hipMemcpyAsync(want_d, A.g_dirs, 12 * n, hipMemcpyDeviceToHost, stream));
+        if (want_p && np) HIP_TRY(ctx, hipMemcpyAsync(want_p, A.g_positions, np * sizeof(float), hipMemcpyDeviceToHost, stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    if (info) {
+        float ms = 0.0f;
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+        info->device_ms = ms;
+        info->hit_rays = words[QGRAD_W_HIT];
+        info->skipped_rays = words[QGRAD_W_SKIPPED];
+        info->unit_exponent = A.unit_exponent;
+        info->max_contribution = m;
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1575,6 +1713,7 @@ void prt_destroy(prt_ctx * ctx) {
     ctx->ref_spheres.release();
     ctx->q_leaf_map.release(); ctx->q_work.release(); ctx->q_slow.release(); ctx->q_exact_stack.release(); ctx->q_io.release(); ctx->q_occ.release();
     ctx->rf_table.release(); ctx->rf_boxes.release(); ctx->rf_bounds.release(); ctx->rf_in.release();
+    ctx->qg_idx.release(); ctx->qg_runs.release(); ctx->qg_acc.release(); ctx->qg_words.release(); ctx->qg_io.release();
     for (int c = 0; c < PRT_MAX_CHAINS; ++c) {
         prt_ctx::ChainWs & w = ctx->chain[c];
         w.f4.release(); w.rng.release(); w.counts.release(); w.overflow.release(); w.slow_stack.release();
@@ -1635,6 +1774,7 @@ int prt_upload_scene(prt_ctx * ctx, const prt_scene_desc * s) {
     ctx->q_tri_order.clear();
     ctx->q_groups.clear();
     ctx->rf_table.release();
+    ctx->qg_idx.release(); ctx->qg_runs.release(); ctx->qg_acc.release();
     ctx->rf_idx_positions.clear();
     ctx->rf_idx_normals.clear();
     ctx->rf_level_first.clear();
@@ -2072,6 +2212,21 @@ int prt_update_geometry_device(prt_ctx * ctx, const prt_geometry_update * update
     PRT_API_TRY
     return update_geometry(ctx, update, info, true);
     PRT_API_CATCH_RC(ctx, "prt_update_geometry_device")
+}
+
+int prt_trace_rays_backward(prt_ctx * ctx, const prt_ray_batch * batch, const int32_t * group, const uint32_t * vertex0, const float * positions,
+                            uint32_t position_count, const prt_hit_grads * gout, const prt_query_grads * gin, prt_grad_info * info) {
+    PRT_API_TRY
+    return query_backward(ctx, batch, group, vertex0, positions, position_count, gout, gin, info, false);
+    PRT_API_CATCH_RC(ctx, "prt_trace_rays_backward")
+}
+
+int prt_trace_rays_backward_device(prt_ctx * ctx, const prt_ray_batch * batch, const int32_t * group, const uint32_t * vertex0,
+                                   const float * positions, uint32_t position_count, const prt_hit_grads * gout,
+                                   const prt_query_grads * gin, prt_grad_info * info) {
+    PRT_API_TRY
+    return query_backward(ctx, batch, group, vertex0, positions, position_count, gout, gin, info, true);
+    PRT_API_CATCH_RC(ctx, "prt_trace_rays_backward_device")
 }
 
 // The geometric check of bvh_check.cpp on the tree as it lies on the device NOW (after any number of updates), against the
