@@ -355,6 +355,8 @@ int prt_update_geometry_device(prt_ctx * ctx, const prt_geometry_update * update
  *                  OVERWRITTEN (not accumulated into); origins, directions: count x 3.
  * A ray is SKIPPED - zeros in origins / directions, nothing added to positions - when the named triangle does not face it
  * (dd <= 0) or any of its 15 gradient components is not finite (a grazing hit that overflows, a NaN vertex or ray, a NaN in gout).
+ * Only per-ray non-finite contributions are skipped: a sum of finite contributions that exceeds float32 resolves to +-inf in
+ * gin->positions; it is neither refused nor clamped.
  * Determinism: the vertex gradient is a sum over rays.  Every contribution is rounded once to a multiple of 2^unit_exponent and
  * added as a 64-bit integer, so the result is the same bits for every order of the rays, every launch shape and every run;
  * unit_exponent = E + L - 62 with 2^(E-1) <= max_contribution < 2^E and L the smallest integer with 3 * count <= 2^L: the sum cannot

@@ -209,3 +209,126 @@ def run_harness(exe, cases, directory):
 
 def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+# ---- cases for the wave merge, the capped grid and the fixed point, with a reference that shares nothing with the kernels' sum
+
+WAVE = 64
+LAYOUT_RAYS = 32 * WAVE + 37                     # 33 waves, the last one partial
+
+
+def exact_integer_sum(mesh, case, result):
+    """The vertex gradient from the harness's per-ray contributions and unit exponent alone: rint(contrib * 2^-u) as int64,
+    scatter-added through idx_positions, float32(float64(acc) * 2^u).  Independent of the kernels' accumulation and merge."""
+    p, idx, runs = mesh
+    u = int(result["unit_exponent"])
+    contrib = np.asarray(result["contrib"], np.float64)
+    q = np.rint(np.ldexp(contrib, -u))                        # the scaling by a power of two is exact, rint rounds ties to even
+    group = np.asarray(case["group"])
+    sel = np.nonzero((group >= 0) & np.any(contrib != 0.0, axis=1))[0]
+    corner = runs[group[sel], 0].astype(np.int64) + np.asarray(case["vertex0"])[sel].astype(np.int64)
+    acc = np.zeros((p.shape[0], 3), np.int64)
+    load = np.zeros((p.shape[0], 3), np.float64)              # sum of |q|: below 2^63 it proves that acc did not wrap
+    for c in range(3):
+        vi = idx[corner + c].astype(np.int64)
+        for k in range(3):
+            np.add.at(acc[:, k], vi, q[sel, 3 * c + k].astype(np.int64))
+            np.add.at(load[:, k], vi, np.abs(q[sel, 3 * c + k]))
+    assert load.max(initial=0.0) < 2.0 ** 63 and np.abs(acc).max(initial=0) < 2 ** 62
+    with np.errstate(over="ignore"):
+        return np.ldexp(acc.astype(np.float64), u).astype(np.float32)
+
+
+def _case_with_dead_classes(mesh, o, d, group, vertex0, g, miss, back, nan, inf, merge):
+    """Turns the masked rays into the four classes that add nothing and returns Q.case(...) with "hit_rays", "skipped_rays" and
+    the masks "contributing", "skipped" from this bookkeeping.  A miss wins over the three skipped classes (the kernels look at the
+    reference first)."""
+    group[miss] = -1
+    vertex0[miss] = 0xFFFFFFFF
+    d[back] = -d[back]                                        # the reference stays: dd <= 0, the step refuses the ray
+    o[nan, 1] = np.nan
+    g["t"][inf] = np.inf
+    skipped = (back | nan | inf) & ~miss
+    contributing = ~miss & ~skipped
+    c = case(mesh, o, d, group, vertex0, 1e-3, g, merge)
+    c.update(hit_rays=int(contributing.sum()), skipped_rays=int(skipped.sum()), contributing=contributing, skipped=skipped)
+    return c
+
+
+def wave_layout_case(mesh, seed, merge):
+    """LAYOUT_RAYS rays laid out by wave (64 consecutive rays) and lane for k_qgrad_scatter<true>.  Waves not named below: random
+    triangles; ray i is a miss when i % 5 == 0, back-facing when i % 7 == 3, has a NaN origin when i % 11 == 5 and g_t = inf when
+    i % 13 == 7 - the strides are coprime to 64, so the dead lanes move from wave to wave.  The named waves are clean except where
+    said:
+        3   64 misses                       5   lane 0 is the only live lane      6   lane 63 is the only live lane
+        7   64 lanes on one triangle        8   lanes 2k, 2k + 1 on triangle k (mod the mesh's count: 32 pairs where it has 32)
+        9   lane 0 alone on its triangle, the lanes after it in groups of three on others
+        32  (37 lanes) ten groups of three, two lone lanes, then a miss, a back-facing, a NaN, an inf ray and a miss.
+    Returns Q.case(...) with "hit_rays", "skipped_rays" and the masks "contributing", "skipped" from the builder's own bookkeeping."""
+    p, idx, runs = mesh
+    n, n_tris = LAYOUT_RAYS, idx.size // 3
+    assert n_tris >= 12
+    rng = np.random.default_rng(seed)
+    i = np.arange(n)
+    wave, lane = i // WAVE, i % WAVE
+    tri = rng.integers(0, n_tris, n)
+    special = np.isin(wave, (3, 5, 6, 7, 8, 9, 32))
+    miss, back, nan, inf = (~special & (i % m == r) for m, r in ((5, 0), (7, 3), (11, 5), (13, 7)))
+    miss |= (wave == 3) | ((wave == 5) & (lane != 0)) | ((wave == 6) & (lane != 63))
+    tri[wave == 7] = tri[7 * WAVE]
+    tri[wave == 8] = (lane[wave == 8] // 2) % n_tris
+    tri[wave == 9] = np.where(lane[wave == 9] == 0, 0, 1 + ((lane[wave == 9] - 1) // 3) % (n_tris - 1))
+    last = lane[wave == 32]
+    tri[wave == 32] = np.where(last < 30, last // 3, np.minimum(last, 31) - 20)      # groups on 0..9, lone lanes on 10 and 11
+    for m, l in ((miss, 32), (back, 33), (nan, 34), (inf, 35), (miss, 36)):
+        m[32 * WAVE + l] = True
+    o, d, group, vertex0 = recipe_rays(mesh, n, seed + 1, triangles=tri)
+    return _case_with_dead_classes(mesh, o, d, group, vertex0, random_grads(n, seed + 2), miss, back, nan, inf, merge)
+
+
+def regular_case(mesh, seed=300, merge=False, n=LAYOUT_RAYS):
+    """n recipe rays on random triangles; a miss every fifth ray and wave 3 entirely, the three skipped classes on strides 7, 11
+    and 13 (as wave_layout_case's unnamed waves)."""
+    i = np.arange(n)
+    miss, back, nan, inf = (i % m == r for m, r in ((5, 0), (7, 3), (11, 5), (13, 7)))
+    miss = miss | (i // WAVE == 3)
+    o, d, group, vertex0 = recipe_rays(mesh, n, seed)
+    return _case_with_dead_classes(mesh, o, d, group, vertex0, random_grads(n, seed + 1), miss, back, nan, inf, merge)
+
+
+SCALED_EXPONENTS = (-140, 100, 122, 124)
+
+
+def scaled_grads_case(mesh, exponent, merge=False):
+    """LAYOUT_RAYS clean recipe rays whose four output gradients are standard normal times 2^exponent, rounded to float32 (at -140
+    they are denormal floats).  -140: the largest contribution is a denormal float; +100: a positive unit exponent; +122, +124:
+    part of the rays' contributions overflow float32 and are skipped - how many, the harness says."""
+    n = LAYOUT_RAYS
+    o, d, group, vertex0 = recipe_rays(mesh, n, 400)
+    g = {k: np.ldexp(v.astype(np.float64), exponent).astype(np.float32) for k, v in random_grads(n, 401).items()}
+    assert all(np.all(np.isfinite(v)) for v in g.values())
+    return case(mesh, o, d, group, vertex0, 1e-3, g, merge)
+
+
+def repeated_ray_case(mesh, count, merge=False):
+    """One recipe ray and its output gradients, `count` times: every accumulator holds count times the ray's integer."""
+    o, d, group, vertex0 = recipe_rays(mesh, 1, 500)
+    g = random_grads(1, 501)
+    rep = lambda a: np.ascontiguousarray(np.repeat(a, count, axis=0))          # noqa: E731
+    return case(mesh, rep(o), rep(d), rep(group), rep(vertex0), 1e-3, {k: rep(v) for k, v in g.items()}, merge)
+
+
+def repeated_ray_expectation(mesh, c, result):
+    """count x q per corner component as Python integers, from the harness's contribution of ray 0 and its unit exponent."""
+    p, idx, runs = mesh
+    count, u = len(c["group"]), int(result["unit_exponent"])
+    corner = int(runs[c["group"][0], 0]) + int(c["vertex0"][0])
+    expect = np.zeros((p.shape[0], 3), np.float32)
+    top = 0
+    for cn in range(3):
+        for k in range(3):
+            total = count * int(np.rint(np.ldexp(np.float64(result["contrib"][0, 3 * cn + k]), -u)))
+            top = max(top, abs(total))
+            expect[idx[corner + cn], k] = np.float32(np.ldexp(np.float64(total), u))
+    assert top < 2 ** 62
+    return expect, top.bit_length()

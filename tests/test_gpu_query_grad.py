@@ -1,7 +1,8 @@
 """prt_trace_rays_backward on the GPU: the device's bits against the host harness's (tests/query_grad_host_harness.cpp runs the same
 kernels lane by lane), the accuracy yardstick (torch CPU autograd in float64, tests/query_grad_cases.py), independence of ray order
 and of the run, subsets and refusals, a moved scene, torch autograd through par_raytracer_amd.autograd, and the 8-wide library.
-The tests always feed the forward call's own (group, vertex0) to the backward call."""
+Those tests feed the forward call's own (group, vertex0) to the backward call.  The tests of mixed waves, of batches past one pass of
+the capped grid and of the fixed point's extremes take the cases of tests/query_grad_cases.py, which carry their own references."""
 from __future__ import annotations
 
 import os
@@ -226,6 +227,120 @@ def test_autograd_equals_the_direct_call_and_descends(scenes):
     rq.update_geometry(quad[0])                                   # leave the cached scene as it was uploaded
 
 
+# ---- mixed waves, batches past one pass of the capped grid, the fixed point's extremes.  The backward call does not trace: the
+# cases of tests/query_grad_cases.py carry their own references and are the ones tests/test_query_grad_host.py proves on the CPU.
+
+def backward_case(r, c, torch_path, merge=None):
+    r.set_option("QGRAD_MERGE", merge)
+    try:
+        return backward(r, c["o"], c["d"], c["group"], c["vertex0"], c["mesh"][0], c["ray_bias"], c["gout"], torch_path)
+    finally:
+        r.set_option("QGRAD_MERGE", None)
+
+
+def backward_with_live_rows_behind(r, c, merge):
+    """The device entry point on tensors that are the first `count` rows of longer ones, whose next 64 rows hold contributing rays
+    of the same batch: a lane at or past `count` that was not held back would read a live ray there and add it."""
+    import torch
+    n = len(c["group"])
+    live = np.nonzero(c["contributing"])[0][:64]
+    assert live.size == 64 and n % 64 != 0
+    cv = lambda a: torch.from_numpy(np.ascontiguousarray(np.concatenate([a, a[live]]))).cuda()[:n]      # noqa: E731
+    g = c["gout"]
+    r.set_option("QGRAD_MERGE", merge)
+    try:
+        res = r.trace_rays_backward(cv(c["o"]), cv(c["d"]), cv(c["group"]), cv(c["vertex0"].view(np.int32)),
+                                    torch.from_numpy(c["mesh"][0]).cuda(), ray_bias=c["ray_bias"], grad_t=cv(g["t"]), grad_bw=cv(g["bw"]),
+                                    grad_position=cv(g["position"]), grad_normal=cv(g["normal"]))
+    finally:
+        r.set_option("QGRAD_MERGE", None)
+    return {k: (v.cpu().numpy() if k != "info" else v) for k, v in res.items()}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["cornell_box", "icosphere_l3"])
+def test_mixed_waves_equal_the_host_harness(scenes, harness, name):
+    r, mesh = scenes(name)
+    c = Q.wave_layout_case(mesh, 200, False)
+    h = harness([c])[0]
+    expect = Q.exact_integer_sum(mesh, c, h)
+    assert (h["hit_rays"], h["skipped_rays"]) == (c["hit_rays"], c["skipped_rays"])
+    for merge in (0, 1):
+        for torch_path in (False, True):
+            res = backward_case(r, c, torch_path, merge)
+            same_as_harness(res, h)
+            assert (res["info"].hit_rays, res["info"].skipped_rays) == (c["hit_rays"], c["skipped_rays"]), (merge, torch_path)
+            assert np.array_equal(bits(res["positions"]), bits(expect)), (merge, torch_path)
+            assert np.all(bits(res["origins"][~c["contributing"]]) == 0) and np.all(bits(res["directions"][~c["contributing"]]) == 0)
+        same_as_harness(backward_with_live_rows_behind(r, c, merge), h)
+
+
+@pytest.mark.gpu
+def test_batches_past_one_grid_pass(scenes, harness):
+    """query_backward caps the grid at 8 * cu_count blocks of 256: this batch is two full passes of it, three waves and 37 lanes."""
+    import time
+    import torch
+    # The context's own cu_count is not exported.  It starts as hipGetDeviceProperties' multiProcessorCount - the figure torch
+    # reports - and PRT_RESERVE_CUS can only lower it, which makes a pass shorter: the second pass is reached either way.
+    assert not os.environ.get("PRT_RESERVE_CUS")
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    count = 2 * 8 * cus * 256 + 3 * 64 + 37
+    assert count > 8 * cus * 256 and count % 64 == 37
+    r, mesh = scenes("cornell_box")
+    t0 = time.perf_counter()
+    o, d, group, vertex0 = Q.recipe_rays(mesh, count, 600)
+    rand = Q.case(mesh, o, d, group, vertex0, 1e-3, Q.random_grads(count, 601))
+    rep = Q.repeated_ray_case(mesh, count)
+    h_rand, h_rep = harness([rand, rep])
+    t1 = time.perf_counter()
+    assert h_rand["hit_rays"] == count and h_rep["hit_rays"] == count
+    expect_rand = Q.exact_integer_sum(mesh, rand, h_rand)
+    expect_rep, top_bits = Q.repeated_ray_expectation(mesh, rep, h_rep)
+    first = None
+    for merge in (0, 1):
+        res = backward_case(r, rand, True, merge)
+        same_as_harness(res, h_rand)
+        assert np.array_equal(bits(res["positions"]), bits(expect_rand)), merge
+        first = res
+        res = backward_case(r, rep, True, merge)              # merge 0: every ray's 9 adds land on the same 9 words
+        same_as_harness(res, h_rep)
+        assert np.array_equal(bits(res["positions"]), bits(expect_rep)), merge
+    same_as_harness(backward_case(r, rand, False), h_rand)    # the host entry point
+    p = np.random.default_rng(602).permutation(count)
+    perm = backward_case(r, Q.case(mesh, o[p], d[p], group[p], vertex0[p], 1e-3, {k: v[p] for k, v in rand["gout"].items()}), True)
+    assert np.array_equal(bits(perm["positions"]), bits(first["positions"]))
+    assert np.array_equal(bits(perm["origins"]), bits(first["origins"][p]))
+    t2 = time.perf_counter()
+    print("CUs %d, count %d, the repeated ray's largest accumulator has %d bits; cases and harness %.2f s, device calls and checks %.2f s"
+          % (cus, count, top_bits, t1 - t0, t2 - t1))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["cornell_box", "icosphere_l3"])
+def test_fixed_point_extremes_on_the_device(scenes, harness, name):
+    r, mesh = scenes(name)
+    cases = [Q.scaled_grads_case(mesh, e) for e in Q.SCALED_EXPONENTS]
+    n = Q.LAYOUT_RAYS
+    for e, c, h in zip(Q.SCALED_EXPONENTS, cases, harness(cases)):
+        m = float(h["max_contribution"])
+        print("%s 2^%d: M %.3g, unit exponent %d, hit %d, skipped %d" % (name, e, m, h["unit_exponent"], h["hit_rays"], h["skipped_rays"]))
+        # the regimes, from the harness: a denormal M, a positive unit exponent, a batch skipped in part, a sum that is +-inf
+        if e == -140:
+            assert 0 < m < 2.0 ** -126 and h["skipped_rays"] == 0 and np.abs(h["positions"]).max() > 0
+        if e == 100:
+            assert h["unit_exponent"] > 0
+        if (e, name) in ((122, "icosphere_l3"), (124, "cornell_box")):
+            assert 0 < h["skipped_rays"] < n
+        if (e, name) == (124, "cornell_box"):
+            assert np.isinf(h["positions"]).any()
+        expect = Q.exact_integer_sum(mesh, c, h)
+        for merge in (0, 1):
+            for torch_path in (False, True):
+                res = backward_case(r, c, torch_path, merge)
+                same_as_harness(res, h)
+                assert np.array_equal(bits(res["positions"]), bits(expect)), (e, merge, torch_path)
+
+
 CHILD = r"""
 import os, sys
 sys.path.insert(0, %(root)r); sys.path.insert(0, os.path.join(%(root)r, "tests")); sys.path.insert(0, os.path.join(%(root)r, "oracle"))
@@ -245,6 +360,12 @@ exe = Q.build_harness(%(tmp)r, sanitize=False)
 h = Q.run_harness(exe, [Q.case(mesh, o, d, group, vertex0, 1e-3, g)], %(tmp)r)[0]
 for torch_path in (False, True):
     same_as_harness(backward(r, o, d, group, vertex0, mesh[0], 1e-3, g, torch_path), h)
+c = Q.wave_layout_case(mesh, 200, False)                      # the mixed waves: the gradient kernels read nothing of the tree
+h = Q.run_harness(exe, [c], %(tmp)r)[0]
+res = backward(r, c["o"], c["d"], c["group"], c["vertex0"], mesh[0], c["ray_bias"], c["gout"], True)
+same_as_harness(res, h)
+assert (res["info"].hit_rays, res["info"].skipped_rays) == (c["hit_rays"], c["skipped_rays"])
+assert np.array_equal(Q.bits(res["positions"]), Q.bits(Q.exact_integer_sum(mesh, c, h)))
 r.close()
 print("bvh8 query gradients ok")
 """

@@ -439,6 +439,101 @@ def test_refused_updates_write_nothing():
         r.close()
 
 
+# ---- 7b. more corners than one pass of k_refit_bounds' capped grid ----------------------------------------------------------
+
+def triangle_soup(n_tris, seed):
+    """n_tris small triangles, one per cell of a jittered square grid of unit cells, each owning its three vertices (so every
+    vertex is exactly one corner of k_refit_bounds' loop); all face +z, none touches another.  A mesh of tests/query_grad_cases.py."""
+    rng = np.random.default_rng(seed)
+    side = int(np.ceil(np.sqrt(n_tris)))
+    cell = np.arange(n_tris)
+    centre = np.stack([cell % side + 0.5, cell // side + 0.5, np.zeros(n_tris)], 1) + rng.uniform(-0.1, 0.1, (n_tris, 3))
+    angle = rng.uniform(0, 2 * np.pi, n_tris)[:, None] + np.array([0.0, 2.1, 4.2])[None, :]          # counter-clockwise seen from +z
+    radius = rng.uniform(0.15, 0.3, (n_tris, 3))
+    corners = centre[:, None, :] + np.stack([radius * np.cos(angle), radius * np.sin(angle), rng.uniform(-0.05, 0.05, (n_tris, 3))], 2)
+    p = np.ascontiguousarray(corners.reshape(-1, 3), np.float32)
+    return p, np.arange(3 * n_tris, dtype=np.uint32), np.array([[0, 3 * n_tris]], np.uint32)
+
+
+@pytest.mark.gpu
+def test_a_soup_larger_than_one_pass_of_the_bounds_kernel():
+    """update_geometry caps k_refit_bounds' grid at 8 * cu_count blocks of 256 lanes; this soup has one and a half times as many
+    corners, plus 111.  Single-vertex probes spread over the index range - a third of them in the second pass - must each be seen
+    by the reduction: 1e6 is the new abs_max, NaN refuses the update."""
+    import time
+    import torch
+    import query_grad_cases as Q
+    from par_raytracer_amd import capi
+    lib = capi.hip_lib()
+    # The context's own cu_count is not exported.  It starts as hipGetDeviceProperties' multiProcessorCount - the figure torch
+    # reports - and PRT_RESERVE_CUS can only lower it, which makes a pass shorter: the second pass is reached either way.
+    assert not os.environ.get("PRT_RESERVE_CUS")
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    one_pass = 8 * cus * 256
+    T = one_pass // 2 + 37
+    assert one_pass < 3 * T < 2 * one_pass and (3 * T) % 64 != 0
+    t0 = time.perf_counter()
+    mesh = triangle_soup(T, 7)
+    p, idx, runs = mesh
+    ext = float(p.max())
+    k = np.float32(2.0 * np.pi / ext)
+    moved_p = np.ascontiguousarray((p + np.float32(0.02 * ext) * np.sin(p[:, [1, 2, 0]] * k + np.float32(0.7))).astype(np.float32))
+    moved_mesh = (moved_p, idx, runs)
+    rng = np.random.default_rng(9)
+    target = rng.integers(0, T, 4096)
+    o, d, _, _ = Q.recipe_rays(moved_mesh, 4096, 8, triangles=target)
+    a, b, c = (moved_p[3 * target + j].astype(np.float64) for j in range(3))
+    reach = 0.25 * np.sqrt(np.linalg.norm(np.cross(b - a, c - a), axis=1))       # the recipe's distance to its target: tmax on both sides of it
+    g = {"origins": o, "directions": d, "tmax": (reach * rng.uniform(0.25, 2.0, 4096)).astype(np.float32), "ray_bias": np.zeros(4096, np.float32)}
+    ra, rb = make_renderer("lbvh"), make_renderer("lbvh")
+    try:
+        ra.upload(Q.flat_desc(mesh))
+        assert ra.scene_info().triangle_count == T
+        before = _queries(ra, g, False)
+        t1 = time.perf_counter()
+        info = ra.update_geometry(moved_p)
+        assert info.abs_max == np.abs(moved_p).max()
+        fresh = Q.flat_desc(moved_mesh)
+        rb.upload(fresh)
+        chk = ra.check_refit(fresh)
+        assert chk["violations"] == 0 and chk["refs"] == T, chk
+        t2 = time.perf_counter()
+        got, exp = _queries(ra, g, False), _queries(rb, g, False)
+        for key in exp:
+            assert np.array_equal(got[key], exp[key]), key
+        hits = int((exp["group"].view(np.int32) >= 0).sum())
+        assert hits >= 0.9 * 4096 and 0 < exp["occluded_tmax"].sum() < exp["occluded"].sum()
+        assert any(np.any(before[key] != exp[key]) for key in CLOSEST), "the move was meant to change the hits"
+
+        def refused(positions):
+            u = capi.PrtGeometryUpdate()
+            u.positions, u.position_count = positions.ctypes.data, positions.size // 3
+            return lib.prt_update_geometry(ra._ctx, C.byref(u), None)
+
+        # k_refit_bounds walks the leaf slots of the LBVH tree, not the vertex index: which probes fall into the second pass (slots
+        # from one_pass / 3 on, the last third) depends on the builder's order, which no call exports, so the test cannot name
+        # them.  The tree is built over Morton codes of the grid; vertices spread evenly over the row-major index cover every
+        # row of it, and only a builder that put all 32 into the first two thirds of its order would hide a dropped pass.
+        t3 = time.perf_counter()
+        for vertex in np.linspace(0, 3 * T - 1, 32).astype(np.int64):
+            probe = moved_p.copy()
+            probe[vertex, 2] = 1e6
+            assert ra.update_geometry(probe).abs_max == np.float32(1e6), vertex
+            kept = _queries(ra, g, False)
+            probe[vertex, 2] = np.nan
+            assert refused(probe) == -1, vertex
+            assert lib.prt_last_error(ra._ctx).decode().startswith("prt_update_geometry"), vertex
+            after = _queries(ra, g, False)
+            for key in kept:
+                assert np.array_equal(after[key], kept[key]), (vertex, key)
+        t4 = time.perf_counter()
+        print("CUs %d, T %d, %d corners; soup, upload and first queries %.2f s, update, fresh upload and check %.2f s, "
+              "queries %.2f s, 32 probes %.2f s" % (cus, T, 3 * T, t1 - t0, t2 - t1, t3 - t2, t4 - t3))
+    finally:
+        ra.close()
+        rb.close()
+
+
 # ---- 8. several devices behind one handle ----------------------------------------------------------------------------------
 
 @pytest.mark.gpu

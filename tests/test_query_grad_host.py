@@ -128,6 +128,97 @@ def test_65_rays_on_one_triangle_sum_as_python_integers(harness, meshes, merge):
     assert np.array_equal(bits(r["positions"]), bits(expect))
 
 
+# ---- the shared cases of the GPU suite (tests/query_grad_cases.py), proven here before a device sees them
+
+def both_merges_against_the_integer_sum(run, mesh, build):
+    """build(merge) -> case.  The harness with and without the merge gives the same bits, the vertex gradient equals
+    exact_integer_sum, rays that add nothing get zero origin and direction gradients.  Returns the merge-off result."""
+    cases = [build(False), build(True)]
+    off, on = run(cases)
+    assert off["rc"] == 0 and on["rc"] == 0
+    for k in Q.GRADS + ("contrib",):
+        assert np.array_equal(bits(off[k]), bits(on[k])), k
+    for k in ("hit_rays", "skipped_rays", "unit_exponent"):
+        assert off[k] == on[k], k
+    assert bits(off["max_contribution"]) == bits(on["max_contribution"])
+    assert np.array_equal(bits(off["positions"]), bits(Q.exact_integer_sum(mesh, cases[0], off)))
+    dead = ~np.any(off["contrib"] != 0, axis=1)
+    assert int((~dead).sum()) == off["hit_rays"]
+    assert np.all(bits(off["origins"][dead]) == 0) and np.all(bits(off["directions"][dead]) == 0)
+    return cases[0], off
+
+
+@pytest.mark.parametrize("name", ["cornell_box", "icosphere_l3"])
+@pytest.mark.parametrize("layout", ["waves", "regular"])
+def test_mixed_wave_layouts_sum_as_integers(harness, meshes, name, layout):
+    mesh = meshes[name]
+    build = (lambda m: Q.wave_layout_case(mesh, 200, m)) if layout == "waves" else (lambda m: Q.regular_case(mesh, merge=m))
+    c, r = both_merges_against_the_integer_sum(harness, mesh, build)
+    n = len(c["group"])
+    assert n == Q.LAYOUT_RAYS == 2085 and n % 64 == 37
+    assert (r["hit_rays"], r["skipped_rays"]) == (c["hit_rays"], c["skipped_rays"])
+    assert 0 < c["hit_rays"] and 0 < c["skipped_rays"] and c["hit_rays"] + c["skipped_rays"] < n
+    assert np.array_equal(np.any(r["contrib"] != 0, axis=1), c["contributing"])
+    assert np.all(np.any(r["origins"][c["contributing"]] != 0, axis=1)) and np.abs(r["positions"]).max() > 0
+    if layout == "waves":                                      # the layout is what its docstring says
+        live = c["contributing"].reshape(-1)
+        w = lambda k: live[64 * k:64 * k + 64]                                    # noqa: E731
+        key = c["mesh"][2][np.maximum(c["group"], 0), 0].astype(np.int64) + c["vertex0"]
+        assert not w(3).any() and list(np.nonzero(w(5))[0]) == [0] and list(np.nonzero(w(6))[0]) == [63]
+        assert w(7).all() and len(set(key[64 * 7:64 * 8])) == 1
+        assert w(8).all() and np.array_equal(key[64 * 8:64 * 9:2], key[64 * 8 + 1:64 * 9:2])
+        if name == "icosphere_l3":
+            assert len(set(key[64 * 8:64 * 9])) == 32
+        k9 = key[64 * 9:64 * 10]
+        assert w(9).all() and (k9 == k9[0]).sum() == 1 and all((k9 == k).sum() >= 3 for k in k9[1:])
+        last, kl = w(32), key[64 * 32:]
+        assert last.size == 37 and last[:32].all() and not last[32:].any()
+        assert all((kl[:32] == k).sum() == 3 for k in kl[:30]) and all((kl[:32] == k).sum() == 1 for k in kl[30:32])
+
+
+@pytest.mark.parametrize("name", ["cornell_box", "icosphere_l3"])
+@pytest.mark.parametrize("exponent", Q.SCALED_EXPONENTS)
+def test_fixed_point_extremes(harness, meshes, name, exponent):
+    mesh = meshes[name]
+    c, r = both_merges_against_the_integer_sum(harness, mesh, lambda m: Q.scaled_grads_case(mesh, exponent, m))
+    n = len(c["group"])
+    m = float(r["max_contribution"])
+    print("%s 2^%d: M %.3g, unit exponent %d, hit %d, skipped %d, %d non-finite entries" % (
+        name, exponent, m, r["unit_exponent"], r["hit_rays"], r["skipped_rays"], int((~np.isfinite(r["positions"])).sum())))
+    assert r["hit_rays"] + r["skipped_rays"] == n and np.float32(np.abs(r["contrib"]).max()) == r["max_contribution"]
+    if exponent == -140:
+        assert 0 < m < 2.0 ** -126 and r["skipped_rays"] == 0 and r["unit_exponent"] < -149
+        assert np.abs(r["positions"]).max() > 0
+    if exponent == 100:
+        assert r["unit_exponent"] > 0 and r["skipped_rays"] == 0
+    if (exponent, name) in ((122, "icosphere_l3"), (124, "cornell_box")):
+        assert 0 < r["skipped_rays"] < n
+    if (exponent, name) == (124, "cornell_box"):              # finite contributions whose exact sum exceeds float32: +-inf
+        assert np.all(np.isfinite(r["contrib"])) and np.isinf(r["positions"]).any() and not np.isnan(r["positions"]).any()
+
+
+@pytest.fixture(scope="module")
+def plain_harness(tmp_path_factory):
+    """Without the sanitizers, for the half million rays of the batch that passes the capped grid on the device."""
+    d = tmp_path_factory.mktemp("query_grad_host_plain")
+    exe = Q.build_harness(d, sanitize=False)
+    return lambda cases: Q.run_harness(exe, cases, d)
+
+
+def test_a_repeated_ray_sums_to_count_times_its_integer(harness, plain_harness, meshes):
+    """At 2,085 rays on the sanitized harness, and at 2 * 8 * 256 * 256 + 3 * 64 + 37 = 1,048,805 - the device suite's batch on a
+    256-CU part - on the plain one."""
+    mesh = meshes["cornell_box"]
+    for run, count in ((harness, Q.LAYOUT_RAYS), (plain_harness, 2 * 8 * 256 * 256 + 3 * 64 + 37)):
+        c, r = both_merges_against_the_integer_sum(run, mesh, lambda m: Q.repeated_ray_case(mesh, count, m))
+        expect, top_bits = Q.repeated_ray_expectation(mesh, c, r)
+        print("count %d: the largest accumulator has %d bits" % (count, top_bits))
+        # the largest |q| is at least 2^(61 - L) and count > 2^L / 6, so the largest accumulator is at least 2^61 / 6 > 2^58
+        assert r["hit_rays"] == count and 59 <= top_bits <= 62
+        assert np.array_equal(bits(r["positions"]), bits(expect))
+        assert np.all(bits(r["origins"]) == bits(r["origins"][0])) and np.all(bits(r["directions"]) == bits(r["directions"][0]))
+
+
 def test_invalid_references_are_refused_before_anything_is_written(harness, meshes):
     mesh = meshes["cornell_box"]
     p, idx, runs = mesh
