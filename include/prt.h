@@ -382,6 +382,48 @@ int prt_trace_rays_backward_device(prt_ctx * ctx, const prt_ray_batch * batch, c
                                    const float * positions, uint32_t position_count, const prt_hit_grads * gout,
                                    const prt_query_grads * gin, prt_grad_info * info);
 
+/* ---- closest points: the nearest point of the uploaded surface, for batches of points ------------------------------------------
+ * The spatial query beside the rays: point-to-surface and chamfer losses when a mesh is fitted to scanned points, collision and
+ * penetration tests, projecting samples onto the surface.  One call answers `count` independent points against the scene as it
+ * lies on the device now (after any number of prt_update_geometry calls).
+ * THE DEFINITION (csrc/dev_closest.h).  For a triangle record (a, ab = b - a, ac = c - a),
+ * closest_on_triangle is the region walk of Ericson, Real-Time Collision Detection 5.1.5, in float32 and a fixed expression
+ * order: it gives (v, w), q = (a + ab * v) + ac * w and d2 = Dot(p - q, p - q).  Both sides count: there is no facing test.  A
+ * triangle whose d2, v or w is not finite is no candidate.  The answer for p is, among the triangles with d2 <= max_dist2[i]
+ * (FLT_MAX with max_dist2 NULL), the one with the smallest d2 and, among equal d2 bits, the smallest (group, vertex0): a pure
+ * function of (scene, point) - the same bits for every tree (SAH, LBVH, 8-wide, refitted), launch shape and run, and the bits
+ * a brute force over all triangles with the same function gives.
+ * A point with a non-finite component, or with max_dist2 negative or NaN, is a miss; it is not an error and does not affect
+ * the other points.  A miss: dist2 = FLT_MAX, point and bw zeros, group = -1, vertex0 = 0xFFFFFFFF (the ray queries'
+ * convention); a scene of 0 triangles makes every point a miss.  max_dist2 = +inf is "no limit", 0 finds points on the surface.
+ * The walk culls boxes by their distance to p, padded by 2^-16 x max(scene extent, max |finite point component| of the batch);
+ * points far from the scene (many extents away) are exact but slow: their box distances all tie within the pad and much of the
+ * tree is visited.
+ * Counters: ray_count = count; node_visits / tri_tests with PRT_FLAG_COUNT_VISITS in `flags`; render_ms = the call's device
+ * time, trace_kernel_ms = the walk kernels'; pipeline = 0.  prt_get_render_stats (the last render's) is left alone.
+ * Errors: -1 NULL batch or buffers struct, NULL points with count > 0; -2 no scene; -10 a HIP call failed.  count == 0 writes
+ * nothing and returns 0.
+ * Shares the ray queries' leaf -> (group, vertex0) table (built by the first query of either kind after an upload). */
+typedef struct prt_point_batch {
+    const float * points;          /* count x 3 */
+    const float * max_dist2;       /* count squared radii; NULL = no limit */
+    uint32_t count;
+} prt_point_batch;
+/* Every pointer may be NULL: that field is not written. */
+typedef struct prt_closest_buffers {
+    float * dist2;                 /* d2; FLT_MAX on a miss */
+    float * point;                 /* x3: q */
+    float * bw;                    /* x3: (1 - v - w, v, w), as prt_hit_buffers.bw */
+    uint32_t * vertex0;            /* as prt_hit_buffers.vertex0; 0xFFFFFFFF on a miss */
+    int32_t * group;               /* as prt_hit_buffers.group; -1 on a miss */
+} prt_closest_buffers;
+/* Host pointers (batch arrays and buffers). */
+int prt_closest_points(prt_ctx * ctx, const prt_point_batch * batch, const prt_closest_buffers * out, uint32_t flags,
+                       prt_counters * counters);
+/* Device pointers on the context's device; the stream contract of prt_trace_rays_device. */
+int prt_closest_points_device(prt_ctx * ctx, const prt_point_batch * batch, const prt_closest_buffers * out, uint32_t flags,
+                              prt_counters * counters);
+
 /* ---- several devices behind one handle --------------------------------------------------------------------------------
  * SURVEY.md 8(b)'s prt_create(const int * device_ids, int n_dev): what the host mirror's Render() uses for n GPUs, in place
  * of the reference's one-rank-per-core partition + MPI_Gather (main.cpp:311-347).  The scene is replicated (as every MPI rank

@@ -400,6 +400,85 @@ class Renderer:
         out["counters"] = counters
         return out
 
+    # (name, components per point, numpy dtype) of prt_closest_buffers' fields
+    CLOSEST_POINT_FIELDS = (("dist2", 1, np.float32), ("point", 3, np.float32), ("bw", 3, np.float32), ("vertex0", 1, np.uint32),
+                            ("group", 1, np.int32))
+
+    def closest_points(self, points, *, max_dist=None, fields: Optional[Sequence[str]] = None, count_visits: bool = False) -> dict:
+        """The nearest point of the uploaded surface for n points (prt_closest_points, include/prt.h).
+
+        points: float32 (n, 3), contiguous - a numpy array (host entry point, numpy results) or a torch tensor on this context's
+        device (device entry point, tensors on that device).  max_dist: None, or float32 (n,) DISTANCES: the wrapper squares them
+        in float32 (max_dist * max_dist, rounded once) and passes the squares as max_dist2; a triangle is a candidate when its
+        squared distance is <= that square.  fields: any of dist2, point, bw, vertex0, group (default all).  Returns {field: array}
+        plus "distance" = sqrt(dist2) when dist2 is among the fields - inf on a miss - and "counters" (PrtCounters)."""
+        spec = {name: (k, dt) for name, k, dt in self.CLOSEST_POINT_FIELDS}
+        if fields is None:
+            fields = tuple(spec)
+        for f in fields:
+            if f not in spec:
+                raise ValueError("unknown closest-point field %r" % (f,))
+        is_torch = type(points).__module__.split(".")[0] == "torch"
+        if is_torch:
+            import torch
+
+            def check(x, what, cols):
+                if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or not x.is_contiguous():
+                    raise ValueError("%s must be a contiguous float32 torch tensor" % what)
+                if x.device.type != "cuda" or (x.device.index or 0) != self.device_id:
+                    raise ValueError("%s must live on this context's device (cuda:%d)" % (what, self.device_id))
+                if (cols and (x.dim() != 2 or x.shape[1] != 3)) or (not cols and x.dim() != 1):
+                    raise ValueError("%s has shape %s" % (what, tuple(x.shape)))
+            check(points, "points", True)
+            n = points.shape[0]
+            max_d2 = None
+            if max_dist is not None:
+                check(max_dist, "max_dist", False)
+                if max_dist.shape[0] != n:
+                    raise ValueError("max_dist has %d entries for %d points" % (max_dist.shape[0], n))
+                max_d2 = (max_dist * max_dist).contiguous()
+            tdt = {np.float32: torch.float32, np.uint32: torch.int32, np.int32: torch.int32}     # vertex0: int32 with the same bits
+            out = {f: torch.empty((n, spec[f][0]) if spec[f][0] > 1 else (n,), dtype=tdt[spec[f][1]], device=points.device)
+                   for f in fields}
+            ptr = lambda x: x.data_ptr() if x is not None else None    # noqa: E731
+            # the library's stream is not ordered against torch's: whatever torch still has queued on the inputs must be done
+            torch.cuda.current_stream(points.device).synchronize()
+            entry = self._lib.prt_closest_points_device
+        else:
+            def as_np(x, what, cols):
+                a = np.asarray(x)
+                if a.dtype != np.float32 or not a.flags["C_CONTIGUOUS"]:
+                    raise ValueError("%s must be a contiguous float32 array" % what)
+                if (cols and (a.ndim != 2 or a.shape[1] != 3)) or (not cols and a.ndim != 1):
+                    raise ValueError("%s has shape %s" % (what, a.shape))
+                return a
+            points = as_np(points, "points", True)
+            n = points.shape[0]
+            max_d2 = None
+            if max_dist is not None:
+                max_dist = as_np(max_dist, "max_dist", False)
+                if max_dist.shape[0] != n:
+                    raise ValueError("max_dist has %d entries for %d points" % (max_dist.shape[0], n))
+                with np.errstate(over="ignore"):
+                    max_d2 = np.ascontiguousarray(max_dist * max_dist, np.float32)
+            out = {f: np.empty((n, spec[f][0]) if spec[f][0] > 1 else (n,), dtype=spec[f][1]) for f in fields}
+            ptr = lambda x: x.ctypes.data if x is not None else None    # noqa: E731
+            entry = self._lib.prt_closest_points
+        batch = capi.PrtPointBatch(ptr(points), ptr(max_d2), n)
+        cb = capi.PrtClosestBuffers(*[ptr(out[name]) if name in out else None for name, _, _ in self.CLOSEST_POINT_FIELDS])
+        counters = PrtCounters()
+        flags = capi.FLAG_COUNT_VISITS if count_visits else 0
+        self._check(entry(self._ctx, C.byref(batch), C.byref(cb), flags, C.byref(counters)),
+                    "prt_closest_points_device" if is_torch else "prt_closest_points")
+        if "dist2" in out:
+            d2 = out["dist2"]
+            if is_torch:
+                out["distance"] = torch.where(d2 < 3.4028234663852886e38, d2.sqrt(), torch.full_like(d2, float("inf")))
+            else:
+                out["distance"] = np.where(d2 < np.float32(3.4028234663852886e38), np.sqrt(d2), np.float32(np.inf)).astype(np.float32)
+        out["counters"] = counters
+        return out
+
     GRAD_NAMES = ("positions", "origins", "directions")
 
     def trace_rays_backward(self, origins, directions, group, vertex0, positions, *, ray_bias: float = 0.0, grad_t=None, grad_bw=None,

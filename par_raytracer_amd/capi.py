@@ -105,6 +105,14 @@ class PrtHitBuffers(C.Structure):
                 ("position", C.c_void_p), ("normal", C.c_void_p), ("occluded", C.c_void_p)]
 
 
+class PrtPointBatch(C.Structure):
+    _fields_ = [("points", C.c_void_p), ("max_dist2", C.c_void_p), ("count", C.c_uint32)]
+
+
+class PrtClosestBuffers(C.Structure):
+    _fields_ = [("dist2", C.c_void_p), ("point", C.c_void_p), ("bw", C.c_void_p), ("vertex0", C.c_void_p), ("group", C.c_void_p)]
+
+
 class PrtGeometryUpdate(C.Structure):
     _fields_ = [("positions", C.c_void_p), ("position_count", C.c_uint32), ("normals", C.c_void_p), ("normal_count", C.c_uint32),
                 ("tangents", C.c_void_p), ("spheres", C.POINTER(PrtBSphere)), ("sphere_group", C.POINTER(C.c_int32)),
@@ -147,7 +155,8 @@ PRT_SYMBOLS = ["prt_create", "prt_destroy", "prt_last_error", "prt_abi_version",
                "prt_multi_upload_scene", "prt_multi_render", "prt_multi_depth", "prt_multi_submit", "prt_multi_wait", "prt_debug_throw",
                "prt_trace_rays", "prt_trace_rays_device", "prt_get_region_stats",
                "prt_update_geometry", "prt_update_geometry_device", "prt_multi_update_geometry", "prt_debug_check_refit",
-               "prt_trace_rays_backward", "prt_trace_rays_backward_device"]
+               "prt_trace_rays_backward", "prt_trace_rays_backward_device",
+               "prt_closest_points", "prt_closest_points_device"]
 # PRT_REGION_* of include/prt.h, in index order (tests/test_host_side.py's header check keeps the symbol list in step; the
 # region test compares this list with the header's enum)
 REGION_NAMES = ["round", "topup", "topup_pass", "trace_outer", "refill", "walk_pass", "node_step", "node_descend", "node_pop", "node_push", "leaf",
@@ -238,6 +247,10 @@ def hip_lib() -> C.CDLL:
             lib.prt_trace_rays_backward.argtypes = [C.c_void_p, C.POINTER(PrtRayBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                                     C.POINTER(PrtHitGrads), C.POINTER(PrtQueryGrads), C.POINTER(PrtGradInfo)]
             lib.prt_trace_rays_backward_device.argtypes = lib.prt_trace_rays_backward.argtypes
+        if hasattr(lib, "prt_closest_points"):         # (absent from a PRT_HIP_LIB build of an earlier commit)
+            lib.prt_closest_points.argtypes = [C.c_void_p, C.POINTER(PrtPointBatch), C.POINTER(PrtClosestBuffers), C.c_uint32,
+                                               C.POINTER(PrtCounters)]
+            lib.prt_closest_points_device.argtypes = lib.prt_closest_points.argtypes
         _hip = lib
     return _hip
 

@@ -31,6 +31,7 @@
 #include "kernels_query.h"
 #include "kernels_refit.h"
 #include "kernels_query_grad.h"
+#include "kernels_closest.h"
 
 using namespace prt;
 
@@ -1168,22 +1169,27 @@ int launch_query(prt_ctx * ctx, const QueryArgs & A, const uint2 * leaf_map, uns
     return 0;
 }
 
+// The leaf -> (group, vertex0) table of the queries (prt_trace_rays, prt_closest_points), built by the first of them after an upload.
+int ensure_leaf_map(prt_ctx * ctx, const char * who) {
+    if (ctx->q_leaf_map.p) return 0;
+    const uint32_t n_tris = ctx->scene.tri_count;
+    if (ctx->q_tri_order.size() != n_tris) { ctx->error = std::string(who) + ": the scene's leaf order is not available"; return -2; }
+    std::vector<uint2> of_input(n_tris), map((size_t)n_tris + 1, make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu));
+    for (uint32_t g = 0; g < (uint32_t)ctx->q_groups.size(); ++g) {
+        const prt_group & pg = ctx->q_groups[g];
+        for (uint32_t k = 0; k < pg.index_count / 3; ++k) of_input[pg.first_index / 3 + k] = make_uint2(g, 3u * k);   // IntersectRayMesh's vertex0 = i
+    }
+    for (uint32_t slot = 0; slot < n_tris; ++slot) map[slot] = of_input[ctx->q_tri_order[slot]];
+    HIP_TRY(ctx, ctx->q_leaf_map.upload(map));
+    HIP_TRY(ctx, hipDeviceSynchronize());              // the upload went through the null stream
+    return 0;
+}
+
 // One batch on the device: A's rays and outputs are device pointers; pad_max < 0 asks k_query_pad for the origins' extent.
 // Synchronous (returns after the context's stream has drained).
 int run_query(prt_ctx * ctx, int mode, QueryArgs A, unsigned int fields, bool count_visits, prt_counters * counters) {
-    // the leaf -> (group, vertex0) table, built on the first query after an upload
-    if (!ctx->q_leaf_map.p) {
-        const uint32_t n_tris = ctx->scene.tri_count;
-        if (ctx->q_tri_order.size() != n_tris) { ctx->error = "prt_trace_rays: the scene's leaf order is not available"; return -2; }
-        std::vector<uint2> of_input(n_tris), map((size_t)n_tris + 1, make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu));
-        for (uint32_t g = 0; g < (uint32_t)ctx->q_groups.size(); ++g) {
-            const prt_group & pg = ctx->q_groups[g];
-            for (uint32_t k = 0; k < pg.index_count / 3; ++k) of_input[pg.first_index / 3 + k] = make_uint2(g, 3u * k);   // IntersectRayMesh's vertex0 = i
-        }
-        for (uint32_t slot = 0; slot < n_tris; ++slot) map[slot] = of_input[ctx->q_tri_order[slot]];
-        HIP_TRY(ctx, ctx->q_leaf_map.upload(map));
-        HIP_TRY(ctx, hipDeviceSynchronize());              // the upload went through the null stream
-    }
+    const int map_rc = ensure_leaf_map(ctx, "prt_trace_rays");
+    if (map_rc) return map_rc;
     hipStream_t stream = ctx->stream;
     ctx->scene.tie_widen_max = (unsigned int)std::max(0ll, std::min(64ll, ctx->opt.tie_widen_max));
     // LDS stack column as the render pipelines size it; k_query_exact's fixed grid gets full-height global columns
@@ -1263,6 +1269,105 @@ int query_check(prt_ctx * ctx, int mode, const prt_ray_batch * b, prt_counters *
     if (!b) { ctx->error = "prt_trace_rays: null batch"; return -1; }
     if (b->count && (!b->origins || !b->directions)) { ctx->error = "prt_trace_rays: null origins or directions"; return -1; }
     if (!ctx->has_scene) { ctx->error = "prt_trace_rays: no scene uploaded"; return -2; }
+    if (b->count == 0) {
+        if (counters) memset(counters, 0, sizeof(*counters));
+        return 1;
+    }
+    return 0;
+}
+
+// ---- closest points (prt_closest_points, kernels_closest.h) ------------------------------------------------------------------
+
+template <bool COUNT>
+int launch_closest(prt_ctx * ctx, const ClosestArgs & A, const uint2 * leaf_map, unsigned int fields) {
+    constexpr int BLOCK = 256;
+    const size_t lds = stack_dwords(A.stack_lds_entries, BLOCK) * sizeof(int);
+    // persistent grid of resident blocks, chunks and lane-refill thresholds as launch_query's
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_closest<BLOCK, COUNT>, BLOCK, lds) != hipSuccess || per_cu < 1) per_cu = 2;
+    per_cu = std::min(per_cu, 8);
+    const PrtOptions & opt = ctx->opt;
+    if (opt.trace_blocks_per_cu >= 0) per_cu = std::max(1, std::min(per_cu, (int)opt.trace_blocks_per_cu));
+    int keep_min = 40, node_min = 32;
+    if (opt.keep_min >= 0) keep_min = std::max(1, std::min(64, (int)opt.keep_min));
+    if (opt.node_min >= 0) node_min = std::max(0, std::min(64, (int)opt.node_min));
+    unsigned int chunk_min = 128;
+    if (opt.chunk_min >= 0) chunk_min = (unsigned int)std::max(64ll, std::min(512ll, opt.chunk_min));
+    const unsigned int grid = std::max(1u, std::min((unsigned int)per_cu * (unsigned int)ctx->cu_count, (A.count + BLOCK - 1) / BLOCK));
+    unsigned int chunk = A.count / (grid * (BLOCK / 64) * 8u);
+    chunk = std::max(chunk_min, std::min(512u, (chunk / 64u) * 64u));
+    hipLaunchKernelGGL((k_closest<BLOCK, COUNT>), dim3(grid), dim3(BLOCK), lds, ctx->stream, ctx->scene, A, leaf_map, fields,
+                       keep_min, node_min, chunk, ctx->counters.p);
+    HIP_TRY(ctx, hipGetLastError());
+    constexpr unsigned int SLOW_BLOCKS = 64;               // A.exact_stack holds SLOW_BLOCKS * 256 columns
+    hipLaunchKernelGGL((k_closest_exact<COUNT>), dim3(SLOW_BLOCKS), dim3(256), 0, ctx->stream, ctx->scene, A, leaf_map, fields, ctx->counters.p);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+// One batch on the device: A's points and outputs are device pointers; pad_max < 0 asks k_closest_pad for the points' extent.
+// Synchronous (returns after the context's stream has drained).  The work words, the slow list and the exact stacks are the ray
+// queries' (a context runs one call at a time).
+int run_closest(prt_ctx * ctx, ClosestArgs A, unsigned int fields, bool count_visits, prt_counters * counters) {
+    const int map_rc = ensure_leaf_map(ctx, "prt_closest_points");
+    if (map_rc) return map_rc;
+    hipStream_t stream = ctx->stream;
+    unsigned int stack_cap = STACK_LDS_CAP_DEFAULT;
+    if (ctx->opt.stack_cap >= 0) stack_cap = (unsigned int)std::max(2ll, std::min(40ll, ctx->opt.stack_cap));
+    A.stack_lds_entries = std::min(ctx->stack_bound, stack_cap);
+    const size_t exact_lanes = 64 * 256;
+    HIP_TRY(ctx, ctx->q_exact_stack.ensure(stack_dwords(std::max(ctx->stack_bound, 4u), exact_lanes)));
+    A.exact_stack = ctx->q_exact_stack.p;
+    A.exact_stack_stride = (unsigned int)exact_lanes;
+    HIP_TRY(ctx, ctx->q_work.ensure(4));
+    HIP_TRY(ctx, ctx->q_slow.ensure(A.count));
+    HIP_TRY(ctx, ctx->counters.ensure(1));
+    A.work = ctx->q_work.p;
+    A.slow = ctx->q_slow.p;
+    const bool device_pad = A.pad_max < 0.0f;
+    if (device_pad) A.pad_max = ctx->scene_abs_max;
+
+    HIP_TRY(ctx, hipMemsetAsync(ctx->counters.p, 0, sizeof(DevCounters), stream));
+    HIP_TRY(ctx, hipMemsetAsync(A.work, 0, 4 * sizeof(unsigned int), stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev[0], stream));
+    if (device_pad) {
+        hipLaunchKernelGGL(k_closest_pad, dim3(std::min(1024u, (A.count + 255) / 256)), dim3(256), 0, stream, A);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev[2], stream));
+    const int rc = count_visits ? launch_closest<true>(ctx, A, ctx->q_leaf_map.p, fields) : launch_closest<false>(ctx, A, ctx->q_leaf_map.p, fields);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev[3], stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->host_counters, ctx->counters.p, sizeof(DevCounters), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev[1], stream));
+    HIP_TRY(ctx, hipEventSynchronize(ctx->ev[1]));
+    const DevCounters h = *ctx->host_counters;
+    if (counters) {
+        float ms = 0.0f, tms = 0.0f;
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+        HIP_TRY(ctx, hipEventElapsedTime(&tms, ctx->ev[2], ctx->ev[3]));
+        memset(counters, 0, sizeof(*counters));
+        counters->ray_count = A.count;
+        counters->node_visits = h.node_visits;
+        counters->tri_tests = h.tri_tests;
+        counters->render_ms = ms;
+        counters->trace_kernel_ms = tms;
+        counters->trace_kernel_launches = 2;
+        counters->pipeline = 0;
+    }
+    return 0;
+}
+
+unsigned int closest_fields(const prt_closest_buffers * o) {
+    return (o->dist2 ? CF_DIST2 : 0) | (o->point ? CF_POINT : 0) | (o->bw ? CF_BW : 0) | (o->vertex0 ? CF_VERTEX0 : 0) | (o->group ? CF_GROUP : 0);
+}
+
+// The checks both entry points share; 1 = nothing to do (count 0: counters zeroed), 0 = go on, < 0 = error.
+int closest_check(prt_ctx * ctx, const prt_point_batch * b, const prt_closest_buffers * o, prt_counters * counters) {
+    if (!ctx) return -1;
+    if (!b || !o) { ctx->error = "prt_closest_points: null batch or buffers"; return -1; }
+    if (b->count && !b->points) { ctx->error = "prt_closest_points: null points"; return -1; }
+    if (!ctx->has_scene) { ctx->error = "prt_closest_points: no scene uploaded"; return -2; }
     if (b->count == 0) {
         if (counters) memset(counters, 0, sizeof(*counters));
         return 1;
@@ -2200,6 +2305,67 @@ int prt_trace_rays(prt_ctx * ctx, int mode, const prt_ray_batch * batch, const p
     HIP_TRY(ctx, hipStreamSynchronize(stream));
     return 0;
     PRT_API_CATCH_RC(ctx, "prt_trace_rays")
+}
+
+int prt_closest_points_device(prt_ctx * ctx, const prt_point_batch * batch, const prt_closest_buffers * out, uint32_t flags,
+                              prt_counters * counters) {
+    PRT_API_TRY
+    const int chk = closest_check(ctx, batch, out, counters);
+    if (chk) return chk > 0 ? 0 : chk;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ClosestArgs A;
+    memset(&A, 0, sizeof(A));
+    A.points = batch->points; A.max_dist2 = batch->max_dist2; A.count = batch->count;
+    A.dist2 = out->dist2; A.point = out->point; A.bw = out->bw; A.vertex0 = out->vertex0; A.group = out->group;
+    A.pad_max = -1.0f;                                     // the points' extent is reduced on the device (k_closest_pad)
+    return run_closest(ctx, A, closest_fields(out), (flags & PRT_FLAG_COUNT_VISITS) != 0, counters);
+    PRT_API_CATCH_RC(ctx, "prt_closest_points_device")
+}
+
+int prt_closest_points(prt_ctx * ctx, const prt_point_batch * batch, const prt_closest_buffers * out, uint32_t flags,
+                       prt_counters * counters) {
+    PRT_API_TRY
+    const int chk = closest_check(ctx, batch, out, counters);
+    if (chk) return chk > 0 ? 0 : chk;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t n = batch->count;
+    const unsigned int fields = closest_fields(out);
+    // device copies: points, max_dist2, then the requested fields (float-sized words)
+    const size_t f_in = 3 * n + (batch->max_dist2 ? n : 0);
+    const size_t f_out = ((fields & CF_DIST2) ? n : 0) + ((fields & CF_POINT) ? 3 * n : 0) + ((fields & CF_BW) ? 3 * n : 0) +
+                         ((fields & CF_VERTEX0) ? n : 0) + ((fields & CF_GROUP) ? n : 0);
+    HIP_TRY(ctx, ctx->q_io.ensure(f_in + f_out));
+    float * p = ctx->q_io.p;
+    ClosestArgs A;
+    memset(&A, 0, sizeof(A));
+    A.points = p; p += 3 * n;
+    if (batch->max_dist2) { A.max_dist2 = p; p += n; }
+    if (fields & CF_DIST2) { A.dist2 = p; p += n; }
+    if (fields & CF_POINT) { A.point = p; p += 3 * n; }
+    if (fields & CF_BW) { A.bw = p; p += 3 * n; }
+    if (fields & CF_VERTEX0) { A.vertex0 = reinterpret_cast<unsigned int *>(p); p += n; }
+    if (fields & CF_GROUP) { A.group = reinterpret_cast<int *>(p); p += n; }
+    A.count = batch->count;
+    // the box pad from the points' extent, on the host (the same rule as k_closest_pad)
+    float extent = ctx->scene_abs_max;
+    for (size_t i = 0; i < n; ++i) {
+        const f3 q = ld3(batch->points + 3 * i);
+        if (std::isfinite(q.x) && std::isfinite(q.y) && std::isfinite(q.z)) extent = std::max(extent, std::max(std::max(fabsf(q.x), fabsf(q.y)), fabsf(q.z)));
+    }
+    A.pad_max = extent;
+    hipStream_t stream = ctx->stream;
+    HIP_TRY(ctx, hipMemcpyAsync(const_cast<float *>(A.points), batch->points, 12 * n, hipMemcpyHostToDevice, stream));
+    if (batch->max_dist2) HIP_TRY(ctx, hipMemcpyAsync(const_cast<float *>(A.max_dist2), batch->max_dist2, 4 * n, hipMemcpyHostToDevice, stream));
+    int rc = run_closest(ctx, A, fields, (flags & PRT_FLAG_COUNT_VISITS) != 0, counters);
+    if (rc) return rc;
+    if (fields & CF_DIST2) HIP_TRY(ctx, hipMemcpyAsync(out->dist2, A.dist2, 4 * n, hipMemcpyDeviceToHost, stream));
+    if (fields & CF_POINT) HIP_TRY(ctx, hipMemcpyAsync(out->point, A.point, 12 * n, hipMemcpyDeviceToHost, stream));
+    if (fields & CF_BW) HIP_TRY(ctx, hipMemcpyAsync(out->bw, A.bw, 12 * n, hipMemcpyDeviceToHost, stream));
+    if (fields & CF_VERTEX0) HIP_TRY(ctx, hipMemcpyAsync(out->vertex0, A.vertex0, 4 * n, hipMemcpyDeviceToHost, stream));
+    if (fields & CF_GROUP) HIP_TRY(ctx, hipMemcpyAsync(out->group, A.group, 4 * n, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    return 0;
+    PRT_API_CATCH_RC(ctx, "prt_closest_points")
 }
 
 int prt_update_geometry(prt_ctx * ctx, const prt_geometry_update * update, prt_update_info * info) {
