@@ -254,7 +254,11 @@ int prt_render_pixel_list(prt_ctx * ctx, const prt_camera * cam, const prt_param
  *                       against t = FLT_MAX, gives a hit with t < tmax (independent of visit order; with tmax NULL it equals
  *                       TraceRay(...) == true).  Any-hit traversal.
  * A ray with a non-finite origin or direction component (or biased origin), or a zero direction, is a miss / not occluded; it is
- * not an error and does not affect the other rays.  The box padding is computed from
+ * not an error and does not affect the other rays; a scene of 0 triangles makes every ray a miss / not occluded.  tmax = +inf is
+ * "no limit" (as NULL and as FLT_MAX: every accepted t is below FLT_MAX); a tmax that is 0, negative or NaN makes the ray not
+ * occluded (t < tmax holds for no hit) and does not affect the other rays.  A ray's answer is a pure function of (scene, ray,
+ * ray_bias, tmax): the same bits whatever else is in the batch, in whatever order, for every launch shape and option.
+ * The box padding is computed from
  * max(scene extent, max |biased origin component| of the batch), so origins may lie anywhere.  The reference's sphere test assumes
  * a unit direction and an origin near the scene: CLOSEST rays with |d|^2 further than 2^-18 from 1, or an origin beyond 64 x the
  * scene's largest coordinate, are replayed in the reference's visit order (exact, slower); OCCLUDED rays from such origins take

@@ -27,8 +27,9 @@ def _bits(a):
     return a.view(np.uint32) if a.dtype in (np.float32, np.int32) else a
 
 
-def check_fixture(r, g, torch_path: bool):
-    """Every ray of fixture g through Renderer r, one call per distinct ray_bias; returns the number of rays compared."""
+def check_fixture(r, g, torch_path: bool, count_visits: bool = False):
+    """Every ray of fixture g (or of a case of tests/trace_cases.py, as_fixture) through Renderer r, one call per distinct
+    ray_bias; returns the number of rays compared.  count_visits: the calls run the counting instantiations of the kernels."""
     if torch_path:
         import torch
         dev = torch.device("cuda", r.device_id)
@@ -41,7 +42,7 @@ def check_fixture(r, g, torch_path: bool):
     for bias in np.unique(g["ray_bias"]):
         sel = np.nonzero(g["ray_bias"] == bias)[0]
         o, d, tm = conv(g["origins"][sel]), conv(g["directions"][sel]), conv(g["tmax"][sel])
-        res = r.trace_rays(o, d, ray_bias=float(bias))
+        res = r.trace_rays(o, d, ray_bias=float(bias), count_visits=count_visits)
         assert res["counters"].ray_count == len(sel) and res["counters"].pipeline == 0
         for k in CLOSEST:
             got = back(res[k])
@@ -51,9 +52,9 @@ def check_fixture(r, g, torch_path: bool):
             bad = np.nonzero(np.any((_bits(got) != _bits(exp)).reshape(len(sel), -1), axis=1))[0]
             assert bad.size == 0, ("%s: field %s differs on %d of %d rays (bias %g), first ray %d: got %r, expected %r, near tie %d" % (
                 str(g["scene"]), k, bad.size, len(sel), bias, sel[bad[0]], got[bad[0]], exp[bad[0]], int(g["near_tie"][sel[bad[0]]])))
-        occ = back(r.trace_rays(o, d, mode="occluded", ray_bias=float(bias))["occluded"])
+        occ = back(r.trace_rays(o, d, mode="occluded", ray_bias=float(bias), count_visits=count_visits)["occluded"])
         assert np.array_equal(occ, g["occluded"][sel]), (str(g["scene"]), "occluded", int((occ != g["occluded"][sel]).sum()))
-        occ_t = back(r.trace_rays(o, d, mode="occluded", tmax=tm, ray_bias=float(bias))["occluded"])
+        occ_t = back(r.trace_rays(o, d, mode="occluded", tmax=tm, ray_bias=float(bias), count_visits=count_visits)["occluded"])
         bad = np.nonzero(occ_t != g["occluded_tmax"][sel])[0]
         assert bad.size == 0, [(str(g["scene"]), "occluded below tmax", int(sel[i]), float(g["tmax"][sel[i]]), float(g["t"][sel[i]]),
                                 int(occ_t[i]), int(g["occluded_tmax"][sel[i]]), int(g["near_tie"][sel[i]]), float(bias),
