@@ -400,10 +400,14 @@ int prt_trace_rays_backward_device(prt_ctx * ctx, const prt_ray_batch * batch, c
  * A point with a non-finite component, or with max_dist2 negative or NaN, is a miss; it is not an error and does not affect
  * the other points.  A miss: dist2 = FLT_MAX, point and bw zeros, group = -1, vertex0 = 0xFFFFFFFF (the ray queries'
  * convention); a scene of 0 triangles makes every point a miss.  max_dist2 = +inf is "no limit", 0 finds points on the surface.
+ * A triangle whose d2 overflows to inf is no candidate, so a point more than 2^64 away from every triangle misses without a radius.
+ * A zero-area triangle is a candidate exactly when the function returns finite values for the point: in its vertex and edge
+ * regions, not where the interior branch divides by its zero area.
  * The walk culls boxes by their distance to p, padded by 2^-16 x max(scene extent, max |finite point component| of the batch);
  * points far from the scene (many extents away) are exact but slow: their box distances all tie within the pad and much of the
  * tree is visited.
- * Counters: ray_count = count; node_visits / tri_tests with PRT_FLAG_COUNT_VISITS in `flags`; render_ms = the call's device
+ * Counters: ray_count = count; node_visits / tri_tests with PRT_FLAG_COUNT_VISITS in `flags` - sums over the points' walks, which
+ * depend on the tree, the batch, STACK_CAP and the pad but not on the schedule options or the entry point; render_ms = the call's device
  * time, trace_kernel_ms = the walk kernels'; pipeline = 0.  prt_get_render_stats (the last render's) is left alone.
  * Errors: -1 NULL batch or buffers struct, NULL points with count > 0; -2 no scene; -10 a HIP call failed.  count == 0 writes
  * nothing and returns 0.

@@ -2,19 +2,23 @@
 // with tests/hip_shim and run one lane at a time: the tree is built by bvh_build.cpp (4-wide by default, -DPRT_BVH8: 8-wide), the
 // records and the leaf -> (group, vertex0) table laid out as prt_upload_scene and the queries lay them out, and every point is
 // answered twice - by closest_point_walk over the tree, and by a brute force of closest_on_triangle over every triangle with the
-// tie rule (closest_takes).  tests/closest_cases.py writes the cases and reads the results; tests/test_closest_host.py asserts on
-// them, tests/test_gpu_closest.py compares the device with the brute force.
+// tie rule (closest_takes).  A case that carries a stack cap is walked a third time, the way one lane of k_closest walks it: on an
+// LDS stack column of that many entries, to tell which points the kernel hands to k_closest_exact.  tests/closest_cases.py writes
+// the cases and reads the results; tests/test_closest_host.py and tests/test_closest_cases_host.py assert on them,
+// tests/test_gpu_closest.py and tests/test_gpu_closest_schedules.py compare the device with the brute force.
 //
 //   g++ -O1 -std=c++17 -ffp-contract=off -Itests/hip_shim -Ipar_raytracer_amd/csrc tests/closest_host_harness.cpp
 //       par_raytracer_amd/csrc/bvh_build.cpp -pthread -o /tmp/closest_host && /tmp/closest_host cases.bin results.bin
 //
-// cases.bin: u32 case count, then per case 6 x u32 (points, positions, indices, groups, flags, 0), the points (x3 f32), with
-// flag 1 max_dist2 (f32 per point), with flag 2 an input triangle per point (u32), then positions (x3 f32), idx_positions (u32),
-// the groups' (first_index, index_count) (2 x u32).
+// cases.bin: u32 case count, then per case 6 x u32 (points, positions, indices, groups, flags, stack cap - read with flag 4, else
+// 0), the points (x3 f32), with flag 1 max_dist2 (f32 per point), with flag 2 an input triangle per point (u32), then positions
+// (x3 f32), idx_positions (u32), the groups' (first_index, index_count) (2 x u32).
 // results.bin, per case: i32 mismatches between walk and brute force, u32 points decided by the tie rule, u64 node visits and
 // u64 triangle tests of the walk, then dist2, point (x3), bw (x3), vertex0, group of the brute force and the same five arrays of
-// the walk.  With flag 2 nothing is walked: per case the same 24-byte header (zeros), then d2, v, w (f32) and finite (u32) of
-// closest_on_triangle(point i, its triangle).
+// the walk.  With flag 4 then: u32 the cap in effect (the case's, clamped to 2..40 and to the tree's stack_bound as run_closest
+// clamps STACK_CAP) and per point u32 listed = the marker of the capped walk carries TRAV_FLAG_OVERFLOW (0 for an invalid point,
+// which is never walked).  With flag 2 nothing is walked: per case the same 24-byte header (zeros), then d2, v, w (f32) and
+// finite (u32) of closest_on_triangle(point i, its triangle).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -68,6 +72,23 @@ struct Answers {
     }
     void write(FILE * f) const { wr(f, dist2); wr(f, point); wr(f, bw); wr(f, vertex0); wr(f, group); }
 };
+
+// One point as one lane of k_closest walks it (kernels_closest.h): an LDS stack column of `cap` entries, node steps and leaf steps
+// in turn until the walk is done, then the marker's flags.  True when a push was dropped: the kernel lists the point.
+static bool lane_lists_point(const DevScene & sc, f3 p, float max_d2, float pad, unsigned int cap, std::vector<int> & lds,
+                             const uint2 * leaf_map) {
+    LdsStack<1> stack;
+    stack.attach(lds.data(), 0);
+    stack.cap = cap;
+    TravRay r;
+    TraceStats st;
+    point_init(r, p, max_d2, stack);
+    while (!trav_done(r)) {
+        while (trav_walking(r)) point_node_step<LdsStack<1>, false>(sc, r, stack, st, pad);
+        if (!trav_done(r)) point_leaf<LdsStack<1>, false>(sc, r, stack, st, leaf_map);
+    }
+    return (trav_end_flags(r, stack) & TRAV_FLAG_OVERFLOW) != 0;
+}
 
 int main(int argc, char ** argv) {
     if (argc < 3) { fprintf(stderr, "usage: closest_host cases.bin results.bin\n"); return 2; }
@@ -143,6 +164,10 @@ int main(int argc, char ** argv) {
         }
         const float pad = extent * (1.0f / 65536.0f);
 
+        const unsigned int cap = std::min((unsigned int)bvh.stack_bound, std::max(2u, std::min(40u, hd[5])));
+        std::vector<int> lds((size_t)cap * STACK_ENTRY_INTS, 0);
+        std::vector<uint32_t> listed((flags & 4u) ? n : 0, 0u);
+
         Answers brute(n), walk(n);
         int32_t mismatches = 0;
         uint32_t tie_points = 0;
@@ -170,6 +195,7 @@ int main(int argc, char ** argv) {
                     if (equal > 1) tie_points++;
                 }
                 h = closest_point_walk<GlobalStack, true>(sc, p, max_d2, pad, stk, st, leaf_map.data());
+                if (flags & 4u) listed[i] = lane_lists_point(sc, p, max_d2, pad, cap, lds, leaf_map.data()) ? 1u : 0u;
             }
             brute.emit(i, b, tris, leaf_map);
             walk.emit(i, h, tris, leaf_map);
@@ -184,6 +210,7 @@ int main(int argc, char ** argv) {
         fwrite(header, 8, 2, fout);
         brute.write(fout);
         walk.write(fout);
+        if (flags & 4u) { fwrite(&cap, 4, 1, fout); wr(fout, listed); }
         printf("case %u: %u triangles, %u nodes, %u points, %d mismatches, %u decided by the tie rule, %.1f node visits and %.1f triangle tests per point\n",
                ci, n_tris, bvh.node_count, n, mismatches, tie_points, n ? (double)st.nodes / n : 0.0, n ? (double)st.tris / n : 0.0);
     }
