@@ -432,6 +432,52 @@ int prt_closest_points(prt_ctx * ctx, const prt_point_batch * batch, const prt_c
 int prt_closest_points_device(prt_ctx * ctx, const prt_point_batch * batch, const prt_closest_buffers * out, uint32_t flags,
                               prt_counters * counters);
 
+/* ---- gradients of closest-point queries: how dist2, point and bw change with the vertices and with the points -----------------
+ * The counterpart of prt_trace_rays_backward for prt_closest_points; it closes the loop for point-to-surface and chamfer losses
+ * when a mesh is fitted to scanned points: prt_update_geometry moves the mesh, prt_closest_points queries it, and this call turns
+ * the gradients of a loss with respect to dist2, point and bw into gradients with respect to the vertex positions and the points.
+ * What is differentiated is the real-valued function behind closest_on_triangle on the triangle (a, b, c) the forward query
+ * REPORTED (group, vertex0 -> corners idx_positions[first_index + vertex0 + 0..2]), inside the region R that the float32 walk
+ * takes for p (recomputed by this call, never passed in); with ab = b - a, ac = c - a, ap = p - a, d1..d6, va, vb, vc of Ericson
+ * 5.1.5 (csrc/dev_closest.h):
+ *     R 0 vertex a: v = 0, w = 0     1 vertex b: v = 1, w = 0     3 vertex c: v = 0, w = 1
+ *     R 2 edge ab:  v = d1 / (d1 - d3), w = 0                     4 edge ac:  v = 0, w = d2 / (d2 - d6)
+ *     R 5 edge bc:  w = (d4 - d3) / ((d4 - d3) + (d5 - d6)), v = 1 - w
+ *     R 6 interior: v = vb / ((va + vb) + vc), w = vc / ((va + vb) + vc)
+ *     point = q = (a + ab v) + ac w     dist2 = Dot(p - q, p - q)     bw = (1 - v - w, v, w)
+ * The constants 0 and 1 have zero derivative.  A change of region, or of the winning triangle, is not modelled (the stance
+ * prt_trace_rays_backward takes on silhouettes).
+ *   batch          the forward call's points; max_dist2 is ignored
+ *   group, vertex0 the forward call's references, count each.  group < 0 is a miss and contributes nothing.
+ *   positions      the vertex positions the forward query saw - the uploaded ones, or those last given to prt_update_geometry;
+ *                  position_count must equal the upload's
+ *   gout           dL/ddist2 (count), dL/dpoint, dL/dbw (count x 3); a NULL array, or gout NULL, means zero
+ *   gin            where the results go; a NULL array is not computed.  positions: position_count x 3, summed over the points,
+ *                  OVERWRITTEN (not accumulated into); points: count x 3.
+ * A point is SKIPPED - zeros in gin->points, nothing added to positions - when the named triangle is no candidate for it (d2, v
+ * or w not finite: the forward query would not have reported it) or any of its 12 gradient components is not finite (a NaN
+ * vertex or point, a NaN in gout, an overflow).  dL/dbw reaches those components only through the derivatives of v and w, and a
+ * region reads only the barycentric it computes: neither in a vertex region, dL/dv = dL/dbw[1] - dL/dbw[0] on edge ab,
+ * dL/dw = dL/dbw[2] - dL/dbw[0] on edge ac, both on edge bc and in the interior.  A NaN in an entry of dL/dbw that the point's
+ * region does not read is not seen and does not skip the point.
+ * Only per-point non-finite contributions are skipped: a sum of finite contributions that exceeds float32 resolves to +-inf in
+ * gin->positions; it is neither refused nor clamped.
+ * Determinism, prt_grad_info (hit_rays = points that contributed, skipped_rays = reported hits that were skipped), the errors
+ * (-1 NULL batch; NULL points, group, vertex0 or positions with count > 0; a position_count that differs from the upload's; an
+ * invalid reference, found BEFORE any output is written; -2 no scene; -10 a HIP call failed), count == 0, the stream contract and
+ * what the call leaves alone are prt_trace_rays_backward's, word for word; the two calls share their device buffers.  The option
+ * QGRAD_MERGE governs both (same bits either way).  DESIGN.md section 4.11. */
+typedef struct prt_closest_grads { const float * dist2; const float * point; const float * bw; } prt_closest_grads;   /* dL/doutputs; NULL = zero */
+typedef struct prt_point_grads   { float * positions; float * points; } prt_point_grads;      /* NULL = not computed */
+/* Host pointers (batch arrays, group, vertex0, positions, gout's and gin's arrays); info may be NULL. */
+int prt_closest_points_backward(prt_ctx * ctx, const prt_point_batch * batch, const int32_t * group, const uint32_t * vertex0,
+                                const float * positions, uint32_t position_count, const prt_closest_grads * gout,
+                                const prt_point_grads * gin, prt_grad_info * info);
+/* The same with device pointers on the context's device (hipMalloc'ed or torch tensors' data_ptr). */
+int prt_closest_points_backward_device(prt_ctx * ctx, const prt_point_batch * batch, const int32_t * group, const uint32_t * vertex0,
+                                       const float * positions, uint32_t position_count, const prt_closest_grads * gout,
+                                       const prt_point_grads * gin, prt_grad_info * info);
+
 /* ---- several devices behind one handle --------------------------------------------------------------------------------
  * SURVEY.md 8(b)'s prt_create(const int * device_ids, int n_dev): what the host mirror's Render() uses for n GPUs, in place
  * of the reference's one-rank-per-core partition + MPI_Gather (main.cpp:311-347).  The scene is replicated (as every MPI rank

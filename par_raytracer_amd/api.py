@@ -548,6 +548,73 @@ class Renderer:
         out["info"] = info
         return out
 
+    POINT_GRAD_NAMES = ("positions", "points")
+
+    def closest_points_backward(self, points, group, vertex0, positions, *, grad_dist2=None, grad_point=None, grad_bw=None,
+                                want: Sequence[str] = ("positions", "points")) -> dict:
+        """Gradients of a closest-point query (prt_closest_points_backward, include/prt.h): from dL/ddist2, dL/dpoint, dL/dbw of n
+        points (None = zero) to dL/dpositions (summed over the points; the same bits for every order of the points) and
+        dL/dpoints - whichever `want` names.
+
+        points, group, vertex0: the forward closest_points call's input and references (vertex0 uint32, or int32 holding the same
+        bits); positions: float32 (P, 3), the vertices that call saw.  numpy arrays go to the host entry point, torch tensors on
+        this context's device to the device entry point.  Returns {name: array} plus "info" (PrtGradInfo)."""
+        for w in want:
+            if w not in self.POINT_GRAD_NAMES:
+                raise ValueError("unknown gradient %r" % (w,))
+        is_torch = type(points).__module__.split(".")[0] == "torch"
+        if is_torch:
+            import torch
+
+            def check(x, what, shape, dtypes=(torch.float32,)):
+                if not isinstance(x, torch.Tensor) or x.dtype not in dtypes or not x.is_contiguous():
+                    raise ValueError("%s must be a contiguous %s torch tensor" % (what, " or ".join(str(d) for d in dtypes)))
+                if x.device.type != "cuda" or (x.device.index or 0) != self.device_id:
+                    raise ValueError("%s must live on this context's device (cuda:%d)" % (what, self.device_id))
+                if tuple(x.shape) != shape:
+                    raise ValueError("%s has shape %s, not %s" % (what, tuple(x.shape), shape))
+                return x
+            ints = (torch.int32,)
+            empty = lambda shape: torch.empty(shape, dtype=torch.float32, device=points.device)     # noqa: E731
+            ptr = lambda x: x.data_ptr() if x is not None else None                                # noqa: E731
+            entry, name = self._lib.prt_closest_points_backward_device, "prt_closest_points_backward_device"
+        else:
+            def check(x, what, shape, dtypes=(np.float32,)):
+                a = np.asarray(x)
+                if a.dtype not in dtypes or not a.flags["C_CONTIGUOUS"]:
+                    raise ValueError("%s must be a contiguous %s array" % (what, " or ".join(np.dtype(d).name for d in dtypes)))
+                if a.shape != shape:
+                    raise ValueError("%s has shape %s, not %s" % (what, a.shape, shape))
+                return a
+            ints = (np.int32, np.uint32)
+            empty = lambda shape: np.empty(shape, dtype=np.float32)                                  # noqa: E731
+            ptr = lambda x: x.ctypes.data if x is not None else None                                 # noqa: E731
+            entry, name = self._lib.prt_closest_points_backward, "prt_closest_points_backward"
+        if getattr(points, "ndim", 0) != 2:
+            raise ValueError("points must have shape (n, 3)")
+        n = int(points.shape[0])
+        if getattr(positions, "ndim", 0) != 2:
+            raise ValueError("positions must have shape (P, 3)")
+        n_pos = int(positions.shape[0])
+        points = check(points, "points", (n, 3))
+        group = check(group, "group", (n,), ints[:1])
+        vertex0 = check(vertex0, "vertex0", (n,), ints)
+        positions = check(positions, "positions", (n_pos, 3))
+        gouts = [None if g is None else check(g, what, shape) for g, what, shape in
+                 ((grad_dist2, "grad_dist2", (n,)), (grad_point, "grad_point", (n, 3)), (grad_bw, "grad_bw", (n, 3)))]
+        out = {w: empty((n_pos, 3) if w == "positions" else (n, 3)) for w in want}
+        if is_torch:
+            # the library's stream is not ordered against torch's: whatever torch still has queued on the inputs must be done
+            torch.cuda.current_stream(points.device).synchronize()
+        batch = capi.PrtPointBatch(ptr(points), None, n)
+        go = capi.PrtClosestGrads(*[ptr(g) for g in gouts])
+        gi = capi.PrtPointGrads(*[ptr(out.get(w)) for w in self.POINT_GRAD_NAMES])
+        info = PrtGradInfo()
+        self._check(entry(self._ctx, C.byref(batch), ptr(group), ptr(vertex0), ptr(positions), n_pos, C.byref(go), C.byref(gi),
+                          C.byref(info)), name)
+        out["info"] = info
+        return out
+
     def update_geometry(self, positions, normals=None, tangents=None, spheres=None, sphere_group=None) -> PrtUpdateInfo:
         """Move the uploaded scene's vertices in place and refit the tree on the device (prt_update_geometry, include/prt.h):
         afterwards renders and queries give the bits a fresh upload of the moved scene would.

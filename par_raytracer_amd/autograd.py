@@ -1,4 +1,4 @@
-"""Closest-hit queries as a differentiable torch operation.
+"""Closest-hit queries and closest-point queries as differentiable torch operations.
 
 `trace_rays_differentiable` ties Renderer.update_geometry, Renderer.trace_rays and Renderer.trace_rays_backward into one
 torch.autograd.Function, so that a loss over t, bw, position and normal of a batch of rays can be back-propagated to the vertex
@@ -6,11 +6,17 @@ positions, the ray origins and the ray directions - the optimisation loop over v
 prt_trace_rays were added for (include/prt.h).  The gradient is that of the hit arithmetic on the triangle each ray reported; changes
 of visibility at silhouettes are not modelled.
 
-torch is imported when the function is first called: importing the package stays torch-free.
+`closest_points_differentiable` does the same for Renderer.closest_points and Renderer.closest_points_backward: a loss over
+dist2, point and bw of a batch of points - a point-to-surface or chamfer loss when a mesh is fitted to scanned points - is
+back-propagated to the vertex positions and the points.  The gradient is that of the region walk on the triangle and in the region
+each point reported; a change of region or of the winning triangle is not modelled.
+
+torch is imported when a function is first called: importing the package stays torch-free.
 """
 from __future__ import annotations
 
 _FUNCTION = None
+_POINT_FUNCTION = None
 
 
 def _function():
@@ -57,3 +63,50 @@ def trace_rays_differentiable(renderer, positions, origins, directions, *, ray_b
     Renderer.trace_rays does; the first four are differentiable with respect to whichever of positions, origins and directions
     require a gradient, group and vertex0 are not."""
     return _function().apply(renderer, positions, origins, directions, float(ray_bias), bool(update_geometry))
+
+
+def _point_function():
+    global _POINT_FUNCTION
+    if _POINT_FUNCTION is not None:
+        return _POINT_FUNCTION
+    import torch
+
+    class ClosestPoints(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, renderer, positions, points, max_dist, update_geometry):
+            p, q = (x.detach().contiguous() for x in (positions, points))
+            if update_geometry:
+                renderer.update_geometry(p)
+            res = renderer.closest_points(q, max_dist=None if max_dist is None else max_dist.detach().contiguous())
+            ctx.renderer = renderer
+            ctx.set_materialize_grads(False)              # an output the loss does not use arrives as None = zero, and is not read
+            ctx.save_for_backward(p, q, res["group"], res["vertex0"])
+            ctx.mark_non_differentiable(res["group"], res["vertex0"])
+            return res["dist2"], res["point"], res["bw"], res["group"], res["vertex0"]
+
+        @staticmethod
+        def backward(ctx, g_dist2, g_point, g_bw, _g_group, _g_vertex0):
+            p, q, group, vertex0 = ctx.saved_tensors
+            names = ("positions", "points")
+            want = tuple(n for n, needed in zip(names, ctx.needs_input_grad[1:3]) if needed)
+            if not want:
+                return (None,) * 5
+            grads = [None if g is None else g.contiguous() for g in (g_dist2, g_point, g_bw)]
+            res = ctx.renderer.closest_points_backward(q, group, vertex0, p, grad_dist2=grads[0], grad_point=grads[1], grad_bw=grads[2],
+                                                       want=want)
+            return (None,) + tuple(res.get(n) for n in names) + (None, None)
+
+    _POINT_FUNCTION = ClosestPoints
+    return _POINT_FUNCTION
+
+
+def closest_points_differentiable(renderer, positions, points, *, max_dist=None, update_geometry: bool = True):
+    """The nearest surface point of `points` on the renderer's scene with its vertices at `positions`.
+
+    positions (P, 3) and points (n, 3): float32 torch tensors on the renderer's device; max_dist: None or float32 (n,) distances,
+    as Renderer.closest_points takes them (not differentiated).  With update_geometry (the default) the scene's vertices are first
+    moved to `positions` (Renderer.update_geometry: P must be the uploaded scene's count); without it `positions` must be what
+    the scene holds already.  Returns (dist2, point, bw, group, vertex0) as Renderer.closest_points does; the first three are
+    differentiable with respect to whichever of positions and points require a gradient, group and vertex0 are not.  A miss (a
+    point with a non-finite component, or nothing within max_dist) has dist2 = FLT_MAX, point and bw zeros, and zero gradient."""
+    return _point_function().apply(renderer, positions, points, max_dist, bool(update_geometry))

@@ -134,6 +134,14 @@ class PrtQueryGrads(C.Structure):
     _fields_ = [("positions", C.c_void_p), ("origins", C.c_void_p), ("directions", C.c_void_p)]
 
 
+class PrtClosestGrads(C.Structure):
+    _fields_ = [("dist2", C.c_void_p), ("point", C.c_void_p), ("bw", C.c_void_p)]
+
+
+class PrtPointGrads(C.Structure):
+    _fields_ = [("positions", C.c_void_p), ("points", C.c_void_p)]
+
+
 class PrtGradInfo(C.Structure):
     _fields_ = [("device_ms", C.c_double), ("hit_rays", C.c_uint32), ("skipped_rays", C.c_uint32), ("unit_exponent", C.c_int32),
                 ("max_contribution", C.c_float)]
@@ -156,7 +164,8 @@ PRT_SYMBOLS = ["prt_create", "prt_destroy", "prt_last_error", "prt_abi_version",
                "prt_trace_rays", "prt_trace_rays_device", "prt_get_region_stats",
                "prt_update_geometry", "prt_update_geometry_device", "prt_multi_update_geometry", "prt_debug_check_refit",
                "prt_trace_rays_backward", "prt_trace_rays_backward_device",
-               "prt_closest_points", "prt_closest_points_device"]
+               "prt_closest_points", "prt_closest_points_device",
+               "prt_closest_points_backward", "prt_closest_points_backward_device"]
 # PRT_REGION_* of include/prt.h, in index order (tests/test_host_side.py's header check keeps the symbol list in step; the
 # region test compares this list with the header's enum)
 REGION_NAMES = ["round", "topup", "topup_pass", "trace_outer", "refill", "walk_pass", "node_step", "node_descend", "node_pop", "node_push", "leaf",
@@ -251,6 +260,10 @@ def hip_lib() -> C.CDLL:
             lib.prt_closest_points.argtypes = [C.c_void_p, C.POINTER(PrtPointBatch), C.POINTER(PrtClosestBuffers), C.c_uint32,
                                                C.POINTER(PrtCounters)]
             lib.prt_closest_points_device.argtypes = lib.prt_closest_points.argtypes
+        if hasattr(lib, "prt_closest_points_backward"):    # (absent from a PRT_HIP_LIB build of an earlier commit)
+            lib.prt_closest_points_backward.argtypes = [C.c_void_p, C.POINTER(PrtPointBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                        C.POINTER(PrtClosestGrads), C.POINTER(PrtPointGrads), C.POINTER(PrtGradInfo)]
+            lib.prt_closest_points_backward_device.argtypes = lib.prt_closest_points_backward.argtypes
         _hip = lib
     return _hip
 

@@ -41,8 +41,17 @@
 
 namespace prt {
 
-// Ericson 5.1.5 on (a, ab, ac).  Returns false when d2, v or w is not finite.
-PRT_D bool closest_on_triangle(f3 p, f3 a, f3 ab, f3 ac, float & d2, float & v, float & w) {
+// The regions of the walk, in the order of its tests.
+enum { CLOSEST_VERTEX_A = 0, CLOSEST_VERTEX_B = 1, CLOSEST_EDGE_AB = 2, CLOSEST_VERTEX_C = 3, CLOSEST_EDGE_AC = 4, CLOSEST_EDGE_BC = 5,
+       CLOSEST_INTERIOR = 6 };
+
+// The six dot products and three areas of Ericson 5.1.5 on (a, ab, ac), for the walk below and for its derivative
+// (dev_closest_grad.h).
+struct ClosestTerms { f3 ap, bp, cp; float d1, d2, d3, d4, d5, d6, va, vb, vc; };
+
+// Ericson 5.1.5 on (a, ab, ac): v, w, d2 and the region (CLOSEST_*) whose branch produced them.  Host and device: the gradient's
+// step and its host harness recompute the region with it.
+PRT_HD int closest_region_walk(f3 p, f3 a, f3 ab, f3 ac, float & d2, float & v, float & w, ClosestTerms & t) {
     const f3 ap = p - a;
     const float d1 = dot3(ab, ap), d2_ = dot3(ac, ap);
     const f3 bp = ap - ab;
@@ -52,22 +61,34 @@ PRT_D bool closest_on_triangle(f3 p, f3 a, f3 ab, f3 ac, float & d2, float & v, 
     const float vc = d1 * d4 - d3 * d2_;
     const float vb = d5 * d2_ - d1 * d6;
     const float va = d3 * d6 - d5 * d4;
-    if (d1 <= 0.0f && d2_ <= 0.0f) { v = 0.0f; w = 0.0f; }                              // vertex a
-    else if (d3 >= 0.0f && d4 <= d3) { v = 1.0f; w = 0.0f; }                            // vertex b
-    else if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) { v = d1 / (d1 - d3); w = 0.0f; }  // edge ab
-    else if (d6 >= 0.0f && d5 <= d6) { v = 0.0f; w = 1.0f; }                            // vertex c
-    else if (vb <= 0.0f && d2_ >= 0.0f && d6 <= 0.0f) { v = 0.0f; w = d2_ / (d2_ - d6); }   // edge ac
-    else if (va <= 0.0f && (d4 - d3) >= 0.0f && (d5 - d6) >= 0.0f) {                    // edge bc
+    int region;
+    if (d1 <= 0.0f && d2_ <= 0.0f) { v = 0.0f; w = 0.0f; region = CLOSEST_VERTEX_A; }
+    else if (d3 >= 0.0f && d4 <= d3) { v = 1.0f; w = 0.0f; region = CLOSEST_VERTEX_B; }
+    else if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) { v = d1 / (d1 - d3); w = 0.0f; region = CLOSEST_EDGE_AB; }
+    else if (d6 >= 0.0f && d5 <= d6) { v = 0.0f; w = 1.0f; region = CLOSEST_VERTEX_C; }
+    else if (vb <= 0.0f && d2_ >= 0.0f && d6 <= 0.0f) { v = 0.0f; w = d2_ / (d2_ - d6); region = CLOSEST_EDGE_AC; }
+    else if (va <= 0.0f && (d4 - d3) >= 0.0f && (d5 - d6) >= 0.0f) {
         w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
         v = 1.0f - w;
-    } else {                                                                            // interior
+        region = CLOSEST_EDGE_BC;
+    } else {
         const float denom = 1.0f / ((va + vb) + vc);
         v = vb * denom;
         w = vc * denom;
+        region = CLOSEST_INTERIOR;
     }
     const f3 q = (a + ab * v) + ac * w;
     const f3 e = p - q;
     d2 = dot3(e, e);
+    t.ap = ap; t.bp = bp; t.cp = cp;
+    t.d1 = d1; t.d2 = d2_; t.d3 = d3; t.d4 = d4; t.d5 = d5; t.d6 = d6; t.va = va; t.vb = vb; t.vc = vc;
+    return region;
+}
+
+// Ericson 5.1.5 on (a, ab, ac).  Returns false when d2, v or w is not finite.
+PRT_D bool closest_on_triangle(f3 p, f3 a, f3 ab, f3 ac, float & d2, float & v, float & w) {
+    ClosestTerms t;
+    closest_region_walk(p, a, ab, ac, d2, v, w, t);
     return isfinite(d2) && isfinite(v) && isfinite(w);
 }
 

@@ -1,0 +1,102 @@
+// kernels_closest_grad.h - prt_closest_points_backward on the device: dL/d(vertex positions) and dL/d(points) of a batch of
+// closest-point queries, from the gradients of their outputs (dev_closest_grad.h has the per-point step; the fixed point, the
+// reference check and the wave merge are those of the ray queries' gradients: dev_query_grad.h, kernels_query_grad.h).
+//
+//   k_cgrad_scan     grid-stride, one lane per point: resolves the point's triangle from (group, vertex0), validates the
+//                    reference, runs the step and reduces four words - the largest |vertex contribution| of the batch (one
+//                    atomicMax on the float's bits per wave) and the counts of contributing, skipped and invalid points (one
+//                    atomicAdd per wave each).  Runs FIRST and writes only those words; the host reads them and launches
+//                    nothing else when a reference is invalid, so a refused call has written none of the caller's outputs.
+//   k_cgrad_scatter  reruns the step per point, writes the point's own gradient with plain stores and adds its 9 vertex
+//                    contributions, in units of 2^u, into 64-bit integer accumulators with no-return relaxed agent-scope
+//                    atomics.  MERGE: qgrad_wave_add9 - neighbouring points of a scan land on the same triangle as a rule.
+//   k_qgrad_resolve  (kernels_query_grad.h, as it is) accumulator x 2^u -> the caller's float.
+//
+// No lane waits for another workgroup: no spin loop, no polled flag, no cooperative launch.  The only ordering is that of the
+// launches on the context's stream.
+#pragma once
+
+#include "dev_closest_grad.h"
+#include "kernels_query_grad.h"
+
+namespace prt {
+
+struct CGradArgs {
+    const float * points;                // count x 3
+    const int * group;                   // count: the forward query's references
+    const unsigned int * vertex0;
+    const float * positions;             // position_count x 3: the vertices the forward query saw
+    const float * g_dist2, * g_point, * g_bw;         // the output gradients; null = zero
+    float * g_points;                    // count x 3; null = not wanted
+    const unsigned int * idx_positions;  // the upload's position index buffer
+    const unsigned int * group_runs;     // (first_index, index_count) per group
+    long long * acc;                     // position_count x 3 accumulators; null: the scatter adds nothing
+    unsigned int * words;                // QGRAD_WORDS control words
+    unsigned int count, group_count, position_count;
+    int unit_exponent;                   // u (set by the host between the scan and the scatter)
+};
+
+// Point i: QGRAD_MISS / QGRAD_INVALID, or QGRAD_HIT with vi = the three position indices, *ok = the step's verdict (false:
+// skipped) and *g its result.  Position indices were validated at upload against the position count the entry point insists on.
+PRT_HD int cgrad_point(const CGradArgs & A, unsigned int i, unsigned int * first_corner, unsigned int * vi, bool * ok, CGradOut * g) {
+    const int kind = qgrad_reference(A.group[i], A.vertex0[i], A.group_runs, A.group_count, first_corner);
+    if (kind != QGRAD_HIT) return kind;
+    for (int c = 0; c < 3; ++c) vi[c] = A.idx_positions[*first_corner + c];
+    *ok = false;
+    g->region = -1;
+    if (vi[0] >= A.position_count || vi[1] >= A.position_count || vi[2] >= A.position_count) return QGRAD_HIT;   // (never, after upload)
+    *ok = cgrad_step(qgrad_ld3(A.points, i), qgrad_ld3(A.positions, vi[0]), qgrad_ld3(A.positions, vi[1]), qgrad_ld3(A.positions, vi[2]),
+                     A.g_dist2 ? A.g_dist2[i] : 0.0f, qgrad_ld3(A.g_point, i), qgrad_ld3(A.g_bw, i), g);
+    return QGRAD_HIT;
+}
+
+__global__ __launch_bounds__(256) void k_cgrad_scan(CGradArgs A) {
+    float m = 0.0f;
+    int hit = 0, skipped = 0, invalid = 0;
+    for (unsigned int i = blockIdx.x * blockDim.x + threadIdx.x; i < A.count; i += gridDim.x * blockDim.x) {
+        unsigned int first, vi[3];
+        bool ok = false;
+        CGradOut g;
+        const int kind = cgrad_point(A, i, &first, vi, &ok, &g);
+        if (kind == QGRAD_INVALID) ++invalid;
+        if (kind == QGRAD_HIT && !ok) ++skipped;
+        if (kind == QGRAD_HIT && ok) { ++hit; m = fmaxf(m, cgrad_abs_max(g)); }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        m = fmaxf(m, __shfl_xor(m, off));
+        hit += __shfl_xor(hit, off);
+        skipped += __shfl_xor(skipped, off);
+        invalid += __shfl_xor(invalid, off);
+    }
+    if ((threadIdx.x & 63u) == 0u) {
+        if (m > 0.0f) atomicMax(A.words + QGRAD_W_MAX, __float_as_uint(m));      // non-negative floats order like their bits
+        if (hit) atomicAdd(A.words + QGRAD_W_HIT, (unsigned int)hit);
+        if (skipped) atomicAdd(A.words + QGRAD_W_SKIPPED, (unsigned int)skipped);
+        if (invalid) atomicAdd(A.words + QGRAD_W_INVALID, (unsigned int)invalid);
+    }
+}
+
+// The loop runs per WAVE (its bound does not depend on the lane), so every lane of a wave reaches the ballots and shuffles of the
+// merge together.  blockDim.x is a multiple of 64.
+template <bool MERGE>
+__global__ __launch_bounds__(256) void k_cgrad_scatter(CGradArgs A) {
+    const unsigned int lane = threadIdx.x & 63u;
+    for (unsigned int base = blockIdx.x * blockDim.x + (threadIdx.x - lane); base < A.count; base += gridDim.x * blockDim.x) {
+        const unsigned int i = base + lane;
+        unsigned int key = 0xFFFFFFFFu, vi[3] = { 0u, 0u, 0u };
+        long long q[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+        bool live = false;
+        if (i < A.count) {
+            CGradOut g;
+            bool ok = false;
+            const bool adds = cgrad_point(A, i, &key, vi, &ok, &g) == QGRAD_HIT && ok;
+            const f3 gp = adds ? g.gp : mk3(0.0f, 0.0f, 0.0f);                    // a miss, a skipped point: zeros
+            if (A.g_points) { A.g_points[3 * (size_t)i] = gp.x; A.g_points[3 * (size_t)i + 1] = gp.y; A.g_points[3 * (size_t)i + 2] = gp.z; }
+            live = adds && A.acc != nullptr;
+            if (live) cgrad_fixed9(g, A.unit_exponent, q);
+        }
+        qgrad_wave_add9<MERGE>(A.acc, lane, live, key, vi, q);
+    }
+}
+
+}  // namespace prt

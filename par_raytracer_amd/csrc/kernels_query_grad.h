@@ -10,7 +10,7 @@
 //                    vertex contributions, in units of 2^u, into 64-bit integer accumulators with no-return relaxed agent-scope
 //                    atomics (accum_add's of dev_scene.h).  MERGE: the lanes of a wave that hit the same triangle - camera rays
 //                    do, by the dozen - first sum their integers with shuffles, and one lane issues the 9 adds; a lane alone on
-//                    its triangle adds directly.  The sums are integers, so the merge changes no bit.
+//                    its triangle adds directly (qgrad_wave_add9).  The sums are integers, so the merge changes no bit.
 //   k_qgrad_resolve  one lane per vertex component: accumulator x 2^u -> the caller's float (overwrites).
 //
 // No lane waits for another workgroup: no spin loop, no polled flag, no cooperative launch.  The only ordering is that of the
@@ -94,6 +94,38 @@ PRT_D long long qgrad_shfl_xor64(long long v, int off) {
     return (long long)((unsigned long long)(unsigned int)hi << 32 | (unsigned long long)(unsigned int)lo);
 }
 
+// The scatter's adds for one wave, written once for k_qgrad_scatter and k_cgrad_scatter (kernels_closest_grad.h).  Every lane of
+// the wave calls it together; a live lane holds its triangle's key, its three position indices and its 9 integers.  MERGE: one
+// pass per distinct triangle of the wave - the lanes on it sum their integers with xor-shuffles and the first of them issues
+// the 9 adds; a lane alone on its triangle adds directly, after the loop, together with the other lone lanes.
+template <bool MERGE>
+PRT_D void qgrad_wave_add9(long long * acc, unsigned int lane, bool live, unsigned int key, const unsigned int * vi, const long long * q) {
+    if (MERGE) {
+        bool alone = false;
+        unsigned long long todo = __ballot(live);
+        while (todo) {                                                // one pass per distinct triangle of the wave
+            const int leader = __ffsll((long long)todo) - 1;
+            const unsigned int k = (unsigned int)__shfl((int)key, leader);
+            const bool mine = live && key == k;
+            const unsigned long long same = __ballot(mine);
+            if (__popcll(same) == 1) {
+                alone = alone || mine;                                // adds with the other lone lanes, after the loop
+            } else {
+                long long s[9];
+                for (int c = 0; c < 9; ++c) {
+                    s[c] = mine ? q[c] : 0;
+                    for (int off = 32; off > 0; off >>= 1) s[c] += qgrad_shfl_xor64(s[c], off);
+                }
+                if ((int)lane == leader) qgrad_add9(acc, vi, s);
+            }
+            todo &= ~same;
+        }
+        if (alone) qgrad_add9(acc, vi, q);
+    } else if (live) {
+        qgrad_add9(acc, vi, q);
+    }
+}
+
 // The loop runs per WAVE (its bound does not depend on the lane), so every lane of a wave reaches the ballots and shuffles of the
 // merge together.  blockDim.x is a multiple of 64.
 template <bool MERGE>
@@ -114,30 +146,7 @@ __global__ __launch_bounds__(256) void k_qgrad_scatter(QGradArgs A) {
             live = adds && A.acc != nullptr;
             if (live) qgrad_fixed9(g, A.unit_exponent, q);
         }
-        if (MERGE) {
-            bool alone = false;
-            unsigned long long todo = __ballot(live);
-            while (todo) {                                                // one pass per distinct triangle of the wave
-                const int leader = __ffsll((long long)todo) - 1;
-                const unsigned int k = (unsigned int)__shfl((int)key, leader);
-                const bool mine = live && key == k;
-                const unsigned long long same = __ballot(mine);
-                if (__popcll(same) == 1) {
-                    alone = alone || mine;                                // adds with the other lone lanes, after the loop
-                } else {
-                    long long s[9];
-                    for (int c = 0; c < 9; ++c) {
-                        s[c] = mine ? q[c] : 0;
-                        for (int off = 32; off > 0; off >>= 1) s[c] += qgrad_shfl_xor64(s[c], off);
-                    }
-                    if ((int)lane == leader) qgrad_add9(A.acc, vi, s);
-                }
-                todo &= ~same;
-            }
-            if (alone) qgrad_add9(A.acc, vi, q);
-        } else if (live) {
-            qgrad_add9(A.acc, vi, q);
-        }
+        qgrad_wave_add9<MERGE>(A.acc, lane, live, key, vi, q);
     }
 }
 

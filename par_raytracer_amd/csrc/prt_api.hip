@@ -32,6 +32,7 @@
 #include "kernels_refit.h"
 #include "kernels_query_grad.h"
 #include "kernels_closest.h"
+#include "kernels_closest_grad.h"
 
 using namespace prt;
 
@@ -45,7 +46,7 @@ using namespace prt;
 #define PRT_POOL_BLOCK 256        // threads per workgroup of the fixed-spp pool kernel (experiments: 320, 640 with block-shared pools)
 #endif
 #ifndef PRT_QGRAD_MERGE_DEFAULT
-#define PRT_QGRAD_MERGE_DEFAULT 1 // prt_trace_rays_backward: lanes of a wave on one triangle merge their adds (same bits either way)
+#define PRT_QGRAD_MERGE_DEFAULT 1 // prt_trace_rays_backward, prt_closest_points_backward: lanes of a wave on one triangle merge their adds (same bits either way)
 #endif
 #ifndef PRT_DEEP_WAVES
 #define PRT_DEEP_WAVES PRT_POOL_WAVES   // waves per SIMD of the fixed-spp kernel for bounce trees of more than 15 draws (C5)
@@ -193,7 +194,7 @@ struct prt_ctx {
     DevBuf<RefitBox> rf_boxes;            // every node's exact float box
     DevBuf<unsigned int> rf_bounds;       // k_refit_bounds' two words
     DevBuf<float> rf_in;                  // host entry point: positions, normals, tangents on the device
-    // query gradients (prt_trace_rays_backward, kernels_query_grad.h).  Built by the first call after an upload from what the
+    // query gradients (prt_trace_rays_backward, kernels_query_grad.h; prt_closest_points_backward, kernels_closest_grad.h).  Built by the first call after an upload from what the
     // upload kept on the host (rf_idx_positions, q_groups); like q_leaf_map not in prt_scene_info.device_bytes, reused by later
     // calls, freed by the next upload.
     DevBuf<unsigned int> qg_idx;          // the position index buffer
@@ -1583,6 +1584,79 @@ int update_geometry(prt_ctx * ctx, const prt_geometry_update * u, prt_update_inf
     return 0;
 }
 
+// ---- what the two gradient calls share (prt_trace_rays_backward, prt_closest_points_backward): the device data, the scan's
+// verdict, the vertex gradient's last step and the info.  `what` is the entry point's name, for the error text.
+
+// The grid of the scan and scatter kernels: one lane per query, capped at 8 blocks of 256 per compute unit.
+unsigned int grad_grid(const prt_ctx * ctx, uint32_t count) {
+    return std::max(1u, std::min((count + 255u) / 256u, (unsigned int)std::max(1, ctx->cu_count) * 8u));
+}
+
+// The calls' own device data, built on the first gradient call of either kind after an upload: the position index buffer and
+// the groups' runs; the control words; np accumulators when the vertex gradient is wanted.
+int grad_prepare(prt_ctx * ctx, const char * what, size_t np, bool want_positions) {
+    if (ctx->rf_idx_positions.size() != 3 * (size_t)ctx->scene.tri_count) { ctx->error = std::string(what) + ": the scene's index buffer is not available"; return -2; }
+    if (!ctx->qg_idx.p || !ctx->qg_runs.p) {
+        std::vector<unsigned int> runs(2 * ctx->q_groups.size());
+        for (size_t g = 0; g < ctx->q_groups.size(); ++g) { runs[2 * g] = ctx->q_groups[g].first_index; runs[2 * g + 1] = ctx->q_groups[g].index_count; }
+        HIP_TRY(ctx, ctx->qg_idx.upload(ctx->rf_idx_positions));
+        HIP_TRY(ctx, ctx->qg_runs.upload(runs));
+        HIP_TRY(ctx, hipDeviceSynchronize());                     // the uploads went through the null stream
+    }
+    HIP_TRY(ctx, ctx->qg_words.ensure(QGRAD_WORDS));
+    if (want_positions) HIP_TRY(ctx, ctx->qg_acc.ensure(np));
+    return 0;
+}
+
+struct GradScan { unsigned int words[QGRAD_WORDS]; float m; int unit_exponent; };
+
+// After the scan kernel's launch: its four words on the host.  An invalid reference refuses the call (-1) - no output of the
+// caller's has been written yet.  Else M and the unit exponent of the batch.
+int grad_scan_verdict(prt_ctx * ctx, const char * what, const char * queries, uint32_t count, hipStream_t stream, GradScan * out) {
+    HIP_TRY(ctx, hipGetLastError());
+    memset(out, 0, sizeof(*out));
+    HIP_TRY(ctx, hipMemcpyAsync(out->words, ctx->qg_words.p, sizeof(out->words), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    if (out->words[QGRAD_W_INVALID]) {
+        char msg[240];
+        snprintf(msg, sizeof(msg), "%s: %u %s name a triangle the scene does not have (group out of range, vertex0 not a multiple of 3 or past its "
+                 "group's run)", what, out->words[QGRAD_W_INVALID], queries);
+        ctx->error = msg;
+        return -1;
+    }
+    memcpy(&out->m, &out->words[QGRAD_W_MAX], 4);
+    out->unit_exponent = out->m > 0.0f ? qgrad_unit_exponent(out->m, count) : 0;
+    return 0;
+}
+
+// After the scatter: the accumulators to the caller's floats, or zeros when nothing was added; then the call's closing event.
+int grad_resolve(prt_ctx * ctx, bool adds, float * g_positions, uint32_t position_count, int unit_exponent, hipStream_t stream) {
+    const size_t np = 3 * (size_t)position_count;
+    if (adds) {
+        QGradArgs R;                                              // k_qgrad_resolve reads these four fields
+        memset(&R, 0, sizeof(R));
+        R.g_positions = g_positions; R.acc = ctx->qg_acc.p; R.position_count = position_count; R.unit_exponent = unit_exponent;
+        hipLaunchKernelGGL(k_qgrad_resolve, dim3((unsigned int)((np + 255) / 256)), dim3(256), 0, stream, R);
+        HIP_TRY(ctx, hipGetLastError());
+    } else if (g_positions && np) {
+        HIP_TRY(ctx, hipMemsetAsync(g_positions, 0, np * sizeof(float), stream));
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev[1], stream));
+    return 0;
+}
+
+int grad_fill_info(prt_ctx * ctx, const GradScan & scan, prt_grad_info * info) {
+    if (!info) return 0;
+    float ms = 0.0f;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+    info->device_ms = ms;
+    info->hit_rays = scan.words[QGRAD_W_HIT];
+    info->skipped_rays = scan.words[QGRAD_W_SKIPPED];
+    info->unit_exponent = scan.unit_exponent;
+    info->max_contribution = scan.m;
+    return 0;
+}
+
 // prt_trace_rays_backward / prt_trace_rays_backward_device: `device` says where the caller's arrays live.  Nothing of the tree is
 // read and nothing of the scene, the render stats or the counters is written.  k_qgrad_scan validates every hit reference before
 // the first write to an output of the caller's.
@@ -1608,17 +1682,7 @@ int query_backward(prt_ctx * ctx, const prt_ray_batch * b, const int32_t * group
         }
         return 0;
     }
-    if (ctx->rf_idx_positions.size() != 3 * (size_t)ctx->scene.tri_count) { ctx->error = "prt_trace_rays_backward: the scene's index buffer is not available"; return -2; }
-    // ---- the call's own device data, built on the first call after an upload
-    if (!ctx->qg_idx.p || !ctx->qg_runs.p) {
-        std::vector<unsigned int> runs(2 * ctx->q_groups.size());
-        for (size_t g = 0; g < ctx->q_groups.size(); ++g) { runs[2 * g] = ctx->q_groups[g].first_index; runs[2 * g + 1] = ctx->q_groups[g].index_count; }
-        HIP_TRY(ctx, ctx->qg_idx.upload(ctx->rf_idx_positions));
-        HIP_TRY(ctx, ctx->qg_runs.upload(runs));
-        HIP_TRY(ctx, hipDeviceSynchronize());                     // the uploads went through the null stream
-    }
-    HIP_TRY(ctx, ctx->qg_words.ensure(QGRAD_WORDS));
-    if (want_p) HIP_TRY(ctx, ctx->qg_acc.ensure(np));
+    if (const int rc = grad_prepare(ctx, "prt_trace_rays_backward", np, want_p != nullptr)) return rc;
     QGradArgs A;
     memset(&A, 0, sizeof(A));
     A.origins = b->origins; A.dirs = b->directions; A.group = group; A.vertex0 = vertex0; A.positions = positions;
@@ -1656,25 +1720,14 @@ int query_backward(prt_ctx * ctx, const prt_ray_batch * b, const int32_t * group
     A.ray_bias = b->ray_bias;
 
     // ---- the references and the batch's largest contribution, before any output is written
-    const unsigned int grid = std::max(1u, std::min((b->count + 255u) / 256u, (unsigned int)std::max(1, ctx->cu_count) * 8u));
+    const unsigned int grid = grad_grid(ctx, b->count);
     HIP_TRY(ctx, hipEventRecord(ctx->ev[0], stream));
     HIP_TRY(ctx, hipMemsetAsync(A.words, 0, QGRAD_WORDS * sizeof(unsigned int), stream));
     hipLaunchKernelGGL(k_qgrad_scan, dim3(grid), dim3(256), 0, stream, A);
-    HIP_TRY(ctx, hipGetLastError());
-    unsigned int words[QGRAD_WORDS] = { 0u, 0u, 0u, 0u };
-    HIP_TRY(ctx, hipMemcpyAsync(words, A.words, sizeof(words), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(ctx, hipStreamSynchronize(stream));
-    if (words[QGRAD_W_INVALID]) {
-        char msg[200];
-        snprintf(msg, sizeof(msg), "prt_trace_rays_backward: %u rays name a triangle the scene does not have (group out of range, vertex0 not a "
-                 "multiple of 3 or past its group's run)", words[QGRAD_W_INVALID]);
-        ctx->error = msg;
-        return -1;
-    }
-    float m;
-    memcpy(&m, &words[QGRAD_W_MAX], 4);
-    const bool adds = want_p && words[QGRAD_W_HIT] && m > 0.0f;   // else the vertex gradient is zero
-    A.unit_exponent = m > 0.0f ? qgrad_unit_exponent(m, b->count) : 0;
+    GradScan scan;
+    if (const int rc = grad_scan_verdict(ctx, "prt_trace_rays_backward", "rays", b->count, stream, &scan)) return rc;
+    const bool adds = want_p && scan.words[QGRAD_W_HIT] && scan.m > 0.0f;   // else the vertex gradient is zero
+    A.unit_exponent = scan.unit_exponent;
     A.acc = adds ? ctx->qg_acc.p : nullptr;
     if (adds) HIP_TRY(ctx, hipMemsetAsync(A.acc, 0, np * sizeof(long long), stream));
     if (adds || want_o || want_d) {
@@ -1684,29 +1737,101 @@ int query_backward(prt_ctx * ctx, const prt_ray_batch * b, const int32_t * group
             hipLaunchKernelGGL(k_qgrad_scatter<false>, dim3(grid), dim3(256), 0, stream, A);
         HIP_TRY(ctx, hipGetLastError());
     }
-    if (adds) {
-        hipLaunchKernelGGL(k_qgrad_resolve, dim3((unsigned int)((np + 255) / 256)), dim3(256), 0, stream, A);
-        HIP_TRY(ctx, hipGetLastError());
-    } else if (want_p && np) {
-        HIP_TRY(ctx, hipMemsetAsync(A.g_positions, 0, np * sizeof(float), stream));
-    }
-    HIP_TRY(ctx, hipEventRecord(ctx->ev[1], stream));
+    if (const int rc = grad_resolve(ctx, adds, A.g_positions, position_count, A.unit_exponent, stream)) return rc;
     if (!device) {
         if (want_o) HIP_TRY(ctx, hipMemcpyAsync(want_o, A.g_origins, 12 * n, hipMemcpyDeviceToHost, stream));
         if (want_d) HIP_TRY(ctx, hipMemcpyAsync(want_d, A.g_dirs, 12 * n, hipMemcpyDeviceToHost, stream));
         if (want_p && np) HIP_TRY(ctx, hipMemcpyAsync(want_p, A.g_positions, np * sizeof(float), hipMemcpyDeviceToHost, stream));
     }
     HIP_TRY(ctx, hipStreamSynchronize(stream));
-    if (info) {
-        float ms = 0.0f;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-        info->device_ms = ms;
-        info->hit_rays = words[QGRAD_W_HIT];
-        info->skipped_rays = words[QGRAD_W_SKIPPED];
-        info->unit_exponent = A.unit_exponent;
-        info->max_contribution = m;
+    return grad_fill_info(ctx, scan, info);
+}
+
+// prt_closest_points_backward / prt_closest_points_backward_device: query_backward's shape for the point queries - the same
+// lazily built index buffer, runs, accumulators, control words and transfer slab, the same grid rule and event timing.  Nothing
+// of the tree is read and nothing of the scene, the render stats or the counters is written.  k_cgrad_scan validates every
+// reference before the first write to an output of the caller's.
+int closest_backward(prt_ctx * ctx, const prt_point_batch * b, const int32_t * group, const uint32_t * vertex0, const float * positions,
+                     uint32_t position_count, const prt_closest_grads * gout, const prt_point_grads * gin, prt_grad_info * info, bool device) {
+    if (!ctx) return -1;
+    if (info) memset(info, 0, sizeof(*info));
+    if (!b) { ctx->error = "prt_closest_points_backward: null batch"; return -1; }
+    if (b->count && (!b->points || !group || !vertex0 || !positions)) {
+        ctx->error = "prt_closest_points_backward: null points, group, vertex0 or positions";
+        return -1;
     }
-    return 0;
+    if (!ctx->has_scene) { ctx->error = "prt_closest_points_backward: no scene uploaded"; return -2; }
+    if (position_count != ctx->rf_position_count) { ctx->error = "prt_closest_points_backward: position_count differs from the uploaded scene's"; return -1; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    const size_t n = b->count, np = 3 * (size_t)position_count;
+    float * want_p = gin ? gin->positions : nullptr, * want_q = gin ? gin->points : nullptr;
+    if (n == 0) {                                                 // no point: the vertex gradient is zero
+        if (want_p && np) {
+            if (device) { HIP_TRY(ctx, hipMemsetAsync(want_p, 0, np * sizeof(float), stream)); HIP_TRY(ctx, hipStreamSynchronize(stream)); }
+            else memset(want_p, 0, np * sizeof(float));
+        }
+        return 0;
+    }
+    if (const int rc = grad_prepare(ctx, "prt_closest_points_backward", np, want_p != nullptr)) return rc;
+    CGradArgs A;
+    memset(&A, 0, sizeof(A));
+    A.points = b->points; A.group = group; A.vertex0 = vertex0; A.positions = positions;
+    if (gout) { A.g_dist2 = gout->dist2; A.g_point = gout->point; A.g_bw = gout->bw; }
+    A.g_points = want_q;
+    float * g_positions = want_p;
+    if (!device) {                                                // inputs, then the requested gradients, in one slab of 4-byte words
+        const size_t f_in = 5 * n + np + (A.g_dist2 ? n : 0) + (A.g_point ? 3 * n : 0) + (A.g_bw ? 3 * n : 0);
+        const size_t f_out = (want_q ? 3 * n : 0) + (want_p ? np : 0);
+        HIP_TRY(ctx, ctx->qg_io.ensure(f_in + f_out));
+        float * p = ctx->qg_io.p;
+        auto in = [&](const void * src, size_t words) -> float * {
+            float * at = p;
+            p += words;
+            return hipMemcpyAsync(at, src, words * 4, hipMemcpyHostToDevice, stream) == hipSuccess ? at : nullptr;
+        };
+        bool ok = true;
+        ok = (A.points = in(b->points, 3 * n)) && ok;
+        ok = (A.group = reinterpret_cast<const int *>(in(group, n))) && ok;
+        ok = (A.vertex0 = reinterpret_cast<const unsigned int *>(in(vertex0, n))) && ok;
+        ok = (A.positions = in(positions, np)) && ok;
+        if (A.g_dist2) ok = (A.g_dist2 = in(gout->dist2, n)) && ok;
+        if (A.g_point) ok = (A.g_point = in(gout->point, 3 * n)) && ok;
+        if (A.g_bw) ok = (A.g_bw = in(gout->bw, 3 * n)) && ok;
+        if (!ok) { ctx->error = "prt_closest_points_backward: copying the inputs to the device failed"; return -10; }
+        if (want_q) { A.g_points = p; p += 3 * n; }
+        if (want_p) { g_positions = p; p += np; }
+    }
+    A.idx_positions = ctx->qg_idx.p;
+    A.group_runs = ctx->qg_runs.p;
+    A.words = ctx->qg_words.p;
+    A.count = b->count; A.group_count = (unsigned int)ctx->q_groups.size(); A.position_count = position_count;
+
+    // ---- the references and the batch's largest contribution, before any output is written
+    const unsigned int grid = grad_grid(ctx, b->count);
+    HIP_TRY(ctx, hipEventRecord(ctx->ev[0], stream));
+    HIP_TRY(ctx, hipMemsetAsync(A.words, 0, QGRAD_WORDS * sizeof(unsigned int), stream));
+    hipLaunchKernelGGL(k_cgrad_scan, dim3(grid), dim3(256), 0, stream, A);
+    GradScan scan;
+    if (const int rc = grad_scan_verdict(ctx, "prt_closest_points_backward", "points", b->count, stream, &scan)) return rc;
+    const bool adds = want_p && scan.words[QGRAD_W_HIT] && scan.m > 0.0f;   // else the vertex gradient is zero
+    A.unit_exponent = scan.unit_exponent;
+    A.acc = adds ? ctx->qg_acc.p : nullptr;
+    if (adds) HIP_TRY(ctx, hipMemsetAsync(A.acc, 0, np * sizeof(long long), stream));
+    if (adds || want_q) {
+        if (ctx->opt.qgrad_merge < 0 ? PRT_QGRAD_MERGE_DEFAULT != 0 : ctx->opt.qgrad_merge != 0)
+            hipLaunchKernelGGL(k_cgrad_scatter<true>, dim3(grid), dim3(256), 0, stream, A);
+        else
+            hipLaunchKernelGGL(k_cgrad_scatter<false>, dim3(grid), dim3(256), 0, stream, A);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    if (const int rc = grad_resolve(ctx, adds, g_positions, position_count, A.unit_exponent, stream)) return rc;
+    if (!device) {
+        if (want_q) HIP_TRY(ctx, hipMemcpyAsync(want_q, A.g_points, 12 * n, hipMemcpyDeviceToHost, stream));
+        if (want_p && np) HIP_TRY(ctx, hipMemcpyAsync(want_p, g_positions, np * sizeof(float), hipMemcpyDeviceToHost, stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    return grad_fill_info(ctx, scan, info);
 }
 
 }  // namespace
@@ -2393,6 +2518,22 @@ int prt_trace_rays_backward_device(prt_ctx * ctx, const prt_ray_batch * batch, c
     PRT_API_TRY
     return query_backward(ctx, batch, group, vertex0, positions, position_count, gout, gin, info, true);
     PRT_API_CATCH_RC(ctx, "prt_trace_rays_backward_device")
+}
+
+int prt_closest_points_backward(prt_ctx * ctx, const prt_point_batch * batch, const int32_t * group, const uint32_t * vertex0,
+                                const float * positions, uint32_t position_count, const prt_closest_grads * gout,
+                                const prt_point_grads * gin, prt_grad_info * info) {
+    PRT_API_TRY
+    return closest_backward(ctx, batch, group, vertex0, positions, position_count, gout, gin, info, false);
+    PRT_API_CATCH_RC(ctx, "prt_closest_points_backward")
+}
+
+int prt_closest_points_backward_device(prt_ctx * ctx, const prt_point_batch * batch, const int32_t * group, const uint32_t * vertex0,
+                                       const float * positions, uint32_t position_count, const prt_closest_grads * gout,
+                                       const prt_point_grads * gin, prt_grad_info * info) {
+    PRT_API_TRY
+    return closest_backward(ctx, batch, group, vertex0, positions, position_count, gout, gin, info, true);
+    PRT_API_CATCH_RC(ctx, "prt_closest_points_backward_device")
 }
 
 // The geometric check of bvh_check.cpp on the tree as it lies on the device NOW (after any number of updates), against the

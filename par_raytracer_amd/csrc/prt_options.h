@@ -44,7 +44,7 @@ struct PrtOptions {
     long long work_reverse = 0;             // experiment: hand the call's pixels out last-to-first (dev_scene.h DevParams::work_reverse_n)
     long long pool_shared_cap = -1;         // ... slots per WAVE of a shared pool before the x4 (experiments)
     long long pass_samples = -1, pass_mb = -1, stack_cap = -1, no_tiles = 0;
-    long long qgrad_merge = -1;             // prt_trace_rays_backward: 1 = lanes of a wave on one triangle merge their adds, 0 = every lane adds; -1 = the default (same bits)
+    long long qgrad_merge = -1;             // prt_trace_rays_backward and prt_closest_points_backward (both scatter kernels): 1 = lanes of a wave on one triangle merge their adds, 0 = every lane adds; -1 = the default (same bits)
     long long reserve_cus = 0;              // creation only: compute units the context's streams leave free
     long long reserve_pattern = 2;          // creation only: which bits of the CU mask are cleared - 2 = every (n / k)-th (k = 8: one compute unit per XCD),
                                             // experiments: 0 = the last k, 1 = the first k, 3 = none (profiles/r03_cu_mask.txt)
