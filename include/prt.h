@@ -592,6 +592,26 @@ int prt_debug_check_bvh(const prt_scene_desc * scene, uint64_t * out);
 /* The same check on the tree of the GPU LBVH builder (option BVH_BUILDER=lbvh at upload: radix tree built on the
  * device, bvh_lbvh.h; an alternative for scenes that change every frame - ~10x faster to build, slower to traverse). */
 int prt_debug_check_bvh_lbvh(prt_ctx * ctx, const prt_scene_desc * scene, uint64_t * out);
+/* The radix tree of that builder as the device made it, before the host back end (GPU test-suite: compared element by
+ * element, with ==, against a host construction).  verts9: n_tris x 9 floats, the un-indexed corners; the scene bounds are
+ * taken from them exactly as an upload takes them.  Every output is caller-allocated and may be NULL (then it is not
+ * returned); with ni = max(n_tris - 1, 1): left, right, first, last [ni], node_box [6 ni], leaf_box [6 n_tris],
+ * sorted_ids [n_tris], sorted_keys [n_tris] (the one array an upload does not transfer).  What they hold:
+ *   - key of a triangle: the 63-bit Morton code (x in bits 0, 3, .., y in 1, 4, .., z in 2, 5, ..) of
+ *     q = (unsigned)clamp((0.5f * (box lo + box hi) - scene lo) * s, 0, 2097151), float32 throughout, s = 2097151 / extent
+ *     - and s = 0 on an axis of extent 0: a flat axis contributes q = 0 for every triangle;
+ *   - sorted_keys ascending; equal keys keep their input order (stable sort), sorted_ids[k] = input triangle at position k;
+ *   - the hierarchy is the radix tree over (key, sorted position): equal keys are told apart by position, so it is unique;
+ *     internal node i has children left[i] / right[i] (>= 0 internal node, < 0 = ~sorted position of one triangle) and covers
+ *     positions [first[i], last[i]];
+ *   - numbering: the root is node 0; a node that splits after position g has left child node g (leaf ~g when first == g)
+ *     and right child node g + 1 (leaf ~(g + 1) when last == g + 1);
+ *   - leaf_box: lo xyz, hi xyz of each triangle in sorted order; node_box: exact min / max over [first, last];
+ *   - n_tris == 1: leaf_box, sorted_ids and sorted_keys hold the triangle; the five per-node arrays (length 1) are
+ *     UNSPECIFIED - there is no internal node.
+ * n_tris == 0 or a coordinate that is not finite / above 1e18 returns -1. */
+int prt_debug_lbvh_tree(prt_ctx * ctx, uint32_t n_tris, const float * verts9, int32_t * left, int32_t * right, uint32_t * first,
+                        uint32_t * last, float * node_box, float * leaf_box, uint32_t * sorted_ids, uint64_t * sorted_keys);
 /* The same check on the tree as it lies on the context's device NOW - after any number of prt_update_geometry calls -
  * against the un-indexed triangles of moved_scene (its positions and idx_positions; the triangle count must be the uploaded
  * scene's): the GPU test-suite's geometric proof that a refitted tree is conservative. */

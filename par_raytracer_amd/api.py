@@ -685,6 +685,22 @@ class Renderer:
         self._check(self._lib.prt_debug_check_refit(self._ctx, desc, out), "prt_debug_check_refit")
         return dict(zip(("violations", "nodes", "depth", "stack_bound", "leaves", "refs"), (int(v) for v in out)))
 
+    def lbvh_tree(self, verts9, keys: bool = True) -> dict:
+        """prt_debug_lbvh_tree: the GPU builder's radix tree over the un-indexed triangles verts9 (float32, n x 9 or n x 3 x 3), as the
+        device made it: left, right, first, last, node_box (ni, 6), leaf_box (n, 6), sorted_ids and - keys=True - sorted_keys
+        (uint64).  ni = max(n - 1, 1); for n = 1 the per-node arrays are unspecified (include/prt.h)."""
+        v = np.ascontiguousarray(verts9, np.float32).reshape(-1, 9)
+        n = v.shape[0]
+        ni = max(n - 1, 1)
+        out = dict(left=np.zeros(ni, np.int32), right=np.zeros(ni, np.int32), first=np.zeros(ni, np.uint32), last=np.zeros(ni, np.uint32),
+                   node_box=np.zeros((ni, 6), np.float32), leaf_box=np.zeros((n, 6), np.float32), sorted_ids=np.zeros(n, np.uint32))
+        if keys:
+            out["sorted_keys"] = np.zeros(n, np.uint64)
+        names = ("left", "right", "first", "last", "node_box", "leaf_box", "sorted_ids", "sorted_keys")
+        self._check(self._lib.prt_debug_lbvh_tree(self._ctx, n, v.ctypes.data, *[out[k].ctypes.data if k in out else None for k in names]),
+                    "prt_debug_lbvh_tree")
+        return out
+
     def close(self):
         if self._ctx:
             self._lib.prt_destroy(self._ctx)

@@ -158,7 +158,7 @@ BUILD_EXPERIMENTAL, BUILD_BVH4 = 1, 2
 
 # Every symbol include/prt.h declares; tests/test_capi_symbols.py checks the library exports them all.
 PRT_SYMBOLS = ["prt_create", "prt_destroy", "prt_last_error", "prt_abi_version", "prt_set_option", "prt_build_flags", "prt_upload_scene", "prt_render",
-               "prt_render_device", "prt_shard_rows", "prt_render_shard_device", "prt_render_shard", "prt_render_pixel_list", "prt_get_scene_info", "prt_get_render_stats", "prt_debug_check_bvh", "prt_debug_check_bvh_lbvh", "prt_debug_device_kat",
+               "prt_render_device", "prt_shard_rows", "prt_render_shard_device", "prt_render_shard", "prt_render_pixel_list", "prt_get_scene_info", "prt_get_render_stats", "prt_debug_check_bvh", "prt_debug_check_bvh_lbvh", "prt_debug_lbvh_tree", "prt_debug_device_kat",
                "prt_multi_create", "prt_multi_destroy", "prt_multi_last_error", "prt_multi_device_count", "prt_multi_context",
                "prt_multi_upload_scene", "prt_multi_render", "prt_multi_depth", "prt_multi_submit", "prt_multi_wait", "prt_debug_throw",
                "prt_trace_rays", "prt_trace_rays_device", "prt_get_region_stats",
@@ -226,6 +226,8 @@ def hip_lib() -> C.CDLL:
             lib.prt_get_region_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32]
         lib.prt_debug_check_bvh.argtypes = [C.POINTER(PrtSceneDesc), C.POINTER(C.c_uint64)]
         lib.prt_debug_check_bvh_lbvh.argtypes = [C.c_void_p, C.POINTER(PrtSceneDesc), C.POINTER(C.c_uint64)]
+        if hasattr(lib, "prt_debug_lbvh_tree"):        # (absent from a PRT_HIP_LIB build of an earlier commit)
+            lib.prt_debug_lbvh_tree.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 9
         lib.prt_debug_device_kat.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32,
                                              C.POINTER(PrtCamera)]
         lib.prt_multi_create.restype = C.c_void_p

@@ -25,6 +25,7 @@ struct LbvhTree {                        // host copies of the device result, se
     std::vector<uint32_t> first, last;
     std::vector<float> node_box, leaf_box;
     std::vector<uint32_t> sorted_ids;
+    std::vector<uint64_t> sorted_keys;   // only when build_lbvh_tree is asked for them (the debug entry): the upload does not pay for them
 };
 
 namespace lbvh {
@@ -129,9 +130,34 @@ __global__ void k_fit(const float * boxes, const unsigned int * ids, int n, cons
 
 }  // namespace lbvh
 
+// The scene bounds the Morton grid spans: min / max over every corner, as the upload and the debug entry both take them.
+inline void lbvh_scene_bounds(const float * verts, uint32_t n, float * lo, float * hi) {
+    for (int a = 0; a < 3; ++a) lo[a] = hi[a] = 0.0f;
+    for (size_t i = 0; i < (size_t)n * 3; ++i)
+        for (int a = 0; a < 3; ++a) {
+            const float v = verts[i * 3 + a];
+            if (i == 0 || v < lo[a]) lo[a] = v;
+            if (i == 0 || v > hi[a]) hi[a] = v;
+        }
+}
+
 // verts: 9 floats per triangle on the HOST (copied in); scene bounds from the caller.  Returns hipSuccess and fills `t`.
+//
+// What the result is, element by element (tests/test_gpu_lbvh_tree.py holds the device to it with ==):
+//   keys        spread21(qx) | spread21(qy) << 1 | spread21(qz) << 2, q = (unsigned)clamp((0.5f * (lo + hi) - scene_lo) * s, 0, 2097151)
+//               in float32, s = 2097151 / extent - and 0 on an axis of extent 0, so that a flat axis gives q = 0 for every triangle;
+//   order       the keys ascending, equal keys in input order (the pair sort is stable): sorted_ids[k] = input triangle at position k;
+//   hierarchy   the radix tree over (key, sorted position) - equal keys are told apart by their positions, so the tree is unique:
+//               a node covering [first, last] splits after gamma, the last position that shares with `first` the longest prefix
+//               of key << 32 | position that `last` does not share;
+//   numbering   the root is node 0; the left child covering [first, gamma] is internal node gamma, or leaf ~gamma when first == gamma;
+//               the right child covering [gamma + 1, last] is internal node gamma + 1, or leaf ~(gamma + 1) when last == gamma + 1;
+//   boxes       exact float32 min / max: leaf_box of the three corners (sorted order), node_box over [first, last];
+//   n = 1       no hierarchy: leaf_box, sorted_ids (and keys) hold the one triangle, the five node arrays have length 1 and are
+//               NOT written (unspecified values).
+// want_keys: also copy the sorted keys back (t->sorted_keys), one more transfer that the upload leaves out.
 inline hipError_t build_lbvh_tree(const float * verts, uint32_t n, const float * scene_lo, const float * scene_hi, hipStream_t stream,
-                                  LbvhTree * t, double * device_ms) {
+                                  LbvhTree * t, double * device_ms, bool want_keys = false) {
     *t = LbvhTree();
     if (n == 0) return hipSuccess;
     hipError_t e = hipSuccess;
@@ -200,6 +226,10 @@ inline hipError_t build_lbvh_tree(const float * verts, uint32_t n, const float *
     }
     LB_TRY(hipMemcpy(t->leaf_box.data(), d_leaf_box, (size_t)n * 24, hipMemcpyDeviceToHost));
     LB_TRY(hipMemcpy(t->sorted_ids.data(), d_ids2, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (want_keys) {
+        t->sorted_keys.resize(n);
+        LB_TRY(hipMemcpy(t->sorted_keys.data(), d_keys2, (size_t)n * 8, hipMemcpyDeviceToHost));
+    }
 done:
 #undef LB_TRY
     (void)hipFree(d_verts); (void)hipFree(d_boxes); (void)hipFree(d_leaf_box); (void)hipFree(d_node_box); (void)hipFree(d_keys); (void)hipFree(d_keys2);

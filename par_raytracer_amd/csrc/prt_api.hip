@@ -722,13 +722,8 @@ void launch_resolve(hipStream_t stream, const void * samples, float4 * out, unsi
 
 // GPU radix-tree build + host collapse / quantise.  verts: 9 floats per triangle.
 int build_bvh_lbvh(prt_ctx * ctx, const float * verts, uint32_t n_tris, uint32_t leaf_max, BvhWide * bvh) {
-    float lo[3] = { 0, 0, 0 }, hi[3] = { 0, 0, 0 };
-    for (uint32_t i = 0; i < n_tris * 3u; ++i)
-        for (int a = 0; a < 3; ++a) {
-            const float v = verts[(size_t)i * 3 + a];
-            if (i == 0 || v < lo[a]) lo[a] = v;
-            if (i == 0 || v > hi[a]) hi[a] = v;
-        }
+    float lo[3], hi[3];
+    lbvh_scene_bounds(verts, n_tris, lo, hi);
     LbvhTree tree;
     double device_ms = 0.0;
     HIP_TRY(ctx, build_lbvh_tree(verts, n_tris, lo, hi, ctx->stream, &tree, &device_ms));
@@ -2641,6 +2636,32 @@ int prt_debug_check_bvh_lbvh(prt_ctx * ctx, const prt_scene_desc * s, uint64_t *
     check_bvh_wide(verts.data(), n_tris, bvh, out);
     return 0;
     PRT_API_CATCH_RC(ctx, "prt_debug_check_bvh_lbvh")
+}
+
+// The device's radix tree itself, before the host back end: the arrays build_lbvh_tree returns, copied out (include/prt.h).
+int prt_debug_lbvh_tree(prt_ctx * ctx, uint32_t n_tris, const float * verts, int32_t * left, int32_t * right, uint32_t * first, uint32_t * last,
+                        float * node_box, float * leaf_box, uint32_t * sorted_ids, uint64_t * sorted_keys) {
+    PRT_API_TRY
+    if (!ctx) return -1;
+    if (!n_tris || !verts) { ctx->error = "prt_debug_lbvh_tree: no triangles"; return -1; }
+    for (size_t i = 0; i < (size_t)n_tris * 9; ++i)
+        if (!(fabsf(verts[i]) < 1e18f)) { ctx->error = "prt_debug_lbvh_tree: vertex coordinate is not finite or exceeds 1e18"; return -1; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    float lo[3], hi[3];
+    lbvh_scene_bounds(verts, n_tris, lo, hi);
+    LbvhTree tree;
+    HIP_TRY(ctx, build_lbvh_tree(verts, n_tris, lo, hi, ctx->stream, &tree, nullptr, sorted_keys != nullptr));
+    const size_t n = n_tris, ni = tree.left.size();
+    if (left) memcpy(left, tree.left.data(), ni * 4);
+    if (right) memcpy(right, tree.right.data(), ni * 4);
+    if (first) memcpy(first, tree.first.data(), ni * 4);
+    if (last) memcpy(last, tree.last.data(), ni * 4);
+    if (node_box) memcpy(node_box, tree.node_box.data(), ni * 24);
+    if (leaf_box) memcpy(leaf_box, tree.leaf_box.data(), n * 24);
+    if (sorted_ids) memcpy(sorted_ids, tree.sorted_ids.data(), n * 4);
+    if (sorted_keys) memcpy(sorted_keys, tree.sorted_keys.data(), n * 8);
+    return 0;
+    PRT_API_CATCH_RC(ctx, "prt_debug_lbvh_tree")
 }
 
 }  // extern "C"
