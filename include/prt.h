@@ -478,6 +478,54 @@ int prt_closest_points_backward_device(prt_ctx * ctx, const prt_point_batch * ba
                                        const float * positions, uint32_t position_count, const prt_closest_grads * gout,
                                        const prt_point_grads * gin, prt_grad_info * info);
 
+/* ---- signed distances: which side of the surface a point is on --------------------------------------------------------------
+ * prt_closest_points plus a sign, for signed distance fields, penetration depths, containment tests and occupancy labels.  The
+ * sign comes from the closest feature and its angle-weighted pseudonormal (Baerentzen & Aanaes, "Signed distance computation
+ * using the angle weighted pseudonormal", 2005); no ray is cast and nothing is counted.
+ * THE DEFINITION (csrc/dev_signed.h).  For a point p take the winner (group, vertex0, v, w, d2) exactly
+ * as prt_closest_points defines it: the walk, the tie rule and the pad are unchanged, and the five closest fields are the bits
+ * prt_closest_points writes.  R = the region 0..6 that closest_region_walk (csrc/dev_closest.h; the numbering of
+ * prt_closest_points_backward above) takes on the winner's record for p, q = (a + ab v) + ac w, e = p - q, and
+ *     R = 6 interior   N = cross(ab, ac), unnormalised
+ *     R = 2, 4, 5      N = the pseudonormal of the edge ab, ac, bc: the sum of n over the triangles that have the edge
+ *     R = 0, 1, 3      N = the pseudonormal of the vertex a, b, c: the sum of (interior angle at the vertex) x n over the
+ *                      triangles that have the vertex
+ *     s = Dot(e, N)    signed_dist = s < 0 ? -sqrtf(d2) : sqrtf(d2)
+ * with n = Normalize(cross(ab, ac)) of a triangle's record.  NaN, s == 0 and d2 == 0 give the non-negative branch.  Positive is
+ * the side cross(ab, ac) points to - the side PRT_QUERY_CLOSEST calls front-facing.  A miss has signed_dist = FLT_MAX and
+ * feature = 255.
+ * Vertices are the entries of `positions`, identified by their index in idx_positions; an edge is an unordered pair of position
+ * indices; the triangles of all groups count.  Two positions with equal coordinates but different indices are different
+ * vertices, and an edge between them is a boundary edge: welding is the caller's business.
+ * The sums are exact and ordered by nothing: every component of a contribution (float32, fixed expression order, angles from
+ * signed_acos of csrc/dev_signed.h - no libm call) is rounded once to a multiple of 2^-32 and added as a 64-bit integer; a
+ * triangle whose n or angles are not all finite contributes nothing; N = (float)sum x 2^-32.  The result is a pure function of
+ * (scene as it lies on the device, point): the same bits for every tree (SAH, LBVH, 8-wide, refitted), schedule option,
+ * STACK_CAP, entry point, batch order and run, and the bits a brute force over all triangles gives on the host.
+ * LIMITS.  On a closed, consistently wound mesh the sign is inside (negative) / outside.  On an open or inconsistently wound
+ * mesh it is the side of the nearest surface element: deterministic, but not an occupancy.  Within rounding of a region
+ * boundary the float32 region can differ from the real-valued one, and then another feature's normal is read.  Gradients of the
+ * sign are not modelled.
+ * TABLES.  The first signed query after an upload builds the adjacency (per triangle the three position indices and three edge
+ * ids: 24 B per triangle) and allocates the accumulators (24 B per position and 24 B per edge); the first signed query after an
+ * upload or after a successful prt_update_geometry[_device] refills the accumulators on the device from the records as they lie
+ * there (its time counts in render_ms, not in trace_kernel_ms).  Like the leaf table they are not in
+ * prt_scene_info.device_bytes and are freed by the next upload.  A call that requests neither signed_dist nor feature builds
+ * nothing and is prt_closest_points.
+ * Errors, count == 0, the counters, the stream contract and the treatment of invalid points are prt_closest_points's, word for
+ * word. */
+typedef struct prt_signed_buffers {
+    prt_closest_buffers closest;   /* as prt_closest_points writes them; any pointer may be NULL */
+    float * signed_dist;           /* +-sqrt(d2); FLT_MAX on a miss */
+    uint8_t * feature;             /* the region R 0..6 whose normal decided; 255 on a miss */
+} prt_signed_buffers;
+/* Host pointers (batch arrays and buffers). */
+int prt_signed_distance(prt_ctx * ctx, const prt_point_batch * batch, const prt_signed_buffers * out, uint32_t flags,
+                        prt_counters * counters);
+/* Device pointers on the context's device; the stream contract of prt_trace_rays_device. */
+int prt_signed_distance_device(prt_ctx * ctx, const prt_point_batch * batch, const prt_signed_buffers * out, uint32_t flags,
+                               prt_counters * counters);
+
 /* ---- several devices behind one handle --------------------------------------------------------------------------------
  * SURVEY.md 8(b)'s prt_create(const int * device_ids, int n_dev): what the host mirror's Render() uses for n GPUs, in place
  * of the reference's one-rank-per-core partition + MPI_Gather (main.cpp:311-347).  The scene is replicated (as every MPI rank

@@ -412,12 +412,30 @@ class Renderer:
         in float32 (max_dist * max_dist, rounded once) and passes the squares as max_dist2; a triangle is a candidate when its
         squared distance is <= that square.  fields: any of dist2, point, bw, vertex0, group (default all).  Returns {field: array}
         plus "distance" = sqrt(dist2) when dist2 is among the fields - inf on a miss - and "counters" (PrtCounters)."""
-        spec = {name: (k, dt) for name, k, dt in self.CLOSEST_POINT_FIELDS}
+        return self._point_query(points, max_dist, fields, count_visits, False)
+
+    # prt_signed_buffers' own fields, behind prt_closest_buffers'
+    SIGNED_DISTANCE_FIELDS = (("signed_distance", 1, np.float32), ("feature", 1, np.uint8))
+
+    def signed_distance(self, points, *, max_dist=None, fields: Optional[Sequence[str]] = None, count_visits: bool = False) -> dict:
+        """The nearest point of the uploaded surface and the side of it that n points lie on (prt_signed_distance, include/prt.h).
+
+        points, max_dist, count_visits: as closest_points takes them.  fields: any of closest_points' fields, signed_distance and
+        feature (default all).  Returns what closest_points returns plus "signed_distance" (+-sqrt(dist2), FLT_MAX on a miss),
+        "feature" (uint8: the region 0..6 whose normal decided the sign, 255 on a miss) and, with signed_distance among the
+        fields, "inside" = signed_distance < 0 (bool).  On a closed, consistently wound mesh inside is containment; on an open
+        mesh it is the side of the nearest surface element."""
+        return self._point_query(points, max_dist, fields, count_visits, True)
+
+    def _point_query(self, points, max_dist, fields, count_visits, signed) -> dict:
+        """closest_points and signed_distance: the same batch and buffers, one of the two entry points."""
+        all_fields = self.CLOSEST_POINT_FIELDS + (self.SIGNED_DISTANCE_FIELDS if signed else ())
+        spec = {name: (k, dt) for name, k, dt in all_fields}
         if fields is None:
             fields = tuple(spec)
         for f in fields:
             if f not in spec:
-                raise ValueError("unknown closest-point field %r" % (f,))
+                raise ValueError("unknown %s field %r" % ("signed-distance" if signed else "closest-point", f))
         is_torch = type(points).__module__.split(".")[0] == "torch"
         if is_torch:
             import torch
@@ -437,13 +455,14 @@ class Renderer:
                 if max_dist.shape[0] != n:
                     raise ValueError("max_dist has %d entries for %d points" % (max_dist.shape[0], n))
                 max_d2 = (max_dist * max_dist).contiguous()
-            tdt = {np.float32: torch.float32, np.uint32: torch.int32, np.int32: torch.int32}     # vertex0: int32 with the same bits
+            tdt = {np.float32: torch.float32, np.uint32: torch.int32, np.int32: torch.int32,     # vertex0: int32 with the same bits
+                   np.uint8: torch.uint8}
             out = {f: torch.empty((n, spec[f][0]) if spec[f][0] > 1 else (n,), dtype=tdt[spec[f][1]], device=points.device)
                    for f in fields}
             ptr = lambda x: x.data_ptr() if x is not None else None    # noqa: E731
             # the library's stream is not ordered against torch's: whatever torch still has queued on the inputs must be done
             torch.cuda.current_stream(points.device).synchronize()
-            entry = self._lib.prt_closest_points_device
+            name = "prt_signed_distance_device" if signed else "prt_closest_points_device"
         else:
             def as_np(x, what, cols):
                 a = np.asarray(x)
@@ -463,19 +482,22 @@ class Renderer:
                     max_d2 = np.ascontiguousarray(max_dist * max_dist, np.float32)
             out = {f: np.empty((n, spec[f][0]) if spec[f][0] > 1 else (n,), dtype=spec[f][1]) for f in fields}
             ptr = lambda x: x.ctypes.data if x is not None else None    # noqa: E731
-            entry = self._lib.prt_closest_points
+            name = "prt_signed_distance" if signed else "prt_closest_points"
         batch = capi.PrtPointBatch(ptr(points), ptr(max_d2), n)
-        cb = capi.PrtClosestBuffers(*[ptr(out[name]) if name in out else None for name, _, _ in self.CLOSEST_POINT_FIELDS])
+        cb = capi.PrtClosestBuffers(*[ptr(out[f]) if f in out else None for f, _, _ in self.CLOSEST_POINT_FIELDS])
+        if signed:
+            cb = capi.PrtSignedBuffers(cb, *[ptr(out[f]) if f in out else None for f, _, _ in self.SIGNED_DISTANCE_FIELDS])
         counters = PrtCounters()
         flags = capi.FLAG_COUNT_VISITS if count_visits else 0
-        self._check(entry(self._ctx, C.byref(batch), C.byref(cb), flags, C.byref(counters)),
-                    "prt_closest_points_device" if is_torch else "prt_closest_points")
+        self._check(getattr(self._lib, name)(self._ctx, C.byref(batch), C.byref(cb), flags, C.byref(counters)), name)
         if "dist2" in out:
             d2 = out["dist2"]
             if is_torch:
                 out["distance"] = torch.where(d2 < 3.4028234663852886e38, d2.sqrt(), torch.full_like(d2, float("inf")))
             else:
                 out["distance"] = np.where(d2 < np.float32(3.4028234663852886e38), np.sqrt(d2), np.float32(np.inf)).astype(np.float32)
+        if "signed_distance" in out:
+            out["inside"] = out["signed_distance"] < 0
         out["counters"] = counters
         return out
 

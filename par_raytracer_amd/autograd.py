@@ -11,6 +11,9 @@ dist2, point and bw of a batch of points - a point-to-surface or chamfer loss wh
 back-propagated to the vertex positions and the points.  The gradient is that of the region walk on the triangle and in the region
 each point reported; a change of region or of the winning triangle is not modelled.
 
+`signed_distance_differentiable` puts the sign of Renderer.signed_distance on the distance of `closest_points_differentiable`: a
+signed distance whose gradient is that of the unsigned distance times the sign.  A gradient of the sign itself is not modelled.
+
 torch is imported when a function is first called: importing the package stays torch-free.
 """
 from __future__ import annotations
@@ -110,3 +113,33 @@ def closest_points_differentiable(renderer, positions, points, *, max_dist=None,
     differentiable with respect to whichever of positions and points require a gradient, group and vertex0 are not.  A miss (a
     point with a non-finite component, or nothing within max_dist) has dist2 = FLT_MAX, point and bw zeros, and zero gradient."""
     return _point_function().apply(renderer, positions, points, max_dist, bool(update_geometry))
+
+
+def signed_distance_differentiable(renderer, positions, points, *, max_dist=None, update_geometry: bool = True):
+    """The signed distance of `points` to the renderer's scene with its vertices at `positions` (Renderer.signed_distance).
+
+    positions, points, max_dist and update_geometry: as closest_points_differentiable takes them.  The signed query runs once
+    without a graph - after moving the geometry when update_geometry is set - and gives the sign and the value; dist2 comes from
+    closest_points_differentiable on the geometry already moved, and the result is sign x sqrt(dist2): the bits of
+    Renderer.signed_distance's signed_distance (FLT_MAX on a miss), differentiable with respect to whichever of positions and
+    points require a gradient.  The gradient with respect to the positions is closest_points_differentiable's.  The gradient
+    with respect to a point is that of |p - q|^2 with the returned nearest point q held fixed, sign x (p - q) / dist: the
+    distance to a nearest point does not change to first order when the nearest point moves along its feature, so the
+    derivative of q through v and w - which the region's formula carries, and which in float32 is the tangential rounding noise of
+    p - q rather than zero - is left out.  Where dist2 == 0, and on a miss, the gradient is zero (not inf or NaN)."""
+    import torch
+    with torch.no_grad():
+        if update_geometry:
+            renderer.update_geometry(positions.detach().contiguous())
+        res = renderer.signed_distance(points.detach().contiguous(), max_dist=None if max_dist is None else max_dist.detach().contiguous(),
+                                       fields=("signed_distance", "feature"))
+    signed = res["signed_distance"].detach()
+    dist2, point, _bw, group, _vertex0 = closest_points_differentiable(renderer, positions, points.detach(), max_dist=max_dist,
+                                                                       update_geometry=False)
+    live = (group >= 0) & (dist2 > 0)
+    e = torch.where(live[:, None], points - point.detach(), torch.zeros_like(points))
+    own = (e * e).sum(-1)
+    dist2 = dist2 + (own - own.detach())                 # dist2's bits and gradient to the positions, 2 (p - q) to the points
+    dist = torch.where(live, torch.where(live, dist2, torch.ones_like(dist2)).sqrt(), torch.zeros_like(dist2))
+    g = torch.where(signed < 0, -dist, dist)
+    return signed + (g - g.detach())                     # the library's bits, the gradient of sign x sqrt(dist2)

@@ -113,6 +113,10 @@ class PrtClosestBuffers(C.Structure):
     _fields_ = [("dist2", C.c_void_p), ("point", C.c_void_p), ("bw", C.c_void_p), ("vertex0", C.c_void_p), ("group", C.c_void_p)]
 
 
+class PrtSignedBuffers(C.Structure):
+    _fields_ = [("closest", PrtClosestBuffers), ("signed_dist", C.c_void_p), ("feature", C.c_void_p)]
+
+
 class PrtGeometryUpdate(C.Structure):
     _fields_ = [("positions", C.c_void_p), ("position_count", C.c_uint32), ("normals", C.c_void_p), ("normal_count", C.c_uint32),
                 ("tangents", C.c_void_p), ("spheres", C.POINTER(PrtBSphere)), ("sphere_group", C.POINTER(C.c_int32)),
@@ -165,7 +169,8 @@ PRT_SYMBOLS = ["prt_create", "prt_destroy", "prt_last_error", "prt_abi_version",
                "prt_update_geometry", "prt_update_geometry_device", "prt_multi_update_geometry", "prt_debug_check_refit",
                "prt_trace_rays_backward", "prt_trace_rays_backward_device",
                "prt_closest_points", "prt_closest_points_device",
-               "prt_closest_points_backward", "prt_closest_points_backward_device"]
+               "prt_closest_points_backward", "prt_closest_points_backward_device",
+               "prt_signed_distance", "prt_signed_distance_device"]
 # PRT_REGION_* of include/prt.h, in index order (tests/test_host_side.py's header check keeps the symbol list in step; the
 # region test compares this list with the header's enum)
 REGION_NAMES = ["round", "topup", "topup_pass", "trace_outer", "refill", "walk_pass", "node_step", "node_descend", "node_pop", "node_push", "leaf",
@@ -266,6 +271,10 @@ def hip_lib() -> C.CDLL:
             lib.prt_closest_points_backward.argtypes = [C.c_void_p, C.POINTER(PrtPointBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                                         C.POINTER(PrtClosestGrads), C.POINTER(PrtPointGrads), C.POINTER(PrtGradInfo)]
             lib.prt_closest_points_backward_device.argtypes = lib.prt_closest_points_backward.argtypes
+        if hasattr(lib, "prt_signed_distance"):        # (absent from a PRT_HIP_LIB build of an earlier commit)
+            lib.prt_signed_distance.argtypes = [C.c_void_p, C.POINTER(PrtPointBatch), C.POINTER(PrtSignedBuffers), C.c_uint32,
+                                                C.POINTER(PrtCounters)]
+            lib.prt_signed_distance_device.argtypes = lib.prt_signed_distance.argtypes
         _hip = lib
     return _hip
 

@@ -9,14 +9,16 @@
 //                    written at once.  A point whose push did not fit the LDS column goes to a list.
 //   k_closest_exact  walks the listed points again, from the start, on a full-height global stack.
 // Only the fields the caller asked for are written (a wave-uniform mask), with plain vector stores.
+// prt_signed_distance runs the same two kernels with CF_SIGNED / CF_FEATURE in the mask and the tables of dev_signed.h in the
+// arguments: closest_emit then signs the winner (signed_of_winner).  Without those bits nothing of it is read or executed.
 #pragma once
 
-#include "dev_closest.h"
+#include "dev_signed.h"
 #include "kernels_wave.h"            // lane_id
 
 namespace prt {
 
-enum { CF_DIST2 = 1, CF_POINT = 2, CF_BW = 4, CF_VERTEX0 = 8, CF_GROUP = 16 };
+enum { CF_DIST2 = 1, CF_POINT = 2, CF_BW = 4, CF_VERTEX0 = 8, CF_GROUP = 16, CF_SIGNED = 32, CF_FEATURE = 64 };
 
 struct ClosestArgs {
     const float * points;            // count x 3
@@ -35,6 +37,10 @@ struct ClosestArgs {
     unsigned int stack_lds_entries;
     int * exact_stack;               // k_closest_exact's full-height global stack columns
     unsigned int exact_stack_stride;
+    // prt_signed_distance (null / unused unless CF_SIGNED or CF_FEATURE is in the mask)
+    float * signed_dist;
+    unsigned char * feature;
+    SignedTables sign;
 };
 
 PRT_D float closest_pad(const ClosestArgs & A) {
@@ -73,6 +79,18 @@ PRT_D void closest_emit(const DevScene & sc, const ClosestArgs & A, const uint2 
         const uint2 m = hit ? leaf_map[h.tri] : make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);      // (group, vertex0)
         if (fields & CF_GROUP) A.group[i] = (int)m.x;
         if (fields & CF_VERTEX0) A.vertex0[i] = m.y;
+    }
+    if (fields & (CF_SIGNED | CF_FEATURE)) {
+        float sd = 3.402823466e+38f;
+        unsigned int feature = 255u;
+        if (hit) {
+            const float4 * tp = reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(sc.tris) + (unsigned int)h.tri * 48u);
+            const float4 r0 = tp[0], r1 = tp[1], r2 = tp[2];
+            const f3 p = mk3(A.points[3u * i], A.points[3u * i + 1u], A.points[3u * i + 2u]);
+            sd = signed_of_winner(A.sign, (unsigned int)h.tri, p, mk3(r0.x, r0.y, r0.z), mk3(r0.w, r1.x, r1.y), mk3(r1.z, r1.w, r2.x), h.t, feature);
+        }
+        if (fields & CF_SIGNED) A.signed_dist[i] = sd;
+        if (fields & CF_FEATURE) A.feature[i] = (unsigned char)feature;
     }
 }
 

@@ -33,6 +33,7 @@
 #include "kernels_query_grad.h"
 #include "kernels_closest.h"
 #include "kernels_closest_grad.h"
+#include "kernels_signed.h"
 
 using namespace prt;
 
@@ -202,6 +203,15 @@ struct prt_ctx {
     DevBuf<long long> qg_acc;             // position_count x 3 fixed-point accumulators
     DevBuf<unsigned int> qg_words;        // k_qgrad_scan's control words
     DevBuf<float> qg_io;                  // host entry point: the inputs and the requested gradients on the device
+    // signed distances (prt_signed_distance, dev_signed.h).  The adjacency table is topology: built by the first signed query
+    // after an upload from rf_idx_positions and q_tri_order.  The accumulators are geometry: k_signed_normals refills them at the
+    // first signed query after an upload or a prt_update_geometry, which both bump geom_generation.  Like q_leaf_map not in
+    // prt_scene_info.device_bytes, freed by the next upload.
+    uint64_t geom_generation = 0;         // of the records on the device
+    uint64_t sg_generation = 0;           // of the records sg_acc was filled from; 0 = never
+    DevBuf<unsigned int> sg_adj;          // leaf slot -> three position indices, three edge ids (24 B per triangle)
+    DevBuf<long long> sg_acc;             // (position_count + sg_edge_count) x 3 fixed-point accumulators (24 B each)
+    uint32_t sg_edge_count = 0;
 };
 
 namespace {
@@ -1274,6 +1284,8 @@ int query_check(prt_ctx * ctx, int mode, const prt_ray_batch * b, prt_counters *
 
 // ---- closest points (prt_closest_points, kernels_closest.h) ------------------------------------------------------------------
 
+int ensure_signed_tables(prt_ctx * ctx, ClosestArgs & A);
+
 template <bool COUNT>
 int launch_closest(prt_ctx * ctx, const ClosestArgs & A, const uint2 * leaf_map, unsigned int fields) {
     constexpr int BLOCK = 256;
@@ -1326,6 +1338,10 @@ int run_closest(prt_ctx * ctx, ClosestArgs A, unsigned int fields, bool count_vi
     HIP_TRY(ctx, hipMemsetAsync(ctx->counters.p, 0, sizeof(DevCounters), stream));
     HIP_TRY(ctx, hipMemsetAsync(A.work, 0, 4 * sizeof(unsigned int), stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev[0], stream));
+    if (fields & (CF_SIGNED | CF_FEATURE)) {                   // prt_signed_distance: a refill of the accumulators counts in render_ms
+        const int sg_rc = ensure_signed_tables(ctx, A);
+        if (sg_rc) return sg_rc;
+    }
     if (device_pad) {
         hipLaunchKernelGGL(k_closest_pad, dim3(std::min(1024u, (A.count + 255) / 256)), dim3(256), 0, stream, A);
         HIP_TRY(ctx, hipGetLastError());
@@ -1356,6 +1372,69 @@ int run_closest(prt_ctx * ctx, ClosestArgs A, unsigned int fields, bool count_vi
 
 unsigned int closest_fields(const prt_closest_buffers * o) {
     return (o->dist2 ? CF_DIST2 : 0) | (o->point ? CF_POINT : 0) | (o->bw ? CF_BW : 0) | (o->vertex0 ? CF_VERTEX0 : 0) | (o->group ? CF_GROUP : 0);
+}
+
+unsigned int signed_fields(const prt_signed_buffers * o) {
+    return closest_fields(&o->closest) | (o->signed_dist ? CF_SIGNED : 0) | (o->feature ? CF_FEATURE : 0);
+}
+
+// The tables of prt_signed_distance (dev_signed.h) into A.sign: the adjacency once per upload, the accumulators once per
+// geometry generation (k_signed_normals on the context's stream, ahead of the walk that reads them).
+int ensure_signed_tables(prt_ctx * ctx, ClosestArgs & A) {
+    const uint32_t n_tris = ctx->scene.tri_count, n_pos = ctx->rf_position_count;
+    if (ctx->q_tri_order.size() != n_tris || ctx->rf_idx_positions.size() != 3 * (size_t)n_tris) {
+        ctx->error = "prt_signed_distance: the scene's index buffer is not available";
+        return -2;
+    }
+    if (!ctx->sg_adj.p) {
+        // edge ids: the distinct unordered pairs of position indices, numbered in sorted order
+        std::vector<uint64_t> keys(3 * (size_t)n_tris);
+        for (uint32_t t = 0; t < n_tris; ++t) {
+            const uint32_t * v = &ctx->rf_idx_positions[3 * (size_t)t];
+            const uint32_t pair[3][2] = { { v[0], v[1] }, { v[0], v[2] }, { v[1], v[2] } };      // ab, ac, bc
+            for (int k = 0; k < 3; ++k)
+                keys[3 * (size_t)t + k] = (uint64_t)std::min(pair[k][0], pair[k][1]) << 32 | std::max(pair[k][0], pair[k][1]);
+        }
+        std::vector<uint64_t> edges(keys);
+        std::sort(edges.begin(), edges.end());
+        edges.erase(std::unique(edges.begin(), edges.end()), edges.end());
+        std::vector<unsigned int> adj(6 * (size_t)n_tris);
+        for (uint32_t slot = 0; slot < n_tris; ++slot) {
+            const uint32_t t = ctx->q_tri_order[slot];
+            for (int k = 0; k < 3; ++k) {
+                adj[6 * (size_t)slot + k] = ctx->rf_idx_positions[3 * (size_t)t + k];
+                adj[6 * (size_t)slot + 3 + k] = (unsigned int)(std::lower_bound(edges.begin(), edges.end(), keys[3 * (size_t)t + k]) - edges.begin());
+            }
+        }
+        hipError_t e = ctx->sg_adj.upload(adj);
+        if (e == hipSuccess) e = ctx->sg_acc.ensure(3 * ((size_t)n_pos + edges.size()));
+        if (e == hipSuccess) e = hipDeviceSynchronize();          // the upload went through the null stream
+        if (e != hipSuccess) {
+            ctx->sg_adj.release(); ctx->sg_acc.release();
+            ctx->error = std::string("prt_signed_distance: table upload: ") + hipGetErrorString(e);
+            return -10;
+        }
+        ctx->sg_edge_count = (uint32_t)edges.size();
+        ctx->sg_generation = 0;
+    }
+    A.sign.adj = ctx->sg_adj.p;
+    A.sign.acc = ctx->sg_acc.p;
+    A.sign.position_count = n_pos;
+    A.sign.edge_count = ctx->sg_edge_count;
+    if (ctx->sg_generation != ctx->geom_generation) {
+        const size_t words = 3 * ((size_t)n_pos + ctx->sg_edge_count);
+        const unsigned int cap = (unsigned int)std::max(1, ctx->cu_count) * 8u;
+        const unsigned int grid0 = (unsigned int)std::max<size_t>(1, std::min<size_t>((words + 255) / 256, cap));
+        hipLaunchKernelGGL(k_signed_normals, dim3(grid0), dim3(256), 0, ctx->stream, ctx->tris.p, n_tris, A.sign, 0);
+        HIP_TRY(ctx, hipGetLastError());
+        if (n_tris) {
+            const unsigned int grid1 = std::max(1u, std::min((n_tris + 255u) / 256u, cap));
+            hipLaunchKernelGGL(k_signed_normals, dim3(grid1), dim3(256), 0, ctx->stream, ctx->tris.p, n_tris, A.sign, 1);
+            HIP_TRY(ctx, hipGetLastError());
+        }
+        ctx->sg_generation = ctx->geom_generation;
+    }
+    return 0;
 }
 
 // The checks both entry points share; 1 = nothing to do (count 0: counters zeroed), 0 = go on, < 0 = error.
@@ -1575,6 +1654,7 @@ int update_geometry(prt_ctx * ctx, const prt_geometry_update * u, prt_update_inf
     ctx->info.device_bytes = ctx->info.device_bytes - old_sphere_bytes + (ref_spheres.empty() ? 0 : ctx->ref_spheres.bytes());
     ctx->scene_abs_max = abs_max;
     ctx->tuned.clear();                                           // a refitted tree may change which pipeline wins a try-out
+    ctx->geom_generation++;                                       // the pseudonormals of prt_signed_distance are of the old records
     if (info) { info->device_ms = ms; info->abs_max = abs_max; }
     return 0;
 }
@@ -1829,6 +1909,66 @@ int closest_backward(prt_ctx * ctx, const prt_point_batch * b, const int32_t * g
     return grad_fill_info(ctx, scan, info);
 }
 
+// prt_closest_points_device and prt_signed_distance_device after their checks: `o` holds the requested fields' device pointers.
+int closest_on_device(prt_ctx * ctx, const prt_point_batch * batch, const prt_signed_buffers & o, unsigned int fields, uint32_t flags,
+                      prt_counters * counters) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ClosestArgs A;
+    memset(&A, 0, sizeof(A));
+    A.points = batch->points; A.max_dist2 = batch->max_dist2; A.count = batch->count;
+    A.dist2 = o.closest.dist2; A.point = o.closest.point; A.bw = o.closest.bw; A.vertex0 = o.closest.vertex0; A.group = o.closest.group;
+    A.signed_dist = o.signed_dist; A.feature = o.feature;
+    A.pad_max = -1.0f;                                     // the points' extent is reduced on the device (k_closest_pad)
+    return run_closest(ctx, A, fields, (flags & PRT_FLAG_COUNT_VISITS) != 0, counters);
+}
+
+// prt_closest_points and prt_signed_distance after their checks: `o` holds the requested fields' host pointers.
+int closest_on_host(prt_ctx * ctx, const prt_point_batch * batch, const prt_signed_buffers & o, unsigned int fields, uint32_t flags,
+                    prt_counters * counters) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t n = batch->count;
+    // device copies: points, max_dist2, then the requested fields (float-sized words; the feature bytes last, rounded up)
+    const size_t f_in = 3 * n + (batch->max_dist2 ? n : 0);
+    const size_t f_out = ((fields & CF_DIST2) ? n : 0) + ((fields & CF_POINT) ? 3 * n : 0) + ((fields & CF_BW) ? 3 * n : 0) +
+                         ((fields & CF_VERTEX0) ? n : 0) + ((fields & CF_GROUP) ? n : 0) + ((fields & CF_SIGNED) ? n : 0) +
+                         ((fields & CF_FEATURE) ? (n + 3) / 4 : 0);
+    HIP_TRY(ctx, ctx->q_io.ensure(f_in + f_out));
+    float * p = ctx->q_io.p;
+    ClosestArgs A;
+    memset(&A, 0, sizeof(A));
+    A.points = p; p += 3 * n;
+    if (batch->max_dist2) { A.max_dist2 = p; p += n; }
+    if (fields & CF_DIST2) { A.dist2 = p; p += n; }
+    if (fields & CF_POINT) { A.point = p; p += 3 * n; }
+    if (fields & CF_BW) { A.bw = p; p += 3 * n; }
+    if (fields & CF_VERTEX0) { A.vertex0 = reinterpret_cast<unsigned int *>(p); p += n; }
+    if (fields & CF_GROUP) { A.group = reinterpret_cast<int *>(p); p += n; }
+    if (fields & CF_SIGNED) { A.signed_dist = p; p += n; }
+    if (fields & CF_FEATURE) { A.feature = reinterpret_cast<unsigned char *>(p); p += (n + 3) / 4; }
+    A.count = batch->count;
+    // the box pad from the points' extent, on the host (the same rule as k_closest_pad)
+    float extent = ctx->scene_abs_max;
+    for (size_t i = 0; i < n; ++i) {
+        const f3 q = ld3(batch->points + 3 * i);
+        if (std::isfinite(q.x) && std::isfinite(q.y) && std::isfinite(q.z)) extent = std::max(extent, std::max(std::max(fabsf(q.x), fabsf(q.y)), fabsf(q.z)));
+    }
+    A.pad_max = extent;
+    hipStream_t stream = ctx->stream;
+    HIP_TRY(ctx, hipMemcpyAsync(const_cast<float *>(A.points), batch->points, 12 * n, hipMemcpyHostToDevice, stream));
+    if (batch->max_dist2) HIP_TRY(ctx, hipMemcpyAsync(const_cast<float *>(A.max_dist2), batch->max_dist2, 4 * n, hipMemcpyHostToDevice, stream));
+    int rc = run_closest(ctx, A, fields, (flags & PRT_FLAG_COUNT_VISITS) != 0, counters);
+    if (rc) return rc;
+    if (fields & CF_DIST2) HIP_TRY(ctx, hipMemcpyAsync(o.closest.dist2, A.dist2, 4 * n, hipMemcpyDeviceToHost, stream));
+    if (fields & CF_POINT) HIP_TRY(ctx, hipMemcpyAsync(o.closest.point, A.point, 12 * n, hipMemcpyDeviceToHost, stream));
+    if (fields & CF_BW) HIP_TRY(ctx, hipMemcpyAsync(o.closest.bw, A.bw, 12 * n, hipMemcpyDeviceToHost, stream));
+    if (fields & CF_VERTEX0) HIP_TRY(ctx, hipMemcpyAsync(o.closest.vertex0, A.vertex0, 4 * n, hipMemcpyDeviceToHost, stream));
+    if (fields & CF_GROUP) HIP_TRY(ctx, hipMemcpyAsync(o.closest.group, A.group, 4 * n, hipMemcpyDeviceToHost, stream));
+    if (fields & CF_SIGNED) HIP_TRY(ctx, hipMemcpyAsync(o.signed_dist, A.signed_dist, 4 * n, hipMemcpyDeviceToHost, stream));
+    if (fields & CF_FEATURE) HIP_TRY(ctx, hipMemcpyAsync(o.feature, A.feature, n, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2000,6 +2140,8 @@ int prt_upload_scene(prt_ctx * ctx, const prt_scene_desc * s) {
     ctx->q_groups.clear();
     ctx->rf_table.release();
     ctx->qg_idx.release(); ctx->qg_runs.release(); ctx->qg_acc.release();
+    ctx->sg_adj.release(); ctx->sg_acc.release();
+    ctx->sg_edge_count = 0;
     ctx->rf_idx_positions.clear();
     ctx->rf_idx_normals.clear();
     ctx->rf_level_first.clear();
@@ -2255,6 +2397,7 @@ int prt_upload_scene(prt_ctx * ctx, const prt_scene_desc * s) {
     HIP_TRY(ctx, hipDeviceSynchronize());      // uploads went through the null stream; renders use the context's non-blocking streams
     ctx->has_scene = true;
     ctx->scene_epoch++;
+    ctx->geom_generation++;
     ctx->tuned.clear();
     return 0;
     PRT_API_CATCH_RC(ctx, "prt_upload_scene")
@@ -2432,13 +2575,8 @@ int prt_closest_points_device(prt_ctx * ctx, const prt_point_batch * batch, cons
     PRT_API_TRY
     const int chk = closest_check(ctx, batch, out, counters);
     if (chk) return chk > 0 ? 0 : chk;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ClosestArgs A;
-    memset(&A, 0, sizeof(A));
-    A.points = batch->points; A.max_dist2 = batch->max_dist2; A.count = batch->count;
-    A.dist2 = out->dist2; A.point = out->point; A.bw = out->bw; A.vertex0 = out->vertex0; A.group = out->group;
-    A.pad_max = -1.0f;                                     // the points' extent is reduced on the device (k_closest_pad)
-    return run_closest(ctx, A, closest_fields(out), (flags & PRT_FLAG_COUNT_VISITS) != 0, counters);
+    const prt_signed_buffers o = { *out, nullptr, nullptr };
+    return closest_on_device(ctx, batch, o, closest_fields(out), flags, counters);
     PRT_API_CATCH_RC(ctx, "prt_closest_points_device")
 }
 
@@ -2447,45 +2585,27 @@ int prt_closest_points(prt_ctx * ctx, const prt_point_batch * batch, const prt_c
     PRT_API_TRY
     const int chk = closest_check(ctx, batch, out, counters);
     if (chk) return chk > 0 ? 0 : chk;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t n = batch->count;
-    const unsigned int fields = closest_fields(out);
-    // device copies: points, max_dist2, then the requested fields (float-sized words)
-    const size_t f_in = 3 * n + (batch->max_dist2 ? n : 0);
-    const size_t f_out = ((fields & CF_DIST2) ? n : 0) + ((fields & CF_POINT) ? 3 * n : 0) + ((fields & CF_BW) ? 3 * n : 0) +
-                         ((fields & CF_VERTEX0) ? n : 0) + ((fields & CF_GROUP) ? n : 0);
-    HIP_TRY(ctx, ctx->q_io.ensure(f_in + f_out));
-    float * p = ctx->q_io.p;
-    ClosestArgs A;
-    memset(&A, 0, sizeof(A));
-    A.points = p; p += 3 * n;
-    if (batch->max_dist2) { A.max_dist2 = p; p += n; }
-    if (fields & CF_DIST2) { A.dist2 = p; p += n; }
-    if (fields & CF_POINT) { A.point = p; p += 3 * n; }
-    if (fields & CF_BW) { A.bw = p; p += 3 * n; }
-    if (fields & CF_VERTEX0) { A.vertex0 = reinterpret_cast<unsigned int *>(p); p += n; }
-    if (fields & CF_GROUP) { A.group = reinterpret_cast<int *>(p); p += n; }
-    A.count = batch->count;
-    // the box pad from the points' extent, on the host (the same rule as k_closest_pad)
-    float extent = ctx->scene_abs_max;
-    for (size_t i = 0; i < n; ++i) {
-        const f3 q = ld3(batch->points + 3 * i);
-        if (std::isfinite(q.x) && std::isfinite(q.y) && std::isfinite(q.z)) extent = std::max(extent, std::max(std::max(fabsf(q.x), fabsf(q.y)), fabsf(q.z)));
-    }
-    A.pad_max = extent;
-    hipStream_t stream = ctx->stream;
-    HIP_TRY(ctx, hipMemcpyAsync(const_cast<float *>(A.points), batch->points, 12 * n, hipMemcpyHostToDevice, stream));
-    if (batch->max_dist2) HIP_TRY(ctx, hipMemcpyAsync(const_cast<float *>(A.max_dist2), batch->max_dist2, 4 * n, hipMemcpyHostToDevice, stream));
-    int rc = run_closest(ctx, A, fields, (flags & PRT_FLAG_COUNT_VISITS) != 0, counters);
-    if (rc) return rc;
-    if (fields & CF_DIST2) HIP_TRY(ctx, hipMemcpyAsync(out->dist2, A.dist2, 4 * n, hipMemcpyDeviceToHost, stream));
-    if (fields & CF_POINT) HIP_TRY(ctx, hipMemcpyAsync(out->point, A.point, 12 * n, hipMemcpyDeviceToHost, stream));
-    if (fields & CF_BW) HIP_TRY(ctx, hipMemcpyAsync(out->bw, A.bw, 12 * n, hipMemcpyDeviceToHost, stream));
-    if (fields & CF_VERTEX0) HIP_TRY(ctx, hipMemcpyAsync(out->vertex0, A.vertex0, 4 * n, hipMemcpyDeviceToHost, stream));
-    if (fields & CF_GROUP) HIP_TRY(ctx, hipMemcpyAsync(out->group, A.group, 4 * n, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(ctx, hipStreamSynchronize(stream));
-    return 0;
+    const prt_signed_buffers o = { *out, nullptr, nullptr };
+    return closest_on_host(ctx, batch, o, closest_fields(out), flags, counters);
     PRT_API_CATCH_RC(ctx, "prt_closest_points")
+}
+
+int prt_signed_distance_device(prt_ctx * ctx, const prt_point_batch * batch, const prt_signed_buffers * out, uint32_t flags,
+                               prt_counters * counters) {
+    PRT_API_TRY
+    const int chk = closest_check(ctx, batch, out ? &out->closest : nullptr, counters);
+    if (chk) return chk > 0 ? 0 : chk;
+    return closest_on_device(ctx, batch, *out, signed_fields(out), flags, counters);
+    PRT_API_CATCH_RC(ctx, "prt_signed_distance_device")
+}
+
+int prt_signed_distance(prt_ctx * ctx, const prt_point_batch * batch, const prt_signed_buffers * out, uint32_t flags,
+                        prt_counters * counters) {
+    PRT_API_TRY
+    const int chk = closest_check(ctx, batch, out ? &out->closest : nullptr, counters);
+    if (chk) return chk > 0 ? 0 : chk;
+    return closest_on_host(ctx, batch, *out, signed_fields(out), flags, counters);
+    PRT_API_CATCH_RC(ctx, "prt_signed_distance")
 }
 
 int prt_update_geometry(prt_ctx * ctx, const prt_geometry_update * update, prt_update_info * info) {
