@@ -317,6 +317,48 @@ class Renderer:
                                                    C.byref(cam) if cam is not None else None), "prt_debug_device_kat")
         return out
 
+    def _arrays(self, first):
+        """What the batched queries do to their arrays, decided by the call's first one: numpy arrays go to the host entry points,
+        torch tensors on this context's device to the `_device` ones.  Returns (check, empty, ptr, sync, suffix):
+        check(x, what, shape, dtypes=(np.float32,)) returns x as a contiguous array or tensor of that shape (None in it: any
+        length) or raises ValueError, empty(shape, dtype) allocates an output where the inputs live, ptr(x) is its address (None
+        for None), sync() orders the library's stream behind torch's, suffix names the entry point.  dtypes are numpy's; torch
+        has no uint32 and carries those bits as int32 (vertex0: a miss, 0xFFFFFFFF, reads -1)."""
+        def fits(got, shape):
+            return len(got) == len(shape) and all(s is None or s == g for g, s in zip(got, shape))
+
+        def shown(shape):
+            return "(%s)" % ", ".join("n" if s is None else str(s) for s in shape) if None in shape else str(shape)
+        if type(first).__module__.split(".")[0] == "torch":
+            import torch
+            tdt = {np.float32: torch.float32, np.uint32: torch.int32, np.int32: torch.int32, np.uint8: torch.uint8}
+
+            def check(x, what, shape, dtypes=(np.float32,)):
+                names = " or ".join(str(d) for d in dict.fromkeys(tdt[d] for d in dtypes))
+                if not isinstance(x, torch.Tensor) or x.dtype not in [tdt[d] for d in dtypes] or not x.is_contiguous():
+                    raise ValueError("%s must be a contiguous %s torch tensor" % (what, names))
+                if x.device.type != "cuda" or (x.device.index or 0) != self.device_id:
+                    raise ValueError("%s must live on this context's device (cuda:%d)" % (what, self.device_id))
+                if not fits(tuple(x.shape), shape):
+                    raise ValueError("%s has shape %s, not %s" % (what, tuple(x.shape), shown(shape)))
+                return x
+            empty = lambda shape, dtype=np.float32: torch.empty(shape, dtype=tdt[dtype], device=first.device)    # noqa: E731
+            ptr = lambda x: x.data_ptr() if x is not None else None                                             # noqa: E731
+            # the library's stream is not ordered against torch's: whatever torch still has queued on the inputs must be done
+            sync = lambda: torch.cuda.current_stream(first.device).synchronize()                                # noqa: E731
+            return check, empty, ptr, sync, "_device"
+
+        def check(x, what, shape, dtypes=(np.float32,)):
+            a = np.asarray(x)
+            if a.dtype not in dtypes or not a.flags["C_CONTIGUOUS"]:
+                raise ValueError("%s must be a contiguous %s array" % (what, " or ".join(np.dtype(d).name for d in dtypes)))
+            if not fits(a.shape, shape):
+                raise ValueError("%s has shape %s, not %s" % (what, a.shape, shown(shape)))
+            return a
+        empty = lambda shape, dtype=np.float32: np.empty(shape, dtype=dtype)    # noqa: E731
+        ptr = lambda x: x.ctypes.data if x is not None else None                # noqa: E731
+        return check, empty, ptr, lambda: None, ""
+
     # (name, components per ray, numpy dtype) of prt_hit_buffers' fields
     HIT_FIELDS = (("t", 1, np.float32), ("bw", 3, np.float32), ("vertex0", 1, np.uint32), ("group", 1, np.int32),
                   ("position", 3, np.float32), ("normal", 3, np.float32), ("occluded", 1, np.uint8))
@@ -342,61 +384,21 @@ class Renderer:
                 raise ValueError("unknown hit field %r" % (f,))
             if (f == "occluded") != (m == capi.QUERY_OCCLUDED):
                 raise ValueError("field %r is not written in mode %r" % (f, mode))
-        is_torch = type(origins).__module__.split(".")[0] == "torch"
-        if is_torch:
-            import torch
-
-            def check(x, what, cols):
-                if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or not x.is_contiguous():
-                    raise ValueError("%s must be a contiguous float32 torch tensor" % what)
-                if x.device.type != "cuda" or (x.device.index or 0) != self.device_id:
-                    raise ValueError("%s must live on this context's device (cuda:%d)" % (what, self.device_id))
-                if (cols and (x.dim() != 2 or x.shape[1] != 3)) or (not cols and x.dim() != 1):
-                    raise ValueError("%s has shape %s" % (what, tuple(x.shape)))
-            check(origins, "origins", True)
-            check(directions, "directions", True)
-            n = origins.shape[0]
-            if directions.shape[0] != n:
-                raise ValueError("origins and directions differ in length")
-            if tmax is not None:
-                check(tmax, "tmax", False)
-                if tmax.shape[0] != n:
-                    raise ValueError("tmax has %d entries for %d rays" % (tmax.shape[0], n))
-            # torch has no uint32: vertex0 comes back as int32 holding the same bits (a miss, 0xFFFFFFFF, reads -1)
-            tdt = {np.float32: torch.float32, np.uint32: torch.int32, np.int32: torch.int32, np.uint8: torch.uint8}
-            out = {f: torch.empty((n, spec[f][0]) if spec[f][0] > 1 else (n,), dtype=tdt[spec[f][1]], device=origins.device)
-                   for f in fields}
-            ptr = lambda x: x.data_ptr() if x is not None else None    # noqa: E731
-            # the library's stream is not ordered against torch's: whatever torch still has queued on the inputs must be done
-            torch.cuda.current_stream(origins.device).synchronize()
-            entry = self._lib.prt_trace_rays_device
-        else:
-            def as_np(x, what, cols):
-                a = np.asarray(x)
-                if a.dtype != np.float32 or not a.flags["C_CONTIGUOUS"]:
-                    raise ValueError("%s must be a contiguous float32 array" % what)
-                if (cols and (a.ndim != 2 or a.shape[1] != 3)) or (not cols and a.ndim != 1):
-                    raise ValueError("%s has shape %s" % (what, a.shape))
-                return a
-            origins = as_np(origins, "origins", True)
-            directions = as_np(directions, "directions", True)
-            n = origins.shape[0]
-            if directions.shape[0] != n:
-                raise ValueError("origins and directions differ in length")
-            if tmax is not None:
-                tmax = as_np(tmax, "tmax", False)
-                if tmax.shape[0] != n:
-                    raise ValueError("tmax has %d entries for %d rays" % (tmax.shape[0], n))
-            out = {f: np.empty((n, spec[f][0]) if spec[f][0] > 1 else (n,), dtype=spec[f][1]) for f in fields}
-            ptr = lambda x: x.ctypes.data if x is not None else None    # noqa: E731
-            entry = self._lib.prt_trace_rays
+        check, empty, ptr, sync, suffix = self._arrays(origins)
+        origins = check(origins, "origins", (None, 3))
+        n = int(origins.shape[0])
+        directions = check(directions, "directions", (n, 3))
+        if tmax is not None:
+            tmax = check(tmax, "tmax", (n,))
+        out = {f: empty((n, spec[f][0]) if spec[f][0] > 1 else (n,), spec[f][1]) for f in fields}
+        sync()
         batch = capi.PrtRayBatch(ptr(origins), ptr(directions), ptr(tmax) if m == capi.QUERY_OCCLUDED else None, n,
                                  float(ray_bias))
         hb = capi.PrtHitBuffers(*[ptr(out[name]) if name in out else None for name, _, _ in self.HIT_FIELDS])
         counters = PrtCounters()
         flags = capi.FLAG_COUNT_VISITS if count_visits else 0
-        self._check(entry(self._ctx, m, C.byref(batch), C.byref(hb), flags, C.byref(counters)),
-                    "prt_trace_rays_device" if is_torch else "prt_trace_rays")
+        name = "prt_trace_rays" + suffix
+        self._check(getattr(self._lib, name)(self._ctx, m, C.byref(batch), C.byref(hb), flags, C.byref(counters)), name)
         out["counters"] = counters
         return out
 
@@ -436,53 +438,20 @@ class Renderer:
         for f in fields:
             if f not in spec:
                 raise ValueError("unknown %s field %r" % ("signed-distance" if signed else "closest-point", f))
-        is_torch = type(points).__module__.split(".")[0] == "torch"
-        if is_torch:
-            import torch
-
-            def check(x, what, cols):
-                if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or not x.is_contiguous():
-                    raise ValueError("%s must be a contiguous float32 torch tensor" % what)
-                if x.device.type != "cuda" or (x.device.index or 0) != self.device_id:
-                    raise ValueError("%s must live on this context's device (cuda:%d)" % (what, self.device_id))
-                if (cols and (x.dim() != 2 or x.shape[1] != 3)) or (not cols and x.dim() != 1):
-                    raise ValueError("%s has shape %s" % (what, tuple(x.shape)))
-            check(points, "points", True)
-            n = points.shape[0]
-            max_d2 = None
-            if max_dist is not None:
-                check(max_dist, "max_dist", False)
-                if max_dist.shape[0] != n:
-                    raise ValueError("max_dist has %d entries for %d points" % (max_dist.shape[0], n))
+        check, empty, ptr, sync, suffix = self._arrays(points)
+        points = check(points, "points", (None, 3))
+        n = int(points.shape[0])
+        max_d2 = None
+        if max_dist is not None:
+            max_dist = check(max_dist, "max_dist", (n,))
+            if suffix:
                 max_d2 = (max_dist * max_dist).contiguous()
-            tdt = {np.float32: torch.float32, np.uint32: torch.int32, np.int32: torch.int32,     # vertex0: int32 with the same bits
-                   np.uint8: torch.uint8}
-            out = {f: torch.empty((n, spec[f][0]) if spec[f][0] > 1 else (n,), dtype=tdt[spec[f][1]], device=points.device)
-                   for f in fields}
-            ptr = lambda x: x.data_ptr() if x is not None else None    # noqa: E731
-            # the library's stream is not ordered against torch's: whatever torch still has queued on the inputs must be done
-            torch.cuda.current_stream(points.device).synchronize()
-            name = "prt_signed_distance_device" if signed else "prt_closest_points_device"
-        else:
-            def as_np(x, what, cols):
-                a = np.asarray(x)
-                if a.dtype != np.float32 or not a.flags["C_CONTIGUOUS"]:
-                    raise ValueError("%s must be a contiguous float32 array" % what)
-                if (cols and (a.ndim != 2 or a.shape[1] != 3)) or (not cols and a.ndim != 1):
-                    raise ValueError("%s has shape %s" % (what, a.shape))
-                return a
-            points = as_np(points, "points", True)
-            n = points.shape[0]
-            max_d2 = None
-            if max_dist is not None:
-                max_dist = as_np(max_dist, "max_dist", False)
-                if max_dist.shape[0] != n:
-                    raise ValueError("max_dist has %d entries for %d points" % (max_dist.shape[0], n))
+            else:
                 with np.errstate(over="ignore"):
                     max_d2 = np.ascontiguousarray(max_dist * max_dist, np.float32)
-            out = {f: np.empty((n, spec[f][0]) if spec[f][0] > 1 else (n,), dtype=spec[f][1]) for f in fields}
-            ptr = lambda x: x.ctypes.data if x is not None else None    # noqa: E731
-            name = "prt_signed_distance" if signed else "prt_closest_points"
+        out = {f: empty((n, spec[f][0]) if spec[f][0] > 1 else (n,), spec[f][1]) for f in fields}
+        sync()
+        name = ("prt_signed_distance" if signed else "prt_closest_points") + suffix
         batch = capi.PrtPointBatch(ptr(points), ptr(max_d2), n)
         cb = capi.PrtClosestBuffers(*[ptr(out[f]) if f in out else None for f, _, _ in self.CLOSEST_POINT_FIELDS])
         if signed:
@@ -492,7 +461,8 @@ class Renderer:
         self._check(getattr(self._lib, name)(self._ctx, C.byref(batch), C.byref(cb), flags, C.byref(counters)), name)
         if "dist2" in out:
             d2 = out["dist2"]
-            if is_torch:
+            if suffix:
+                import torch
                 out["distance"] = torch.where(d2 < 3.4028234663852886e38, d2.sqrt(), torch.full_like(d2, float("inf")))
             else:
                 out["distance"] = np.where(d2 < np.float32(3.4028234663852886e38), np.sqrt(d2), np.float32(np.inf)).astype(np.float32)
@@ -515,34 +485,8 @@ class Renderer:
         for w in want:
             if w not in self.GRAD_NAMES:
                 raise ValueError("unknown gradient %r" % (w,))
-        is_torch = type(origins).__module__.split(".")[0] == "torch"
-        if is_torch:
-            import torch
-
-            def check(x, what, shape, dtypes=(torch.float32,)):
-                if not isinstance(x, torch.Tensor) or x.dtype not in dtypes or not x.is_contiguous():
-                    raise ValueError("%s must be a contiguous %s torch tensor" % (what, " or ".join(str(d) for d in dtypes)))
-                if x.device.type != "cuda" or (x.device.index or 0) != self.device_id:
-                    raise ValueError("%s must live on this context's device (cuda:%d)" % (what, self.device_id))
-                if tuple(x.shape) != shape:
-                    raise ValueError("%s has shape %s, not %s" % (what, tuple(x.shape), shape))
-                return x
-            ints = (torch.int32,)
-            empty = lambda shape: torch.empty(shape, dtype=torch.float32, device=origins.device)     # noqa: E731
-            ptr = lambda x: x.data_ptr() if x is not None else None                                 # noqa: E731
-            entry, name = self._lib.prt_trace_rays_backward_device, "prt_trace_rays_backward_device"
-        else:
-            def check(x, what, shape, dtypes=(np.float32,)):
-                a = np.asarray(x)
-                if a.dtype not in dtypes or not a.flags["C_CONTIGUOUS"]:
-                    raise ValueError("%s must be a contiguous %s array" % (what, " or ".join(np.dtype(d).name for d in dtypes)))
-                if a.shape != shape:
-                    raise ValueError("%s has shape %s, not %s" % (what, a.shape, shape))
-                return a
-            ints = (np.int32, np.uint32)
-            empty = lambda shape: np.empty(shape, dtype=np.float32)                                  # noqa: E731
-            ptr = lambda x: x.ctypes.data if x is not None else None                                 # noqa: E731
-            entry, name = self._lib.prt_trace_rays_backward, "prt_trace_rays_backward"
+        check, empty, ptr, sync, suffix = self._arrays(origins)
+        name = "prt_trace_rays_backward" + suffix
         if getattr(origins, "ndim", 0) != 2:
             raise ValueError("origins must have shape (n, 3)")
         n = int(origins.shape[0])
@@ -551,22 +495,20 @@ class Renderer:
         n_pos = int(positions.shape[0])
         origins = check(origins, "origins", (n, 3))
         directions = check(directions, "directions", (n, 3))
-        group = check(group, "group", (n,), ints[:1])
-        vertex0 = check(vertex0, "vertex0", (n,), ints)
+        group = check(group, "group", (n,), (np.int32,))
+        vertex0 = check(vertex0, "vertex0", (n,), (np.int32, np.uint32))
         positions = check(positions, "positions", (n_pos, 3))
         gouts = [None if g is None else check(g, what, shape) for g, what, shape in
                  ((grad_t, "grad_t", (n,)), (grad_bw, "grad_bw", (n, 3)), (grad_position, "grad_position", (n, 3)),
                   (grad_normal, "grad_normal", (n, 3)))]
         out = {w: empty((n_pos, 3) if w == "positions" else (n, 3)) for w in want}
-        if is_torch:
-            # the library's stream is not ordered against torch's: whatever torch still has queued on the inputs must be done
-            torch.cuda.current_stream(origins.device).synchronize()
+        sync()
         batch = capi.PrtRayBatch(ptr(origins), ptr(directions), None, n, float(ray_bias))
         go = capi.PrtHitGrads(*[ptr(g) for g in gouts])
         gi = capi.PrtQueryGrads(*[ptr(out.get(w)) for w in self.GRAD_NAMES])
         info = PrtGradInfo()
-        self._check(entry(self._ctx, C.byref(batch), ptr(group), ptr(vertex0), ptr(positions), n_pos, C.byref(go), C.byref(gi),
-                          C.byref(info)), name)
+        self._check(getattr(self._lib, name)(self._ctx, C.byref(batch), ptr(group), ptr(vertex0), ptr(positions), n_pos, C.byref(go),
+                                             C.byref(gi), C.byref(info)), name)
         out["info"] = info
         return out
 
@@ -584,34 +526,8 @@ class Renderer:
         for w in want:
             if w not in self.POINT_GRAD_NAMES:
                 raise ValueError("unknown gradient %r" % (w,))
-        is_torch = type(points).__module__.split(".")[0] == "torch"
-        if is_torch:
-            import torch
-
-            def check(x, what, shape, dtypes=(torch.float32,)):
-                if not isinstance(x, torch.Tensor) or x.dtype not in dtypes or not x.is_contiguous():
-                    raise ValueError("%s must be a contiguous %s torch tensor" % (what, " or ".join(str(d) for d in dtypes)))
-                if x.device.type != "cuda" or (x.device.index or 0) != self.device_id:
-                    raise ValueError("%s must live on this context's device (cuda:%d)" % (what, self.device_id))
-                if tuple(x.shape) != shape:
-                    raise ValueError("%s has shape %s, not %s" % (what, tuple(x.shape), shape))
-                return x
-            ints = (torch.int32,)
-            empty = lambda shape: torch.empty(shape, dtype=torch.float32, device=points.device)     # noqa: E731
-            ptr = lambda x: x.data_ptr() if x is not None else None                                # noqa: E731
-            entry, name = self._lib.prt_closest_points_backward_device, "prt_closest_points_backward_device"
-        else:
-            def check(x, what, shape, dtypes=(np.float32,)):
-                a = np.asarray(x)
-                if a.dtype not in dtypes or not a.flags["C_CONTIGUOUS"]:
-                    raise ValueError("%s must be a contiguous %s array" % (what, " or ".join(np.dtype(d).name for d in dtypes)))
-                if a.shape != shape:
-                    raise ValueError("%s has shape %s, not %s" % (what, a.shape, shape))
-                return a
-            ints = (np.int32, np.uint32)
-            empty = lambda shape: np.empty(shape, dtype=np.float32)                                  # noqa: E731
-            ptr = lambda x: x.ctypes.data if x is not None else None                                 # noqa: E731
-            entry, name = self._lib.prt_closest_points_backward, "prt_closest_points_backward"
+        check, empty, ptr, sync, suffix = self._arrays(points)
+        name = "prt_closest_points_backward" + suffix
         if getattr(points, "ndim", 0) != 2:
             raise ValueError("points must have shape (n, 3)")
         n = int(points.shape[0])
@@ -619,21 +535,19 @@ class Renderer:
             raise ValueError("positions must have shape (P, 3)")
         n_pos = int(positions.shape[0])
         points = check(points, "points", (n, 3))
-        group = check(group, "group", (n,), ints[:1])
-        vertex0 = check(vertex0, "vertex0", (n,), ints)
+        group = check(group, "group", (n,), (np.int32,))
+        vertex0 = check(vertex0, "vertex0", (n,), (np.int32, np.uint32))
         positions = check(positions, "positions", (n_pos, 3))
         gouts = [None if g is None else check(g, what, shape) for g, what, shape in
                  ((grad_dist2, "grad_dist2", (n,)), (grad_point, "grad_point", (n, 3)), (grad_bw, "grad_bw", (n, 3)))]
         out = {w: empty((n_pos, 3) if w == "positions" else (n, 3)) for w in want}
-        if is_torch:
-            # the library's stream is not ordered against torch's: whatever torch still has queued on the inputs must be done
-            torch.cuda.current_stream(points.device).synchronize()
+        sync()
         batch = capi.PrtPointBatch(ptr(points), None, n)
         go = capi.PrtClosestGrads(*[ptr(g) for g in gouts])
         gi = capi.PrtPointGrads(*[ptr(out.get(w)) for w in self.POINT_GRAD_NAMES])
         info = PrtGradInfo()
-        self._check(entry(self._ctx, C.byref(batch), ptr(group), ptr(vertex0), ptr(positions), n_pos, C.byref(go), C.byref(gi),
-                          C.byref(info)), name)
+        self._check(getattr(self._lib, name)(self._ctx, C.byref(batch), ptr(group), ptr(vertex0), ptr(positions), n_pos, C.byref(go),
+                                             C.byref(gi), C.byref(info)), name)
         out["info"] = info
         return out
 

@@ -285,6 +285,59 @@ int build_spec_table(prt_ctx * ctx, unsigned int spec_samples) {
     return 0;
 }
 
+// ---- the persistent traversal grid, written once: k_trace (wavefront pipeline), k_query, k_closest ----------------------------
+
+// Blocks of `kernel` (`block` threads, `lds` bytes of dynamic LDS) resident on a compute unit, 8 at the most; `fallback` where the
+// runtime cannot say.
+template <typename Kernel>
+int resident_blocks(Kernel kernel, int block, size_t lds, int fallback) {
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, lds) != hipSuccess || per_cu < 1) per_cu = fallback;
+    return std::min(per_cu, 8);
+}
+
+// Blocks per compute unit, the lane-refill thresholds and the smallest chunk of a persistent grid, after the options' clamps
+// (tuning knobs for experiments, not part of the ABI).  k_pool takes its keep_min and node_min from here too.
+struct TraceRule {
+    int per_cu, keep_min, node_min;
+    unsigned int chunk_min;
+};
+
+TraceRule trace_rule(const PrtOptions & opt, int resident) {
+    TraceRule r = { resident, 40, 32, 128u };
+    if (opt.trace_blocks_per_cu >= 0) r.per_cu = std::max(1, std::min(resident, (int)opt.trace_blocks_per_cu));
+    if (opt.keep_min >= 0) r.keep_min = std::max(1, std::min(64, (int)opt.keep_min));
+    if (opt.node_min >= 0) r.node_min = std::max(0, std::min(64, (int)opt.node_min));
+    if (opt.chunk_min >= 0) r.chunk_min = (unsigned int)std::max(64ll, std::min(512ll, opt.chunk_min));
+    return r;
+}
+
+// The rule of a kernel with 256-thread blocks: as many blocks as are resident.
+template <typename Kernel>
+TraceRule trace_rule(const prt_ctx * ctx, Kernel kernel, size_t lds) {
+    return trace_rule(ctx->opt, resident_blocks(kernel, 256, lds, 2));
+}
+
+struct TraceGrid { unsigned int grid, chunk; };
+
+// The grid for n_rays under `per_cu` blocks of 256 per compute unit, and the rays reserved per head atomic: ~1/8 of a wave's
+// fair share, whole waves, chunk_min..512.
+TraceGrid trace_grid(const prt_ctx * ctx, int per_cu, unsigned int chunk_min, unsigned int n_rays) {
+    constexpr unsigned int BLOCK = 256;
+    TraceGrid g;
+    g.grid = std::max(1u, std::min((unsigned int)per_cu * (unsigned int)ctx->cu_count, (n_rays + BLOCK - 1) / BLOCK));
+    g.chunk = n_rays / (g.grid * (BLOCK / 64) * 8u);
+    g.chunk = std::max(chunk_min, std::min(512u, (g.chunk / 64u) * 64u));
+    return g;
+}
+
+// The LDS stack column's entries per lane (dev_trace.h LdsStack); option STACK_CAP is a test hook that forces the spill area into use.
+unsigned int lds_stack_entries(const prt_ctx * ctx) {
+    unsigned int stack_cap = STACK_LDS_CAP_DEFAULT;
+    if (ctx->opt.stack_cap >= 0) stack_cap = (unsigned int)std::max(2ll, std::min(40ll, ctx->opt.stack_cap));
+    return std::min(ctx->stack_bound, stack_cap);
+}
+
 struct PixelSet {
     uint32_t n_pixels;
     uint32_t first_pixel;                      // contiguous range when nranks <= 1
@@ -359,8 +412,8 @@ int chain_setup(prt_ctx * ctx, Chain & c, int index, const DevParams & P, bool r
 }
 
 struct WaveTuning {
-    int per_cu, keep_min, node_min, multi_light, shade_block;
-    unsigned int chunk_min;
+    TraceRule rule;                            // per_cu: what a chain's k_trace may take (render_wavefront)
+    int multi_light, shade_block;
     bool ring, count_visits;
     size_t lds;
 };
@@ -373,18 +426,14 @@ int chain_issue_round(prt_ctx * ctx, Chain & c, const WaveTuning & t) {
     c.rays += (unsigned long long)c.n_closest + c.n_shadow;
     HIP_TRY(ctx, hipMemsetAsync(B.counts, 0, 32, stream));
     const unsigned int total = c.n_closest + c.n_shadow;
-    const unsigned int max_blocks = (unsigned int)t.per_cu * (unsigned int)ctx->cu_count;
-    const unsigned int grid = std::max(1u, std::min(max_blocks, (total + BLOCK - 1) / BLOCK));
-    // rays reserved per head atomic: ~1/8 of a wave's fair share, whole waves, 64..512
-    unsigned int chunk = total / (grid * (BLOCK / 64) * 8u);
-    chunk = std::max(t.chunk_min, std::min(512u, (chunk / 64u) * 64u));
+    const TraceGrid g = trace_grid(ctx, t.rule.per_cu, t.rule.chunk_min, total);
     HIP_TRY(ctx, hipEventRecord(c.ws->ev_t0, stream));
     if (t.count_visits)
-        hipLaunchKernelGGL((k_trace<BLOCK, true>), dim3(grid), dim3(BLOCK), t.lds, stream, ctx->scene, c.P, B, c.cur, c.n_closest, c.n_shadow,
-                           t.keep_min, t.node_min, chunk, t.multi_light, ctx->counters.p);
+        hipLaunchKernelGGL((k_trace<BLOCK, true>), dim3(g.grid), dim3(BLOCK), t.lds, stream, ctx->scene, c.P, B, c.cur, c.n_closest, c.n_shadow,
+                           t.rule.keep_min, t.rule.node_min, g.chunk, t.multi_light, ctx->counters.p);
     else
-        hipLaunchKernelGGL((k_trace<BLOCK, false>), dim3(grid), dim3(BLOCK), t.lds, stream, ctx->scene, c.P, B, c.cur, c.n_closest, c.n_shadow,
-                           t.keep_min, t.node_min, chunk, t.multi_light, ctx->counters.p);
+        hipLaunchKernelGGL((k_trace<BLOCK, false>), dim3(g.grid), dim3(BLOCK), t.lds, stream, ctx->scene, c.P, B, c.cur, c.n_closest, c.n_shadow,
+                           t.rule.keep_min, t.rule.node_min, g.chunk, t.multi_light, ctx->counters.p);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(c.ws->ev_t1, stream));
     if (c.round == 0) HIP_TRY(ctx, hipEventRecord(c.ws->ev_first, stream));
@@ -445,28 +494,15 @@ int render_wavefront(prt_ctx * ctx, const DevCamera & cam, const DevParams & P, 
     t.lds = lds;
     t.ring = ring;
     t.count_visits = count_visits;
-    // persistent grid: as many blocks as are resident
-    int per_cu = 0;
-    hipError_t oe = count_visits ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_trace<BLOCK, true>, BLOCK, lds)
-                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_trace<BLOCK, false>, BLOCK, lds);
-    if (oe != hipSuccess || per_cu < 1) per_cu = 2;
-    per_cu = std::min(per_cu, 8);
-    t.keep_min = 40;
-    t.node_min = 32;
-    t.chunk_min = 128;
+    t.rule = count_visits ? trace_rule(ctx, k_trace<BLOCK, true>, lds) : trace_rule(ctx, k_trace<BLOCK, false>, lds);
     const PrtOptions & opt = ctx->opt;
-    if (opt.chunk_min >= 0) t.chunk_min = (unsigned int)std::max(64ll, std::min(512ll, opt.chunk_min));
     int n_chains = n_samples >= (1u << 23) ? 2 : 1;          // measured +2 % on 16.6 M samples; small frames: not worth the extra launches
-    int split_per_cu = 4;
-    // tuning knobs for experiments (not part of the ABI)
-    if (opt.trace_blocks_per_cu >= 0) { per_cu = std::max(1, std::min(per_cu, (int)opt.trace_blocks_per_cu)); split_per_cu = per_cu; }
-    if (opt.keep_min >= 0) t.keep_min = std::max(1, std::min(64, (int)opt.keep_min));
-    if (opt.node_min >= 0) t.node_min = std::max(0, std::min(64, (int)opt.node_min));
+    const int split_per_cu = opt.trace_blocks_per_cu >= 0 ? t.rule.per_cu : 4;
     if (opt.chains >= 0) n_chains = std::max(1, std::min((int)PRT_MAX_CHAINS, (int)opt.chains));
     // chains start on a pixel and a wave boundary
     const unsigned int unit = P.spp * 64u;
     while (n_chains > 1 && (unsigned long long)unit * n_chains > n_samples) n_chains--;
-    t.per_cu = n_chains >= 2 ? std::min(per_cu, split_per_cu) : per_cu;
+    if (n_chains >= 2) t.rule.per_cu = std::min(t.rule.per_cu, split_per_cu);
     t.shade_block = n_chains >= 2 ? 256 : 1024;
     if (opt.shade_block >= 0) t.shade_block = opt.shade_block == 256 ? 256 : 1024;
     t.multi_light = ctx->scene.light_count > 1 ? 1 : 0;
@@ -554,12 +590,12 @@ int launch_pool(prt_ctx * ctx, bool count, const DevCamera & cam, DevParams P, u
     // shards 1.5 - 3.5 % -; OFF for the adaptive mode, whose short rounds lose 11 % to the four waves waiting for each other at
     // every phase boundary, and for deep bounce trees (C5: 886 -> 949 ms; that variant spills 59 dwords shared, 31 private).
     const bool shared = !exact_only && (opt.pool_shared >= 0 ? opt.pool_shared != 0 : (PRT_POOL_SHARED_DEFAULT != 0 && !ADAPT && !TEX && RINGMEM == 0));
-    hipError_t oe = exact_only ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pool<BLOCK, WAVES, LDSTAB, RING, false, TEX, ADAPT, RINGMEM, true, false>, BLOCK, lds)
-                  : shared     ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pool<BLOCK, WAVES, LDSTAB, RING, false, TEX, ADAPT, RINGMEM, false, true>, BLOCK, lds)
-                  : count      ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pool<BLOCK, WAVES, LDSTAB, RING, true, TEX, ADAPT, RINGMEM, false, false>, BLOCK, lds)
-                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pool<BLOCK, WAVES, LDSTAB, RING, false, TEX, ADAPT, RINGMEM, false, false>, BLOCK, lds);
-    if (oe != hipSuccess || per_cu < 1) per_cu = 1;
-    per_cu = std::min(per_cu, 8);
+    void (* const sized_as)(const PoolArgs *, DevCounters *) =
+        exact_only ? k_pool<BLOCK, WAVES, LDSTAB, RING, false, TEX, ADAPT, RINGMEM, true, false>
+        : shared   ? k_pool<BLOCK, WAVES, LDSTAB, RING, false, TEX, ADAPT, RINGMEM, false, true>
+        : count    ? k_pool<BLOCK, WAVES, LDSTAB, RING, true, TEX, ADAPT, RINGMEM, false, false>
+                   : k_pool<BLOCK, WAVES, LDSTAB, RING, false, TEX, ADAPT, RINGMEM, false, false>;
+    per_cu = resident_blocks(sized_as, BLOCK, lds, 1);
     if (opt.pool_blocks_per_cu >= 0) per_cu = std::max(1, std::min(per_cu, (int)opt.pool_blocks_per_cu));
     if (opt.debug_util) fprintf(stderr, "[prt] k_pool<%d,%d,%d>: %d blocks per CU\n", BLOCK, WAVES, (int)LDSTAB, per_cu);
     const unsigned int max_blocks = (unsigned int)per_cu * (unsigned int)ctx->cu_count;
@@ -673,9 +709,7 @@ int launch_pool(prt_ctx * ctx, bool count, const DevCamera & cam, DevParams P, u
     Q.topup_max = topup_max == 0xFFFFFFFFu ? topup_max : topup_max * (shared ? (unsigned int)(BLOCK / 64) : 1u);
     Q.topup_min = ADAPT ? std::max(64u, cap / 2u) : std::max(64u, cap / 4u);
     if (opt.pool_topup >= 0) Q.topup_min = (unsigned int)std::max(1ll, std::min((long long)cap, opt.pool_topup * (shared ? BLOCK / 64 : 1)));   // the option counts per wave
-    int keep_min = 40, node_min = 32;
-    if (opt.keep_min >= 0) keep_min = std::max(1, std::min(64, (int)opt.keep_min));
-    if (opt.node_min >= 0) node_min = std::max(0, std::min(64, (int)opt.node_min));
+    const TraceRule lanes = trace_rule(opt, per_cu);         // for its two lane thresholds; the pool's grid has options of its own
     const int multi_light = ctx->scene.light_count > 1 ? 1 : 0;
     PoolArgs A;
     memset(&A, 0, sizeof(A));
@@ -684,8 +718,8 @@ int launch_pool(prt_ctx * ctx, bool count, const DevCamera & cam, DevParams P, u
     A.P = P;
     A.B = B;
     A.Q = Q;
-    A.keep_min = keep_min;
-    A.node_min = node_min;
+    A.keep_min = lanes.keep_min;
+    A.node_min = lanes.node_min;
     A.node_frac = 4;
     if (opt.node_frac >= 0) A.node_frac = std::max(0, std::min(8, (int)opt.node_frac));
     A.multi_light = multi_light;
@@ -946,9 +980,7 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
     // - 3 pushes per 4-wide level are possible, nothing real comes close - lives in a per-lane global column behind it
     // (dev_trace.h LdsStack).
     constexpr int BLOCK = 256;
-    unsigned int stack_cap = STACK_LDS_CAP_DEFAULT;
-    if (opt.stack_cap >= 0) stack_cap = (unsigned int)std::max(2ll, std::min(40ll, opt.stack_cap));   // test hook: force the spill area into use
-    const unsigned int stack_entries = std::min(ctx->stack_bound, stack_cap);
+    const unsigned int stack_entries = lds_stack_entries(ctx);
     const size_t lds = stack_dwords(stack_entries, BLOCK) * sizeof(int);
     P.stack_lds_entries = stack_entries;
     P.stack_spill = nullptr;
@@ -1146,34 +1178,56 @@ int render_pixels(prt_ctx * ctx, const prt_camera * cam_in, const prt_params * p
     return -7;
 }
 
-// ---- ray queries (prt_trace_rays, kernels_query.h) ---------------------------------------------------------------------------
+// ---- batched queries: what the five of them share -------------------------------------------------------------------------------
 
-template <int MODE, bool COUNT>
-int launch_query(prt_ctx * ctx, const QueryArgs & A, const uint2 * leaf_map, unsigned int fields) {
-    constexpr int BLOCK = 256;
-    const size_t lds = stack_dwords(A.stack_lds_entries, BLOCK) * sizeof(int);
-    // persistent grid of resident blocks, chunks and lane-refill thresholds as the wavefront pipeline's k_trace
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_query<BLOCK, MODE, COUNT>, BLOCK, lds) != hipSuccess || per_cu < 1) per_cu = 2;
-    per_cu = std::min(per_cu, 8);
-    const PrtOptions & opt = ctx->opt;
-    if (opt.trace_blocks_per_cu >= 0) per_cu = std::max(1, std::min(per_cu, (int)opt.trace_blocks_per_cu));
-    int keep_min = 40, node_min = 32;
-    if (opt.keep_min >= 0) keep_min = std::max(1, std::min(64, (int)opt.keep_min));
-    if (opt.node_min >= 0) node_min = std::max(0, std::min(64, (int)opt.node_min));
-    unsigned int chunk_min = 128;
-    if (opt.chunk_min >= 0) chunk_min = (unsigned int)std::max(64ll, std::min(512ll, opt.chunk_min));
-    const unsigned int grid = std::max(1u, std::min((unsigned int)per_cu * (unsigned int)ctx->cu_count, (A.count + BLOCK - 1) / BLOCK));
-    unsigned int chunk = A.count / (grid * (BLOCK / 64) * 8u);
-    chunk = std::max(chunk_min, std::min(512u, (chunk / 64u) * 64u));
-    hipLaunchKernelGGL((k_query<BLOCK, MODE, COUNT>), dim3(grid), dim3(BLOCK), lds, ctx->stream, ctx->scene, A, leaf_map, fields,
-                       keep_min, node_min, chunk, ctx->counters.p);
-    HIP_TRY(ctx, hipGetLastError());
-    constexpr unsigned int SLOW_BLOCKS = 64;               // A.exact_stack holds SLOW_BLOCKS * 256 columns
-    hipLaunchKernelGGL((k_query_exact<MODE, COUNT>), dim3(SLOW_BLOCKS), dim3(256), 0, ctx->stream, ctx->scene, A, leaf_map, fields, ctx->counters.p);
-    HIP_TRY(ctx, hipGetLastError());
-    return 0;
-}
+// The arrays of a call whose arrays are host pointers.  Each is described once - the pointer in the kernel's argument struct (it
+// holds the caller's host pointer on entry), its bytes, whether it is wanted and which way it travels - and carve(), upload() and
+// download() loop over the description.  The device copies lie in one slab of 4-byte words, in the order of the description.
+struct StageList {
+    struct Field {
+        void * slot;                       // the address of the pointer: the caller's array before carve(), the device copy after it
+        void * host;
+        size_t bytes;
+        bool on, out, in_slab;
+    };
+    Field f[16];                           // (the ray gradients' twelve arrays are the most a call has)
+    size_t n = 0;
+    template <typename T>
+    void in(T ** slot, size_t bytes) { f[n++] = { (void *)slot, nullptr, bytes, *slot != nullptr, false, true }; }
+    // in_slab = false: device memory of its own, which the caller puts into the slot after carve()
+    template <typename T>
+    void out(T ** slot, size_t bytes, bool on, bool in_slab = true) { f[n++] = { (void *)slot, nullptr, bytes, on, true, in_slab }; }
+
+    static size_t words(const Field & x) { return (x.bytes + 3) / 4; }
+    // Sizes the slab and points every slot at its part of it; the slot of an array that is not wanted becomes null.
+    hipError_t carve(DevBuf<float> & slab) {
+        size_t total = 0;
+        for (size_t i = 0; i < n; ++i) if (f[i].on && f[i].in_slab) total += words(f[i]);
+        const hipError_t e = slab.ensure(total);
+        if (e != hipSuccess) return e;
+        float * p = slab.p;
+        for (size_t i = 0; i < n; ++i) {
+            memcpy(&f[i].host, f[i].slot, sizeof(void *));
+            void * dev = nullptr;
+            if (f[i].on && f[i].in_slab) { dev = p; p += words(f[i]); }
+            if (f[i].in_slab || !f[i].on) memcpy(f[i].slot, &dev, sizeof(void *));
+        }
+        return hipSuccess;
+    }
+    hipError_t copy(bool out, hipStream_t stream) const {
+        for (size_t i = 0; i < n; ++i) {
+            if (!f[i].on || f[i].out != out || (out && !f[i].bytes)) continue;
+            void * dev;
+            memcpy(&dev, f[i].slot, sizeof(void *));
+            const hipError_t e = out ? hipMemcpyAsync(f[i].host, dev, f[i].bytes, hipMemcpyDeviceToHost, stream)
+                                     : hipMemcpyAsync(dev, f[i].host, f[i].bytes, hipMemcpyHostToDevice, stream);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
+    hipError_t upload(hipStream_t stream) const { return copy(false, stream); }
+    hipError_t download(hipStream_t stream) const { return copy(true, stream); }
+};
 
 // The leaf -> (group, vertex0) table of the queries (prt_trace_rays, prt_closest_points), built by the first of them after an upload.
 int ensure_leaf_map(prt_ctx * ctx, const char * who) {
@@ -1191,17 +1245,85 @@ int ensure_leaf_map(prt_ctx * ctx, const char * who) {
     return 0;
 }
 
-// One batch on the device: A's rays and outputs are device pointers; pad_max < 0 asks k_query_pad for the origins' extent.
-// Synchronous (returns after the context's stream has drained).
-int run_query(prt_ctx * ctx, int mode, QueryArgs A, unsigned int fields, bool count_visits, prt_counters * counters) {
-    const int map_rc = ensure_leaf_map(ctx, "prt_trace_rays");
+int ensure_signed_tables(prt_ctx * ctx, ClosestArgs & A);
+
+// The fast walk on its persistent grid, then the exact kernel for the items it set aside; its fixed grid reads the list's length
+// on the device.
+template <typename Fast, typename Exact, typename Args>
+int launch_walk(prt_ctx * ctx, Fast fast, Exact exact, const Args & A, unsigned int fields) {
+    constexpr int BLOCK = 256;
+    const size_t lds = stack_dwords(A.stack_lds_entries, BLOCK) * sizeof(int);
+    const TraceRule rule = trace_rule(ctx, fast, lds);
+    const TraceGrid g = trace_grid(ctx, rule.per_cu, rule.chunk_min, A.count);
+    hipLaunchKernelGGL(fast, dim3(g.grid), dim3(BLOCK), lds, ctx->stream, ctx->scene, A, ctx->q_leaf_map.p, fields, rule.keep_min, rule.node_min,
+                       g.chunk, ctx->counters.p);
+    HIP_TRY(ctx, hipGetLastError());
+    constexpr unsigned int SLOW_BLOCKS = 64;               // A.exact_stack holds SLOW_BLOCKS * 256 columns
+    hipLaunchKernelGGL(exact, dim3(SLOW_BLOCKS), dim3(256), 0, ctx->stream, ctx->scene, A, ctx->q_leaf_map.p, fields, ctx->counters.p);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+// What a query supplies to run_batch: its argument struct, its name in the error texts, and the steps that are its own.
+struct RayWalk {
+    typedef QueryArgs Args;
+    int mode;
+    static const char * name() { return "prt_trace_rays"; }
+    void prepare(prt_ctx * ctx, QueryArgs & A) const {
+        ctx->scene.tie_widen_max = (unsigned int)std::max(0ll, std::min(64ll, ctx->opt.tie_widen_max));
+        A.replay_beyond = 64.0f * ctx->scene_abs_max;
+    }
+    int tables(prt_ctx *, QueryArgs &, unsigned int) const { return 0; }
+    static void (*pad_kernel())(QueryArgs) { return k_query_pad; }
+    int launch(prt_ctx * ctx, const QueryArgs & A, unsigned int fields, bool count) const {
+        if (mode == PRT_QUERY_OCCLUDED)
+            return count ? launch_walk(ctx, k_query<256, QUERY_OCCLUDED, true>, k_query_exact<QUERY_OCCLUDED, true>, A, fields)
+                         : launch_walk(ctx, k_query<256, QUERY_OCCLUDED, false>, k_query_exact<QUERY_OCCLUDED, false>, A, fields);
+        return count ? launch_walk(ctx, k_query<256, QUERY_CLOSEST, true>, k_query_exact<QUERY_CLOSEST, true>, A, fields)
+                     : launch_walk(ctx, k_query<256, QUERY_CLOSEST, false>, k_query_exact<QUERY_CLOSEST, false>, A, fields);
+    }
+    int verdict(prt_ctx * ctx, const DevCounters & h) const {
+        if (h.near_tie_unresolved) {
+            char msg[160];
+            snprintf(msg, sizeof(msg), "prt_trace_rays: %llu near-tied hits could not be resolved within %lld widenings of the candidate set",
+                     (unsigned long long)h.near_tie_unresolved, ctx->opt.tie_widen_max);
+            ctx->error = msg;
+            return -8;
+        }
+        if (ctx->opt.debug_util && h.wave_node_steps)
+            fprintf(stderr, "[prt] k_query: node loop %.1f%% of lanes (%llu wave steps), triangle tests %.1f%% (%llu wave steps, %llu leaf visits), %llu refills\n",
+                    100.0 * (double)h.node_visits / (64.0 * (double)h.wave_node_steps), (unsigned long long)h.wave_node_steps,
+                    100.0 * (double)h.tri_tests / (64.0 * (double)h.wave_tri_steps), (unsigned long long)h.wave_tri_steps,
+                    (unsigned long long)h.wave_leaf_steps, (unsigned long long)h.wave_refills);
+        return 0;
+    }
+};
+
+struct PointWalk {
+    typedef ClosestArgs Args;
+    static const char * name() { return "prt_closest_points"; }
+    void prepare(prt_ctx *, ClosestArgs &) const {}
+    // prt_signed_distance: a refill of the accumulators counts in render_ms
+    int tables(prt_ctx * ctx, ClosestArgs & A, unsigned int fields) const { return (fields & (CF_SIGNED | CF_FEATURE)) ? ensure_signed_tables(ctx, A) : 0; }
+    static void (*pad_kernel())(ClosestArgs) { return k_closest_pad; }
+    int launch(prt_ctx * ctx, const ClosestArgs & A, unsigned int fields, bool count) const {
+        return count ? launch_walk(ctx, k_closest<256, true>, k_closest_exact<true>, A, fields)
+                     : launch_walk(ctx, k_closest<256, false>, k_closest_exact<false>, A, fields);
+    }
+    int verdict(prt_ctx *, const DevCounters &) const { return 0; }
+};
+
+// One batch on the device: A's inputs and outputs are device pointers; pad_max < 0 asks the pad kernel for the inputs' extent.
+// Synchronous (returns after the context's stream has drained).  The work words, the slow list and the exact stacks are shared by
+// all queries (a context runs one call at a time).
+template <typename Walk>
+int run_batch(prt_ctx * ctx, const Walk & q, typename Walk::Args A, unsigned int fields, bool count_visits, prt_counters * counters) {
+    const int map_rc = ensure_leaf_map(ctx, Walk::name());
     if (map_rc) return map_rc;
     hipStream_t stream = ctx->stream;
-    ctx->scene.tie_widen_max = (unsigned int)std::max(0ll, std::min(64ll, ctx->opt.tie_widen_max));
-    // LDS stack column as the render pipelines size it; k_query_exact's fixed grid gets full-height global columns
-    unsigned int stack_cap = STACK_LDS_CAP_DEFAULT;
-    if (ctx->opt.stack_cap >= 0) stack_cap = (unsigned int)std::max(2ll, std::min(40ll, ctx->opt.stack_cap));
-    A.stack_lds_entries = std::min(ctx->stack_bound, stack_cap);
+    q.prepare(ctx, A);
+    // LDS stack column as the render pipelines size it; the exact kernel's fixed grid gets full-height global columns
+    A.stack_lds_entries = lds_stack_entries(ctx);
     const size_t exact_lanes = 64 * 256;
     HIP_TRY(ctx, ctx->q_exact_stack.ensure(stack_dwords(std::max(ctx->stack_bound, 4u), exact_lanes)));
     A.exact_stack = ctx->q_exact_stack.p;
@@ -1211,40 +1333,25 @@ int run_query(prt_ctx * ctx, int mode, QueryArgs A, unsigned int fields, bool co
     HIP_TRY(ctx, ctx->counters.ensure(1));
     A.work = ctx->q_work.p;
     A.slow = ctx->q_slow.p;
-    A.replay_beyond = 64.0f * ctx->scene_abs_max;
     const bool device_pad = A.pad_max < 0.0f;
     if (device_pad) A.pad_max = ctx->scene_abs_max;
 
     HIP_TRY(ctx, hipMemsetAsync(ctx->counters.p, 0, sizeof(DevCounters), stream));
     HIP_TRY(ctx, hipMemsetAsync(A.work, 0, 4 * sizeof(unsigned int), stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev[0], stream));
+    if (const int rc = q.tables(ctx, A, fields)) return rc;
     if (device_pad) {
-        hipLaunchKernelGGL(k_query_pad, dim3(std::min(1024u, (A.count + 255) / 256)), dim3(256), 0, stream, A);
+        hipLaunchKernelGGL(Walk::pad_kernel(), dim3(std::min(1024u, (A.count + 255) / 256)), dim3(256), 0, stream, A);
         HIP_TRY(ctx, hipGetLastError());
     }
     HIP_TRY(ctx, hipEventRecord(ctx->ev[2], stream));
-    int rc = mode == PRT_QUERY_OCCLUDED ? (count_visits ? launch_query<QUERY_OCCLUDED, true>(ctx, A, ctx->q_leaf_map.p, fields)
-                                                        : launch_query<QUERY_OCCLUDED, false>(ctx, A, ctx->q_leaf_map.p, fields))
-                                        : (count_visits ? launch_query<QUERY_CLOSEST, true>(ctx, A, ctx->q_leaf_map.p, fields)
-                                                        : launch_query<QUERY_CLOSEST, false>(ctx, A, ctx->q_leaf_map.p, fields));
-    if (rc) return rc;
+    if (const int rc = q.launch(ctx, A, fields, count_visits)) return rc;
     HIP_TRY(ctx, hipEventRecord(ctx->ev[3], stream));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->host_counters, ctx->counters.p, sizeof(DevCounters), hipMemcpyDeviceToHost, stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev[1], stream));
     HIP_TRY(ctx, hipEventSynchronize(ctx->ev[1]));
     const DevCounters h = *ctx->host_counters;
-    if (h.near_tie_unresolved) {
-        char msg[160];
-        snprintf(msg, sizeof(msg), "prt_trace_rays: %llu near-tied hits could not be resolved within %lld widenings of the candidate set",
-                 (unsigned long long)h.near_tie_unresolved, ctx->opt.tie_widen_max);
-        ctx->error = msg;
-        return -8;
-    }
-    if (ctx->opt.debug_util && h.wave_node_steps)
-        fprintf(stderr, "[prt] k_query: node loop %.1f%% of lanes (%llu wave steps), triangle tests %.1f%% (%llu wave steps, %llu leaf visits), %llu refills\n",
-                100.0 * (double)h.node_visits / (64.0 * (double)h.wave_node_steps), (unsigned long long)h.wave_node_steps,
-                100.0 * (double)h.tri_tests / (64.0 * (double)h.wave_tri_steps), (unsigned long long)h.wave_tri_steps,
-                (unsigned long long)h.wave_leaf_steps, (unsigned long long)h.wave_refills);
+    if (const int rc = q.verdict(ctx, h)) return rc;
     if (counters) {
         float ms = 0.0f, tms = 0.0f;
         HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
@@ -1283,92 +1390,6 @@ int query_check(prt_ctx * ctx, int mode, const prt_ray_batch * b, prt_counters *
 }
 
 // ---- closest points (prt_closest_points, kernels_closest.h) ------------------------------------------------------------------
-
-int ensure_signed_tables(prt_ctx * ctx, ClosestArgs & A);
-
-template <bool COUNT>
-int launch_closest(prt_ctx * ctx, const ClosestArgs & A, const uint2 * leaf_map, unsigned int fields) {
-    constexpr int BLOCK = 256;
-    const size_t lds = stack_dwords(A.stack_lds_entries, BLOCK) * sizeof(int);
-    // persistent grid of resident blocks, chunks and lane-refill thresholds as launch_query's
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_closest<BLOCK, COUNT>, BLOCK, lds) != hipSuccess || per_cu < 1) per_cu = 2;
-    per_cu = std::min(per_cu, 8);
-    const PrtOptions & opt = ctx->opt;
-    if (opt.trace_blocks_per_cu >= 0) per_cu = std::max(1, std::min(per_cu, (int)opt.trace_blocks_per_cu));
-    int keep_min = 40, node_min = 32;
-    if (opt.keep_min >= 0) keep_min = std::max(1, std::min(64, (int)opt.keep_min));
-    if (opt.node_min >= 0) node_min = std::max(0, std::min(64, (int)opt.node_min));
-    unsigned int chunk_min = 128;
-    if (opt.chunk_min >= 0) chunk_min = (unsigned int)std::max(64ll, std::min(512ll, opt.chunk_min));
-    const unsigned int grid = std::max(1u, std::min((unsigned int)per_cu * (unsigned int)ctx->cu_count, (A.count + BLOCK - 1) / BLOCK));
-    unsigned int chunk = A.count / (grid * (BLOCK / 64) * 8u);
-    chunk = std::max(chunk_min, std::min(512u, (chunk / 64u) * 64u));
-    hipLaunchKernelGGL((k_closest<BLOCK, COUNT>), dim3(grid), dim3(BLOCK), lds, ctx->stream, ctx->scene, A, leaf_map, fields,
-                       keep_min, node_min, chunk, ctx->counters.p);
-    HIP_TRY(ctx, hipGetLastError());
-    constexpr unsigned int SLOW_BLOCKS = 64;               // A.exact_stack holds SLOW_BLOCKS * 256 columns
-    hipLaunchKernelGGL((k_closest_exact<COUNT>), dim3(SLOW_BLOCKS), dim3(256), 0, ctx->stream, ctx->scene, A, leaf_map, fields, ctx->counters.p);
-    HIP_TRY(ctx, hipGetLastError());
-    return 0;
-}
-
-// One batch on the device: A's points and outputs are device pointers; pad_max < 0 asks k_closest_pad for the points' extent.
-// Synchronous (returns after the context's stream has drained).  The work words, the slow list and the exact stacks are the ray
-// queries' (a context runs one call at a time).
-int run_closest(prt_ctx * ctx, ClosestArgs A, unsigned int fields, bool count_visits, prt_counters * counters) {
-    const int map_rc = ensure_leaf_map(ctx, "prt_closest_points");
-    if (map_rc) return map_rc;
-    hipStream_t stream = ctx->stream;
-    unsigned int stack_cap = STACK_LDS_CAP_DEFAULT;
-    if (ctx->opt.stack_cap >= 0) stack_cap = (unsigned int)std::max(2ll, std::min(40ll, ctx->opt.stack_cap));
-    A.stack_lds_entries = std::min(ctx->stack_bound, stack_cap);
-    const size_t exact_lanes = 64 * 256;
-    HIP_TRY(ctx, ctx->q_exact_stack.ensure(stack_dwords(std::max(ctx->stack_bound, 4u), exact_lanes)));
-    A.exact_stack = ctx->q_exact_stack.p;
-    A.exact_stack_stride = (unsigned int)exact_lanes;
-    HIP_TRY(ctx, ctx->q_work.ensure(4));
-    HIP_TRY(ctx, ctx->q_slow.ensure(A.count));
-    HIP_TRY(ctx, ctx->counters.ensure(1));
-    A.work = ctx->q_work.p;
-    A.slow = ctx->q_slow.p;
-    const bool device_pad = A.pad_max < 0.0f;
-    if (device_pad) A.pad_max = ctx->scene_abs_max;
-
-    HIP_TRY(ctx, hipMemsetAsync(ctx->counters.p, 0, sizeof(DevCounters), stream));
-    HIP_TRY(ctx, hipMemsetAsync(A.work, 0, 4 * sizeof(unsigned int), stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev[0], stream));
-    if (fields & (CF_SIGNED | CF_FEATURE)) {                   // prt_signed_distance: a refill of the accumulators counts in render_ms
-        const int sg_rc = ensure_signed_tables(ctx, A);
-        if (sg_rc) return sg_rc;
-    }
-    if (device_pad) {
-        hipLaunchKernelGGL(k_closest_pad, dim3(std::min(1024u, (A.count + 255) / 256)), dim3(256), 0, stream, A);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    HIP_TRY(ctx, hipEventRecord(ctx->ev[2], stream));
-    const int rc = count_visits ? launch_closest<true>(ctx, A, ctx->q_leaf_map.p, fields) : launch_closest<false>(ctx, A, ctx->q_leaf_map.p, fields);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipEventRecord(ctx->ev[3], stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->host_counters, ctx->counters.p, sizeof(DevCounters), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev[1], stream));
-    HIP_TRY(ctx, hipEventSynchronize(ctx->ev[1]));
-    const DevCounters h = *ctx->host_counters;
-    if (counters) {
-        float ms = 0.0f, tms = 0.0f;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-        HIP_TRY(ctx, hipEventElapsedTime(&tms, ctx->ev[2], ctx->ev[3]));
-        memset(counters, 0, sizeof(*counters));
-        counters->ray_count = A.count;
-        counters->node_visits = h.node_visits;
-        counters->tri_tests = h.tri_tests;
-        counters->render_ms = ms;
-        counters->trace_kernel_ms = tms;
-        counters->trace_kernel_launches = 2;
-        counters->pipeline = 0;
-    }
-    return 0;
-}
 
 unsigned int closest_fields(const prt_closest_buffers * o) {
     return (o->dist2 ? CF_DIST2 : 0) | (o->point ? CF_POINT : 0) | (o->bw ? CF_BW : 0) | (o->vertex0 ? CF_VERTEX0 : 0) | (o->group ? CF_GROUP : 0);
@@ -1732,220 +1753,191 @@ int grad_fill_info(prt_ctx * ctx, const GradScan & scan, prt_grad_info * info) {
     return 0;
 }
 
-// prt_trace_rays_backward / prt_trace_rays_backward_device: `device` says where the caller's arrays live.  Nothing of the tree is
-// read and nothing of the scene, the render stats or the counters is written.  k_qgrad_scan validates every hit reference before
-// the first write to an output of the caller's.
-int query_backward(prt_ctx * ctx, const prt_ray_batch * b, const int32_t * group, const uint32_t * vertex0, const float * positions,
-                   uint32_t position_count, const prt_hit_grads * gout, const prt_query_grads * gin, prt_grad_info * info, bool device) {
+// What a gradient call supplies to grad_backward: the caller's arguments, its argument struct filled from them, the description of
+// its arrays for a call with host pointers, its kernels and when its scatter has something to do.
+struct RayGrad {
+    typedef QGradArgs Args;
+    const prt_ray_batch * b;
+    const int32_t * group;
+    const uint32_t * vertex0;
+    const float * positions;
+    const prt_hit_grads * gout;
+    const prt_query_grads * gin;
+    static const char * required() { return "null origins, directions, group, vertex0 or positions"; }
+    static const char * items() { return "rays"; }
+    bool complete() const { return b->origins && b->directions && group && vertex0 && positions; }
+    float * want_positions() const { return gin ? gin->positions : nullptr; }
+    void fill(QGradArgs & A) const {
+        A.origins = b->origins; A.dirs = b->directions; A.group = group; A.vertex0 = vertex0; A.positions = positions;
+        if (gout) { A.g_t = gout->t; A.g_bw = gout->bw; A.g_pos = gout->position; A.g_nrm = gout->normal; }
+        if (gin) { A.g_origins = gin->origins; A.g_dirs = gin->directions; A.g_positions = gin->positions; }
+        A.ray_bias = b->ray_bias;
+    }
+    float ** g_positions(QGradArgs & A, float **) const { return &A.g_positions; }
+    void stage(StageList & l, QGradArgs & A, float ** g_pos, size_t n, size_t np) const {
+        l.in(&A.origins, 12 * n); l.in(&A.dirs, 12 * n); l.in(&A.group, 4 * n); l.in(&A.vertex0, 4 * n); l.in(&A.positions, 4 * np);
+        l.in(&A.g_t, 4 * n); l.in(&A.g_bw, 12 * n); l.in(&A.g_pos, 12 * n); l.in(&A.g_nrm, 12 * n);
+        l.out(&A.g_origins, 12 * n, A.g_origins != nullptr); l.out(&A.g_dirs, 12 * n, A.g_dirs != nullptr);
+        l.out(g_pos, 4 * np, *g_pos != nullptr);
+    }
+    static bool scatter_writes(const QGradArgs & A) { return A.g_origins || A.g_dirs; }
+    static void (*scan())(QGradArgs) { return k_qgrad_scan; }
+    static void (*scatter(bool merge))(QGradArgs) { return merge ? k_qgrad_scatter<true> : k_qgrad_scatter<false>; }
+};
+
+struct PointGrad {
+    typedef CGradArgs Args;
+    const prt_point_batch * b;
+    const int32_t * group;
+    const uint32_t * vertex0;
+    const float * positions;
+    const prt_closest_grads * gout;
+    const prt_point_grads * gin;
+    static const char * required() { return "null points, group, vertex0 or positions"; }
+    static const char * items() { return "points"; }
+    bool complete() const { return b->points && group && vertex0 && positions; }
+    float * want_positions() const { return gin ? gin->positions : nullptr; }
+    void fill(CGradArgs & A) const {
+        A.points = b->points; A.group = group; A.vertex0 = vertex0; A.positions = positions;
+        if (gout) { A.g_dist2 = gout->dist2; A.g_point = gout->point; A.g_bw = gout->bw; }
+        if (gin) A.g_points = gin->points;
+    }
+    float ** g_positions(CGradArgs &, float ** own) const { return own; }      // CGradArgs has none: k_qgrad_resolve gets it
+    void stage(StageList & l, CGradArgs & A, float ** g_pos, size_t n, size_t np) const {
+        l.in(&A.points, 12 * n); l.in(&A.group, 4 * n); l.in(&A.vertex0, 4 * n); l.in(&A.positions, 4 * np);
+        l.in(&A.g_dist2, 4 * n); l.in(&A.g_point, 12 * n); l.in(&A.g_bw, 12 * n);
+        l.out(&A.g_points, 12 * n, A.g_points != nullptr);
+        l.out(g_pos, 4 * np, *g_pos != nullptr);
+    }
+    static bool scatter_writes(const CGradArgs & A) { return A.g_points != nullptr; }
+    static void (*scan())(CGradArgs) { return k_cgrad_scan; }
+    static void (*scatter(bool merge))(CGradArgs) { return merge ? k_cgrad_scatter<true> : k_cgrad_scatter<false>; }
+};
+
+// prt_trace_rays_backward, prt_closest_points_backward and their _device forms: `what` is the name in the error texts, `device`
+// says where the caller's arrays live.  Nothing of the tree is read and nothing of the scene, the render stats or the counters is
+// written.  The scan kernel validates every reference before the first write to an output of the caller's.
+template <typename Grad>
+int grad_backward(prt_ctx * ctx, const char * what, const Grad & q, uint32_t position_count, prt_grad_info * info, bool device) {
     if (!ctx) return -1;
     if (info) memset(info, 0, sizeof(*info));
-    if (!b) { ctx->error = "prt_trace_rays_backward: null batch"; return -1; }
-    if (b->count && (!b->origins || !b->directions || !group || !vertex0 || !positions)) {
-        ctx->error = "prt_trace_rays_backward: null origins, directions, group, vertex0 or positions";
-        return -1;
-    }
-    if (!ctx->has_scene) { ctx->error = "prt_trace_rays_backward: no scene uploaded"; return -2; }
-    if (position_count != ctx->rf_position_count) { ctx->error = "prt_trace_rays_backward: position_count differs from the uploaded scene's"; return -1; }
+    if (!q.b) { ctx->error = std::string(what) + ": null batch"; return -1; }
+    if (q.b->count && !q.complete()) { ctx->error = std::string(what) + ": " + Grad::required(); return -1; }
+    if (!ctx->has_scene) { ctx->error = std::string(what) + ": no scene uploaded"; return -2; }
+    if (position_count != ctx->rf_position_count) { ctx->error = std::string(what) + ": position_count differs from the uploaded scene's"; return -1; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = ctx->stream;
-    const size_t n = b->count, np = 3 * (size_t)position_count;
-    float * want_p = gin ? gin->positions : nullptr, * want_o = gin ? gin->origins : nullptr, * want_d = gin ? gin->directions : nullptr;
-    if (n == 0) {                                                 // no ray: the vertex gradient is zero
+    const uint32_t count = q.b->count;
+    const size_t n = count, np = 3 * (size_t)position_count;
+    float * const want_p = q.want_positions();
+    if (n == 0) {                                                 // nothing to add: the vertex gradient is zero
         if (want_p && np) {
             if (device) { HIP_TRY(ctx, hipMemsetAsync(want_p, 0, np * sizeof(float), stream)); HIP_TRY(ctx, hipStreamSynchronize(stream)); }
             else memset(want_p, 0, np * sizeof(float));
         }
         return 0;
     }
-    if (const int rc = grad_prepare(ctx, "prt_trace_rays_backward", np, want_p != nullptr)) return rc;
-    QGradArgs A;
+    if (const int rc = grad_prepare(ctx, what, np, want_p != nullptr)) return rc;
+    typename Grad::Args A;
     memset(&A, 0, sizeof(A));
-    A.origins = b->origins; A.dirs = b->directions; A.group = group; A.vertex0 = vertex0; A.positions = positions;
-    if (gout) { A.g_t = gout->t; A.g_bw = gout->bw; A.g_pos = gout->position; A.g_nrm = gout->normal; }
-    A.g_origins = want_o; A.g_dirs = want_d; A.g_positions = want_p;
+    q.fill(A);
+    float * own_g_positions = want_p;
+    float ** const g_positions = q.g_positions(A, &own_g_positions);
+    StageList io;
     if (!device) {                                                // inputs, then the requested gradients, in one slab of 4-byte words
-        const size_t f_in = 8 * n + np + (A.g_t ? n : 0) + (A.g_bw ? 3 * n : 0) + (A.g_pos ? 3 * n : 0) + (A.g_nrm ? 3 * n : 0);
-        const size_t f_out = (want_o ? 3 * n : 0) + (want_d ? 3 * n : 0) + (want_p ? np : 0);
-        HIP_TRY(ctx, ctx->qg_io.ensure(f_in + f_out));
-        float * p = ctx->qg_io.p;
-        auto in = [&](const void * src, size_t words) -> float * {
-            float * at = p;
-            p += words;
-            return hipMemcpyAsync(at, src, words * 4, hipMemcpyHostToDevice, stream) == hipSuccess ? at : nullptr;
-        };
-        bool ok = true;
-        ok = (A.origins = in(b->origins, 3 * n)) && ok;
-        ok = (A.dirs = in(b->directions, 3 * n)) && ok;
-        ok = (A.group = reinterpret_cast<const int *>(in(group, n))) && ok;
-        ok = (A.vertex0 = reinterpret_cast<const unsigned int *>(in(vertex0, n))) && ok;
-        ok = (A.positions = in(positions, np)) && ok;
-        if (A.g_t) ok = (A.g_t = in(gout->t, n)) && ok;
-        if (A.g_bw) ok = (A.g_bw = in(gout->bw, 3 * n)) && ok;
-        if (A.g_pos) ok = (A.g_pos = in(gout->position, 3 * n)) && ok;
-        if (A.g_nrm) ok = (A.g_nrm = in(gout->normal, 3 * n)) && ok;
-        if (!ok) { ctx->error = "prt_trace_rays_backward: copying the inputs to the device failed"; return -10; }
-        if (want_o) { A.g_origins = p; p += 3 * n; }
-        if (want_d) { A.g_dirs = p; p += 3 * n; }
-        if (want_p) { A.g_positions = p; p += np; }
+        q.stage(io, A, g_positions, n, np);
+        HIP_TRY(ctx, io.carve(ctx->qg_io));
+        if (io.upload(stream) != hipSuccess) { ctx->error = std::string(what) + ": copying the inputs to the device failed"; return -10; }
     }
     A.idx_positions = ctx->qg_idx.p;
     A.group_runs = ctx->qg_runs.p;
     A.words = ctx->qg_words.p;
-    A.count = b->count; A.group_count = (unsigned int)ctx->q_groups.size(); A.position_count = position_count;
-    A.ray_bias = b->ray_bias;
+    A.count = count; A.group_count = (unsigned int)ctx->q_groups.size(); A.position_count = position_count;
 
     // ---- the references and the batch's largest contribution, before any output is written
-    const unsigned int grid = grad_grid(ctx, b->count);
+    const unsigned int grid = grad_grid(ctx, count);
     HIP_TRY(ctx, hipEventRecord(ctx->ev[0], stream));
     HIP_TRY(ctx, hipMemsetAsync(A.words, 0, QGRAD_WORDS * sizeof(unsigned int), stream));
-    hipLaunchKernelGGL(k_qgrad_scan, dim3(grid), dim3(256), 0, stream, A);
+    hipLaunchKernelGGL(Grad::scan(), dim3(grid), dim3(256), 0, stream, A);
     GradScan scan;
-    if (const int rc = grad_scan_verdict(ctx, "prt_trace_rays_backward", "rays", b->count, stream, &scan)) return rc;
+    if (const int rc = grad_scan_verdict(ctx, what, Grad::items(), count, stream, &scan)) return rc;
     const bool adds = want_p && scan.words[QGRAD_W_HIT] && scan.m > 0.0f;   // else the vertex gradient is zero
     A.unit_exponent = scan.unit_exponent;
     A.acc = adds ? ctx->qg_acc.p : nullptr;
     if (adds) HIP_TRY(ctx, hipMemsetAsync(A.acc, 0, np * sizeof(long long), stream));
-    if (adds || want_o || want_d) {
-        if (ctx->opt.qgrad_merge < 0 ? PRT_QGRAD_MERGE_DEFAULT != 0 : ctx->opt.qgrad_merge != 0)
-            hipLaunchKernelGGL(k_qgrad_scatter<true>, dim3(grid), dim3(256), 0, stream, A);
-        else
-            hipLaunchKernelGGL(k_qgrad_scatter<false>, dim3(grid), dim3(256), 0, stream, A);
+    if (adds || Grad::scatter_writes(A)) {
+        const bool merge = ctx->opt.qgrad_merge < 0 ? PRT_QGRAD_MERGE_DEFAULT != 0 : ctx->opt.qgrad_merge != 0;
+        hipLaunchKernelGGL(Grad::scatter(merge), dim3(grid), dim3(256), 0, stream, A);
         HIP_TRY(ctx, hipGetLastError());
     }
-    if (const int rc = grad_resolve(ctx, adds, A.g_positions, position_count, A.unit_exponent, stream)) return rc;
-    if (!device) {
-        if (want_o) HIP_TRY(ctx, hipMemcpyAsync(want_o, A.g_origins, 12 * n, hipMemcpyDeviceToHost, stream));
-        if (want_d) HIP_TRY(ctx, hipMemcpyAsync(want_d, A.g_dirs, 12 * n, hipMemcpyDeviceToHost, stream));
-        if (want_p && np) HIP_TRY(ctx, hipMemcpyAsync(want_p, A.g_positions, np * sizeof(float), hipMemcpyDeviceToHost, stream));
-    }
+    if (const int rc = grad_resolve(ctx, adds, *g_positions, position_count, A.unit_exponent, stream)) return rc;
+    if (!device) HIP_TRY(ctx, io.download(stream));
     HIP_TRY(ctx, hipStreamSynchronize(stream));
     return grad_fill_info(ctx, scan, info);
 }
 
-// prt_closest_points_backward / prt_closest_points_backward_device: query_backward's shape for the point queries - the same
-// lazily built index buffer, runs, accumulators, control words and transfer slab, the same grid rule and event timing.  Nothing
-// of the tree is read and nothing of the scene, the render stats or the counters is written.  k_cgrad_scan validates every
-// reference before the first write to an output of the caller's.
-int closest_backward(prt_ctx * ctx, const prt_point_batch * b, const int32_t * group, const uint32_t * vertex0, const float * positions,
-                     uint32_t position_count, const prt_closest_grads * gout, const prt_point_grads * gin, prt_grad_info * info, bool device) {
-    if (!ctx) return -1;
-    if (info) memset(info, 0, sizeof(*info));
-    if (!b) { ctx->error = "prt_closest_points_backward: null batch"; return -1; }
-    if (b->count && (!b->points || !group || !vertex0 || !positions)) {
-        ctx->error = "prt_closest_points_backward: null points, group, vertex0 or positions";
-        return -1;
-    }
-    if (!ctx->has_scene) { ctx->error = "prt_closest_points_backward: no scene uploaded"; return -2; }
-    if (position_count != ctx->rf_position_count) { ctx->error = "prt_closest_points_backward: position_count differs from the uploaded scene's"; return -1; }
+// prt_trace_rays and prt_trace_rays_device after query_check: `device` says where the caller's arrays live.
+int trace_rays(prt_ctx * ctx, int mode, const prt_ray_batch * batch, const prt_hit_buffers * hits, uint32_t flags, prt_counters * counters,
+               bool device) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t n = batch->count;
+    const unsigned int fields = query_fields(mode, hits);
+    QueryArgs A;
+    memset(&A, 0, sizeof(A));
+    A.origins = batch->origins; A.dirs = batch->directions; A.tmax = mode == PRT_QUERY_OCCLUDED ? batch->tmax : nullptr;
+    A.count = batch->count; A.ray_bias = batch->ray_bias;
+    if (hits) {
+        A.t = hits->t; A.bw = hits->bw; A.vertex0 = hits->vertex0; A.group = hits->group;
+        A.position = hits->position; A.normal = hits->normal; A.occluded = hits->occluded;
+    }
+    A.pad_max = -1.0f;                                     // the origins' extent is reduced on the device (k_query_pad)
+    const RayWalk walk = { mode };
+    if (device) return run_batch(ctx, walk, A, fields, (flags & PRT_FLAG_COUNT_VISITS) != 0, counters);
+    // device copies: origins, directions, tmax, then the requested fields (float-sized words; occluded in its own bytes)
+    StageList io;
+    io.in(&A.origins, 12 * n); io.in(&A.dirs, 12 * n); io.in(&A.tmax, 4 * n);
+    io.out(&A.t, 4 * n, fields & QF_T); io.out(&A.bw, 12 * n, fields & QF_BW); io.out(&A.vertex0, 4 * n, fields & QF_VERTEX0);
+    io.out(&A.group, 4 * n, fields & QF_GROUP); io.out(&A.position, 12 * n, fields & QF_POSITION); io.out(&A.normal, 12 * n, fields & QF_NORMAL);
+    io.out(&A.occluded, n, fields & QF_OCCLUDED, false);
+    HIP_TRY(ctx, io.carve(ctx->q_io));
+    if (fields & QF_OCCLUDED) { HIP_TRY(ctx, ctx->q_occ.ensure(n)); A.occluded = ctx->q_occ.p; }
+    // the box pad from the origins' extent, on the host (the same rule as k_query_pad)
+    float extent = ctx->scene_abs_max;
+    for (size_t i = 0; i < n; ++i) {
+        const f3 o = ld3(batch->origins + 3 * i), d = ld3(batch->directions + 3 * i), ob = o + d * batch->ray_bias;
+        const bool ok = std::isfinite(o.x) && std::isfinite(o.y) && std::isfinite(o.z) && std::isfinite(d.x) && std::isfinite(d.y) &&
+                        std::isfinite(d.z) && std::isfinite(ob.x) && std::isfinite(ob.y) && std::isfinite(ob.z);
+        if (ok) extent = std::max(extent, std::max(std::max(fabsf(ob.x), fabsf(ob.y)), fabsf(ob.z)));
+    }
+    A.pad_max = extent;
     hipStream_t stream = ctx->stream;
-    const size_t n = b->count, np = 3 * (size_t)position_count;
-    float * want_p = gin ? gin->positions : nullptr, * want_q = gin ? gin->points : nullptr;
-    if (n == 0) {                                                 // no point: the vertex gradient is zero
-        if (want_p && np) {
-            if (device) { HIP_TRY(ctx, hipMemsetAsync(want_p, 0, np * sizeof(float), stream)); HIP_TRY(ctx, hipStreamSynchronize(stream)); }
-            else memset(want_p, 0, np * sizeof(float));
-        }
-        return 0;
-    }
-    if (const int rc = grad_prepare(ctx, "prt_closest_points_backward", np, want_p != nullptr)) return rc;
-    CGradArgs A;
-    memset(&A, 0, sizeof(A));
-    A.points = b->points; A.group = group; A.vertex0 = vertex0; A.positions = positions;
-    if (gout) { A.g_dist2 = gout->dist2; A.g_point = gout->point; A.g_bw = gout->bw; }
-    A.g_points = want_q;
-    float * g_positions = want_p;
-    if (!device) {                                                // inputs, then the requested gradients, in one slab of 4-byte words
-        const size_t f_in = 5 * n + np + (A.g_dist2 ? n : 0) + (A.g_point ? 3 * n : 0) + (A.g_bw ? 3 * n : 0);
-        const size_t f_out = (want_q ? 3 * n : 0) + (want_p ? np : 0);
-        HIP_TRY(ctx, ctx->qg_io.ensure(f_in + f_out));
-        float * p = ctx->qg_io.p;
-        auto in = [&](const void * src, size_t words) -> float * {
-            float * at = p;
-            p += words;
-            return hipMemcpyAsync(at, src, words * 4, hipMemcpyHostToDevice, stream) == hipSuccess ? at : nullptr;
-        };
-        bool ok = true;
-        ok = (A.points = in(b->points, 3 * n)) && ok;
-        ok = (A.group = reinterpret_cast<const int *>(in(group, n))) && ok;
-        ok = (A.vertex0 = reinterpret_cast<const unsigned int *>(in(vertex0, n))) && ok;
-        ok = (A.positions = in(positions, np)) && ok;
-        if (A.g_dist2) ok = (A.g_dist2 = in(gout->dist2, n)) && ok;
-        if (A.g_point) ok = (A.g_point = in(gout->point, 3 * n)) && ok;
-        if (A.g_bw) ok = (A.g_bw = in(gout->bw, 3 * n)) && ok;
-        if (!ok) { ctx->error = "prt_closest_points_backward: copying the inputs to the device failed"; return -10; }
-        if (want_q) { A.g_points = p; p += 3 * n; }
-        if (want_p) { g_positions = p; p += np; }
-    }
-    A.idx_positions = ctx->qg_idx.p;
-    A.group_runs = ctx->qg_runs.p;
-    A.words = ctx->qg_words.p;
-    A.count = b->count; A.group_count = (unsigned int)ctx->q_groups.size(); A.position_count = position_count;
-
-    // ---- the references and the batch's largest contribution, before any output is written
-    const unsigned int grid = grad_grid(ctx, b->count);
-    HIP_TRY(ctx, hipEventRecord(ctx->ev[0], stream));
-    HIP_TRY(ctx, hipMemsetAsync(A.words, 0, QGRAD_WORDS * sizeof(unsigned int), stream));
-    hipLaunchKernelGGL(k_cgrad_scan, dim3(grid), dim3(256), 0, stream, A);
-    GradScan scan;
-    if (const int rc = grad_scan_verdict(ctx, "prt_closest_points_backward", "points", b->count, stream, &scan)) return rc;
-    const bool adds = want_p && scan.words[QGRAD_W_HIT] && scan.m > 0.0f;   // else the vertex gradient is zero
-    A.unit_exponent = scan.unit_exponent;
-    A.acc = adds ? ctx->qg_acc.p : nullptr;
-    if (adds) HIP_TRY(ctx, hipMemsetAsync(A.acc, 0, np * sizeof(long long), stream));
-    if (adds || want_q) {
-        if (ctx->opt.qgrad_merge < 0 ? PRT_QGRAD_MERGE_DEFAULT != 0 : ctx->opt.qgrad_merge != 0)
-            hipLaunchKernelGGL(k_cgrad_scatter<true>, dim3(grid), dim3(256), 0, stream, A);
-        else
-            hipLaunchKernelGGL(k_cgrad_scatter<false>, dim3(grid), dim3(256), 0, stream, A);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    if (const int rc = grad_resolve(ctx, adds, g_positions, position_count, A.unit_exponent, stream)) return rc;
-    if (!device) {
-        if (want_q) HIP_TRY(ctx, hipMemcpyAsync(want_q, A.g_points, 12 * n, hipMemcpyDeviceToHost, stream));
-        if (want_p && np) HIP_TRY(ctx, hipMemcpyAsync(want_p, g_positions, np * sizeof(float), hipMemcpyDeviceToHost, stream));
-    }
+    HIP_TRY(ctx, io.upload(stream));
+    if (const int rc = run_batch(ctx, walk, A, fields, (flags & PRT_FLAG_COUNT_VISITS) != 0, counters)) return rc;
+    HIP_TRY(ctx, io.download(stream));
     HIP_TRY(ctx, hipStreamSynchronize(stream));
-    return grad_fill_info(ctx, scan, info);
+    return 0;
 }
 
-// prt_closest_points_device and prt_signed_distance_device after their checks: `o` holds the requested fields' device pointers.
-int closest_on_device(prt_ctx * ctx, const prt_point_batch * batch, const prt_signed_buffers & o, unsigned int fields, uint32_t flags,
-                      prt_counters * counters) {
+// prt_closest_points, prt_signed_distance and their _device forms after closest_check: `o` holds the requested fields' pointers,
+// `device` says where they and the batch's arrays live.
+int closest_points(prt_ctx * ctx, const prt_point_batch * batch, const prt_signed_buffers & o, unsigned int fields, uint32_t flags,
+                   prt_counters * counters, bool device) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t n = batch->count;
     ClosestArgs A;
     memset(&A, 0, sizeof(A));
     A.points = batch->points; A.max_dist2 = batch->max_dist2; A.count = batch->count;
     A.dist2 = o.closest.dist2; A.point = o.closest.point; A.bw = o.closest.bw; A.vertex0 = o.closest.vertex0; A.group = o.closest.group;
     A.signed_dist = o.signed_dist; A.feature = o.feature;
     A.pad_max = -1.0f;                                     // the points' extent is reduced on the device (k_closest_pad)
-    return run_closest(ctx, A, fields, (flags & PRT_FLAG_COUNT_VISITS) != 0, counters);
-}
-
-// prt_closest_points and prt_signed_distance after their checks: `o` holds the requested fields' host pointers.
-int closest_on_host(prt_ctx * ctx, const prt_point_batch * batch, const prt_signed_buffers & o, unsigned int fields, uint32_t flags,
-                    prt_counters * counters) {
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t n = batch->count;
+    if (device) return run_batch(ctx, PointWalk(), A, fields, (flags & PRT_FLAG_COUNT_VISITS) != 0, counters);
     // device copies: points, max_dist2, then the requested fields (float-sized words; the feature bytes last, rounded up)
-    const size_t f_in = 3 * n + (batch->max_dist2 ? n : 0);
-    const size_t f_out = ((fields & CF_DIST2) ? n : 0) + ((fields & CF_POINT) ? 3 * n : 0) + ((fields & CF_BW) ? 3 * n : 0) +
-                         ((fields & CF_VERTEX0) ? n : 0) + ((fields & CF_GROUP) ? n : 0) + ((fields & CF_SIGNED) ? n : 0) +
-                         ((fields & CF_FEATURE) ? (n + 3) / 4 : 0);
-    HIP_TRY(ctx, ctx->q_io.ensure(f_in + f_out));
-    float * p = ctx->q_io.p;
-    ClosestArgs A;
-    memset(&A, 0, sizeof(A));
-    A.points = p; p += 3 * n;
-    if (batch->max_dist2) { A.max_dist2 = p; p += n; }
-    if (fields & CF_DIST2) { A.dist2 = p; p += n; }
-    if (fields & CF_POINT) { A.point = p; p += 3 * n; }
-    if (fields & CF_BW) { A.bw = p; p += 3 * n; }
-    if (fields & CF_VERTEX0) { A.vertex0 = reinterpret_cast<unsigned int *>(p); p += n; }
-    if (fields & CF_GROUP) { A.group = reinterpret_cast<int *>(p); p += n; }
-    if (fields & CF_SIGNED) { A.signed_dist = p; p += n; }
-    if (fields & CF_FEATURE) { A.feature = reinterpret_cast<unsigned char *>(p); p += (n + 3) / 4; }
-    A.count = batch->count;
+    StageList io;
+    io.in(&A.points, 12 * n); io.in(&A.max_dist2, 4 * n);
+    io.out(&A.dist2, 4 * n, fields & CF_DIST2); io.out(&A.point, 12 * n, fields & CF_POINT); io.out(&A.bw, 12 * n, fields & CF_BW);
+    io.out(&A.vertex0, 4 * n, fields & CF_VERTEX0); io.out(&A.group, 4 * n, fields & CF_GROUP); io.out(&A.signed_dist, 4 * n, fields & CF_SIGNED);
+    io.out(&A.feature, n, fields & CF_FEATURE);
+    HIP_TRY(ctx, io.carve(ctx->q_io));
     // the box pad from the points' extent, on the host (the same rule as k_closest_pad)
     float extent = ctx->scene_abs_max;
     for (size_t i = 0; i < n; ++i) {
@@ -1954,17 +1946,9 @@ int closest_on_host(prt_ctx * ctx, const prt_point_batch * batch, const prt_sign
     }
     A.pad_max = extent;
     hipStream_t stream = ctx->stream;
-    HIP_TRY(ctx, hipMemcpyAsync(const_cast<float *>(A.points), batch->points, 12 * n, hipMemcpyHostToDevice, stream));
-    if (batch->max_dist2) HIP_TRY(ctx, hipMemcpyAsync(const_cast<float *>(A.max_dist2), batch->max_dist2, 4 * n, hipMemcpyHostToDevice, stream));
-    int rc = run_closest(ctx, A, fields, (flags & PRT_FLAG_COUNT_VISITS) != 0, counters);
-    if (rc) return rc;
-    if (fields & CF_DIST2) HIP_TRY(ctx, hipMemcpyAsync(o.closest.dist2, A.dist2, 4 * n, hipMemcpyDeviceToHost, stream));
-    if (fields & CF_POINT) HIP_TRY(ctx, hipMemcpyAsync(o.closest.point, A.point, 12 * n, hipMemcpyDeviceToHost, stream));
-    if (fields & CF_BW) HIP_TRY(ctx, hipMemcpyAsync(o.closest.bw, A.bw, 12 * n, hipMemcpyDeviceToHost, stream));
-    if (fields & CF_VERTEX0) HIP_TRY(ctx, hipMemcpyAsync(o.closest.vertex0, A.vertex0, 4 * n, hipMemcpyDeviceToHost, stream));
-    if (fields & CF_GROUP) HIP_TRY(ctx, hipMemcpyAsync(o.closest.group, A.group, 4 * n, hipMemcpyDeviceToHost, stream));
-    if (fields & CF_SIGNED) HIP_TRY(ctx, hipMemcpyAsync(o.signed_dist, A.signed_dist, 4 * n, hipMemcpyDeviceToHost, stream));
-    if (fields & CF_FEATURE) HIP_TRY(ctx, hipMemcpyAsync(o.feature, A.feature, n, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, io.upload(stream));
+    if (const int rc = run_batch(ctx, PointWalk(), A, fields, (flags & PRT_FLAG_COUNT_VISITS) != 0, counters)) return rc;
+    HIP_TRY(ctx, io.download(stream));
     HIP_TRY(ctx, hipStreamSynchronize(stream));
     return 0;
 }
@@ -2499,17 +2483,7 @@ int prt_trace_rays_device(prt_ctx * ctx, int mode, const prt_ray_batch * batch, 
     PRT_API_TRY
     const int chk = query_check(ctx, mode, batch, counters);
     if (chk) return chk > 0 ? 0 : chk;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    QueryArgs A;
-    memset(&A, 0, sizeof(A));
-    A.origins = batch->origins; A.dirs = batch->directions; A.tmax = mode == PRT_QUERY_OCCLUDED ? batch->tmax : nullptr;
-    A.count = batch->count; A.ray_bias = batch->ray_bias;
-    if (hits) {
-        A.t = hits->t; A.bw = hits->bw; A.vertex0 = hits->vertex0; A.group = hits->group;
-        A.position = hits->position; A.normal = hits->normal; A.occluded = hits->occluded;
-    }
-    A.pad_max = -1.0f;                                     // the origins' extent is reduced on the device (k_query_pad)
-    return run_query(ctx, mode, A, query_fields(mode, hits), (flags & PRT_FLAG_COUNT_VISITS) != 0, counters);
+    return trace_rays(ctx, mode, batch, hits, flags, counters, true);
     PRT_API_CATCH_RC(ctx, "prt_trace_rays_device")
 }
 
@@ -2518,55 +2492,7 @@ int prt_trace_rays(prt_ctx * ctx, int mode, const prt_ray_batch * batch, const p
     PRT_API_TRY
     const int chk = query_check(ctx, mode, batch, counters);
     if (chk) return chk > 0 ? 0 : chk;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t n = batch->count;
-    const bool occ = mode == PRT_QUERY_OCCLUDED;
-    const unsigned int fields = query_fields(mode, hits);
-    // device copies: origins, directions, tmax, then the requested fields (float-sized words; occluded in its own bytes)
-    const bool has_tmax = occ && batch->tmax;
-    const size_t f_in = 6 * n + (has_tmax ? n : 0);
-    const size_t f_out = ((fields & QF_T) ? n : 0) + ((fields & QF_BW) ? 3 * n : 0) + ((fields & QF_VERTEX0) ? n : 0) +
-                         ((fields & QF_GROUP) ? n : 0) + ((fields & QF_POSITION) ? 3 * n : 0) + ((fields & QF_NORMAL) ? 3 * n : 0);
-    HIP_TRY(ctx, ctx->q_io.ensure(f_in + f_out));
-    if (fields & QF_OCCLUDED) HIP_TRY(ctx, ctx->q_occ.ensure(n));
-    float * p = ctx->q_io.p;
-    QueryArgs A;
-    memset(&A, 0, sizeof(A));
-    A.origins = p; p += 3 * n;
-    A.dirs = p; p += 3 * n;
-    if (has_tmax) { A.tmax = p; p += n; }
-    if (fields & QF_T) { A.t = p; p += n; }
-    if (fields & QF_BW) { A.bw = p; p += 3 * n; }
-    if (fields & QF_VERTEX0) { A.vertex0 = reinterpret_cast<unsigned int *>(p); p += n; }
-    if (fields & QF_GROUP) { A.group = reinterpret_cast<int *>(p); p += n; }
-    if (fields & QF_POSITION) { A.position = p; p += 3 * n; }
-    if (fields & QF_NORMAL) { A.normal = p; p += 3 * n; }
-    if (fields & QF_OCCLUDED) A.occluded = ctx->q_occ.p;
-    A.count = batch->count; A.ray_bias = batch->ray_bias;
-    // the box pad from the origins' extent, on the host (the same rule as k_query_pad)
-    float extent = ctx->scene_abs_max;
-    for (size_t i = 0; i < n; ++i) {
-        const f3 o = ld3(batch->origins + 3 * i), d = ld3(batch->directions + 3 * i), ob = o + d * batch->ray_bias;
-        const bool ok = std::isfinite(o.x) && std::isfinite(o.y) && std::isfinite(o.z) && std::isfinite(d.x) && std::isfinite(d.y) &&
-                        std::isfinite(d.z) && std::isfinite(ob.x) && std::isfinite(ob.y) && std::isfinite(ob.z);
-        if (ok) extent = std::max(extent, std::max(std::max(fabsf(ob.x), fabsf(ob.y)), fabsf(ob.z)));
-    }
-    A.pad_max = extent;
-    hipStream_t stream = ctx->stream;
-    HIP_TRY(ctx, hipMemcpyAsync(const_cast<float *>(A.origins), batch->origins, 12 * n, hipMemcpyHostToDevice, stream));
-    HIP_TRY(ctx, hipMemcpyAsync(const_cast<float *>(A.dirs), batch->directions, 12 * n, hipMemcpyHostToDevice, stream));
-    if (has_tmax) HIP_TRY(ctx, hipMemcpyAsync(const_cast<float *>(A.tmax), batch->tmax, 4 * n, hipMemcpyHostToDevice, stream));
-    int rc = run_query(ctx, mode, A, fields, (flags & PRT_FLAG_COUNT_VISITS) != 0, counters);
-    if (rc) return rc;
-    if (fields & QF_T) HIP_TRY(ctx, hipMemcpyAsync(hits->t, A.t, 4 * n, hipMemcpyDeviceToHost, stream));
-    if (fields & QF_BW) HIP_TRY(ctx, hipMemcpyAsync(hits->bw, A.bw, 12 * n, hipMemcpyDeviceToHost, stream));
-    if (fields & QF_VERTEX0) HIP_TRY(ctx, hipMemcpyAsync(hits->vertex0, A.vertex0, 4 * n, hipMemcpyDeviceToHost, stream));
-    if (fields & QF_GROUP) HIP_TRY(ctx, hipMemcpyAsync(hits->group, A.group, 4 * n, hipMemcpyDeviceToHost, stream));
-    if (fields & QF_POSITION) HIP_TRY(ctx, hipMemcpyAsync(hits->position, A.position, 12 * n, hipMemcpyDeviceToHost, stream));
-    if (fields & QF_NORMAL) HIP_TRY(ctx, hipMemcpyAsync(hits->normal, A.normal, 12 * n, hipMemcpyDeviceToHost, stream));
-    if (fields & QF_OCCLUDED) HIP_TRY(ctx, hipMemcpyAsync(hits->occluded, A.occluded, n, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(ctx, hipStreamSynchronize(stream));
-    return 0;
+    return trace_rays(ctx, mode, batch, hits, flags, counters, false);
     PRT_API_CATCH_RC(ctx, "prt_trace_rays")
 }
 
@@ -2576,7 +2502,7 @@ int prt_closest_points_device(prt_ctx * ctx, const prt_point_batch * batch, cons
     const int chk = closest_check(ctx, batch, out, counters);
     if (chk) return chk > 0 ? 0 : chk;
     const prt_signed_buffers o = { *out, nullptr, nullptr };
-    return closest_on_device(ctx, batch, o, closest_fields(out), flags, counters);
+    return closest_points(ctx, batch, o, closest_fields(out), flags, counters, true);
     PRT_API_CATCH_RC(ctx, "prt_closest_points_device")
 }
 
@@ -2586,7 +2512,7 @@ int prt_closest_points(prt_ctx * ctx, const prt_point_batch * batch, const prt_c
     const int chk = closest_check(ctx, batch, out, counters);
     if (chk) return chk > 0 ? 0 : chk;
     const prt_signed_buffers o = { *out, nullptr, nullptr };
-    return closest_on_host(ctx, batch, o, closest_fields(out), flags, counters);
+    return closest_points(ctx, batch, o, closest_fields(out), flags, counters, false);
     PRT_API_CATCH_RC(ctx, "prt_closest_points")
 }
 
@@ -2595,7 +2521,7 @@ int prt_signed_distance_device(prt_ctx * ctx, const prt_point_batch * batch, con
     PRT_API_TRY
     const int chk = closest_check(ctx, batch, out ? &out->closest : nullptr, counters);
     if (chk) return chk > 0 ? 0 : chk;
-    return closest_on_device(ctx, batch, *out, signed_fields(out), flags, counters);
+    return closest_points(ctx, batch, *out, signed_fields(out), flags, counters, true);
     PRT_API_CATCH_RC(ctx, "prt_signed_distance_device")
 }
 
@@ -2604,7 +2530,7 @@ int prt_signed_distance(prt_ctx * ctx, const prt_point_batch * batch, const prt_
     PRT_API_TRY
     const int chk = closest_check(ctx, batch, out ? &out->closest : nullptr, counters);
     if (chk) return chk > 0 ? 0 : chk;
-    return closest_on_host(ctx, batch, *out, signed_fields(out), flags, counters);
+    return closest_points(ctx, batch, *out, signed_fields(out), flags, counters, false);
     PRT_API_CATCH_RC(ctx, "prt_signed_distance")
 }
 
@@ -2623,7 +2549,7 @@ int prt_update_geometry_device(prt_ctx * ctx, const prt_geometry_update * update
 int prt_trace_rays_backward(prt_ctx * ctx, const prt_ray_batch * batch, const int32_t * group, const uint32_t * vertex0, const float * positions,
                             uint32_t position_count, const prt_hit_grads * gout, const prt_query_grads * gin, prt_grad_info * info) {
     PRT_API_TRY
-    return query_backward(ctx, batch, group, vertex0, positions, position_count, gout, gin, info, false);
+    return grad_backward(ctx, "prt_trace_rays_backward", RayGrad{ batch, group, vertex0, positions, gout, gin }, position_count, info, false);
     PRT_API_CATCH_RC(ctx, "prt_trace_rays_backward")
 }
 
@@ -2631,7 +2557,7 @@ int prt_trace_rays_backward_device(prt_ctx * ctx, const prt_ray_batch * batch, c
                                    const float * positions, uint32_t position_count, const prt_hit_grads * gout,
                                    const prt_query_grads * gin, prt_grad_info * info) {
     PRT_API_TRY
-    return query_backward(ctx, batch, group, vertex0, positions, position_count, gout, gin, info, true);
+    return grad_backward(ctx, "prt_trace_rays_backward", RayGrad{ batch, group, vertex0, positions, gout, gin }, position_count, info, true);
     PRT_API_CATCH_RC(ctx, "prt_trace_rays_backward_device")
 }
 
@@ -2639,7 +2565,7 @@ int prt_closest_points_backward(prt_ctx * ctx, const prt_point_batch * batch, co
                                 const float * positions, uint32_t position_count, const prt_closest_grads * gout,
                                 const prt_point_grads * gin, prt_grad_info * info) {
     PRT_API_TRY
-    return closest_backward(ctx, batch, group, vertex0, positions, position_count, gout, gin, info, false);
+    return grad_backward(ctx, "prt_closest_points_backward", PointGrad{ batch, group, vertex0, positions, gout, gin }, position_count, info, false);
     PRT_API_CATCH_RC(ctx, "prt_closest_points_backward")
 }
 
@@ -2647,7 +2573,7 @@ int prt_closest_points_backward_device(prt_ctx * ctx, const prt_point_batch * ba
                                        const float * positions, uint32_t position_count, const prt_closest_grads * gout,
                                        const prt_point_grads * gin, prt_grad_info * info) {
     PRT_API_TRY
-    return closest_backward(ctx, batch, group, vertex0, positions, position_count, gout, gin, info, true);
+    return grad_backward(ctx, "prt_closest_points_backward", PointGrad{ batch, group, vertex0, positions, gout, gin }, position_count, info, true);
     PRT_API_CATCH_RC(ctx, "prt_closest_points_backward_device")
 }
 

@@ -400,7 +400,7 @@ def assert_stacked_expectations(answers, base_mesh, perm, points, limit_units, w
 # ---- the fixed choices the host proofs and the GPU tests share
 
 SCHEDULE_SEEDS = {name: 100 + i for i, name in enumerate(FIXTURES)}       # the recipe seeds of tests/test_gpu_closest.py
-PAD_LANES = 1024 * 256                   # k_closest_pad's grid (run_closest)
+PAD_LANES = 1024 * 256                   # k_closest_pad's grid (run_batch)
 LONG_LIST = 10 * RECIPE_POINTS           # terrain_64's recipe tiled: at STACK_CAP=2 more points are listed than k_closest_exact has lanes
 SCALE_SEED = 21
 # The intermediate stack cap of the overflow tests, per tree width, with the number of terrain_64's 2,048 recipe points (seed 103)

@@ -1,6 +1,6 @@
 // closest_grad_host_harness.cpp - the gradients of closest-point queries (par_raytracer_amd/csrc/dev_closest_grad.h,
 // kernels_closest_grad.h) on the host: runs k_cgrad_scan, k_cgrad_scatter and k_qgrad_resolve one lane at a time, in the order
-// and with the decisions of prt_closest_points_backward (csrc/prt_api.hip closest_backward), on the cases
+// and with the decisions of prt_closest_points_backward (csrc/prt_api.hip grad_backward), on the cases
 // tests/closest_grad_cases.py writes to a file, and writes the results to another.  No GPU library is involved; the GPU suite
 // compares the device's bits with this program's.
 //
@@ -125,7 +125,7 @@ int main(int argc, char ** argv) {
                 }
             }
             if (adds) {
-                QGradArgs R;                                      // as closest_backward fills it
+                QGradArgs R;                                      // as grad_resolve fills it
                 memset(&R, 0, sizeof(R));
                 R.g_positions = gp.data(); R.acc = acc.data(); R.position_count = n_pos; R.unit_exponent = A.unit_exponent;
                 launch(k_qgrad_resolve, 3 * n_pos + 2, R);

@@ -15,7 +15,7 @@
 // (x3 f32), idx_positions (u32), the groups' (first_index, index_count) (2 x u32).
 // results.bin, per case: i32 mismatches between walk and brute force, u32 points decided by the tie rule, u64 node visits and
 // u64 triangle tests of the walk, then dist2, point (x3), bw (x3), vertex0, group of the brute force and the same five arrays of
-// the walk.  With flag 4 then: u32 the cap in effect (the case's, clamped to 2..40 and to the tree's stack_bound as run_closest
+// the walk.  With flag 4 then: u32 the cap in effect (the case's, clamped to 2..40 and to the tree's stack_bound as run_batch
 // clamps STACK_CAP) and per point u32 listed = the marker of the capped walk carries TRAV_FLAG_OVERFLOW (0 for an invalid point,
 // which is never walked).  With flag 2 nothing is walked: per case the same 24-byte header (zeros), then d2, v, w (f32) and
 // finite (u32) of closest_on_triangle(point i, its triangle).

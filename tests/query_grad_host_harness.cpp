@@ -1,6 +1,6 @@
 // query_grad_host_harness.cpp - the gradients of closest-hit queries (par_raytracer_amd/csrc/dev_query_grad.h,
 // kernels_query_grad.h) on the host: runs k_qgrad_scan, k_qgrad_scatter and k_qgrad_resolve one lane at a time, in the order and
-// with the decisions of prt_trace_rays_backward (csrc/prt_api.hip query_backward), on the cases tests/test_query_grad_host.py
+// with the decisions of prt_trace_rays_backward (csrc/prt_api.hip grad_backward), on the cases tests/test_query_grad_host.py
 // writes to a file, and writes the results to another.  No GPU library is involved; the GPU suite compares the device's bits
 // with this program's.
 //

@@ -11,7 +11,7 @@ import pytest
 import closest_cases as K
 from test_closest_host import LIMIT_UNITS
 
-EXACT_LANES = 64 * 256                   # k_closest_exact's grid (launch_closest)
+EXACT_LANES = 64 * 256                   # k_closest_exact's grid (launch_walk)
 SCALE_POINTS = 1024
 MID_CAP = K.MID_CAP                      # the intermediate caps and their measured shares: tests/closest_cases.py
 DEFAULT_CAP = {4: 24, 8: 13}

@@ -162,7 +162,7 @@ def test_mixed_waves_equal_the_host_harness(scenes, harness, name):
 
 @pytest.mark.gpu
 def test_a_repeated_point_past_one_grid_pass(scenes, harness):
-    """closest_backward caps the grid at 8 * cu_count blocks of 256: this batch is two full passes of it, three waves and 37 lanes."""
+    """grad_backward caps the grid at 8 * cu_count blocks of 256: this batch is two full passes of it, three waves and 37 lanes."""
     import torch
     # the context's cu_count starts as the device's multiprocessor count; PRT_RESERVE_CUS can only lower it, which shortens a pass
     assert not os.environ.get("PRT_RESERVE_CUS")

@@ -30,7 +30,7 @@ from test_closest_host import LIMIT_UNITS
 from test_gpu_closest import renderers                              # noqa: F401  (the module-scoped fixture)
 from test_gpu_trace_rays_schedules import KNOBS, options
 
-EXACT_LANES = 64 * 256                 # k_closest_exact's grid (launch_closest)
+EXACT_LANES = 64 * 256                 # k_closest_exact's grid (launch_walk)
 DTYPES = dict(dist2=(1, np.float32), point=(3, np.float32), bw=(3, np.float32), vertex0=(1, np.uint32), group=(1, np.int32))
 
 

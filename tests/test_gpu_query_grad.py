@@ -277,7 +277,7 @@ def test_mixed_waves_equal_the_host_harness(scenes, harness, name):
 
 @pytest.mark.gpu
 def test_batches_past_one_grid_pass(scenes, harness):
-    """query_backward caps the grid at 8 * cu_count blocks of 256: this batch is two full passes of it, three waves and 37 lanes."""
+    """grad_backward caps the grid at 8 * cu_count blocks of 256: this batch is two full passes of it, three waves and 37 lanes."""
     import time
     import torch
     # The context's own cu_count is not exported.  It starts as hipGetDeviceProperties' multiProcessorCount - the figure torch

@@ -29,8 +29,8 @@ from conftest import ROOT, host_scene
 from test_gpu_trace_rays import check_fixture, renderers       # noqa: F401  (renderers: the module-scoped fixture)
 
 PER = 192
-EXACT_LANES = 64 * 256                 # k_query_exact's grid (launch_query)
-PAD_LANES = 1024 * 256                 # k_query_pad's grid (run_query)
+EXACT_LANES = 64 * 256                 # k_query_exact's grid (launch_walk)
+PAD_LANES = 1024 * 256                 # k_query_pad's grid (run_batch)
 KNOBS = [dict(KEEP_MIN=1), dict(KEEP_MIN=64), dict(NODE_MIN=0), dict(NODE_MIN=64), dict(CHUNK_MIN=64, KEEP_MIN=64), dict(CHUNK_MIN=512),
          dict(TRACE_BLOCKS_PER_CU=1)]
 
