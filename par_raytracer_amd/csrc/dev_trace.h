@@ -41,8 +41,7 @@ namespace prt {
 template <class STK, bool COUNT>
 PRT_D HitRec resolve_near_ties(const DevScene & sc, f3 o, f3 d, float pad, float min_t, const STK & stk, TraceStats & st) {
     TravRay r;
-    HitRec result;
-    result.t = 3.402823466e+38f; result.v = result.w = 0.0f; result.tri = -1;
+    HitRec result = hit_miss();
     const f3 qp = o - (o + d);
     float bound = min_t * PRT_TIE_NEAR;
     for (unsigned int widen = 0; ; ++widen) {

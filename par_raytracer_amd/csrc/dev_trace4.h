@@ -131,9 +131,7 @@ PRT_D void trav_init(TravRay & r, f3 o, f3 d, int kind, float pad, const STK & s
     r.pnx = (dx < 0.0f ? o.x - pad : o.x + pad) * r.ix;
     r.pny = (dy < 0.0f ? o.y - pad : o.y + pad) * r.iy;
     r.pnz = (dz < 0.0f ? o.z - pad : o.z + pad) * r.iz;
-    r.best.t = 3.402823466e+38f;
-    r.best.v = r.best.w = 0.0f;
-    r.best.tri = -1;
+    r.best = hit_miss();
     r.kind = kind;
     stk.push(0, TRAV_SENTINEL);
     r.sp = 1;

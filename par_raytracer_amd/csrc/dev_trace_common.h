@@ -32,6 +32,12 @@ struct HitRec {
     float v, w;     // bw.y, bw.z (raytracer.cpp:118-119)
     int tri;        // leaf-order triangle index, -1 = miss
 };
+// The record of a miss: what a traversal starts from, and the answer for an item that is a miss by definition.
+PRT_D HitRec hit_miss() {
+    HitRec h;
+    h.t = 3.402823466e+38f; h.v = h.w = 0.0f; h.tri = -1;
+    return h;
+}
 
 enum { TRACE_CLOSEST = 0, TRACE_ANY = 1 };
 

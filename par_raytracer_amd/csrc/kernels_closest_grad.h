@@ -3,10 +3,10 @@
 // reference check and the wave merge are those of the ray queries' gradients: dev_query_grad.h, kernels_query_grad.h).
 //
 //   k_cgrad_scan     grid-stride, one lane per point: resolves the point's triangle from (group, vertex0), validates the
-//                    reference, runs the step and reduces four words - the largest |vertex contribution| of the batch (one
-//                    atomicMax on the float's bits per wave) and the counts of contributing, skipped and invalid points (one
-//                    atomicAdd per wave each).  Runs FIRST and writes only those words; the host reads them and launches
-//                    nothing else when a reference is invalid, so a refused call has written none of the caller's outputs.
+//                    reference, runs the step and reduces four words - the largest |vertex contribution| of the batch and
+//                    the counts of contributing, skipped and invalid points (qgrad_scan_words).  Runs FIRST and writes only
+//                    those words; the host reads them and launches nothing else when a reference is invalid, so a refused
+//                    call has written none of the caller's outputs.
 //   k_cgrad_scatter  reruns the step per point, writes the point's own gradient with plain stores and adds its 9 vertex
 //                    contributions, in units of 2^u, into 64-bit integer accumulators with no-return relaxed agent-scope
 //                    atomics.  MERGE: qgrad_wave_add9 - neighbouring points of a scan land on the same triangle as a rule.
@@ -62,18 +62,7 @@ __global__ __launch_bounds__(256) void k_cgrad_scan(CGradArgs A) {
         if (kind == QGRAD_HIT && !ok) ++skipped;
         if (kind == QGRAD_HIT && ok) { ++hit; m = fmaxf(m, cgrad_abs_max(g)); }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        m = fmaxf(m, __shfl_xor(m, off));
-        hit += __shfl_xor(hit, off);
-        skipped += __shfl_xor(skipped, off);
-        invalid += __shfl_xor(invalid, off);
-    }
-    if ((threadIdx.x & 63u) == 0u) {
-        if (m > 0.0f) atomicMax(A.words + QGRAD_W_MAX, __float_as_uint(m));      // non-negative floats order like their bits
-        if (hit) atomicAdd(A.words + QGRAD_W_HIT, (unsigned int)hit);
-        if (skipped) atomicAdd(A.words + QGRAD_W_SKIPPED, (unsigned int)skipped);
-        if (invalid) atomicAdd(A.words + QGRAD_W_INVALID, (unsigned int)invalid);
-    }
+    qgrad_scan_words(A.words, m, hit, skipped, invalid);
 }
 
 // The loop runs per WAVE (its bound does not depend on the lane), so every lane of a wave reaches the ballots and shuffles of the

@@ -1,30 +1,28 @@
 // kernels_query.h - batched ray queries (prt_trace_rays): the reference's TraceRay (raytracer.cpp:159-232) on rays the caller
 // supplies, without shading.
 //
-//   k_query_pad    max |biased origin component| over the batch, one word (device entry point only: the host entry point
-//                  computes it on the host).  The box pad of dev_trace_common.h assumes origins near the scene; query origins
-//                  can be anywhere, so the pad is 2^-16 x max(scene, origins of this batch).
-//   k_query        PERSISTENT waves shaped like k_trace: a per-lane LDS stack column, chunked atomic fetch of ray indices,
-//                  ballot / mbcnt refill of idle lanes under the context's KEEP_MIN / NODE_MIN, the traversal of dev_trace.h.
-//                  CLOSEST: closest hit; OCCLUDED: any hit below tmax (the best hit starts at tmax: tri_test accepts th < best_t).
-//                  Rays that end flagged (a near tie, or a push that did not fit the LDS column) go to a list, as do CLOSEST rays
-//                  whose direction is not unit length or whose origin is far from the scene (query_replays), and OCCLUDED rays
-//                  from far origins (query_any_unculled).
+//   k_query_pad    max |biased origin component| over the batch's valid rays, one word (device entry point only: the host entry
+//                  point computes it on the host), for batch_pad.
+//   k_query        the wave loop of dev_wave_loop.h over the traversal of dev_trace.h.  CLOSEST: closest hit; OCCLUDED: any hit
+//                  below tmax (the best hit starts at tmax: tri_test accepts th < best_t).  A ray that is a miss by definition is
+//                  written at once.  Rays that end flagged (a near tie, or a push that did not fit the LDS column) go to a list,
+//                  as do CLOSEST rays whose direction is not unit length or whose origin is far from the scene (query_replays),
+//                  and OCCLUDED rays from far origins (query_any_unculled).
 //   k_query_exact  traces the listed rays again on a full-height global stack: trace_ray (near ties decided in the reference's
 //                  visit order by resolve_near_ties), the full replay of TraceRay for non-unit directions, or the any-hit walk
 //                  below tmax.
 // Only the fields the caller asked for are written (a wave-uniform mask), with plain vector stores.
 #pragma once
 
-#include "dev_trace.h"
-#include "kernels_wave.h"            // lane_id
+#include "dev_wave_loop.h"
+#include "dev_wave_reduce.h"
 
 namespace prt {
 
 enum { QUERY_CLOSEST = 0, QUERY_OCCLUDED = 1 };
 enum { QF_T = 1, QF_BW = 2, QF_VERTEX0 = 4, QF_GROUP = 8, QF_POSITION = 16, QF_NORMAL = 32, QF_OCCLUDED = 64 };
 
-struct QueryArgs {
+struct QueryArgs : BatchShared {
     const float * origins;           // count x 3
     const float * dirs;              // count x 3
     const float * tmax;              // count, OCCLUDED only; null = no limit
@@ -38,19 +36,8 @@ struct QueryArgs {
     float * position;                // x3
     float * normal;                  // x3
     unsigned char * occluded;
-    // [0] fetch head, [1] length of `slow`, [2] max |biased origin component| as float bits (k_query_pad)
-    unsigned int * work;
-    unsigned int * slow;             // ray indices for k_query_exact
     float replay_beyond;             // CLOSEST rays whose biased origin lies further out are replayed (query_replays)
-    float pad_max;                   // max(scene, origins) when the host computed it, else the scene's; pad = 2^-16 x max(this, work[2])
-    unsigned int stack_lds_entries;
-    int * exact_stack;               // k_query_exact's full-height global stack columns
-    unsigned int exact_stack_stride;
 };
-
-PRT_D float query_pad(const QueryArgs & A) {
-    return fmaxf(A.pad_max, __uint_as_float(A.work[2])) * (1.0f / 65536.0f);
-}
 
 // Ray i, origin biased as TraceRay does (raytracer.cpp:163).  False for a ray that is a miss by definition: a non-finite
 // origin or direction component, a zero direction.
@@ -114,18 +101,43 @@ PRT_D void query_emit(const DevScene & sc, const QueryArgs & A, const uint2 * le
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// max |biased origin component| of the valid rays -> work[2] (non-negative floats order like their bits: one atomicMax)
+// max |biased origin component| of the valid rays -> work[BATCH_W_EXTENT]
 __global__ __launch_bounds__(256) void k_query_pad(QueryArgs A) {
     float m = 0.0f;
     for (unsigned int i = blockIdx.x * blockDim.x + threadIdx.x; i < A.count; i += gridDim.x * blockDim.x) {
         f3 ob, d;
         if (query_ray(A, i, ob, d)) m = fmaxf(m, fmaxf(fmaxf(fabsf(ob.x), fabsf(ob.y)), fabsf(ob.z)));
     }
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-    if ((threadIdx.x & 63u) == 0u && m > 0.0f) atomicMax(A.work + 2, __float_as_uint(m));
+    wave_max_to_word(A.work + BATCH_W_EXTENT, m);
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// k_query's job for the wave loop: a lane's item is a ray of the batch.
+template <int BLOCK, int MODE, bool COUNT>
+struct QueryJob : RaySteps<BLOCK, COUNT> {
+    const QueryArgs & A;
+    const uint2 * leaf_map;
+    unsigned int fields;
+    PRT_D bool start(unsigned int idx, TravRay & r, const LdsStack<BLOCK> & stack) const {
+        f3 ob, d;
+        const bool valid = query_ray(A, idx, ob, d);
+        if (valid && (MODE == QUERY_CLOSEST ? query_replays(A, ob, d) : query_far(A, ob))) {
+            batch_to_slow_list(A, idx);                                     // query_replays / query_any_unculled
+        } else if (valid) {
+            trav_init(r, ob, d, MODE == QUERY_OCCLUDED ? TRACE_ANY : TRACE_CLOSEST, this->pad, stack);
+            if (MODE == QUERY_OCCLUDED && A.tmax) r.best.t = A.tmax[idx];
+            return true;
+        } else {
+            query_emit<MODE>(this->sc, A, leaf_map, fields, idx, ob, d, hit_miss());
+        }
+        return false;
+    }
+    PRT_D void finish(unsigned int idx, const TravRay & r, const LdsStack<BLOCK> & stack) const {
+        if (trav_needs_slow_path(r, stack)) batch_to_slow_list(A, idx);
+        else query_emit<MODE>(this->sc, A, leaf_map, fields, idx, r.o, r.d, r.best);       // r.o: the biased origin
+    }
+};
+
 // Persistent traversal of the batch.  grid = resident blocks; dynamic LDS = stack_lds_entries * BLOCK * 4.
 template <int BLOCK, int MODE, bool COUNT>
 __global__ __launch_bounds__(BLOCK, 6) void k_query(DevScene sc, QueryArgs A, const uint2 * leaf_map, unsigned int fields,
@@ -134,83 +146,9 @@ __global__ __launch_bounds__(BLOCK, 6) void k_query(DevScene sc, QueryArgs A, co
     LdsStack<BLOCK> stack;
     stack.attach(s_stack, threadIdx.x);
     stack.cap = A.stack_lds_entries;
-    const unsigned int total = A.count;
-    const unsigned int lane = lane_id();
-    const float pad = query_pad(A);
-    unsigned int * head = A.work;
-
-    TravRay r;
-    trav_idle(r);
-    int ray = -1;                        // batch index of the lane's ray, -1 = idle
-    bool exhausted = false;              // wave-uniform: the batch has no more rays to hand out
     TraceStats st;
-
-    unsigned int chunk_next = 0, chunk_end = 0;      // wave-uniform: rays reserved for this wave, not yet handed out
-    for (;;) {
-        // ---- refill idle lanes from the wave's reserved chunk (as k_trace); a ray that is a miss by definition is written at once
-        const unsigned long long idle = __ballot(ray < 0);
-        if (idle != 0ull && !(exhausted && chunk_next == chunk_end)) {
-            if (chunk_next == chunk_end) {
-                unsigned int base = 0;
-                if (lane == 0) base = atomicAdd(head, chunk);
-                base = (unsigned int)__shfl((int)base, 0);
-                if (base >= total) {
-                    exhausted = true;
-                } else {
-                    chunk_next = base;
-                    chunk_end = base + chunk < total ? base + chunk : total;
-                }
-            }
-            const unsigned int avail = chunk_end - chunk_next;
-            if (COUNT && avail && lane == 0) st.wrefills++;
-            if (avail) {
-                const unsigned int prefix = __builtin_amdgcn_mbcnt_hi((unsigned int)(idle >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)idle, 0u));
-                const unsigned int n_idle = (unsigned int)__popcll(idle);
-                const unsigned int take = n_idle < avail ? n_idle : avail;
-                if (ray < 0 && prefix < take) {
-                    const unsigned int idx = chunk_next + prefix;
-                    f3 ob, d;
-                    const bool valid = query_ray(A, idx, ob, d);
-                    if (valid && (MODE == QUERY_CLOSEST ? query_replays(A, ob, d) : query_far(A, ob))) {
-                        A.slow[atomicAdd(A.work + 1, 1u)] = idx;                    // query_replays / query_any_unculled
-                    } else if (valid) {
-                        trav_init(r, ob, d, MODE == QUERY_OCCLUDED ? TRACE_ANY : TRACE_CLOSEST, pad, stack);
-                        if (MODE == QUERY_OCCLUDED && A.tmax) r.best.t = A.tmax[idx];
-                        ray = (int)idx;
-                    } else {
-                        HitRec miss;
-                        miss.t = 3.402823466e+38f; miss.v = miss.w = 0.0f; miss.tri = -1;
-                        query_emit<MODE>(sc, A, leaf_map, fields, idx, ob, d, miss);
-                    }
-                }
-                chunk_next += take;
-            }
-        }
-        if (__ballot(ray >= 0) == 0ull) {
-            if (exhausted && chunk_next == chunk_end) break;
-            continue;                    // every ray of the refill was a miss by definition: refill again
-        }
-
-        // ---- traverse until fewer than `leave_below` lanes of the wave are still busy (k_trace's loop)
-        const int leave_below = (exhausted && chunk_next == chunk_end) ? 1 : keep_min;
-        while (ray >= 0) {
-            const int walkers = __popcll(__ballot(trav_walking(r)));
-            const int nmin = node_min < (walkers >> 1) ? node_min : (walkers >> 1);
-            while (trav_walking(r)) {
-                trav_node_step<LdsStack<BLOCK>, COUNT>(sc, r, stack, st, pad);
-                if (__popcll(__ballot(trav_walking(r))) < nmin) break;
-            }
-            bool fin = trav_done(r);
-            if (!fin && !trav_walking(r)) fin = trav_leaf<LdsStack<BLOCK>, COUNT>(sc, r, stack, st);
-            if (fin) {
-                if (trav_needs_slow_path(r, stack)) A.slow[atomicAdd(A.work + 1, 1u)] = (unsigned int)ray;
-                else query_emit<MODE>(sc, A, leaf_map, fields, (unsigned int)ray, r.o, r.d, r.best);   // r.o: the biased origin
-                ray = -1;
-                break;
-            }
-            if (__popcll(__ballot(true)) < leave_below) break;
-        }
-    }
+    QueryJob<BLOCK, MODE, COUNT> job = { { sc, batch_pad(A) }, A, leaf_map, fields };
+    wave_loop<BLOCK, COUNT>(job, stack, st, A.work + BATCH_W_HEAD, A.count, keep_min, node_min, chunk);
     if (COUNT) trace_stats_flush<true>(ctr, st);
 }
 
@@ -238,8 +176,7 @@ PRT_D HitRec query_any_unculled(const DevScene & sc, f3 o, f3 d, float tmax, flo
     trav_init(r, o, d, TRACE_ANY, pad, stk);
     r.best.t = __uint_as_float(0x7F800000u);
     const f3 qp = o - (o + d);                                              // raytracer.cpp:88-89
-    HitRec h;
-    h.t = 3.402823466e+38f; h.v = h.w = 0.0f; h.tri = -1;
+    HitRec h = hit_miss();
     for (;;) {
         while (trav_walking(r)) trav_node_step<STK, COUNT>(sc, r, stk, st, pad);
         if (trav_done(r)) break;
@@ -261,18 +198,12 @@ PRT_D HitRec query_any_unculled(const DevScene & sc, f3 o, f3 d, float tmax, flo
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Slow path of k_query (as k_trace_exact is k_trace's): a small fixed grid that reads the list length on the device.
+// Slow path of k_query (exact_list_walk).
 template <int MODE, bool COUNT>
 __global__ __launch_bounds__(256) void k_query_exact(DevScene sc, QueryArgs A, const uint2 * leaf_map, unsigned int fields,
                                                      DevCounters * ctr) {
-    const unsigned int gid = blockIdx.x * blockDim.x + threadIdx.x;
-    const unsigned int n_slow = A.work[1];
-    const float pad = query_pad(A);
-    TraceStats st;
-    GlobalStack slow;
-    slow.attach(A.exact_stack, gid, A.exact_stack_stride);
-    for (unsigned int i = gid; i < n_slow; i += gridDim.x * blockDim.x) {
-        const unsigned int idx = A.slow[i];
+    const float pad = batch_pad(A);
+    exact_list_walk<COUNT>(A.slow, A.work[BATCH_W_SLOW], A.exact_stack, A.exact_stack_stride, ctr, [&](unsigned int idx, const GlobalStack & slow, TraceStats & st) {
         f3 ob, d;
         (void)query_ray(A, idx, ob, d);                                     // listed rays are valid
         HitRec h;
@@ -285,8 +216,7 @@ __global__ __launch_bounds__(256) void k_query_exact(DevScene sc, QueryArgs A, c
         else
             h = trace_ray<GlobalStack, COUNT>(sc, ob, d, TRACE_CLOSEST, pad, slow, st);
         query_emit<MODE>(sc, A, leaf_map, fields, idx, ob, d, h);
-    }
-    if (COUNT) trace_stats_flush<false>(ctr, st);
+    });
 }
 
 }  // namespace prt

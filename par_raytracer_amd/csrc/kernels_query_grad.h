@@ -2,10 +2,10 @@
 // batch of closest-hit queries, from the gradients of their outputs (dev_query_grad.h has the per-ray step and the fixed point).
 //
 //   k_qgrad_scan     grid-stride, one lane per ray: resolves the ray's triangle from (group, vertex0), validates the reference,
-//                    runs the step and reduces four words - the largest |vertex contribution| of the batch (one atomicMax on the
-//                    float's bits per wave, as k_query_pad) and the counts of contributing, skipped and invalid rays (one
-//                    atomicAdd per wave each).  Runs FIRST and writes only those words; the host reads them and launches
-//                    nothing else when a reference is invalid, so a refused call has written none of the caller's outputs.
+//                    runs the step and reduces four words - the largest |vertex contribution| of the batch and the counts of
+//                    contributing, skipped and invalid rays (one atomic per wave each: dev_wave_reduce.h).  Runs FIRST and
+//                    writes only those words; the host reads them and launches nothing else when a reference is invalid, so a
+//                    refused call has written none of the caller's outputs.
 //   k_qgrad_scatter  reruns the step per ray, writes the ray's origin and direction gradients with plain stores and adds its 9
 //                    vertex contributions, in units of 2^u, into 64-bit integer accumulators with no-return relaxed agent-scope
 //                    atomics (accum_add's of dev_scene.h).  MERGE: the lanes of a wave that hit the same triangle - camera rays
@@ -18,6 +18,7 @@
 #pragma once
 
 #include "dev_query_grad.h"
+#include "dev_wave_reduce.h"
 
 namespace prt {
 
@@ -55,6 +56,14 @@ PRT_HD int qgrad_ray(const QGradArgs & A, unsigned int i, unsigned int * first_c
     return QGRAD_HIT;
 }
 
+// A scan's four words (k_qgrad_scan, k_cgrad_scan) from its lanes' partials.
+PRT_D void qgrad_scan_words(unsigned int * words, float m, int hit, int skipped, int invalid) {
+    wave_max_to_word(words + QGRAD_W_MAX, m);
+    wave_sum_to_word(words + QGRAD_W_HIT, hit);
+    wave_sum_to_word(words + QGRAD_W_SKIPPED, skipped);
+    wave_sum_to_word(words + QGRAD_W_INVALID, invalid);
+}
+
 __global__ __launch_bounds__(256) void k_qgrad_scan(QGradArgs A) {
     float m = 0.0f;
     int hit = 0, skipped = 0, invalid = 0;
@@ -67,18 +76,7 @@ __global__ __launch_bounds__(256) void k_qgrad_scan(QGradArgs A) {
         if (kind == QGRAD_HIT && !ok) ++skipped;
         if (kind == QGRAD_HIT && ok) { ++hit; m = fmaxf(m, qgrad_abs_max(g)); }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        m = fmaxf(m, __shfl_xor(m, off));
-        hit += __shfl_xor(hit, off);
-        skipped += __shfl_xor(skipped, off);
-        invalid += __shfl_xor(invalid, off);
-    }
-    if ((threadIdx.x & 63u) == 0u) {
-        if (m > 0.0f) atomicMax(A.words + QGRAD_W_MAX, __float_as_uint(m));      // non-negative floats order like their bits
-        if (hit) atomicAdd(A.words + QGRAD_W_HIT, (unsigned int)hit);
-        if (skipped) atomicAdd(A.words + QGRAD_W_SKIPPED, (unsigned int)skipped);
-        if (invalid) atomicAdd(A.words + QGRAD_W_INVALID, (unsigned int)invalid);
-    }
+    qgrad_scan_words(A.words, m, hit, skipped, invalid);
 }
 
 PRT_D void qgrad_add9(long long * acc, const unsigned int * vi, const long long * q) {

@@ -1,7 +1,7 @@
 // kernels_refit.h - prt_update_geometry on the device: the uploaded scene's vertices move, the tree's boxes follow them.
 //
-//   k_refit_bounds   grid-stride reduction over the positions the triangles reference: max |coordinate| (one atomicMax on the
-//                    float's bits per wave, as k_query_pad) and a flag for a coordinate that is not finite or not below 1e18 (the
+//   k_refit_bounds   grid-stride reduction over the positions the triangles reference: max |coordinate| (wave_max_to_word of
+//                    dev_wave_reduce.h) and a flag for a coordinate that is not finite or not below 1e18 (the
 //                    upload's rule).  Runs FIRST and writes two words of its own; the host reads them and launches nothing else
 //                    when the flag is set, so a refused update has modified nothing of the scene.
 //   k_refit_records  one lane per leaf slot: gathers the triangle's three positions through the table (dev_refit.h) and writes
@@ -21,6 +21,7 @@
 
 #include "dev_refit.h"
 #include "dev_scene.h"
+#include "dev_wave_reduce.h"
 
 namespace prt {
 
@@ -48,14 +49,9 @@ __global__ __launch_bounds__(256) void k_refit_bounds(RefitArgs A) {
             else m = fmaxf(m, v);
         }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        m = fmaxf(m, __shfl_xor(m, off));
-        bad |= (unsigned int)__shfl_xor((int)bad, off);
-    }
-    if ((threadIdx.x & 63u) == 0u) {
-        if (m > 0.0f) atomicMax(A.bounds, __float_as_uint(m));    // non-negative floats order like their bits
-        if (bad) atomicOr(A.bounds + 1, 1u);
-    }
+    wave_max_to_word(A.bounds, m);
+    for (int off = 32; off > 0; off >>= 1) bad |= (unsigned int)__shfl_xor((int)bad, off);
+    if ((threadIdx.x & 63u) == 0u && bad) atomicOr(A.bounds + 1, 1u);
 }
 
 __global__ __launch_bounds__(256) void k_refit_records(RefitArgs A) {

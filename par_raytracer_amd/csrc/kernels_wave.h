@@ -5,11 +5,8 @@
 // work.  Here rays are independent work items in structure-of-arrays queues in HBM:
 //
 //   k_raygen   one lane per (pixel, sample): seed the RNG, jitter, camera ray -> closest-hit queue
-//   k_trace    PERSISTENT waves pull rays (closest-hit and shadow rays mixed) from the queues through one
-//              atomic head; a lane that finishes its ray goes idle, and when fewer than KEEP_MIN lanes of a
-//              wave are still traversing, the wave leaves the loop, compacts its idle lanes with
-//              ballot / mbcnt and refills them with the next rays.  Traversal state (node, stack pointer,
-//              best hit) stays in registers + the per-lane LDS stack column across refills.
+//   k_trace    PERSISTENT waves pull rays (closest-hit and shadow rays mixed) from the queues: the wave loop of
+//              dev_wave_loop.h over the traversal of dev_trace.h; k_trace_exact traces again what it set aside.
 //   k_shade    one lane per closest-hit result: runs the sample's bounce-tree state machine until the next
 //              ray, appends it (and the shadow rays of the hit) to the next round's queues with one
 //              wave-aggregated atomic per queue.
@@ -27,6 +24,7 @@
 #include "../../include/prt_key.h"
 #include "dev_shade.h"
 #include "dev_texture.h"
+#include "dev_wave_loop.h"
 
 namespace prt {
 
@@ -62,8 +60,6 @@ struct WaveBuffers {
     unsigned int n_samples;      // samples of THIS chain (all per-sample arrays are indexed 0 .. n_samples)
     unsigned int sample_base;    // global id of its first sample (pixel / key derivation only)
 };
-
-PRT_D unsigned int lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 
 // Wave-aggregated queue append: one atomic per wave, slots handed out by rank among the appending lanes.
 PRT_D unsigned int wave_append(unsigned int * counter, bool pred) {
@@ -117,21 +113,6 @@ PRT_D float4 shadow_entry_dir(const DevLight * lights, float4 payload, const flo
 // distance test against w = distance^2 (:396)
 PRT_D bool shadow_lit(const HitRec & h, float w) { return h.tri < 0 || (w >= 0.0f && h.t * h.t <= w); }
 
-// A kernel's TraceStats into the context's counters.  FULL: the persistent kernels' wave-level counters too; else what the
-// slow kernels count.  (culled and k_pool's own counters stay with the kernels that report them.)
-template <bool FULL>
-PRT_D void trace_stats_flush(DevCounters * ctr, const TraceStats & st) {
-    atomicAdd(&ctr->node_visits, (unsigned long long)st.nodes);
-    atomicAdd(&ctr->tri_tests, (unsigned long long)st.tris);
-    if (FULL) {
-        atomicAdd(&ctr->wave_node_steps, (unsigned long long)st.wnodes);
-        atomicAdd(&ctr->wave_leaf_steps, (unsigned long long)st.wleaves);
-        atomicAdd(&ctr->wave_tri_steps, (unsigned long long)st.wtris);
-        atomicAdd(&ctr->wave_refills, (unsigned long long)st.wrefills);
-        atomicMax(&ctr->max_sp, (unsigned long long)st.max_sp);
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------
 template <bool RING>
 __global__ __launch_bounds__(256) void k_raygen(DevCamera cam, DevParams P, WaveBuffers B) {
@@ -152,6 +133,61 @@ __global__ __launch_bounds__(256) void k_raygen(DevCamera cam, DevParams P, Wave
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Entry idx of the round's combined [closest | shadow] ray space: the ray as TraceRay takes it (origin biased,
+// raytracer.cpp:163), its sample, and a shadow ray's payload (a closest-hit ray leaves `payload` as it is).
+struct TraceEntry {
+    f3 ob, d;
+    int kind, sample;
+};
+PRT_D TraceEntry trace_entry(const DevScene & sc, const DevParams & P, const WaveBuffers & B, int cur, unsigned int n_closest,
+                             unsigned int idx, float4 & payload) {
+    float4 ro, rd;
+    TraceEntry e;
+    if (idx < n_closest) {
+        ro = B.rq_o[cur][idx];
+        rd = B.rq_d[cur][idx];
+        e.kind = WF_KIND_CLOSEST;
+    } else {
+        const unsigned int j = idx - n_closest;
+        ro = B.sq_o[j];
+        payload = B.sq_c[j];
+        rd = shadow_entry_dir(sc.lights, payload, B.sq_d, j, e.kind);
+    }
+    e.sample = as_i(ro.w);
+    e.d = mk3(rd.x, rd.y, rd.z);
+    e.ob = mk3(ro.x, ro.y, ro.z) + e.d * P.ray_bias;
+    return e;
+}
+PRT_D int trace_entry_mode(const TraceEntry & e) { return e.kind == WF_KIND_SHADOW_ANY ? TRACE_ANY : TRACE_CLOSEST; }
+// The traced entry's result: a closest-hit ray's record for k_shade; a shadow ray adds its precomputed radiance when unoccluded.
+PRT_D void trace_entry_emit(const WaveBuffers & B, unsigned int n_closest, unsigned int idx, const HitRec & best, float4 payload, int sample) {
+    if (idx < n_closest) B.hits[idx] = make_float4(best.t, best.v, best.w, as_f(best.tri));
+    else if (shadow_lit(best, payload.w)) accum_add(B.accum + sample, mk3(payload.x, payload.y, payload.z));
+}
+
+// k_trace's job for the wave loop: a lane's item is a queue entry; every entry walks.
+template <int BLOCK, bool COUNT>
+struct TraceJob : RaySteps<BLOCK, COUNT> {
+    const DevParams & P;
+    const WaveBuffers & B;
+    int cur;
+    unsigned int n_closest;
+    float4 payload;
+    int sample;
+    PRT_D bool start(unsigned int idx, TravRay & r, const LdsStack<BLOCK> & stack) {
+        const TraceEntry e = trace_entry(this->sc, P, B, cur, n_closest, idx, payload);
+        sample = e.sample;
+        trav_init(r, e.ob, e.d, trace_entry_mode(e), this->pad, stack);
+        return true;
+    }
+    PRT_D void finish(unsigned int idx, const TravRay & r, const LdsStack<BLOCK> & stack) const {
+        // rare: the hit has company within a few ulp and the reference's visit order decides (dev_trace.h), or a push did not
+        // fit the LDS column (never observed on real scenes): hand the ray to k_trace_exact, before k_shade runs
+        if (trav_needs_slow_path(r, stack)) B.overflow[atomicAdd(B.counts + 3, 1u)] = idx;
+        else trace_entry_emit(B, n_closest, idx, r.best, payload, sample);
+    }
+};
+
 // Persistent traversal.  grid = resident blocks; dynamic LDS = stack_entries * BLOCK * 4.
 template <int BLOCK, bool COUNT>
 __global__ __launch_bounds__(BLOCK, 6) void k_trace(DevScene sc, DevParams P, WaveBuffers B, int cur, unsigned int n_closest,
@@ -161,100 +197,9 @@ __global__ __launch_bounds__(BLOCK, 6) void k_trace(DevScene sc, DevParams P, Wa
     LdsStack<BLOCK> stack;
     stack.attach(s_stack, threadIdx.x);
     stack.cap = P.stack_lds_entries;
-    const unsigned int total = n_closest + n_shadow;
-    const unsigned int lane = lane_id();
-    const float4 * rq_o = B.rq_o[cur];
-    const float4 * rq_d = B.rq_d[cur];
-    unsigned int * head = B.counts + 2;
-
-    TravRay r;
-    trav_idle(r);
-    int ray = -1;                        // index into the combined [closest | shadow] ray space, -1 = idle
-    float4 payload = make_float4(0, 0, 0, 0);
-    int sample = 0;
-    bool exhausted = false;              // wave-uniform: the queue has no more rays to hand out
     TraceStats st;
-
-    unsigned int chunk_next = 0, chunk_end = 0;      // wave-uniform: rays reserved for this wave, not yet handed out
-    for (;;) {
-        // ---- refill idle lanes from the wave's reserved chunk; reserve a new chunk when it runs dry.
-        // One atomic per CHUNK rays, not per refill: the head word is a single address (~90 atomics/us chip-wide).
-        const unsigned long long idle = __ballot(ray < 0);
-        if (idle != 0ull && !(exhausted && chunk_next == chunk_end)) {
-            if (chunk_next == chunk_end) {
-                unsigned int base = 0;
-                if (lane == 0) base = atomicAdd(head, chunk);
-                base = (unsigned int)__shfl((int)base, 0);
-                if (base >= total) {
-                    exhausted = true;
-                } else {
-                    chunk_next = base;
-                    chunk_end = base + chunk < total ? base + chunk : total;
-                }
-            }
-            const unsigned int avail = chunk_end - chunk_next;
-            if (COUNT && avail && lane == 0) st.wrefills++;
-            if (avail) {
-                const unsigned int prefix = __builtin_amdgcn_mbcnt_hi((unsigned int)(idle >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)idle, 0u));
-                const unsigned int n_idle = (unsigned int)__popcll(idle);
-                const unsigned int take = n_idle < avail ? n_idle : avail;
-                if (ray < 0 && prefix < take) {
-                    const unsigned int idx = chunk_next + prefix;
-                    float4 ro, rd;
-                    int kind;
-                    if (idx < n_closest) {
-                        ro = rq_o[idx];
-                        rd = rq_d[idx];
-                        kind = WF_KIND_CLOSEST;
-                    } else {
-                        const unsigned int j = idx - n_closest;
-                        ro = B.sq_o[j];
-                        payload = B.sq_c[j];
-                        rd = shadow_entry_dir(sc.lights, payload, B.sq_d, j, kind);
-                    }
-                    sample = as_i(ro.w);
-                    const f3 d = mk3(rd.x, rd.y, rd.z);
-                    const f3 ob = mk3(ro.x, ro.y, ro.z) + d * P.ray_bias;          // raytracer.cpp:163
-                    trav_init(r, ob, d, kind == WF_KIND_SHADOW_ANY ? TRACE_ANY : TRACE_CLOSEST, P.box_pad, stack);
-                    ray = (int)idx;
-                }
-                chunk_next += take;
-            }
-        }
-        if (__ballot(ray >= 0) == 0ull) break;
-
-        // ---- traverse until fewer than `leave_below` lanes of the wave are still busy
-        const int leave_below = (exhausted && chunk_next == chunk_end) ? 1 : keep_min;
-        while (ray >= 0) {
-            // Node phase.  Lanes drop out as they reach a leaf; once fewer than `node_min` lanes are still
-            // walking, the stragglers are suspended too (they keep their node) so the wave can run the leaf
-            // phase for the majority instead of idling behind the longest walk.
-            const int walkers = __popcll(__ballot(trav_walking(r)));
-            const int nmin = node_min < (walkers >> 1) ? node_min : (walkers >> 1);
-            while (trav_walking(r)) {
-                trav_node_step<LdsStack<BLOCK>, COUNT>(sc, r, stack, st, P.box_pad);
-                if (__popcll(__ballot(trav_walking(r))) < nmin) break;
-            }
-            bool fin = trav_done(r);
-            if (!fin && !trav_walking(r)) fin = trav_leaf<LdsStack<BLOCK>, COUNT>(sc, r, stack, st);
-            if (fin) {
-                if (trav_needs_slow_path(r, stack)) {
-                    // rare: the hit has company within a few ulp and the reference's visit order decides (dev_trace.h), or
-                    // a push did not fit the LDS column (never observed on real scenes): hand the ray to k_trace_exact, which
-                    // traces it again on a full-height stack and replays that order, before k_shade runs
-                    B.overflow[atomicAdd(B.counts + 3, 1u)] = (unsigned int)ray;
-                } else if ((unsigned int)ray < n_closest) {
-                    B.hits[ray] = make_float4(r.best.t, r.best.v, r.best.w, as_f(r.best.tri));
-                } else {
-                    // shadow ray: add the precomputed radiance when unoccluded
-                    if (shadow_lit(r.best, payload.w)) accum_add(B.accum + sample, mk3(payload.x, payload.y, payload.z));
-                }
-                ray = -1;
-                break;
-            }
-            if (__popcll(__ballot(true)) < leave_below) break;
-        }
-    }
+    TraceJob<BLOCK, COUNT> job = { { sc, P.box_pad }, P, B, cur, n_closest, make_float4(0, 0, 0, 0), 0 };
+    wave_loop<BLOCK, COUNT>(job, stack, st, B.counts + 2, n_closest + n_shadow, keep_min, node_min, chunk);
     if (COUNT) {
         trace_stats_flush<true>(ctr, st);
         atomicAdd(&ctr->culled, (unsigned long long)st.culled);
@@ -263,42 +208,17 @@ __global__ __launch_bounds__(BLOCK, 6) void k_trace(DevScene sc, DevParams P, Wa
 
 // ---------------------------------------------------------------------------------------------------------
 // Slow path of k_trace: rays whose hit has a near tie or whose LDS stack column overflowed are traced again by trace_ray,
-// which replays the reference's visit order over near-tied candidates (dev_trace.h resolve_near_ties), on a per-lane global
-// stack that holds the full worst-case bound.  A small fixed grid launched after every k_trace; it reads the list length on the device (no host round trip)
-// and normally finds 0.
+// which replays the reference's visit order over near-tied candidates (dev_trace.h resolve_near_ties), on a stack that holds
+// the full worst-case bound (exact_list_walk).
 template <bool COUNT>
 __global__ __launch_bounds__(256) void k_trace_exact(DevScene sc, DevParams P, WaveBuffers B, int cur, unsigned int n_closest,
                                                          int multi_light, DevCounters * ctr) {
-    const unsigned int gid = blockIdx.x * blockDim.x + threadIdx.x;
-    const unsigned int n_overflow = B.counts[3];
-    TraceStats st;
-    GlobalStack slow;
-    slow.attach(P.exact_stack, gid, P.exact_stack_stride);
-    for (unsigned int i = gid; i < n_overflow; i += gridDim.x * blockDim.x) {
-        const unsigned int idx = B.overflow[i];
-        float4 ro, rd, payload = make_float4(0, 0, 0, 0);
-        int kind;
-        if (idx < n_closest) {
-            ro = B.rq_o[cur][idx];
-            rd = B.rq_d[cur][idx];
-            kind = WF_KIND_CLOSEST;
-        } else {
-            const unsigned int j = idx - n_closest;
-            ro = B.sq_o[j];
-            payload = B.sq_c[j];
-            rd = shadow_entry_dir(sc.lights, payload, B.sq_d, j, kind);
-        }
-        const int sample = as_i(ro.w);
-        const f3 d = mk3(rd.x, rd.y, rd.z);
-        const f3 ob = mk3(ro.x, ro.y, ro.z) + d * P.ray_bias;
-        const HitRec best = trace_ray<GlobalStack, COUNT>(sc, ob, d, kind == WF_KIND_SHADOW_ANY ? TRACE_ANY : TRACE_CLOSEST, P.box_pad, slow, st);
-        if (idx < n_closest) {
-            B.hits[idx] = make_float4(best.t, best.v, best.w, as_f(best.tri));
-        } else {
-            if (shadow_lit(best, payload.w)) accum_add(B.accum + sample, mk3(payload.x, payload.y, payload.z));
-        }
-    }
-    if (COUNT) trace_stats_flush<false>(ctr, st);
+    exact_list_walk<COUNT>(B.overflow, B.counts[3], P.exact_stack, P.exact_stack_stride, ctr, [&](unsigned int idx, const GlobalStack & slow, TraceStats & st) {
+        float4 payload = make_float4(0, 0, 0, 0);
+        const TraceEntry e = trace_entry(sc, P, B, cur, n_closest, idx, payload);
+        const HitRec best = trace_ray<GlobalStack, COUNT>(sc, e.ob, e.d, trace_entry_mode(e), P.box_pad, slow, st);
+        trace_entry_emit(B, n_closest, idx, best, payload, e.sample);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------------

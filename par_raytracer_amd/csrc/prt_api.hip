@@ -178,7 +178,7 @@ struct prt_ctx {
     std::vector<uint32_t> q_tri_order;    // leaf slot -> input triangle
     std::vector<prt_group> q_groups;
     DevBuf<uint2> q_leaf_map;             // leaf slot -> (group, vertex0)
-    DevBuf<unsigned int> q_work;          // fetch head, slow-list length, origin extent (QueryArgs::work)
+    DevBuf<unsigned int> q_work;          // the batch's control words (BatchShared::work, dev_wave_loop.h)
     DevBuf<unsigned int> q_slow;          // rays handed to k_query_exact
     DevBuf<int> q_exact_stack;
     DevBuf<float> q_io;                   // host entry point: the batch and the requested fields on the device
@@ -1328,7 +1328,7 @@ int run_batch(prt_ctx * ctx, const Walk & q, typename Walk::Args A, unsigned int
     HIP_TRY(ctx, ctx->q_exact_stack.ensure(stack_dwords(std::max(ctx->stack_bound, 4u), exact_lanes)));
     A.exact_stack = ctx->q_exact_stack.p;
     A.exact_stack_stride = (unsigned int)exact_lanes;
-    HIP_TRY(ctx, ctx->q_work.ensure(4));
+    HIP_TRY(ctx, ctx->q_work.ensure(BATCH_WORDS));
     HIP_TRY(ctx, ctx->q_slow.ensure(A.count));
     HIP_TRY(ctx, ctx->counters.ensure(1));
     A.work = ctx->q_work.p;
@@ -1337,7 +1337,7 @@ int run_batch(prt_ctx * ctx, const Walk & q, typename Walk::Args A, unsigned int
     if (device_pad) A.pad_max = ctx->scene_abs_max;
 
     HIP_TRY(ctx, hipMemsetAsync(ctx->counters.p, 0, sizeof(DevCounters), stream));
-    HIP_TRY(ctx, hipMemsetAsync(A.work, 0, 4 * sizeof(unsigned int), stream));
+    HIP_TRY(ctx, hipMemsetAsync(A.work, 0, BATCH_WORDS * sizeof(unsigned int), stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev[0], stream));
     if (const int rc = q.tables(ctx, A, fields)) return rc;
     if (device_pad) {
@@ -1901,7 +1901,7 @@ int trace_rays(prt_ctx * ctx, int mode, const prt_ray_batch * batch, const prt_h
     io.out(&A.occluded, n, fields & QF_OCCLUDED, false);
     HIP_TRY(ctx, io.carve(ctx->q_io));
     if (fields & QF_OCCLUDED) { HIP_TRY(ctx, ctx->q_occ.ensure(n)); A.occluded = ctx->q_occ.p; }
-    // the box pad from the origins' extent, on the host (the same rule as k_query_pad)
+    // batch_pad's extent from the valid rays' biased origins, on the host (k_query_pad's rule; work[BATCH_W_EXTENT] stays 0)
     float extent = ctx->scene_abs_max;
     for (size_t i = 0; i < n; ++i) {
         const f3 o = ld3(batch->origins + 3 * i), d = ld3(batch->directions + 3 * i), ob = o + d * batch->ray_bias;
@@ -1938,7 +1938,7 @@ int closest_points(prt_ctx * ctx, const prt_point_batch * batch, const prt_signe
     io.out(&A.vertex0, 4 * n, fields & CF_VERTEX0); io.out(&A.group, 4 * n, fields & CF_GROUP); io.out(&A.signed_dist, 4 * n, fields & CF_SIGNED);
     io.out(&A.feature, n, fields & CF_FEATURE);
     HIP_TRY(ctx, io.carve(ctx->q_io));
-    // the box pad from the points' extent, on the host (the same rule as k_closest_pad)
+    // batch_pad's extent from the finite points, on the host (k_closest_pad's rule; work[BATCH_W_EXTENT] stays 0)
     float extent = ctx->scene_abs_max;
     for (size_t i = 0; i < n; ++i) {
         const f3 q = ld3(batch->points + 3 * i);
