@@ -668,7 +668,8 @@ int prt_debug_check_refit(prt_ctx * ctx, const prt_scene_desc * moved_scene, uin
 /* Device known-answer hook (GPU test-suite): runs one device function of the hot path on `n` caller-supplied
  * records (host pointers) and returns its outputs, so tests can compare them bit for bit with the reference's.
  * kinds and record layouts: csrc/kernels_debug.h.  cam may be NULL except for the camera-ray kind; a scene
- * must be uploaded (the diffuse-direction kind reads its table). */
+ * must be uploaded (the diffuse-direction kind reads its table; the texture kinds read its textures, materials
+ * and triangle records, and the call refuses records that name none of them). */
 int prt_debug_device_kat(prt_ctx * ctx, int kind, const void * in, size_t in_bytes, void * out, size_t out_bytes,
                          uint32_t n, const prt_camera * cam);
 

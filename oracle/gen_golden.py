@@ -8,7 +8,9 @@ lattice) and the reference's outputs (float RGB at the lattice pixels, the three
 independently seeded (include/prt_key.h), so any pixel subset of a frame is a valid fixture; the big
 configs are sampled on a sparse lattice to keep fixtures small.
 `kat.npz` holds per-function known-answer vectors (PRNG, Hammersley, bounce directions, Fresnel,
-ray/triangle, ray/sphere, camera rays) produced by calling the reference's own functions.
+ray/triangle, ray/sphere, camera rays) produced by calling the reference's own functions; `kat_texture.npz` the
+same for Texture_SampleBilinear on a table of small in-memory textures (its own file and its own random stream, so
+kat.npz never has to be regenerated for it).
 """
 from __future__ import annotations
 
@@ -71,6 +73,10 @@ FIXTURES = {
     "hdr_gallery_128x96": dict(scene="hdr_gallery", width=128, height=96, spp=4, lattice=1),
     # Softimage PIC: raw / pure / mixed run-length packets, separate alpha packet, 16-bit run counts
     "pic_gallery_128x96": dict(scene="pic_gallery", width=128, height=96, spp=4, lattice=1),
+    # the texture path at its edges: a 2 x 2 map under texture coordinates from -2.5 to 3.5, corners exactly 0 and 1, d 1.5 with an
+    # alpha ramp (alpha x texel crosses 0.05 and 1), a two-channel Ks map, a non-square bump map tiled from a negative origin
+    "texture_edges_64x48": dict(scene="texture_edges", width=64, height=48, spp=2, lattice=1, depth=2),
+    "texture_edges_point_light_64x48": dict(scene="texture_edges", width=64, height=48, spp=2, lattice=1, depth=2, light_mode=2),
     # row N4: the reference's adaptive loop (main.cpp:245-258), one RNG stream per pixel; spp = min_samples
     "cornell_adaptive_4_16": dict(scene="cornell_box", width=96, height=72, spp=4, max_spp=16, lattice=1),
     "gallery_adaptive_10_50": dict(scene="textured_gallery", width=64, height=48, spp=10, max_spp=50, lattice=1),      # reference defaults
@@ -192,6 +198,21 @@ def generate_kat(scene_cache: dict) -> None:
     print("kat.npz: %s" % ", ".join(sorted(out)))
 
 
+def generate_kat_texture() -> None:
+    """kat_texture.npz: the reference's Texture_SampleBilinear on a table of in-memory textures (ref_harness --kat-texture)."""
+    k = orc.run_reference_kat_texture()
+    out = {
+        "texture_dims": np.frombuffer(k["texture_dims"], dtype=np.uint32).copy(),
+        "texture_bytes": np.frombuffer(k["texture_bytes"], dtype=np.uint8).copy(),
+        "tex_in": np.frombuffer(k["tex_in"], dtype=np.float32).reshape(-1, 3).copy(),
+        "tex_out": np.frombuffer(k["tex_out"], dtype=np.float32).reshape(-1, 4).copy(),
+        "srgb_lut": np.frombuffer(k["srgb_lut"], dtype=np.float32).copy(),
+    }
+    np.savez_compressed(os.path.join(GOLDEN, "kat_texture.npz"), **out)
+    print("kat_texture.npz: %d textures (%d texel bytes), %d records" % (out["texture_dims"].size // 3, out["texture_bytes"].size,
+                                                                          len(out["tex_in"])))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", nargs="*", default=None)
@@ -199,10 +220,12 @@ def main():
     if not orc.have_reference():
         raise SystemExit("oracle/_ref/ref_harness missing: run `make -C oracle ref` in the build container")
     cache = {}
-    names = args.only if args.only else ["kat"] + list(FIXTURES) + ["desc_" + k for k in DESC_FIXTURES]
+    names = args.only if args.only else ["kat", "kat_texture"] + list(FIXTURES) + ["desc_" + k for k in DESC_FIXTURES]
     for n in names:
         if n == "kat":
             generate_kat(cache)
+        elif n == "kat_texture":
+            generate_kat_texture()
         elif n.startswith("desc_"):
             generate_desc(n[5:], cache)
         else:

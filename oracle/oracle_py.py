@@ -53,6 +53,8 @@ def lib() -> C.CDLL:
         l.prt_oracle_intersect_triangle.argtypes = [C.c_void_p, C.c_void_p]
         l.prt_oracle_intersect_sphere.argtypes = [C.c_void_p, C.c_void_p]
         l.prt_oracle_camera_ray.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_void_p]
+        l.prt_oracle_sample_bilinear.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_void_p]
+        l.prt_oracle_textured_hit.argtypes = [C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_void_p]
         _lib = l
     return _lib
 
@@ -176,6 +178,18 @@ def run_reference(directory: str, obj_name: str, width: int, height: int, spp: i
         if kat:
             res["kat"] = read_sections(os.path.join(tmp, "kat.bin"))
         return res
+
+
+def run_reference_kat_texture(timeout: float = 600.0) -> Dict[str, bytes]:
+    """ref_harness --kat-texture: the sections texture_dims, texture_bytes, tex_in, tex_out and srgb_lut (no scene is loaded)."""
+    if not have_reference():
+        raise RuntimeError("oracle/_ref/ref_harness is not built (needs /root/reference; `make -C oracle ref`)")
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "kat_texture.bin")
+        proc = subprocess.run([REF_BIN, "--kat-texture", path], cwd=tmp, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout)
+        if proc.returncode != 0:
+            raise RuntimeError("ref_harness failed (%d): %s" % (proc.returncode, proc.stderr.decode()[-2000:]))
+        return read_sections(path)
 
 
 def decode_png_rgba8(data: bytes) -> np.ndarray:

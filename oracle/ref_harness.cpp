@@ -14,7 +14,7 @@
 //   * per-(pixel,sample) reseed Random_Seed(&job.rng, prt_sample_key(seed, pixel, sample)) so pixels
 //     are independent of the rank count and of each other;
 //   * an optional sparse pixel lattice, raw f32 output, scene / sphere-tree dumps and per-function
-//     known-answer vectors for the CPU restatement's unit tests;
+//     known-answer vectors for the CPU restatement's unit tests (--kat; --kat-texture for Texture_SampleBilinear alone);
 //   * --dump-desc: FlattenReferenceScene (include/prt_flatten_ref.h) run over the reference's own Scene graph, every
 //     array of the resulting prt_scene_desc written out - what a maintainer's RenderTask would hand to prt_upload_scene;
 //   * --write-png: the reference's own WriteFramebufferImage (LogAverageLuma + Color_Pack + stbi_write_png,
@@ -72,6 +72,7 @@ struct HarnessArgs {
     const char * out = NULL;
     const char * dump_scene = NULL;
     const char * kat = NULL;
+    const char * kat_texture = NULL;
     const char * stats = NULL;
     const char * dump_desc = NULL;
     const char * write_png = NULL;
@@ -94,6 +95,7 @@ HarnessArgs ParseHarnessArgs(int argc, char ** argv) {
         else if (s == "--out" && has_val) a.out = argv[++i];
         else if (s == "--dump-scene" && has_val) a.dump_scene = argv[++i];
         else if (s == "--kat" && has_val) a.kat = argv[++i];
+        else if (s == "--kat-texture" && has_val) a.kat_texture = argv[++i];
         else if (s == "--stats" && has_val) a.stats = argv[++i];
         else if (s == "--dump-desc" && has_val) a.dump_desc = argv[++i];
         else if (s == "--write-png" && has_val) a.write_png = argv[++i];
@@ -273,6 +275,84 @@ void WriteKnownAnswers(const char * path, Camera * cam) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Known-answer vectors for Texture_SampleBilinear (tests/golden/kat_texture.npz): a table of in-memory textures, a list of
+// (texture, u, v) and what the reference's own function returns for each.  A RandomState of its own: the stream behind
+// kat.npz is not drawn from.
+// ---------------------------------------------------------------------------------------------
+
+void WriteTextureKnownAnswers(const char * path) {
+    FILE * fp = fopen(path, "wb");
+    Section out = { fp };
+    RandomState r;
+    Random_Seed(&r, 0x7E87A11EULL);
+
+    // size_x, size_y, channels; the last one is a ramp in which every byte value occurs (row 0 rising, row 1 falling)
+    const u32 dims[][3] = { { 2, 2, 1 }, { 2, 2, 4 }, { 3, 2, 3 }, { 2, 3, 2 }, { 5, 7, 2 }, { 17, 9, 4 }, { 24, 16, 3 },
+                            { 64, 64, 1 }, { 256, 2, 1 } };
+    const u32 n_tex = array_count(dims);
+    std::vector<u32> dim_v;
+    std::vector<u8> bytes;
+    std::vector<size_t> first;
+    for (u32 t = 0; t < n_tex; ++t) {
+        first.push_back(bytes.size());
+        size_t n = (size_t)dims[t][0] * dims[t][1] * dims[t][2];
+        for (size_t i = 0; i < n; ++i) {
+            u8 b = (u8)(Random_Next(&r) >> 24);
+            if (t == n_tex - 1) b = i < 256 ? (u8)i : (u8)(511 - i);
+            bytes.push_back(b);
+        }
+        dim_v.push_back(dims[t][0]); dim_v.push_back(dims[t][1]); dim_v.push_back(dims[t][2]);
+    }
+    std::vector<Texture> textures(n_tex);
+    for (u32 t = 0; t < n_tex; ++t) {
+        textures[t].size_x = dims[t][0];
+        textures[t].size_y = dims[t][1];
+        textures[t].channels = dims[t][2];
+        textures[t].texels = &bytes[first[t]];
+    }
+
+    const float special[] = { 0.0f, -0.0f, 1.0f, -1.0f, 2.0f, -2.0f, 0.5f, 1.0f - ldexpf(1.0f, -24), 1.0f + ldexpf(1.0f, -23),
+                              ldexpf(1.0f, -30), -ldexpf(1.0f, -30), 3.25f, -3.25f, 16777216.0f, -16777217.0f, 1e30f, -1e30f,
+                              FLT_MAX, -FLT_MAX, 1e-45f, -1e-45f };
+    const float other[] = { 0.25f, -1.75f };                  // the second coordinate of the texel-boundary records
+    std::vector<float> in, res;
+    auto sample = [&](u32 t, float u, float v) {
+        Vector4 c = Texture_SampleBilinear(&textures[t], u, v);
+        in.push_back((float)t); in.push_back(u); in.push_back(v);
+        res.push_back(c.x); res.push_back(c.y); res.push_back(c.z); res.push_back(c.w);
+    };
+    for (u32 t = 0; t < n_tex; ++t) {
+        for (u32 a = 0; a < array_count(special); ++a)
+            for (u32 b = 0; b < array_count(special); ++b) sample(t, special[a], special[b]);
+        // texel boundaries k / (size - 2) and the midpoints between them, along each axis that has more than two texels
+        for (u32 axis = 0; axis < 2; ++axis) {
+            u32 size = dims[t][axis];
+            if (size <= 2) continue;
+            float s = (float)(size - 2);
+            for (u32 k = 0; k <= size - 2; ++k)
+                for (u32 half = 0; half < (k < size - 2 ? 2u : 1u); ++half)
+                    for (u32 o = 0; o < array_count(other); ++o) {
+                        float c = ((float)k + 0.5f * (float)half) / s;
+                        if (axis == 0) sample(t, c, other[o]); else sample(t, other[o], c);
+                    }
+        }
+        for (u32 k = 0; k < 256; ++k) {
+            float u = -4.0f + 8.0f * Random_NextFloat01(&r);
+            float v = -4.0f + 8.0f * Random_NextFloat01(&r);
+            sample(t, u, v);
+        }
+    }
+    std::vector<float> lut;
+    for (u32 i = 0; i < 256; ++i) lut.push_back(Color_SRGBToLinear((float)i * gOneOver255));
+    out.PutVec("texture_dims", dim_v);
+    out.PutVec("texture_bytes", bytes);
+    out.PutVec("tex_in", in);
+    out.PutVec("tex_out", res);
+    out.PutVec("srgb_lut", lut);
+    fclose(fp);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Scene + sphere tree dump (validates the product's OBJ loader and hierarchy builder bit for bit).
 // ---------------------------------------------------------------------------------------------
 
@@ -383,6 +463,11 @@ int main(int argc, char ** argv) {
     MPI_Comm_rank(MPI_COMM_WORLD, &gMPI_CommRank);
 
     HarnessArgs args = ParseHarnessArgs(argc, argv);
+    if (args.kat_texture) {                                   // needs no scene: nothing else is loaded or rendered
+        WriteTextureKnownAnswers(args.kat_texture);
+        MPI_Finalize();
+        return 0;
+    }
     InitParams(argc, argv);                                   // reference flag parser (main.cpp:416-504)
 
     // Same call sequence as the reference's main (main.cpp:546-599).

@@ -1,14 +1,15 @@
 // kernels_debug.h - device known-answer kernel: runs single device functions of the hot path on caller-supplied
 // vectors so the GPU test-suite can compare them, bit for bit, with what the reference's own functions returned
-// (tests/golden/kat.npz).  Test hook only; not part of the render path.
+// (tests/golden/kat.npz, kat_texture.npz) or, for the textured hit, the oracle's.  Test hook only; not part of the render path.
 #pragma once
 
 #include "dev_shade.h"
+#include "dev_texture.h"
 
 namespace prt {
 
 enum { KAT_RNG_NEXT = 0, KAT_RNG_FLOAT01 = 1, KAT_TRIANGLE = 2, KAT_DIFFUSE_DIR = 3, KAT_CAMERA_RAY = 4, KAT_FRESNEL = 5,
-       KAT_TANGENT_TO_WORLD = 6, KAT_RNG_NEXT_COMPACT = 7 };
+       KAT_TANGENT_TO_WORLD = 6, KAT_RNG_NEXT_COMPACT = 7, KAT_TEXTURE = 8, KAT_TEXTURED_HIT = 9 };
 
 __global__ void k_debug_kat(int kind, const void * in, void * out, unsigned int n, DevScene sc, DevCamera cam, u64 * ring_ws) {
     const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -70,6 +71,25 @@ __global__ void k_debug_kat(int kind, const void * in, void * out, unsigned int 
         const f3 dir = tangent_to_world(mk3(p[0], p[1], p[2]), mk3(p[3], p[4], p[5]));
         float * q = (float *)out + (size_t)i * 3;
         q[0] = dir.x; q[1] = dir.y; q[2] = dir.z;
+    } break;
+    case KAT_TEXTURE: {                        // in: texture index (as a float), u, v; out: tex_sample_rgb xyz, tex_sample_r
+        if (!sc.textures) break;               // (the host has checked every index against the uploaded scene's texture table)
+        const float * p = (const float *)in + (size_t)i * 3;
+        const f3 c = tex_sample_rgb(sc, (unsigned int)p[0], p[1], p[2]);
+        float * q = (float *)out + (size_t)i * 4;
+        q[0] = c.x; q[1] = c.y; q[2] = c.z; q[3] = tex_sample_r(sc, (unsigned int)p[0], p[1], p[2]);
+    } break;
+    case KAT_TEXTURED_HIT: {                   // in: triangle slot (as a float), v, w; out: tu tv alpha alpha_tested ka kd ks hit_n (16 floats)
+        const float * p = (const float *)in + (size_t)i * 3;
+        const unsigned int tri = (unsigned int)p[0];
+        if (tri >= sc.tri_count) break;        // (the host has checked this too)
+        const TexturedHit h = textured_hit_at(sc, tri, p[1], p[2]);
+        float * q = (float *)out + (size_t)i * 16;
+        q[0] = h.tu; q[1] = h.tv; q[2] = h.alpha; q[3] = h.alpha_tested ? 1.0f : 0.0f;
+        q[4] = h.ambient.x; q[5] = h.ambient.y; q[6] = h.ambient.z;
+        q[7] = h.diffuse.x; q[8] = h.diffuse.y; q[9] = h.diffuse.z;
+        q[10] = h.specular.x; q[11] = h.specular.y; q[12] = h.specular.z;
+        q[13] = h.normal.x; q[14] = h.normal.y; q[15] = h.normal.z;
     } break;
     default: break;
     }

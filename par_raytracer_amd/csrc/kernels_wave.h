@@ -406,18 +406,10 @@ PRT_D void shade_entry_on(const DevScene & sc, const DevParams & P, const WaveBu
             f.ks = mk3(mat.specular[0], mat.specular[1], mat.specular[2]);
             float tu = 0.0f, tv = 0.0f;
             bool alpha_tested = mat.alpha <= 1.0f;                                  // raytracer.cpp:443
-            const bool any_tex = TEX && (mat.tex[0] & mat.tex[1] & mat.tex[2]) != 0xFFFFFFFFu;
+            const bool any_tex = TEX && textured_hit_any(mat);                      // the textured-hit block: dev_texture.h
             if (TEX && any_tex) {
-                const float4 * up = sc.tri_uv + 2 * (size_t)hit.tri;
-                const float4 u01 = up[0], u2 = up[1];
-                tu = 0.0f + u01.x * bwx; tv = 0.0f + u01.y * bwx;                   // raytracer.cpp:439-442
-                tu = tu + u01.z * bwy; tv = tv + u01.w * bwy;
-                tu = tu + u2.x * bwz; tv = tv + u2.y * bwz;
-                const unsigned int alpha_tex = mat.tex[1] >> 16;
-                if (alpha_tex != DEV_TEX_NONE) {                                    // raytracer.cpp:444-446
-                    alpha *= tex_sample_r(sc, alpha_tex, tu, tv);
-                    alpha_tested = true;
-                }
+                textured_hit_uv(sc, hit.tri, bwx, bwy, bwz, tu, tv);
+                textured_hit_alpha(sc, mat, tu, tv, alpha, alpha_tested);
             }
             // (the non-RING variants only run scenes whose materials all have alpha >= 1: the translucency paths fold away)
             if (TRANS && alpha_tested && alpha <= 0.05f) {                           // raytracer.cpp:443-453
@@ -427,34 +419,8 @@ PRT_D void shade_entry_on(const DevScene & sc, const DevParams & P, const WaveBu
                 next_level = level;
                 mode = M_ENTER;
             } else {
-                if (TEX && any_tex) {                                               // raytracer.cpp:455-462
-                    const unsigned int t_ka = mat.tex[0] & 0xFFFFu, t_kd = mat.tex[0] >> 16, t_ks = mat.tex[1] & 0xFFFFu;
-                    if (t_ka != DEV_TEX_NONE) ka = ka * tex_sample_rgb(sc, t_ka, tu, tv);
-                    if (t_kd != DEV_TEX_NONE) f.kd = f.kd * tex_sample_rgb(sc, t_kd, tu, tv);
-                    if (t_ks != DEV_TEX_NONE) f.ks = tex_sample_rgb(sc, t_ks, tu, tv);      // replaces Ks
-                }
-                f3 interp = mk3(0.0f, 0.0f, 0.0f);                                  // raytracer.cpp:464-467
-                interp = interp + mk3(s0.x, s0.y, s0.z) * bwx;
-                interp = interp + mk3(s0.w, s1.x, s1.y) * bwy;
-                interp = interp + mk3(s1.z, s1.w, s2.x) * bwz;
-                f.hit_n = normalize3(interp);
-                if (TEX && (mat.tex[2] & 0xFFFFu) != DEV_TEX_NONE) {                // raytracer.cpp:468-502
-                    const float4 * tp = sc.tri_tan + 3 * (size_t)hit.tri;
-                    const float4 t0 = tp[0], t1 = tp[1], t2 = tp[2];
-                    f3 tangent = mk3(0.0f, 0.0f, 0.0f);
-                    tangent = tangent + mk3(t0.x, t0.y, t0.z) * bwx;
-                    tangent = tangent + mk3(t0.w, t1.x, t1.y) * bwy;
-                    tangent = tangent + mk3(t1.z, t1.w, t2.x) * bwz;
-                    tangent = normalize3(tangent);
-                    const f3 bitangent = normalize3(cross3(f.hit_n, tangent));
-                    const f3 smp = tex_sample_rgb(sc, mat.tex[2] & 0xFFFFu, tu, tv);
-                    const f3 sn = smp * 2.0f - mk3(1.0f, 1.0f, 1.0f);
-                    // world_from_tangent_space * sn, columns (tangent, bitangent, normal), mathlib.h:697-709; not renormalised
-                    const f3 nn = f.hit_n;
-                    f.hit_n = mk3((tangent.x * sn.x + bitangent.x * sn.y) + nn.x * sn.z,
-                                  (tangent.y * sn.x + bitangent.y * sn.y) + nn.y * sn.z,
-                                  (tangent.z * sn.x + bitangent.z * sn.y) + nn.z * sn.z);
-                }
+                if (TEX && any_tex) textured_hit_colours(sc, mat, tu, tv, ka, f.kd, f.ks);
+                textured_hit_normal<TEX>(sc, mat, hit.tri, s0, s1, s2, bwx, bwy, bwz, tu, tv, f.hit_n);
                 f.hit_pos = pos;
                 f.hit_p = pos + gn * P.ray_bias;                                    // raytracer.cpp:425
                 f.ray_d = ray_d;

@@ -23,6 +23,7 @@
 #include "bvh_build.h"
 #include "prt_options.h"
 #include "dev_scene.h"
+#include "tex_upload.h"
 #include "kernels_wave.h"
 #include "kernels_pool.h"
 #include "kernels_resolve.h"
@@ -130,6 +131,7 @@ struct prt_ctx {
     std::vector<TuneEntry> tuned;
     uint64_t scene_epoch = 0;
     DevBuf<DevTexture> textures;
+    std::vector<DevTexture> kat_textures; // host copy of the texture table: prt_debug_device_kat checks KAT_TEXTURE's indices against it
     DevBuf<unsigned int> texels;
     DevBuf<float> srgb_lut;
     DevBuf<float4> tri_uv, tri_tan;
@@ -2231,17 +2233,12 @@ int prt_upload_scene(prt_ctx * ctx, const prt_scene_desc * s) {
         // gather instead of two; texture coordinates and tangents have their own arrays, only for textured scenes
         shade[(size_t)slot * 4 + 2] = make_float4(n2[2], n.x, n.y, n.z);
         shade[(size_t)slot * 4 + 3] = make_float4(0.0f, 0.0f, 0.0f, mbits);
-        if (textured) {
-            tri_uv[(size_t)slot * 2 + 0] = make_float4(u0[0], u0[1], u1[0], u1[1]);
-            tri_uv[(size_t)slot * 2 + 1] = make_float4(u2[0], u2[1], 0.0f, 0.0f);
-        }
+        if (textured) tex_pack_uv(u0, u1, u2, &tri_uv[(size_t)slot * 2]);              // tex_upload.h
         if (bumped) {                                             // mesh->tangents[idx_normals[...]], raytracer.cpp:470-473
             const float * g0 = s->tangents + 3 * (size_t)s->idx_normals[3 * t + 0];
             const float * g1 = s->tangents + 3 * (size_t)s->idx_normals[3 * t + 1];
             const float * g2 = s->tangents + 3 * (size_t)s->idx_normals[3 * t + 2];
-            tri_tan[(size_t)slot * 3 + 0] = make_float4(g0[0], g0[1], g0[2], g1[0]);
-            tri_tan[(size_t)slot * 3 + 1] = make_float4(g1[1], g1[2], g2[0], g2[1]);
-            tri_tan[(size_t)slot * 3 + 2] = make_float4(g2[2], 0.0f, 0.0f, 0.0f);
+            tex_pack_tangents(g0, g1, g2, &tri_tan[(size_t)slot * 3]);
         }
         rank[slot] = rank_of_input[t];
         for (int k = 0; k < 9; ++k) abs_max = std::max(abs_max, fabsf(verts[(size_t)t * 9 + k]));
@@ -2258,10 +2255,7 @@ int prt_upload_scene(prt_ctx * ctx, const prt_scene_desc * s) {
         d.specular_intensity = pm.specular_intensity;
         d.index_of_refraction = pm.index_of_refraction;
         d.alpha = pm.alpha;
-        auto slot16 = [](int32_t v) { return v < 0 ? (unsigned int)DEV_TEX_NONE : (unsigned int)v; };
-        d.tex[0] = slot16(pm.ambient_texture) | slot16(pm.diffuse_texture) << 16;
-        d.tex[1] = slot16(pm.specular_texture) | slot16(pm.alpha_texture) << 16;
-        d.tex[2] = slot16(pm.bump_texture) | (unsigned int)DEV_TEX_NONE << 16;
+        tex_pack_material_slots(pm, d);
         ctx->material_ns[m] = pm.specular_intensity;
         if (!(pm.alpha >= 1.0f)) ctx->any_translucent = true;      // alpha < 1 (or NaN): continuation rays, unbounded draws
     }
@@ -2269,34 +2263,11 @@ int prt_upload_scene(prt_ctx * ctx, const prt_scene_desc * s) {
     std::vector<DevTexture> dev_tex;
     std::vector<unsigned int> texel_pool;
     std::vector<float> lut;
-    if (textured) {
-        dev_tex.resize(s->texture_count);
-        for (uint32_t ti = 0; ti < s->texture_count; ++ti) {
-            const prt_texture & t = s->textures[ti];
-            DevTexture & d = dev_tex[ti];
-            memset(&d, 0, sizeof(d));
-            if (!t.texels || t.size_x < 2 || t.size_y < 2 || t.channels < 1 || t.channels > 4) continue;     // unreferenced and unusable
-            const size_t n = (size_t)t.size_x * t.size_y;
-            if (texel_pool.size() + n >= (1ull << 32)) { ctx->error = "prt_upload_scene: more than 2^32 texels"; return -1; }
-            d.first_texel = (unsigned int)texel_pool.size();
-            d.size_x = t.size_x;
-            d.size_y = t.size_y;
-            texel_pool.resize(texel_pool.size() + n);
-            unsigned int * out = texel_pool.data() + d.first_texel;
-            for (size_t i = 0; i < n; ++i) {
-                const uint8_t * px = t.texels + i * t.channels;
-                unsigned int r = px[0], g = t.channels >= 2 ? px[1] : 0u, b = t.channels >= 3 ? px[2] : 0u, a = t.channels >= 4 ? px[3] : 255u;
-                if (t.channels == 1) b = g = r;
-                out[i] = r | g << 8 | b << 16 | a << 24;
-            }
-        }
-        lut.resize(256);
-        const float one_over_255 = 1.0f / 255.0f;                  // texture.cpp:15
-        for (int i = 0; i < 256; ++i) {
-            const float srgb = (float)i * one_over_255;
-            lut[i] = srgb <= 0.04045f ? srgb / 12.92f : powf((srgb + 0.055f) / 1.055f, 2.4f);     // color.h:13-21
-        }
+    if (textured) {                                                // tex_upload.h
+        if (!tex_expand_rgba8(s->textures, s->texture_count, dev_tex, texel_pool)) { ctx->error = "prt_upload_scene: more than 2^32 texels"; return -1; }
+        tex_fill_srgb_lut(lut);
     }
+    ctx->kat_textures = dev_tex;
     std::vector<DevLight> lights(std::max(1u, s->light_count));
     memset(lights.data(), 0, lights.size() * sizeof(DevLight));
     for (uint32_t l = 0; l < s->light_count; ++l) {
@@ -2613,6 +2584,24 @@ int prt_debug_device_kat(prt_ctx * ctx, int kind, const void * in, size_t in_byt
     if (!ctx) return -1;
     if (!ctx->has_scene) { ctx->error = "prt_debug_device_kat: upload a scene first"; return -2; }
     if (!in || !out || !n) { ctx->error = "prt_debug_device_kat: null buffers"; return -1; }
+    if (kind == KAT_TEXTURE) {                                  // the kinds that follow indices into the scene: checked here, not on the device
+        if (in_bytes != (size_t)n * 12 || out_bytes != (size_t)n * 16) { ctx->error = "prt_debug_device_kat: KAT_TEXTURE takes 3 floats and gives 4 per record"; return -1; }
+        if (!ctx->textured) { ctx->error = "prt_debug_device_kat: KAT_TEXTURE needs a scene with texture maps"; return -2; }
+        for (uint32_t i = 0; i < n; ++i) {
+            const float ti = ((const float *)in)[3 * (size_t)i];
+            if (!(ti >= 0.0f && ti < (float)ctx->kat_textures.size()) || ctx->kat_textures[(size_t)ti].size_x < 2) {
+                ctx->error = "prt_debug_device_kat: KAT_TEXTURE record names no usable texture";
+                return -1;
+            }
+        }
+    }
+    if (kind == KAT_TEXTURED_HIT) {
+        if (in_bytes != (size_t)n * 12 || out_bytes != (size_t)n * 64) { ctx->error = "prt_debug_device_kat: KAT_TEXTURED_HIT takes 3 floats and gives 16 per record"; return -1; }
+        for (uint32_t i = 0; i < n; ++i) {
+            const float slot = ((const float *)in)[3 * (size_t)i];
+            if (!(slot >= 0.0f && slot < (float)ctx->scene.tri_count)) { ctx->error = "prt_debug_device_kat: KAT_TEXTURED_HIT record names no triangle"; return -1; }
+        }
+    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // scratch buffers owned by DevBuf objects: released on every return path
     struct Scratch {
@@ -2790,6 +2779,7 @@ prt_ctx * clone_context(prt_ctx * src) {
     c->info = src->info;
     c->scene_abs_max = src->scene_abs_max;
     c->any_translucent = src->any_translucent; c->point_lights = src->point_lights; c->textured = src->textured;
+    c->kat_textures = src->kat_textures;
     c->stack_bound = src->stack_bound;
     c->pool_park_cap = src->pool_park_cap; c->pool_spark_cap = src->pool_spark_cap;
     c->has_scene = src->has_scene;

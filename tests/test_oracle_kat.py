@@ -129,6 +129,26 @@ def test_ray_sphere(kat):
         assert np.array_equal(_bits(out), _bits(e))
 
 
+def test_texture_sample_bilinear():
+    """The SampleBilinear the oracle renders with against the reference's Texture_SampleBilinear (tests/golden/kat_texture.npz):
+    all four channels, every record."""
+    from par_raytracer_amd import capi
+    import texture_cases as T
+    lib = orc.lib()
+    g = T.golden()
+    dims = g["texture_dims"].reshape(-1, 3)
+    texels = np.ascontiguousarray(g["texture_bytes"])
+    textures, off = [], 0
+    for sx, sy, ch in dims:
+        t = capi.PrtTexture(int(sx), int(sy), int(ch), C.cast(texels.ctypes.data + off, C.POINTER(C.c_uint8)))
+        textures.append(t)
+        off += int(sx) * int(sy) * int(ch)
+    got = np.zeros((len(g["tex_in"]), 4), dtype=np.float32)
+    for i, (t, u, v) in enumerate(g["tex_in"]):
+        lib.prt_oracle_sample_bilinear(C.byref(textures[int(t)]), float(u), float(v), got[i].ctypes.data_as(C.c_void_p))
+    T.assert_same_bits(got, g["tex_out"], "prt_oracle_sample_bilinear")
+
+
 def test_camera_rays(kat):
     from par_raytracer_amd import api, scenes
     lib = orc.lib()

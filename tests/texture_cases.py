@@ -1,0 +1,323 @@
+"""Shared by the texture tests (tests/test_texture_host.py, tests/test_oracle_kat.py, tests/test_gpu_texture.py): the golden vectors
+of the reference's Texture_SampleBilinear (tests/golden/kat_texture.npz, oracle/gen_golden.py), a float32 numpy restatement of that
+function, this machine's sRGB table by the C library's powf, one-triangle scenes (the golden's texture table; one material per case
+of the textured-hit block) with their (v, w) records and the oracle's answers, and the runner of tests/texture_host_harness.cpp
+(csrc/dev_texture.h and csrc/tex_upload.h compiled for the host)."""
+from __future__ import annotations
+
+import ctypes as C
+import ctypes.util
+import os
+import struct
+import subprocess
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F = np.float32
+
+
+def golden():
+    """kat_texture.npz: texture_dims (T x 3), texture_bytes, tex_in (n x 3: texture, u, v), tex_out (n x 4), srgb_lut (256)."""
+    g = np.load(os.path.join(ROOT, "tests", "golden", "kat_texture.npz"), allow_pickle=False)
+    return {k: g[k] for k in g.files}
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+# ---- Texture_SampleBilinear in float32 numpy: every operation rounds to float32 (texture.cpp:5-83)
+
+def _max(a, b):                                             # mathlib.h: a > b ? a : b, signed zeros and all
+    return np.where(a > b, a, b).astype(F)
+
+
+def _min(a, b):
+    return np.where(a < b, a, b).astype(F)
+
+
+def wrap_f32(x):
+    """WrapUV (texture.cpp:5-13): fmodf(uv, 1) for uv >= 0, 1 + fmodf(uv, 1) below."""
+    x = np.asarray(x, F)
+    frac = np.fmod(x, F(1)).astype(F)
+    return np.where(x >= 0, frac, (F(1) + frac).astype(F)).astype(F)
+
+
+def _first_bytes(dims):
+    d = np.asarray(dims, np.int64).reshape(-1, 3)
+    return np.concatenate([[0], np.cumsum(d[:, 0] * d[:, 1] * d[:, 2])[:-1]])
+
+
+def _texel_bytes(dims, texels, tex, x, y):
+    """GetTexel's bytes (texture.cpp:17-42) as (n, 4) uint8: missing alpha 255, one channel grey, two channels (r, g, 0)."""
+    d = np.asarray(dims, np.int64).reshape(-1, 3)
+    texels = np.asarray(texels, np.uint8)
+    sx, ch = d[tex, 0], d[tex, 2]
+    base = _first_bytes(dims)[tex] + (y * sx + x) * ch
+    out = np.zeros((len(tex), 4), np.uint8)
+    for c in range(4):
+        have = ch > c
+        out[have, c] = texels[base[have] + c]
+    out[ch < 4, 3] = 255
+    grey = ch == 1
+    out[grey, 1] = out[grey, 0]
+    out[grey, 2] = out[grey, 0]
+    return out
+
+
+def bilinear_f32(lut, dims, texels, tex, u, v):
+    """(rgba (n, 4) float32, tx0, ty0, fx, fy) of Texture_SampleBilinear for the records (tex, u, v), with the sRGB table `lut`.
+    The lerps are associated as texture.cpp:82 associates them: Lerp(Lerp(s00, s01, fy), Lerp(s10, s11, fy), fx), Lerp(a, b, t) =
+    a + (b - a) * t."""
+    lut = np.asarray(lut, F)
+    d = np.asarray(dims, np.int64).reshape(-1, 3)
+    tex = np.asarray(tex).astype(np.int64)
+    uw = wrap_f32(u)
+    vw = (F(1) - wrap_f32(v)).astype(F)
+    sx = (d[tex, 0] - 2).astype(F)
+    sy = (d[tex, 1] - 2).astype(F)
+    zero = np.zeros(len(tex), F)
+    tx = _min(_max((uw * sx).astype(F), zero), sx)
+    ty = _min(_max((vw * sy).astype(F), zero), sy)
+    tx0 = np.floor(tx).astype(np.int64)
+    ty0 = np.floor(ty).astype(np.int64)
+    fx = (tx - tx0.astype(F)).astype(F)
+    fy = (ty - ty0.astype(F)).astype(F)
+
+    def texel(x, y):
+        return lut[_texel_bytes(dims, texels, tex, x, y)]
+
+    def lerp(a, b, t):
+        return (a + ((b - a).astype(F) * t[:, None]).astype(F)).astype(F)
+    s00, s01, s10, s11 = texel(tx0, ty0), texel(tx0, ty0 + 1), texel(tx0 + 1, ty0), texel(tx0 + 1, ty0 + 1)
+    return lerp(lerp(s00, s01, fy), lerp(s10, s11, fy), fx), tx0, ty0, fx, fy
+
+
+def tapped_byte_values(dims, texels, tex, tx0, ty0):
+    """The set of byte values stored in the four texels every record taps (the texture's own channels only)."""
+    d = np.asarray(dims, np.int64).reshape(-1, 3)
+    texels = np.asarray(texels, np.uint8)
+    tex = np.asarray(tex).astype(np.int64)
+    seen = np.zeros(256, bool)
+    first = _first_bytes(dims)[tex]
+    for dx in (0, 1):
+        for dy in (0, 1):
+            base = first + ((ty0 + dy) * d[tex, 0] + tx0 + dx) * d[tex, 2]
+            for c in range(4):
+                have = d[tex, 2] > c
+                seen[texels[base[have] + c]] = True
+    return seen
+
+
+# ---- the sRGB table as this machine's C library computes it (what prt_upload_scene does: csrc/tex_upload.h)
+
+def machine_srgb_lut():
+    libm = C.CDLL(ctypes.util.find_library("m") or "libm.so.6")
+    libm.powf.restype = C.c_float
+    libm.powf.argtypes = [C.c_float, C.c_float]
+    out = np.zeros(256, F)
+    one_over_255 = F(1) / F(255)
+    for i in range(256):
+        srgb = F(i) * one_over_255
+        if srgb <= F(0.04045):
+            out[i] = srgb / F(12.92)
+        else:
+            out[i] = libm.powf(float((srgb + F(0.055)) / F(1.055)), float(F(2.4)))
+    return out
+
+
+# ---- a scene that carries a texture table: one triangle, one material
+
+def one_triangle_scene(texture_dims, texture_bytes, material=None, positions=None, normals=None, texcoords=None, tangents=None):
+    """api.FlatDesc of one triangle in one group with one material.  `material`: dict of capi.PrtMaterial fields over a plain white
+    default that references texture 0 as its diffuse map (so the upload builds the texture tables)."""
+    from par_raytracer_amd import api, capi
+    m = capi.PrtMaterial()
+    m.specular_intensity, m.index_of_refraction, m.alpha = 10.0, 1.5, 1.0
+    for k in range(4):
+        m.ambient_color[k] = m.diffuse_color[k] = m.specular_color[k] = 1.0
+    m.ambient_texture = m.specular_texture = m.alpha_texture = m.bump_texture = -1
+    m.diffuse_texture = 0
+    for key, val in (material or {}).items():
+        if key.endswith("_color"):
+            for k in range(4):
+                getattr(m, key)[k] = float(val[k])
+        else:
+            setattr(m, key, val)
+    group = capi.PrtGroup(0, 3, 0)
+    pos = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0]], F) if positions is None else np.asarray(positions, F)
+    zu8 = np.zeros(0, np.uint8)
+
+    def raw(s):
+        return np.frombuffer(bytes(s), np.uint8).copy()
+    arrays = {
+        "positions": pos.reshape(-1),
+        "normals": np.ascontiguousarray(np.array([[0, 0, 1]] * 3, F) if normals is None else np.asarray(normals, F)).reshape(-1),
+        "texcoords": np.ascontiguousarray(np.array([[0, 0], [1, 0], [0, 1]], F) if texcoords is None else np.asarray(texcoords, F)).reshape(-1),
+        "tangents": np.ascontiguousarray(np.array([[1, 0, 0]] * 3, F) if tangents is None else np.asarray(tangents, F)).reshape(-1),
+        "idx_positions": np.arange(3, dtype=np.uint32), "idx_texcoords": np.arange(3, dtype=np.uint32),
+        "idx_normals": np.arange(3, dtype=np.uint32),
+        "groups": raw(group), "materials": raw(m), "lights": zu8, "spheres": zu8, "sphere_group": np.zeros(0, np.int32),
+        "texture_dims": np.asarray(texture_dims, np.uint32).reshape(-1), "texture_bytes": np.asarray(texture_bytes, np.uint8),
+    }
+    scene = api.FlatDesc(arrays)
+    scene.material_bytes = bytes(m)                         # what the host harness is given: the same material and corner values
+    scene.corner_values = (arrays["normals"], arrays["texcoords"], arrays["tangents"])
+    scene.texture_table = (arrays["texture_dims"], arrays["texture_bytes"])
+    return scene
+
+
+# ---- textured hits: scenes of one triangle and one material, and the (v, w) records asked of each
+
+def hit_textures():
+    """(dims, bytes) of the texture table every hit scene carries, texel bytes from a fixed seed: 0 ambient 5 x 7 x 3, 1 diffuse
+    17 x 9 x 4, 2 specular 24 x 16 x 3, 3 alpha 32 x 8 x 1 (a ramp from 0, so that alpha x texel reaches below 0.05), 4 the bump
+    slot's normal map 24 x 16 x 3, 5 a two-channel specular map 13 x 11 x 2, 6 a 2 x 2 x 3 map."""
+    rng = np.random.default_rng(20250918)
+    dims = np.array([[5, 7, 3], [17, 9, 4], [24, 16, 3], [32, 8, 1], [24, 16, 3], [13, 11, 2], [2, 2, 3]], np.uint32)
+    blobs = [rng.integers(0, 256, int(sx) * int(sy) * int(ch), dtype=np.uint8) for sx, sy, ch in dims]
+    blobs[3] = np.tile(np.linspace(0, 255, 32).round().astype(np.uint8), 8)
+    return dims.reshape(-1), np.concatenate(blobs)
+
+
+_NO_MAPS = dict(ambient_texture=-1, diffuse_texture=-1, specular_texture=-1, alpha_texture=-1, bump_texture=-1)
+_COLOURS = dict(ambient_color=(0.6, 0.5, 0.4, 1.0), diffuse_color=(0.9, 0.8, 0.7, 1.0), specular_color=(0.3, 0.2, 0.1, 1.0))
+# vertex texture coordinates outside [0, 1], negative, and exactly integer
+HIT_TEXCOORDS = np.array([[-2.0, 3.0], [1.75, -0.5], [0.25, 2.5]], F)
+HIT_SCENES = {
+    "no_maps": dict(),
+    "map_ka": dict(ambient_texture=0),
+    "map_kd": dict(diffuse_texture=1),
+    "map_ks": dict(specular_texture=2),
+    "map_d": dict(alpha=0.8, alpha_texture=3),
+    "map_bump": dict(bump_texture=4),
+    "all_five": dict(ambient_texture=0, diffuse_texture=1, specular_texture=2, alpha_texture=3, bump_texture=4),
+    "map_ks_two_channels": dict(specular_texture=5),
+    "alpha_1p5_with_map": dict(alpha=1.5, alpha_texture=3),             # tested only because of the map
+    "alpha_0p9_without_map": dict(alpha=0.9),
+    "alpha_1_map_below_0p05": dict(alpha=1.0, alpha_texture=3),
+    "bump_three_normals_and_tangents": dict(bump_texture=4, diffuse_texture=6),
+}
+
+
+def hit_scene(name):
+    """The one-triangle api.FlatDesc of HIT_SCENES[name]."""
+    material = dict(_NO_MAPS, **_COLOURS)
+    material.update(HIT_SCENES[name])
+    normals = tangents = None
+    if name == "bump_three_normals_and_tangents":
+        normals = np.array([[0.1, -0.2, 0.97], [-0.3, 0.1, 0.9], [0.2, 0.4, 0.85]], F)           # not unit: the reference normalises the sum
+        tangents = np.array([[0.98, 0.05, -0.1], [0.9, -0.2, 0.3], [0.95, 0.25, 0.1]], F)
+    dims, texels = hit_textures()
+    return one_triangle_scene(dims, texels, material, normals=normals, texcoords=HIT_TEXCOORDS, tangents=tangents)
+
+
+def hit_records(seed=11):
+    """About 300 (v, w) float32 pairs: the three corners, points on each edge (one barycentric exactly zero), pairs with
+    v + w = 1 + 2^-23 and the like (1 - v - w a tiny negative, as real hits produce), random interior points."""
+    rng = np.random.default_rng(seed)
+    rec = [(0.0, 0.0), (1.0, 0.0), (0.0, 1.0)]
+    k = np.arange(1, 16, dtype=np.float64) / 16.0
+    rec += [(t, 0.0) for t in k] + [(0.0, t) for t in k] + [(t, 1.0 - t) for t in k]           # w = 0, v = 0, 1 - v - w = 0 (exact in float32)
+    over = np.nextafter((1.0 - k).astype(F), F(2))                                             # v + w one ulp of w above 1
+    rec += [(float(t), float(o)) for t, o in zip(k, over)]
+    rec += [(0.5, float(F(0.5) + F(2.0 ** -23)))]                                              # 1 - v - w = -2^-23 exactly
+    v = rng.uniform(0.0, 1.0, 240)
+    w = rng.uniform(0.0, 1.0, 240) * (1.0 - v)
+    rec += list(zip(v, w))
+    return np.ascontiguousarray(np.array(rec, np.float64).astype(F))
+
+
+def oracle_hits(scene, records):
+    """(n, 16) float32: prt_oracle_textured_hit on triangle 0 of `scene` for the (v, w) records."""
+    import oracle_py as orc
+    lib = orc.lib()
+    out = np.zeros((len(records), 16), F)
+    for i, (v, w) in enumerate(records):
+        rc = lib.prt_oracle_textured_hit(C.cast(scene.desc, C.c_void_p), 0, float(v), float(w), out[i].ctypes.data_as(C.c_void_p))
+        assert rc == 0
+    return out
+
+
+def run_hit_harness(exe, scenes, records, directory):
+    """[(n, 16) float32 per scene]: textured_hit_at of csrc/dev_texture.h on the host, for the same (v, w) records in every scene."""
+    fin, fout = os.path.join(str(directory), "hit_cases.bin"), os.path.join(str(directory), "hit_results.bin")
+    rec = np.ascontiguousarray(records, F).reshape(-1, 2)
+    with open(fin, "wb") as f:
+        f.write(struct.pack("<II", 1, len(scenes)))
+        for s in scenes:
+            dims, texels = s.texture_table
+            f.write(struct.pack("<I", dims.size // 3))
+            f.write(np.ascontiguousarray(dims, np.uint32).tobytes())
+            f.write(struct.pack("<I", texels.size))
+            f.write(np.ascontiguousarray(texels, np.uint8).tobytes())
+            assert len(s.material_bytes) == 80
+            f.write(s.material_bytes)
+            for a in s.corner_values:
+                f.write(np.ascontiguousarray(a, F).tobytes())
+            f.write(struct.pack("<I", len(rec)))
+            f.write(rec.tobytes())
+    run = subprocess.run([exe, fin, fout], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
+    assert run.returncode == 0, run.stdout.decode()[-4000:]
+    blob = np.fromfile(fout, F)
+    assert blob.size == 16 * len(rec) * len(scenes)
+    return list(blob.reshape(len(scenes), len(rec), 16).copy())
+
+
+def has_maps(name):
+    return any(k.endswith("_texture") for k in HIT_SCENES[name])
+
+
+def assert_same_hits(got, expect, what, compare_uv=True):
+    """Bit for bit, except that a NaN matches a NaN.  compare_uv False (a material without maps): tu and tv are left out - the
+    reference interpolates them and never reads them, the device does not form them (an untextured scene has no tri_uv array) and
+    reports 0."""
+    g, e = np.asarray(got, F), np.asarray(expect, F)
+    if not compare_uv:
+        assert np.all(g[:, :2] == 0)
+        g, e = g[:, 2:], e[:, 2:]
+    both_nan = np.isnan(g) & np.isnan(e)
+    bad = np.nonzero(((bits(g) != bits(e)) & ~both_nan).any(1))[0]
+    assert bad.size == 0, "%s: %d of %d records differ, first %d:\n got      %r\n expected %r" % (
+        what, bad.size, len(g), bad[0], g[bad[0]].tolist(), e[bad[0]].tolist())
+
+
+# ---- the host harness
+
+def build_harness(directory):
+    exe = os.path.join(str(directory), "texture_host")
+    cmd = ["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off",
+           "-I" + os.path.join(ROOT, "tests", "hip_shim"), "-I" + os.path.join(ROOT, "par_raytracer_amd", "csrc"),
+           os.path.join(ROOT, "tests", "texture_host_harness.cpp"), "-o", exe]
+    build = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    assert build.returncode == 0, build.stdout.decode()
+    return exe
+
+
+def run_harness(exe, texture_dims, texture_bytes, records, directory):
+    """(srgb table (256), samples (n, 5): tex_sample_rgb's x, y, z, tex_sample_r and the fourth channel by tex_channel) of the
+    records (n, 3: texture, u, v)."""
+    fin, fout = os.path.join(str(directory), "texture_cases.bin"), os.path.join(str(directory), "texture_results.bin")
+    dims = np.ascontiguousarray(texture_dims, np.uint32).reshape(-1)
+    texels = np.ascontiguousarray(texture_bytes, np.uint8)
+    rec = np.ascontiguousarray(records, F).reshape(-1, 3)
+    with open(fin, "wb") as f:
+        f.write(struct.pack("<II", 0, dims.size // 3))
+        f.write(dims.tobytes())
+        f.write(struct.pack("<I", texels.size))
+        f.write(texels.tobytes())
+        f.write(struct.pack("<I", len(rec)))
+        f.write(rec.tobytes())
+    run = subprocess.run([exe, fin, fout], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
+    assert run.returncode == 0, run.stdout.decode()[-4000:]
+    blob = np.fromfile(fout, F)
+    assert blob.size == 256 + 5 * len(rec)
+    return blob[:256].copy(), blob[256:].reshape(-1, 5).copy()
+
+
+def assert_same_bits(got, expect, what):
+    g, e = bits(got), bits(expect)
+    bad = np.nonzero((g != e).reshape(len(g), -1).any(1))[0]
+    assert bad.size == 0, "%s: %d of %d records differ, first %d: got %r, expected %r" % (
+        what, bad.size, len(g), bad[0], np.asarray(got)[bad[0]].tolist(), np.asarray(expect)[bad[0]].tolist())
