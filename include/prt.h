@@ -251,8 +251,9 @@ int prt_render_pixel_list(prt_ctx * ctx, const prt_camera * cam, const prt_param
  *                       near-tied hits included (decided in the reference's visit order, as the render pipelines do).  A miss is
  *                       the reference's zero-filled record with t = FLT_MAX, except group = -1 and vertex0 = 0xFFFFFFFF.
  *   PRT_QUERY_OCCLUDED  occluded = 1 exactly when some front-facing triangle, tested with the reference's IntersectRayTriangle
- *                       against t = FLT_MAX, gives a hit with t < tmax (independent of visit order; with tmax NULL it equals
- *                       TraceRay(...) == true).  Any-hit traversal.
+ *                       against t = FLT_MAX, gives a hit with t < tmax (independent of visit order, and of the reference's
+ *                       sphere tree: with tmax NULL it is 1 for every ray TraceRay hits, and also for the few rays whose hit
+ *                       TraceRay loses to a sphere test its float arithmetic fails).  Any-hit traversal.
  * A ray with a non-finite origin or direction component (or biased origin), or a zero direction, is a miss / not occluded; it is
  * not an error and does not affect the other rays; a scene of 0 triangles makes every ray a miss / not occluded.  tmax = +inf is
  * "no limit" (as NULL and as FLT_MAX: every accepted t is below FLT_MAX); a tmax that is 0, negative or NaN makes the ray not
@@ -262,14 +263,18 @@ int prt_render_pixel_list(prt_ctx * ctx, const prt_camera * cam, const prt_param
  * max(scene extent, max |biased origin component| of the batch), so origins may lie anywhere.  The reference's sphere test assumes
  * a unit direction and an origin near the scene: CLOSEST rays with |d|^2 further than 2^-18 from 1, or an origin beyond 64 x the
  * scene's largest coordinate, are replayed in the reference's visit order (exact, slower); OCCLUDED rays from such origins take
- * a walk that does not cull by tmax.
+ * a walk that does not cull by tmax.  So is a CLOSEST hit whose group TraceRay would not have scanned (a ray that grazes the
+ * group's bounding sphere at a vertex).  The boxes are walked along the ray IntersectRayTriangle tests, (o + d) - o in floats,
+ * whatever its length; a ray whose products in that test can pass FLT_MAX (|d| x |o - vertex| x the scene's size near 2^127) is
+ * tested against every triangle in the reference's order, linear in the scene.
  * Counters: ray_count = count (one TraceRay call per ray); node_visits / tri_tests with PRT_FLAG_COUNT_VISITS in `flags`;
  * render_ms = the call's device time, trace_kernel_ms = the traversal kernels'; pipeline = 0.  A query leaves
  * prt_get_render_stats (the last render's) unchanged.
  * Errors: -1 NULL origins / directions with count > 0, unknown mode, NULL batch; -2 no scene; -8 near ties unresolved;
  * -10 a HIP call failed.  count == 0 does nothing and returns 0.
  * The first query after an upload builds a leaf -> (group, vertex0) table on the device (8 B per triangle; not in
- * prt_scene_info.device_bytes; freed by the next upload). */
+ * prt_scene_info.device_bytes; freed by the next upload), and prt_trace_rays the inverse of the visit ranks beside it (4 B per
+ * triangle, the same lifetime; built again after a prt_update_geometry). */
 enum { PRT_QUERY_CLOSEST = 0, PRT_QUERY_OCCLUDED = 1 };
 typedef struct prt_ray_batch {
     const float * origins;         /* count x 3 */

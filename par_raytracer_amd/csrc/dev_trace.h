@@ -5,6 +5,7 @@
 // Both implement one interface, and everything below the #include is written against it once:
 //   TravRay; LdsStack<BLOCK>, LdsSpillStack<BLOCK>, GlobalStack; StackEntry, STACK_ENTRY_INTS, BVH_NODE_BYTES
 //   trav_idle(r), trav_init(r, o, d, kind, pad, stk)                          no ray / a ray at the root
+//   trav_start<ANY_LENGTH>(r, o, d, kind, pad, stk)                           the same, for directions of any length (below)
 //   trav_walking(r), trav_done(r)                                             wants a node step / ended; neither: holds a leaf
 //   trav_node_step<STK, COUNT>(sc, r, stk, st, pad), trav_leaf<STK, COUNT>(sc, r, stk, st)
 //   trav_leaf_range(r, first, count), trav_leaf_next(r, stk)                  the held leaf's triangles, and the step past it
@@ -19,6 +20,43 @@
 #endif
 
 namespace prt {
+
+// ---------------------------------------------------------------------------------------------------------------------
+// trav_init walks the boxes along the direction it is given and clamps its components away from 0 at an ABSOLUTE 1e-30: sound
+// for a unit direction from an origin near the scene, which is all the render kernels ever trace.  A query's origin and
+// direction are anything (include/prt.h), and two things then part the box test from the triangle test:
+//   * IntersectRayTriangle does not test the ray o + t d but o + t w, w = (o + d) - o as floats (qp = o - (o + d),
+//     raytracer.cpp:88-89).  For a unit direction in a scene scaled by 2^20, w is d rounded to quarters: another ray.
+//     trav_start<true> - the query paths - walks the boxes along w.  (w = 0: no triangle can be hit; any walk will do.)
+//   * the clamp is absolute.  At |d| = 1e-29 it is a tenth of the ray and bends it out of the boxes its triangles lie in; in a
+//     scene of coordinates beyond 3e8 the clamped component's 1 / 1e-30 times a coordinate is inf, and inf - inf = NaN culls
+//     the box.  trav_start<true> clamps at 2^-40 of the direction's largest component m instead (across the whole scene a
+//     2^-22th of the pad; 1 / component times a coordinate stays finite up to coordinates of 2^67 m), after bringing m into
+//     [1, 2) where it is below 2^-20, by a power of two, which is exact.  The box parameters of such a short direction then
+//     come out 2^k times too SMALL beside the ray's own t (the best hit, tmax), so a box is culled against the best hit later
+//     than it could be and never sooner: conservative.  Unit directions are walked as they are.
+// The triangle tests see the caller's direction, bit for bit.  trav_start<false> is trav_init.
+template <bool ANY_LENGTH, class STK>
+PRT_D void trav_start(TravRay & r, f3 o, f3 d, int kind, float pad, const STK & stk) {
+    if (ANY_LENGTH) {
+        f3 w = (o + d) - o;
+        if (w.x == 0.0f && w.y == 0.0f && w.z == 0.0f) w = d;
+        float m = fmaxf(fmaxf(fabsf(w.x), fabsf(w.y)), fabsf(w.z));
+        if (m < 9.5367431640625e-7f) {                                      // 2^-20
+            const int k = -ilogbf(m);
+            w = mk3(ldexpf(w.x, k), ldexpf(w.y, k), ldexpf(w.z, k));
+            m = ldexpf(m, k);
+        }
+        const float tiny = m * 9.094947017729282e-13f;                      // 2^-40
+        if (fabsf(w.x) < tiny) w.x = copysignf(tiny, w.x);
+        if (fabsf(w.y) < tiny) w.y = copysignf(tiny, w.y);
+        if (fabsf(w.z) < tiny) w.z = copysignf(tiny, w.z);
+        trav_init(r, o, w, kind, pad, stk);
+        r.d = d;
+        return;
+    }
+    trav_init(r, o, d, kind, pad, stk);
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Near ties: the reference's answer for a ray whose closest hit has company within a few ulp.
@@ -38,7 +76,7 @@ namespace prt {
 // counted (DevScene::near_tie_unresolved: the render call then fails - it has never been seen to happen).
 // The reference also skips a whole GROUP whose bounding sphere it enters later than its best hit so far
 // (raytracer.cpp:176-181): RefSphereWalk (dev_trace_common.h) replays that on the uploaded sphere tree.
-template <class STK, bool COUNT>
+template <class STK, bool COUNT, bool ANY_LENGTH = false>
 PRT_D HitRec resolve_near_ties(const DevScene & sc, f3 o, f3 d, float pad, float min_t, const STK & stk, TraceStats & st) {
     TravRay r;
     HitRec result = hit_miss();
@@ -57,7 +95,7 @@ PRT_D HitRec resolve_near_ties(const DevScene & sc, f3 o, f3 d, float pad, float
             // the member of N with the smallest rank >= next_rank
             unsigned int c_rank = 0xFFFFFFFFu;
             int c_tri = -1;
-            trav_init(r, o, d, TRACE_CLOSEST, pad, stk);
+            trav_start<ANY_LENGTH>(r, o, d, TRACE_CLOSEST, pad, stk);
             r.best.t = moat;                                        // the boxes are culled against the moat's far side
             for (;;) {
                 while (trav_walking(r)) trav_node_step<STK, COUNT>(sc, r, stk, st, pad);
@@ -101,18 +139,78 @@ PRT_D HitRec resolve_near_ties(const DevScene & sc, f3 o, f3 d, float pad, float
 // Whole-ray traversal, "while-while" (Aila & Laine): every lane first walks internal nodes until it holds a leaf (or runs out
 // of work), and only then does the wave run the triangle code.  With 64 lanes a fused node-or-leaf loop would execute the (4x
 // longer) leaf body in almost every iteration.  Near ties are decided on the spot: this is the form for the slow paths, on a
-// stack that cannot overflow.
-template <class STK, bool COUNT>
+// stack that cannot overflow.  ANY_LENGTH: the queries' form (trav_start).
+template <class STK, bool COUNT, bool ANY_LENGTH = false>
 PRT_D HitRec trace_ray(const DevScene & sc, f3 o, f3 d, int kind, float pad, const STK & stk, TraceStats & st) {
     TravRay r;
-    trav_init(r, o, d, kind, pad, stk);
+    trav_start<ANY_LENGTH>(r, o, d, kind, pad, stk);
     for (;;) {
         while (trav_walking(r)) trav_node_step<STK, COUNT>(sc, r, stk, st, pad);
         if (trav_done(r)) break;
         if (trav_leaf<STK, COUNT>(sc, r, stk, st)) return r.best;           // any-hit ray: found its occluder
     }
-    if (trav_wants_resolve(r, stk)) return resolve_near_ties<STK, COUNT>(sc, o, d, pad, r.best.t, stk, st);
+    if (trav_wants_resolve(r, stk)) return resolve_near_ties<STK, COUNT, ANY_LENGTH>(sc, o, d, pad, r.best.t, stk, st);
     return r.best;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Rays whose triangle test overflows.  IntersectRayTriangle multiplies the direction, the origin's distance from a vertex and the
+// triangle's edges (raytracer.cpp:82-125): where such a product passes FLT_MAX the sums behind it are inf - inf = NaN, every
+// comparison with a NaN is false, and the reference ACCEPTS a triangle the ray's line is nowhere near (a direction of length
+// 2^120 from 10^4 scene extents away).  No box test can find such a hit, so a query traces these rays without one:
+// ray_overflows is true when a bound of the products' exponents - s: the scene's largest |coordinate| -
+//     |qp| < 2^ed   |ap| < 2^eo   |ab|, |ac| < 2^(es + 1)   |n| < 2^(2 es + 3)
+//     dd < 2^(ed + 2 es + 5)   t < 2^(eo + 2 es + 5)   |e| < 2^(ed + eo + 1)   v, w < 2^(ed + eo + es + 4)
+// reaches 2^127; scan_closest is then TraceRay as written - every triangle in the reference's visit order (slot_of_rank: the
+// inverse of tri_rank) through RefSphereWalk and the reference's filter - and scan_any_below the brute-force rule of OCCLUDED.
+// Linear in the scene per ray; unit directions near the scene never come here.
+PRT_D bool ray_overflows(float scene_max, f3 o, f3 d) {
+    const float D = fmaxf(fmaxf(fabsf(d.x), fabsf(d.y)), fabsf(d.z)), O = fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z));
+    const float s = fmaxf(scene_max, 1.17549435e-38f);
+    const int es = ilogbf(s) + 1, eo = ilogbf(fmaxf(O, s)) + 2;
+    const int ed = ilogbf(fmaxf(fmaxf(D, O * 1.1920929e-7f), 1.17549435e-38f)) + 2;          // qp = o - (o + d): d, or the rounding of o + d
+    const int top = (ed > eo ? ed : eo) + 2 * es + 5, mixed = ed + eo + es + 4;
+    return (top > mixed ? top : mixed) >= 127;
+}
+
+template <bool COUNT>
+PRT_D HitRec scan_closest(const DevScene & sc, const unsigned int * slot_of_rank, f3 o, f3 d, TraceStats & st) {
+    const f3 qp = o - (o + d);
+    HitRec h = hit_miss();
+    RefSphereWalk walk;
+    walk.reset();
+    for (unsigned int rank = 0; rank < sc.tri_count; ++rank) {
+        if (!walk.offers(sc, o, d, rank, h.t)) {
+            if (walk.skip_until > rank) rank = walk.skip_until - 1u;        // the refused sphere's range ends there
+            continue;
+        }
+        const unsigned int ti = slot_of_rank[rank];
+        const float4 * tp = sc.tris + 3 * (size_t)ti;
+        const float4 r0 = tp[0], r1 = tp[1], r2 = tp[2];
+        float t, v, w;
+        if (COUNT) st.tris++;
+        if (tri_test_ref(o, qp, mk3(r0.x, r0.y, r0.z), mk3(r0.w, r1.x, r1.y), mk3(r1.z, r1.w, r2.x), mk3(r2.y, r2.z, r2.w), h.t, t, v, w)) {
+            h.t = t; h.v = v; h.w = w; h.tri = (int)ti;
+        }
+    }
+    return h;
+}
+
+template <bool COUNT>
+PRT_D HitRec scan_any_below(const DevScene & sc, f3 o, f3 d, float tmax, TraceStats & st) {
+    const f3 qp = o - (o + d);
+    HitRec h = hit_miss();
+    for (unsigned int ti = 0; ti < sc.tri_count; ++ti) {
+        const float4 * tp = sc.tris + 3 * (size_t)ti;
+        const float4 r0 = tp[0], r1 = tp[1], r2 = tp[2];
+        float t, dd, v, w;
+        if (COUNT) st.tris++;
+        if (!tri_geom(o, qp, mk3(r0.x, r0.y, r0.z), mk3(r0.w, r1.x, r1.y), mk3(r1.z, r1.w, r2.x), mk3(r2.y, r2.z, r2.w), t, dd, v, w)) continue;
+        if (t > 3.402823466e+38f * dd) continue;                            // raytracer.cpp:104 against FLT_MAX
+        const float th = t * (1.0f / dd);
+        if (th < tmax) { h.t = th; h.tri = (int)ti; return h; }
+    }
+    return h;
 }
 
 }  // namespace prt

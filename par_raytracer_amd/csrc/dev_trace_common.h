@@ -147,10 +147,15 @@ PRT_D bool tri_test(f3 o, f3 d, f3 qp, f3 a, f3 ab, f3 ac, f3 n, float best_t, f
 // ---------------------------------------------------------------------------------------------------------------------
 // The reference's bounding-sphere tree, as far as it is OBSERVABLE: TraceRay (raytracer.cpp:159-232) walks it depth first,
 // c1 before c0, and never scans a group that lies below a sphere the ray misses or ENTERS LATER THAN ITS BEST HIT SO FAR
-// (:176-181).  For a closest hit with room around it that changes nothing (a hit lies inside its group's sphere, which the ray
-// therefore enters no later).  When several hits are within an ulp or two of each other - resolve_near_ties() - a candidate that
-// sits on the very surface of its group's sphere can be passed over by the reference because the sphere's own rounded entry
-// distance exceeds the best hit by an ulp.  RefSphereWalk replays exactly that: candidates come in the reference's visit order
+// (:176-181).  In exact arithmetic that changes nothing for a closest hit with room around it: a hit lies inside its group's
+// sphere, which the ray therefore enters no later.  In the reference's float arithmetic it does, in two ways.  When several hits
+// are within an ulp or two of each other - resolve_near_ties() - a candidate that sits on the very surface of its group's sphere
+// can be passed over because the sphere's own rounded entry distance exceeds the best hit by an ulp.  And a ray through one of
+// the extreme vertices a sphere was built through grazes it: IntersectRaySphere's discriminant comes out negative and the
+// whole group is dropped, however clear the hit (measured: 30 of 8,192 axis-parallel rays through vertices and edge midpoints
+// of cornell_box, none on icosphere_l3 or coincident).  The render kernels keep the assumption - a jittered camera ray grazes a
+// sphere with probability zero, and the parity goldens have always passed; the queries do not (kernels_query.h
+// query_hit_stands).  RefSphereWalk replays exactly what the reference does: candidates come in the reference's visit order
 // (tri_rank ascending); every sphere on the way to a candidate's group is tested the first time the walk meets it, against
 // the replayed best hit of that moment, with IntersectRaySphere's own float expressions (raytracer.cpp:32-60); a sphere that
 // fails takes its whole rank range out.  Spheres are visited in ascending `pre` (their position in the reference's pop order),

@@ -7,10 +7,13 @@
 //                  below tmax (the best hit starts at tmax: tri_test accepts th < best_t).  A ray that is a miss by definition is
 //                  written at once.  Rays that end flagged (a near tie, or a push that did not fit the LDS column) go to a list,
 //                  as do CLOSEST rays whose direction is not unit length or whose origin is far from the scene (query_replays),
-//                  and OCCLUDED rays from far origins (query_any_unculled).
+//                  and OCCLUDED rays from far origins (query_any_unculled), rays whose triangle test overflows (ray_overflows,
+//                  dev_trace.h), and CLOSEST hits whose group the reference would
+//                  not have scanned (query_hit_stands).
 //   k_query_exact  traces the listed rays again on a full-height global stack: trace_ray (near ties decided in the reference's
-//                  visit order by resolve_near_ties), the full replay of TraceRay for non-unit directions, or the any-hit walk
-//                  below tmax.
+//                  visit order by resolve_near_ties), the full replay of TraceRay for non-unit directions and for hits that do
+//                  not stand, the any-hit walk below tmax, or the scan of every triangle for rays that overflow.
+// Directions have any length: every traversal here starts with trav_start<true> (dev_trace.h).
 // Only the fields the caller asked for are written (a wave-uniform mask), with plain vector stores.
 #pragma once
 
@@ -37,6 +40,8 @@ struct QueryArgs : BatchShared {
     float * normal;                  // x3
     unsigned char * occluded;
     float replay_beyond;             // CLOSEST rays whose biased origin lies further out are replayed (query_replays)
+    float scene_max;                 // the scene's largest |coordinate| (ray_overflows)
+    const unsigned int * slot_of_rank;      // the inverse of DevScene::tri_rank (scan_closest)
 };
 
 // Ray i, origin biased as TraceRay does (raytracer.cpp:163).  False for a ray that is a miss by definition: a non-finite
@@ -58,11 +63,25 @@ PRT_D bool query_ray(const QueryArgs & A, unsigned int i, f3 & ob, f3 & d) {
 // reference's filter in the reference's visit order, sphere tests included (RefSphereWalk) - TraceRay, step for step.  The same
 // holds for an origin far from the scene (beyond 64 x its largest coordinate): there IntersectRaySphere's c = m.m - r^2 cancels
 // and the reference drops groups at random.
+PRT_D bool query_overflows(const QueryArgs & A, f3 ob, f3 d) { return ray_overflows(A.scene_max, ob, d); }
 PRT_D bool query_far(const QueryArgs & A, f3 ob) { return fmaxf(fmaxf(fabsf(ob.x), fabsf(ob.y)), fabsf(ob.z)) > A.replay_beyond; }
 PRT_D bool query_replays(const QueryArgs & A, f3 ob, f3 d) {
     const float l2 = dot3(d, d);
     const bool unit = l2 >= 1.0f - 3.814697265625e-6f && l2 <= 1.0f + 3.814697265625e-6f;
     return !unit || query_far(A, ob);
+}
+
+// The closest hit over all triangles is TraceRay's hit only if TraceRay scans the hit's group: every sphere on the way down to it
+// must pass IntersectRaySphere and be entered no later than the best hit of that moment.  In exact arithmetic a hit lies inside
+// its group's sphere; in the reference's float arithmetic a ray through one of the extreme vertices the sphere was built
+// through grazes it and can fail the test (an axis-parallel ray up an edge of cornell_box: TraceRay misses the ceiling).  So
+// the winner is put to RefSphereWalk with its own t as the best hit: TraceRay's best at that moment is no smaller, so a sphere
+// that passes here passes there.  A refusal proves nothing - the ray is then replayed in full, which is TraceRay step for step.
+PRT_D bool query_hit_stands(const DevScene & sc, f3 ob, f3 d, const HitRec & h) {
+    if (h.tri < 0 || !sc.ref_spheres) return true;
+    RefSphereWalk walk;
+    walk.reset();
+    return walk.offers(sc, ob, d, sc.tri_rank[h.tri], h.t);
 }
 
 // The RaycastHit of ray i (raytracer.cpp:20-30, 82-125) into the requested fields.  h.tri < 0: a miss - the reference's
@@ -121,10 +140,10 @@ struct QueryJob : RaySteps<BLOCK, COUNT> {
     PRT_D bool start(unsigned int idx, TravRay & r, const LdsStack<BLOCK> & stack) const {
         f3 ob, d;
         const bool valid = query_ray(A, idx, ob, d);
-        if (valid && (MODE == QUERY_CLOSEST ? query_replays(A, ob, d) : query_far(A, ob))) {
-            batch_to_slow_list(A, idx);                                     // query_replays / query_any_unculled
+        if (valid && (query_overflows(A, ob, d) || (MODE == QUERY_CLOSEST ? query_replays(A, ob, d) : query_far(A, ob)))) {
+            batch_to_slow_list(A, idx);                                     // scan_* / query_replays / query_any_unculled
         } else if (valid) {
-            trav_init(r, ob, d, MODE == QUERY_OCCLUDED ? TRACE_ANY : TRACE_CLOSEST, this->pad, stack);
+            trav_start<true>(r, ob, d, MODE == QUERY_OCCLUDED ? TRACE_ANY : TRACE_CLOSEST, this->pad, stack);
             if (MODE == QUERY_OCCLUDED && A.tmax) r.best.t = A.tmax[idx];
             return true;
         } else {
@@ -133,7 +152,7 @@ struct QueryJob : RaySteps<BLOCK, COUNT> {
         return false;
     }
     PRT_D void finish(unsigned int idx, const TravRay & r, const LdsStack<BLOCK> & stack) const {
-        if (trav_needs_slow_path(r, stack)) batch_to_slow_list(A, idx);
+        if (trav_needs_slow_path(r, stack) || (MODE == QUERY_CLOSEST && !query_hit_stands(this->sc, r.o, r.d, r.best))) batch_to_slow_list(A, idx);
         else query_emit<MODE>(this->sc, A, leaf_map, fields, idx, r.o, r.d, r.best);       // r.o: the biased origin
     }
 };
@@ -156,7 +175,7 @@ __global__ __launch_bounds__(BLOCK, 6) void k_query(DevScene sc, QueryArgs A, co
 template <class STK, bool COUNT>
 PRT_D HitRec query_any_below(const DevScene & sc, f3 o, f3 d, float tmax, float pad, const STK & stk, TraceStats & st) {
     TravRay r;
-    trav_init(r, o, d, TRACE_ANY, pad, stk);
+    trav_start<true>(r, o, d, TRACE_ANY, pad, stk);
     r.best.t = tmax;
     for (;;) {
         while (trav_walking(r)) trav_node_step<STK, COUNT>(sc, r, stk, st, pad);
@@ -173,7 +192,7 @@ PRT_D HitRec query_any_below(const DevScene & sc, f3 o, f3 d, float tmax, float 
 template <class STK, bool COUNT>
 PRT_D HitRec query_any_unculled(const DevScene & sc, f3 o, f3 d, float tmax, float pad, const STK & stk, TraceStats & st) {
     TravRay r;
-    trav_init(r, o, d, TRACE_ANY, pad, stk);
+    trav_start<true>(r, o, d, TRACE_ANY, pad, stk);
     r.best.t = __uint_as_float(0x7F800000u);
     const f3 qp = o - (o + d);                                              // raytracer.cpp:88-89
     HitRec h = hit_miss();
@@ -207,14 +226,23 @@ __global__ __launch_bounds__(256) void k_query_exact(DevScene sc, QueryArgs A, c
         f3 ob, d;
         (void)query_ray(A, idx, ob, d);                                     // listed rays are valid
         HitRec h;
-        if (MODE == QUERY_OCCLUDED && query_far(A, ob))
+        if (query_overflows(A, ob, d)) {
+            if (MODE == QUERY_OCCLUDED) h = scan_any_below<COUNT>(sc, ob, d, A.tmax ? A.tmax[idx] : 3.402823466e+38f, st);
+            else h = scan_closest<COUNT>(sc, A.slot_of_rank, ob, d, st);
+        } else if (MODE == QUERY_OCCLUDED && query_far(A, ob))
             h = query_any_unculled<GlobalStack, COUNT>(sc, ob, d, A.tmax ? A.tmax[idx] : 3.402823466e+38f, pad, slow, st);
         else if (MODE == QUERY_OCCLUDED)
             h = query_any_below<GlobalStack, COUNT>(sc, ob, d, A.tmax ? A.tmax[idx] : 3.402823466e+38f, pad, slow, st);
-        else if (query_replays(A, ob, d))
-            h = resolve_near_ties<GlobalStack, COUNT>(sc, ob, d, pad, 3.402823466e+38f, slow, st);      // bound = inf: every candidate
-        else
-            h = trace_ray<GlobalStack, COUNT>(sc, ob, d, TRACE_CLOSEST, pad, slow, st);
+        else {
+            bool replay = query_replays(A, ob, d);
+            if (!replay) {
+                // a miss here is a true miss, or a near tie all of whose members the reference's spheres refused: either way the
+                // full replay decides (for a true miss it is one walk that finds no candidate)
+                h = trace_ray<GlobalStack, COUNT, true>(sc, ob, d, TRACE_CLOSEST, pad, slow, st);
+                replay = h.tri < 0 || !query_hit_stands(sc, ob, d, h);
+            }
+            if (replay) h = resolve_near_ties<GlobalStack, COUNT, true>(sc, ob, d, pad, 3.402823466e+38f, slow, st);      // bound = inf: every candidate
+        }
         query_emit<MODE>(sc, A, leaf_map, fields, idx, ob, d, h);
     });
 }

@@ -180,6 +180,8 @@ struct prt_ctx {
     std::vector<uint32_t> q_tri_order;    // leaf slot -> input triangle
     std::vector<prt_group> q_groups;
     DevBuf<uint2> q_leaf_map;             // leaf slot -> (group, vertex0)
+    DevBuf<unsigned int> q_slot_of_rank;  // prt_trace_rays: the inverse of tri_rank (scan_closest); built with q_leaf_map's lifetime,
+                                          // and again after a prt_update_geometry that ranks the triangles anew
     DevBuf<unsigned int> q_work;          // the batch's control words (BatchShared::work, dev_wave_loop.h)
     DevBuf<unsigned int> q_slow;          // rays handed to k_query_exact
     DevBuf<int> q_exact_stack;
@@ -1271,9 +1273,24 @@ struct RayWalk {
     typedef QueryArgs Args;
     int mode;
     static const char * name() { return "prt_trace_rays"; }
-    void prepare(prt_ctx * ctx, QueryArgs & A) const {
+    int prepare(prt_ctx * ctx, QueryArgs & A) const {
         ctx->scene.tie_widen_max = (unsigned int)std::max(0ll, std::min(64ll, ctx->opt.tie_widen_max));
         A.replay_beyond = 64.0f * ctx->scene_abs_max;
+        A.scene_max = ctx->scene_abs_max;
+        const uint32_t n_tris = ctx->scene.tri_count;
+        if (!ctx->q_slot_of_rank.p && n_tris) {
+            std::vector<unsigned int> rank(n_tris), slot_of_rank(n_tris, 0u);
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));          // an update's copy of the ranks runs on it
+            HIP_TRY(ctx, hipMemcpy(rank.data(), ctx->tri_rank.p, (size_t)n_tris * sizeof(unsigned int), hipMemcpyDeviceToHost));
+            for (uint32_t slot = 0; slot < n_tris; ++slot) {
+                if (rank[slot] >= n_tris) { ctx->error = "prt_trace_rays: the scene's visit ranks are not a permutation"; return -2; }
+                slot_of_rank[rank[slot]] = slot;
+            }
+            HIP_TRY(ctx, ctx->q_slot_of_rank.upload(slot_of_rank));
+            HIP_TRY(ctx, hipDeviceSynchronize());          // the upload went through the null stream
+        }
+        A.slot_of_rank = ctx->q_slot_of_rank.p;
+        return 0;
     }
     int tables(prt_ctx *, QueryArgs &, unsigned int) const { return 0; }
     static void (*pad_kernel())(QueryArgs) { return k_query_pad; }
@@ -1304,7 +1321,7 @@ struct RayWalk {
 struct PointWalk {
     typedef ClosestArgs Args;
     static const char * name() { return "prt_closest_points"; }
-    void prepare(prt_ctx *, ClosestArgs &) const {}
+    int prepare(prt_ctx *, ClosestArgs &) const { return 0; }
     // prt_signed_distance: a refill of the accumulators counts in render_ms
     int tables(prt_ctx * ctx, ClosestArgs & A, unsigned int fields) const { return (fields & (CF_SIGNED | CF_FEATURE)) ? ensure_signed_tables(ctx, A) : 0; }
     static void (*pad_kernel())(ClosestArgs) { return k_closest_pad; }
@@ -1323,7 +1340,7 @@ int run_batch(prt_ctx * ctx, const Walk & q, typename Walk::Args A, unsigned int
     const int map_rc = ensure_leaf_map(ctx, Walk::name());
     if (map_rc) return map_rc;
     hipStream_t stream = ctx->stream;
-    q.prepare(ctx, A);
+    if (const int rc = q.prepare(ctx, A)) return rc;
     // LDS stack column as the render pipelines size it; the exact kernel's fixed grid gets full-height global columns
     A.stack_lds_entries = lds_stack_entries(ctx);
     const size_t exact_lanes = 64 * 256;
@@ -1664,6 +1681,7 @@ int update_geometry(prt_ctx * ctx, const prt_geometry_update * u, prt_update_inf
         REFIT_TRY(hipGetLastError());
     }
     REFIT_TRY(hipMemcpyAsync(ctx->tri_rank.p, rank.data(), rank.size() * sizeof(unsigned int), hipMemcpyHostToDevice, stream));
+    ctx->q_slot_of_rank.release();                                // the next prt_trace_rays inverts the new ranks (the stream has drained by then)
     if (!ref_spheres.empty()) {
         REFIT_TRY(ctx->ref_spheres.ensure(ref_spheres.size()));
         REFIT_TRY(hipMemcpyAsync(ctx->ref_spheres.p, ref_spheres.data(), ref_spheres.size() * sizeof(float4), hipMemcpyHostToDevice, stream));
@@ -2062,7 +2080,7 @@ void prt_destroy(prt_ctx * ctx) {
     ctx->sample_rgb.release(); ctx->frame_out.release(); ctx->counters.release(); ctx->ring_ws.release(); ctx->pixel_list.release(); ctx->wf_counts.release(); ctx->stack_spill.release(); ctx->pool_f4.release(); ctx->pool_park.release(); ctx->pool_fin.release(); ctx->pool_args.release(); ctx->adapt_f4.release(); ctx->wave_times.release();
     ctx->textures.release(); ctx->texels.release(); ctx->srgb_lut.release(); ctx->tri_uv.release(); ctx->tri_tan.release();
     ctx->ref_spheres.release();
-    ctx->q_leaf_map.release(); ctx->q_work.release(); ctx->q_slow.release(); ctx->q_exact_stack.release(); ctx->q_io.release(); ctx->q_occ.release();
+    ctx->q_leaf_map.release(); ctx->q_slot_of_rank.release(); ctx->q_work.release(); ctx->q_slow.release(); ctx->q_exact_stack.release(); ctx->q_io.release(); ctx->q_occ.release();
     ctx->rf_table.release(); ctx->rf_boxes.release(); ctx->rf_bounds.release(); ctx->rf_in.release();
     ctx->qg_idx.release(); ctx->qg_runs.release(); ctx->qg_acc.release(); ctx->qg_words.release(); ctx->qg_io.release();
     for (int c = 0; c < PRT_MAX_CHAINS; ++c) {
@@ -2121,7 +2139,7 @@ int prt_upload_scene(prt_ctx * ctx, const prt_scene_desc * s) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->has_scene = false;
-    ctx->q_leaf_map.release();
+    ctx->q_leaf_map.release(); ctx->q_slot_of_rank.release();
     ctx->q_tri_order.clear();
     ctx->q_groups.clear();
     ctx->rf_table.release();

@@ -23,8 +23,12 @@ def _fixture(name):
 
 
 def _bits(a):
+    """The array's bits, every NaN as one pattern: which NaN an invalid operation gives is the hardware's choice (the oracle's CPU
+    raises the negative one, the GPU the positive one), and TraceRay's barycentrics are NaN where its triangle test overflows."""
     a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype in (np.float32, np.int32) else a
+    if a.dtype == np.float32:
+        return np.where(np.isnan(a), np.uint32(0x7FC00000), a.view(np.uint32))
+    return a.view(np.uint32) if a.dtype == np.int32 else a
 
 
 def check_fixture(r, g, torch_path: bool, count_visits: bool = False):

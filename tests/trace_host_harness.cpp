@@ -7,10 +7,19 @@
 // that any-hit rays agree on occluded / not occluded.  Scene: a wavy height field plus floating, doubled and coplanar
 // triangles (harness_scene.h).  Built and run by tests/test_trace_host.py.
 //
+//   trace_host --file PATH        triangles and rays from a file instead (tests/test_trace_edges_host.py): uint32 triangle count,
+//                                 uint32 ray count, 9 floats per triangle in input order, 3 floats per origin, 3 per direction.
+//                                 The rays go the queries' way: the traversal starts with trav_start<true> (directions of any
+//                                 length), the box pad is 2^-16 of the largest |coordinate| of scene and origins, and a ray
+//                                 whose triangle test overflows (ray_overflows) is scanned over every triangle instead -
+//                                 the count of those is printed.
+//   trace_host --file-plain PATH  the same, but through the renders' start of a traversal (trav_init's absolute clamp), for comparison.
+//
 //   g++ -O1 -std=c++17 -ffp-contract=off -Itests/hip_shim -Ipar_raytracer_amd/csrc tests/trace_host_harness.cpp \
 //       par_raytracer_amd/csrc/bvh_build.cpp -pthread -o /tmp/trace_host && /tmp/trace_host
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "dev_trace.h"
@@ -20,10 +29,28 @@
 
 using namespace prt;
 
+// The file of --file: false when it cannot be read whole.
+static bool load_case(const char * path, std::vector<float> & verts, std::vector<float> & rays) {
+    FILE * f = fopen(path, "rb");
+    if (!f) return false;
+    uint32_t head[2] = { 0, 0 };
+    bool ok = fread(head, 4, 2, f) == 2 && head[0] > 0;
+    if (ok) {
+        verts.resize((size_t)head[0] * 9);
+        rays.resize((size_t)head[1] * 6);
+        ok = fread(verts.data(), 4, verts.size(), f) == verts.size() && fread(rays.data(), 4, rays.size(), f) == rays.size();
+    }
+    fclose(f);
+    return ok;
+}
+
 int main(int argc, char ** argv) {
+    const bool any_length = argc > 2 && !strcmp(argv[1], "--file"), from_file = any_length || (argc > 2 && !strcmp(argv[1], "--file-plain"));
+    std::vector<float> verts, file_rays;
+    if (from_file && !load_case(argv[2], verts, file_rays)) { fprintf(stderr, "cannot read %s\n", argv[2]); return 2; }
     const int grid = argc > 1 ? atoi(argv[1]) : 48;
-    const int n_rays = argc > 2 ? atoi(argv[2]) : 20000;
-    const std::vector<float> verts = harness_scene(grid);
+    const int n_rays = from_file ? (int)(file_rays.size() / 6) : argc > 2 ? atoi(argv[2]) : 20000;
+    if (!from_file) verts = harness_scene(grid);
     const uint32_t n_tris = (uint32_t)(verts.size() / 9);
 
     BvhWide bvh;
@@ -64,11 +91,22 @@ int main(int argc, char ** argv) {
     TraceStats st;
     memset(&st, 0, sizeof(st));
 
-    const float pad = 16.0f / 65536.0f;
+    float pad = 16.0f / 65536.0f, scene_max = 0.0f;
+    unsigned long long scanned = 0;
+    if (from_file) {
+        for (float x : verts) scene_max = fmaxf(scene_max, fabsf(x));
+        float m = scene_max;
+        for (int k = 0; k < 3 * n_rays; ++k) m = fmaxf(m, fabsf(file_rays[k]));
+        pad = m * (1.0f / 65536.0f);
+    }
     unsigned long long mismatches = 0, hits = 0, any_mismatches = 0, near = 0;
     for (int k = 0; k < n_rays; ++k) {
         f3 o, d;
-        if (k % 3 == 0) {                                    // from above, downwards: terrain and decals head-on
+        if (from_file) {
+            o = mk3(file_rays[3 * (size_t)k], file_rays[3 * (size_t)k + 1], file_rays[3 * (size_t)k + 2]);
+            const float * dp = &file_rays[3 * (size_t)n_rays + 3 * (size_t)k];
+            d = mk3(dp[0], dp[1], dp[2]);
+        } else if (k % 3 == 0) {                             // from above, downwards: terrain and decals head-on
             o = mk3((float)(rnd() * 10 - 5), 3.0f, (float)(rnd() * 10 - 5));
             d = normalize3(mk3((float)(rnd() - 0.5) * 0.6f, -1.0f, (float)(rnd() - 0.5) * 0.6f));
         } else if (k % 3 == 1) {                             // grazing
@@ -103,18 +141,25 @@ int main(int argc, char ** argv) {
             }
             if (company > 1) near++;
         }
-        const HitRec h = trace_ray<GlobalStack, true>(sc, o, d, TRACE_CLOSEST, pad, stk, st);
+        const bool scan = from_file && ray_overflows(scene_max, o, d);
+        if (scan) scanned++;
+        const HitRec h = scan ? scan_closest<true>(sc, slot_of_rank.data(), o, d, st)
+                       : any_length ? trace_ray<GlobalStack, true, true>(sc, o, d, TRACE_CLOSEST, pad, stk, st)
+                                    : trace_ray<GlobalStack, true>(sc, o, d, TRACE_CLOSEST, pad, stk, st);
         if (btri >= 0) hits++;
         if (h.tri != btri || (btri >= 0 && (memcmp(&h.t, &best, 4) || memcmp(&h.v, &bv, 4) || memcmp(&h.w, &bw, 4)))) {
             if (mismatches < 10) fprintf(stderr, "ray %d: traversal (t %.9g tri %d) reference (t %.9g tri %d)\n", k, h.t, h.tri, best, btri);
             mismatches++;
         }
-        const HitRec a = trace_ray<GlobalStack, true>(sc, o, d, TRACE_ANY, pad, stk, st);
+        const HitRec a = scan ? scan_any_below<true>(sc, o, d, 3.402823466e+38f, st)
+                       : any_length ? trace_ray<GlobalStack, true, true>(sc, o, d, TRACE_ANY, pad, stk, st)
+                                    : trace_ray<GlobalStack, true>(sc, o, d, TRACE_ANY, pad, stk, st);
         if ((a.tri >= 0) != (btri >= 0)) any_mismatches++;
     }
     printf("%u triangles, %u nodes, depth %u, stack bound %u; %d rays, %llu hits, %llu with a near tie; "
            "closest-hit mismatches %llu, any-hit mismatches %llu, unresolved near ties %llu; %.2f node visits and %.2f triangle tests per traversal\n",
            n_tris, bvh.node_count, bvh.max_depth, bvh.stack_bound, n_rays, hits, near, mismatches, any_mismatches, unresolved,
            (double)st.nodes / (2.0 * n_rays), (double)st.tris / (2.0 * n_rays));
+    if (from_file) printf("%llu rays scanned over every triangle (ray_overflows)\n", scanned);
     return (mismatches || any_mismatches || unresolved) ? 1 : 0;
 }
