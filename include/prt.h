@@ -196,6 +196,10 @@ int prt_abi_version(void);
  *   BVH_BUILDER             "sah" (default): binned-SAH build on the host; "lbvh": radix tree built on the GPU (applies to the
  *                           next prt_upload_scene)
  *   POOL_EXACT              1: the pool pipeline's slow-path kernel renders everything (test hook; same image)
+ * Two of the tuning entries, because tests set them (same image, same counters either way):
+ *   POOL_FORK               pool pipeline, opaque untextured fixed-spp renders: the rays that enter at the last bounce level fly
+ *                           beside their sample's bounce walk instead of in its chain.  1 on, 0 off, -1 (default) = the build's choice
+ *   POOL_FORK_ROOM          the extra list entries those rays get, in eighths of the pool's capacity (default 8; 0: nothing forks)
  * Returns 0, or -1 (unknown name, value that does not parse, RESERVE_CUS after creation). */
 int prt_set_option(prt_ctx * ctx, const char * name, const char * value);
 
@@ -634,6 +638,7 @@ enum {
     PRT_REGION_WALK_CHILD_RAY,       /* after the walk: the surviving child's direction and throughput */
     PRT_REGION_OUTPUTS,              /* RNG state written back; lanes = samples that go on */
     PRT_REGION_WAVE,                 /* waves of the launch (kernel entry and exit) */
+    PRT_REGION_LEAF_RAY,             /* fork step: executions of its ray block; lanes = leaf rays made (marked, flying beside the walk) */
     PRT_REGION_COUNT
 };
 int prt_get_region_stats(const prt_ctx * ctx, uint64_t * out, uint32_t n);

@@ -175,7 +175,7 @@ PRT_SYMBOLS = ["prt_create", "prt_destroy", "prt_last_error", "prt_abi_version",
 # region test compares this list with the header's enum)
 REGION_NAMES = ["round", "topup", "topup_pass", "trace_outer", "refill", "walk_pass", "node_step", "node_descend", "node_pop", "node_push", "leaf",
                 "tri", "finish", "park", "shade_pass", "shade_hit", "shade_miss", "radiance_store", "shadow_block", "shadow_emit", "walk_loop",
-                "walk_next_child", "walk_enter", "walk_return_up", "frame_save", "frame_load", "walk_child_ray", "outputs", "wave"]
+                "walk_next_child", "walk_enter", "walk_return_up", "frame_save", "frame_load", "walk_child_ray", "outputs", "wave", "leaf_ray"]
 PRT_HOST_SYMBOLS = ["prt_host_load_obj", "prt_host_free_scene", "prt_host_scene_desc", "prt_host_scene_hierarchy_seconds",
                     "prt_host_scene_parse_seconds", "prt_host_last_error", "prt_host_make_camera",
                     "prt_host_default_params", "prt_host_render", "prt_host_render_error", "prt_host_write_image", "prt_host_tonemap",

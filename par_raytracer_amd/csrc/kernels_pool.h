@@ -41,6 +41,13 @@
 // four times as wide at the same state in flight, its tail is shared by four waves - the waves that run dry first wait at
 // the barrier, where they issue nothing, instead of walking half-empty - and everything else (lists in HBM, per-sample
 // state, parking, the adopting EXACT launch, which keeps wave-private pools) is unchanged.
+//
+// LEAF RAYS BESIDE THE WALK (constexpr FORKS in k_pool; options POOL_FORK, POOL_FORK_ROOM).  A sample held its pool slot for
+// one round per closest-hit ray of its bounce tree, because the walk keeps one such ray in flight.  The rays that enter at the
+// last level need no such order (kernels_wave.h, the fork step): a hit at the last-but-one level makes all its children at
+// once, marked, and its walk goes on without them.  A marked entry's shade event reads no RNG and no radiance record; with
+// leaves in flight nobody owns the record, so every add but a sample's first is an atomic.  The lists are `lcap` long, `cap`
+// still bounds the entries with a walk in progress, and a hit forks only while the next list has room for its worst case.
 #pragma once
 
 #include "kernels_wave.h"
@@ -67,6 +74,10 @@ struct PoolBuffers {
     unsigned int * park_count;   // [0] closest / finalise entries parked so far, [1] shadow entries
     unsigned int park_cap, spark_cap;
     unsigned int adopt;          // EXACT kernels: 1 = top up from the park list, not from the sample counter
+    // Forking kernels (leaf rays fly beside the walk, see k_pool): the lists hold `lcap` >= cap entries each - [units][2][3][lcap],
+    // hits [units][lcap], scap = lcap * lights - while `cap` stays the bound on entries with a walk in progress.  lcap == cap:
+    // no room for leaves, nothing forks (every other kernel: lcap is not read, the lists are `cap` long).
+    unsigned int lcap;
     // adaptive mode (k_pool<ADAPT>): the unit in the pool is a PIXEL that runs its samples one after the other
     unsigned int * fin;          // [units][cap]         pixels whose current sample has no ray left; finalised after the next trace phase
     float4 * scratch;            // [n_pixels][max_spp]  every sample's colour (RenderPixel's scratch_buffer, main.cpp:232)
@@ -81,9 +92,19 @@ struct PoolBuffers {
 // Emitter of k_pool: appends to the unit's lists, slots by rank among the appending lanes.  Per-wave pools (SHARED = false):
 // the fill counts are wave-uniform registers.  Block-shared pools: they are LDS words that every wave of the block adds to -
 // one ds_add_rtn per wave and call, the lanes' slots follow from the returned base and the ballot rank as before.
-template <bool ADAPT, bool SHARED, bool COUNT>
+// FORKS_: shade_entry_on makes the children of a frame at the last-but-one level all at once, as marked leaf rays (its fork
+// step); BLOCK_ is then the stride of the lanes' frame columns.
+template <bool ADAPT, bool SHARED, bool COUNT, bool FORKS_ = false, int BLOCK_ = 0>
 struct PoolEmit {
     enum { KEEPS_RNG = ADAPT ? 1 : 0 };      // adaptive mode: the pixel's next sample continues the RNG stream of the one that ended
+    enum { FORKS = FORKS_ ? 1 : 0, COL_STRIDE = BLOCK_ };
+    bool may_fork;               // FORKS, per lane: this entry's hit may fork - the next list has room for its worst case
+    int * col;                   // FORKS: this lane's frame column
+    unsigned int m_l;            // FORKS, wave-uniform: leaf entries among the m_c appended (SHARED: s_cnt[3], which only ADAPT uses otherwise)
+    PRT_D void leaves(unsigned int n) {
+        if (SHARED) { if (n != 0u && lane_id() == 0u) atomicAdd(&s_cnt[3], n); }
+        else m_l += n;
+    }
     float4 * co, * cd, * ct;     // next closest list
     float4 * so, * sc, * sd;     // next shadow list
     unsigned int * fin;          // ADAPT: pixels to finalise after the next trace phase
@@ -158,6 +179,7 @@ template <bool SHARED> PRT_D void pool_sync() {
 // LDS control words of a block-shared pool
 enum { PCTL_TRACE_NEXT = 0,      // rays of the trace phase handed out so far
        PCTL_TOPUP_BASE = 1,      // the sample counter's value this top-up got
+       PCTL_FORK_RES = 2,        // forking kernels, shade phase: passes started so far << 20 | closest entries reserved for them
        PCTL_CNT = 4,             // [2][4]: (closest, shadow, finalise, started-ahead) entries of the lists being filled, by parity of `cur`
        PCTL_WORDS = 12 };
 
@@ -229,6 +251,7 @@ __global__ void k_pool_store_args(PoolArgs a, PoolArgs * dst, unsigned int * zer
             a.Q.head = adopt_head;
             a.Q.cap /= adopt_cap_div;             // the fast kernel's pools were block-shared: the adopting launch's are a wave's share of one
             a.Q.scap /= adopt_cap_div;
+            a.Q.lcap /= adopt_cap_div;
             dst[1] = a;
         }
     }
@@ -242,6 +265,11 @@ __global__ void k_pool_store_args(PoolArgs a, PoolArgs * dst, unsigned int * zer
 template <int BLOCK, int WAVES, bool LDSTAB, bool RING, bool COUNT, bool TEX, bool ADAPT, int RINGMEM, bool EXACT, bool SHARED>
 __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, DevCounters * ctr) {
     static_assert(!(SHARED && EXACT), "the adopting EXACT launch keeps wave-private pools");
+    // Leaf rays fly beside the walk (kernels_wave.h shade_entry_on, the fork step) where no leaf can draw: an opaque untextured
+    // scene at fixed spp.  A sample then has up to 1 + (its frame's children) entries in the lists, one of them with a walk in
+    // progress: `cap` bounds those, `lcap` the lists (PoolBuffers::lcap), and a shade pass forks only when the next list has
+    // room for the pass's worst case - otherwise its leaves fly unmarked and the walk waits for them, as in every other kernel.
+    constexpr bool FORKS = !ADAPT && !TEX && RINGMEM == 0;
     extern __shared__ int s_stack[];
     constexpr int LDS_MATS = 32, LDS_LIGHTS = 4;
     __shared__ float4 s_diffuse[LDSTAB ? 1024 : 1];
@@ -290,6 +318,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
     unsigned int n_spec = 0;                   // (ADAPT) of those, pixels whose next camera ray is already in the closest list
     int cur = 0;
     unsigned int n_c = 0, n_s = 0;             // rays in the current closest / shadow list
+    unsigned int n_l = 0;                      // (FORKS) of the n_c, marked leaves: n_c - n_l entries have a walk in progress
     bool fetch_done = false;                   // the sample counter ran past n_samples
     unsigned long long rays = 0ull;            // wave-uniform
     unsigned int shaded_w = 0;                 // wave-uniform
@@ -299,14 +328,15 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
 // this wave's lists, from the arguments as re-read in the current phase
 #define PRT_POOL_LISTS(A)                                                                              \
     const unsigned int cap = (A).Q.cap, scap = (A).Q.scap;                                            \
-    float4 * const cq_base = (A).Q.cq + (size_t)wave * 6u * cap;                                      \
-    float4 * const hits = (A).Q.hits + (size_t)wave * cap;                                            \
+    const unsigned int lcap = FORKS ? (A).Q.lcap : cap;          /* entries per list */                \
+    float4 * const cq_base = (A).Q.cq + (size_t)wave * 6u * lcap;                                     \
+    float4 * const hits = (A).Q.hits + (size_t)wave * lcap;                                           \
     float4 * const sq_o = (A).Q.sq + (size_t)wave * 3u * scap;                                        \
     float4 * const sq_c = sq_o + scap;                                                                \
     float4 * const sq_d = sq_c + scap;                                                                \
-    float4 * const co = cq_base + (size_t)cur * 3u * cap;                                             \
-    float4 * const cd = co + cap;                                                                     \
-    float4 * const ct = cd + cap;                                                                     \
+    float4 * const co = cq_base + (size_t)cur * 3u * lcap;                                            \
+    float4 * const cd = co + lcap;                                                                    \
+    float4 * const ct = cd + lcap;                                                                    \
     (void)hits; (void)sq_o; (void)sq_c; (void)sq_d; (void)ct
 
     unsigned long long ph_topup = 0ull, ph_trace = 0ull, ph_shade = 0ull, ph_final = 0ull;      // COUNT: wave-cycles per phase
@@ -374,8 +404,10 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
                     rays -= cnt;                  // these rays were counted when the first launch traced them (raytracer.cpp:161: one TraceRay each)
                 }
             }
-          } else if (n_c + n_f - n_spec + (!SHARED && Q.guided ? (Q.guided_min < Q.topup_min ? Q.guided_min : Q.topup_min) : Q.topup_min) <= cap) {
-            const unsigned int room = cap - (n_c + n_f - n_spec);
+          } else if ((FORKS ? n_c - n_l : n_c + n_f - n_spec) + (!SHARED && Q.guided ? (Q.guided_min < Q.topup_min ? Q.guided_min : Q.topup_min) : Q.topup_min) <= cap) {
+            // FORKS: a fresh sample needs a walk slot (cap counts the entries with a walk in progress) and a place in the list
+            unsigned int room = cap - (FORKS ? n_c - n_l : n_c + n_f - n_spec);
+            if (FORKS) { const unsigned int lroom = n_c < lcap ? lcap - n_c : 0u; room = room < lroom ? room : lroom; }
             unsigned int want = room < Q.topup_max ? room : Q.topup_max;
             if (!SHARED && Q.guided) {
                 // guided self-scheduling (option POOL_GUIDED; adaptive mode's default): towards the end of the call no wave takes
@@ -595,11 +627,12 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
             tb.materials = sc.material_count <= (unsigned int)LDS_MATS ? s_mats : sc.materials;
             tb.lights = sc.light_count <= (unsigned int)LDS_LIGHTS ? s_lights : sc.lights;
             const int nxt = cur ^ 1;
-            PoolEmit<ADAPT, SHARED, COUNT> emit;
+            PoolEmit<ADAPT, SHARED, COUNT, FORKS, FORKS ? BLOCK : 0> emit;
+            emit.may_fork = false; emit.col = stack.frame_col(); emit.m_l = 0;
             emit.rg = rg;
-            emit.co = cq_base + (size_t)nxt * 3u * cap;
-            emit.cd = emit.co + cap;
-            emit.ct = emit.cd + cap;
+            emit.co = cq_base + (size_t)nxt * 3u * lcap;
+            emit.cd = emit.co + lcap;
+            emit.ct = emit.cd + lcap;
             emit.so = sq_o; emit.sc = sq_c; emit.sd = sq_d;
             emit.fin = fin;
             emit.m_c = 0; emit.m_s = 0; emit.m_f = 0; emit.m_elided = 0;
@@ -784,6 +817,47 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
                     rays -= (unsigned long long)__popcll(__ballot(cancelled));
                 }
                 unsigned int shaded = 0;
+                if (FORKS) {
+                    // Which hits of this pass may fork?  As many as the next list holds at their worst, whatever the rest of the
+                    // phase appends.  A forking hit (unmarked, at the last-but-one level) appends at most its R + S leaves and
+                    // one continuing ray, every other unmarked entry at most one ray, a leaf none - and every entry of the
+                    // passes that have not begun at most one, because a pass that forks asks first.  The first `n_may` forkers
+                    // of the pass fork; the others' leaves fly unmarked, one after the other, and their walks wait for them.
+                    const unsigned int n_child = P.reflection_samples + P.spec_samples;
+                    const bool walks = live && !parked && (pending & (unsigned int)WF_PENDING_LEAF_BIT) == 0u;
+                    const bool forker = walks && hit.tri >= 0 && level == (int)P.bounce_depth - 1;
+                    const unsigned long long m_fork = __ballot(forker);
+                    const unsigned int k_fork = (unsigned int)__popcll(m_fork), k_walk = (unsigned int)__popcll(__ballot(walks));
+                    unsigned int n_may = 0;                                            // wave-uniform
+                    if (lcap > cap && n_child != 0u) {
+                        unsigned int taken, rest;                                      // entries the next list owes to others: appended or reserved; not begun
+                        if (SHARED) {
+                            // The block's waves ask in ONE order - an LDS word counts the passes begun and the entries reserved
+                            // for them.  A pass that forks has seen the sum of the bounds of all passes before it (a bound never
+                            // grows afterwards) and knows that every pass behind it either stays within one ray per entry or
+                            // asks in turn: the last pass that forked has vouched for the whole list.
+                            unsigned int w = 0;
+                            if (lane == 0u) w = atomicAdd(&s_ctl[PCTL_FORK_RES], (1u << 20) + k_walk + k_fork * n_child);
+                            w = (unsigned int)__builtin_amdgcn_readfirstlane((int)w);
+                            // entries of the passes begun, this one included: 64 each, but for the list's last pass, which may
+                            // be among them with fewer (counted as if it were)
+                            const unsigned int short_by = 63u - ((n_c - 1u) & 63u);
+                            const unsigned int begun = ((w >> 20) + 1u) * 64u - short_by;
+                            taken = w & 0xFFFFFu;
+                            rest = n_c > begun ? n_c - begun : 0u;
+                        } else {
+                            taken = emit.m_c;
+                            rest = n_c > b0 + 64u ? n_c - (b0 + 64u) : 0u;
+                        }
+                        const unsigned int owed = taken + k_walk + rest;
+                        n_may = owed < lcap ? (lcap - owed) / n_child : 0u;
+                        if (n_may > k_fork) n_may = k_fork;
+                        // (shared: this pass's bound, corrected downwards to what it may really append)
+                        if (SHARED && n_may < k_fork && lane == 0u) atomicSub(&s_ctl[PCTL_FORK_RES], (k_fork - n_may) * n_child);
+                    }
+                    const unsigned int fork_rank = __builtin_amdgcn_mbcnt_hi((unsigned int)(m_fork >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)m_fork, 0u));
+                    emit.may_fork = forker && fork_rank < n_may;
+                }
                 if (live && !parked && !cancelled) region_count<COUNT>(rg, PRT_REGION_SHADE_PASS);
                 // the frame under construction lives in this lane's (idle) traversal stack column
                 shade_entry_lds<RING, TEX, BLOCK, RINGMEM>(sc, P, B, tb, live && !parked && !cancelled, s, level, pending, ray_o, ray_d, T, hit, emit, shaded, stack.frame_col());
@@ -844,10 +918,15 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
                 __syncthreads();                                               // every wave's appends are counted
                 n_c = emit.s_cnt[0]; n_s = emit.s_cnt[1]; n_f = emit.s_cnt[2];
                 if (ADAPT) n_spec = emit.s_cnt[3];
+                if (FORKS) {
+                    n_l = emit.s_cnt[3];
+                    if (threadIdx.x == 0) s_ctl[PCTL_FORK_RES] = 0u;              // nobody asks again before the next shade phase, two barriers on
+                }
             } else {
                 n_c = emit.m_c;
                 n_s = emit.m_s;
                 n_f = emit.m_f;
+                if (FORKS) n_l = emit.m_l;
             }
             cur = nxt;
         }

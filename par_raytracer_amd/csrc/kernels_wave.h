@@ -12,8 +12,9 @@
 //              wave-aggregated atomic per queue.
 //
 // The reference consumes its RNG in depth-first order of the recursion (raytracer.cpp:413-577), so a
-// sample has at most one closest-hit ray in flight; shadow rays use no RNG and ride along in the same
-// round.  Radiance is accumulated in throughput form: a frame contributes T * (ambient*0.1 + direct*Kd*w_d
+// sample has at most one closest-hit ray in flight WITH A WALK BEHIND IT; shadow rays use no RNG and ride along in the same
+// round, and so do - for emitters with the FORKS trait, k_pool's on opaque fixed-spp renders - the rays that enter at the
+// last level: they draw nothing either, and fly marked (WF_PENDING_LEAF_BIT) beside the walk.  Radiance is accumulated in throughput form: a frame contributes T * (ambient*0.1 + direct*Kd*w_d
 // + spec*Ks) and scales its children by T * Kd*w_d*weight / T * Ks*weight - the same polynomial as
 // raytracer.cpp:543-552 with the products distributed (differences ~1e-7 relative, tolerance 1e-4;
 // control flow - hits, roulette, directions - is bit exact and ray counts are equal).  Frames that still
@@ -34,6 +35,11 @@ enum { WF_STAGE_REFL = 0, WF_STAGE_SPEC = 1, WF_STAGE_ALPHA = 2, WF_STAGE_DONE =
 // closest-hit ray of its sample, so the sample's radiance record holds nothing yet - the shading lane does not read it and
 // writes it whatever it adds (no zero fill when the sample is fetched, no read at its first hit: 56 bytes per sample).
 enum { WF_PENDING_FRESH_BIT = 0x400000 };
+// ... and: this ray is a LEAF that flies beside its sample's walk (emitters with FORKS, see shade_entry_on's fork step).  It
+// entered at the last level, so its hit spawns nothing and draws nothing: its shade event adds its radiance and ends.  The bit
+// travels with the entry through the trace phase, the park list and the adopting launch (0x800000 is k_pool's
+// POOL_SPEC_PENDING_BIT, bits 0..16 the level mask).
+enum { WF_PENDING_LEAF_BIT = 0x200000 };
 
 struct WaveBuffers {
     Accum * accum;               // [N] per-sample radiance (xyz), fixed point (dev_scene.h)
@@ -280,6 +286,11 @@ struct WFrameLds : WFramePos<STRIDE, POS> {
     }
 };
 enum { WFRAME_LDS_DWORDS = 26, WFRAME_LDS_DWORDS_NOPOS = 23 };
+// The rows of WFrameLds by name, for code that reads ANOTHER lane's frame (the fork step of shade_entry_on).  Rows KD .. KS + 2
+// are dead once the light block has run in an untextured kernel (the child ray reads the material table): the fork step keeps
+// its child descriptors there, WF_FORK_GROUP rows of them.
+enum { WFL_HIT_P = 0, WFL_HIT_N = 3, WFL_RAY_D = 6, WFL_T_IN = 9, WFL_KD = 12, WFL_KS = 15, WFL_W_DIFFUSE = 19, WFL_MAT = 20 };
+enum { WF_FORK_GROUP = 6 };
 
 // POS: the frame carries hit_pos (alpha continuation rays start there, raytracer.cpp:547-552): only renders that can meet a
 // translucent material (RING && RINGMEM in the pool pipeline, RING in the wavefront pipeline) pay for that fifth float4.
@@ -347,7 +358,13 @@ PRT_D void shade_entry_on(const DevScene & sc, const DevParams & P, const WaveBu
     const int depth = (int)P.bounce_depth;
     // RINGMEM: 0 = no draw ring in memory (and an opaque scene); 1 = draw ring, materials may be translucent; 2 = draw ring,
     // opaque scene (kernels_pool.h k_pool).  TRANS: the translucency paths exist.  POS: frames carry the hit position.
-    constexpr bool RM = RINGMEM != 0, TRANS = RING && RINGMEM != 2, POS = RING && RINGMEM == 1;
+    // FORKS (a trait of the emitter: k_pool's, on its opaque fixed-spp kernels): leaf rays fly beside the walk, see the fork step.
+    constexpr bool FORKS = Emit::FORKS != 0;
+    constexpr bool RM = RINGMEM != 0, TRANS = RING && RINGMEM != 2 && !FORKS, POS = RING && RINGMEM == 1;
+    static_assert(!FORKS || (!TEX && RINGMEM == 0 && !Emit::KEEPS_RNG), "leaves fork only where none of them can draw");
+    // a leaf's event: no RNG, no radiance record, no walk - the hit or miss, the light block, an atomic add
+    const bool leaf = FORKS && (pending & (unsigned int)WF_PENDING_LEAF_BIT) != 0u;
+    if (FORKS) pending &= ~(unsigned int)WF_PENDING_LEAF_BIT;         // below, `pending` is the level mask
     Rng rng;
     rng.chain = rng.prev = rng.seed0 = 0; rng.k = 0;
     // the sample's radiance record, requested with the rest of its state: this lane owns the sample for the phase (a sample has
@@ -356,13 +373,15 @@ PRT_D void shade_entry_on(const DevScene & sc, const DevParams & P, const WaveBu
     long long acc_x = 0, acc_y = 0, acc_z = 0;
     const bool fresh = (pending & (unsigned int)WF_PENDING_FRESH_BIT) != 0u;     // the sample's first closest-hit ray
     pending &= ~(unsigned int)WF_PENDING_FRESH_BIT;
-    if (live) {
+    if (live && !leaf) {
         const ulonglong2 rs = B.rng[s];
         rng.chain = rs.x; rng.prev = rs.y;
         // (seed word 0, draws so far) matter from the 15th draw on: a render whose samples provably stop before that
         // (RINGMEM = false) neither reads nor writes them - 32 bytes less per shaded hit
         if (RING && RM) { const ulonglong2 ra = B.rng_aux[s]; rng.seed0 = ra.x; rng.k = (u32)ra.y; }
-        if (!fresh) accum_load_owner(B.accum + s, acc_x, acc_y, acc_z);
+        // FORKS: the sample's leaves may be shaded in this very phase, by other lanes - nobody owns the record, every add
+        // but the first is an atomic (below) and nothing is read here
+        if (!FORKS && !fresh) accum_load_owner(B.accum + s, acc_x, acc_y, acc_z);
     }
     // RINGMEM = false: the general-RNG code without its draw ring in memory, for renders whose samples provably make at
     // most 15 draws (dev_rng.h) - a compile-time NULL, so the ring code folds away
@@ -444,7 +463,9 @@ PRT_D void shade_entry_on(const DevScene & sc, const DevParams & P, const WaveBu
     // everything this invocation adds to the sample is known now (the bounce walk below adds nothing): write the record back
     if (live && (fresh || add.x != 0.0f || add.y != 0.0f || add.z != 0.0f)) {
         emit.region(PRT_REGION_RADIANCE_STORE);
-        accum_store_owner(B.accum + s, acc_x, acc_y, acc_z, add);
+        // FORKS: the fresh store stays - a sample's first event has no company, its leaves are made from it or later
+        if (FORKS && !fresh) accum_add(B.accum + s, add);
+        else accum_store_owner(B.accum + s, acc_x, acc_y, acc_z, add);
     }
 
     // ---- shadow rays of this hit (raytracer.cpp:507-511, 378-411): radiance-if-unoccluded rides with the ray
@@ -483,6 +504,92 @@ PRT_D void shade_entry_on(const DevScene & sc, const DevParams & P, const WaveBu
         if (want_shadow && !dead) emit.region(PRT_REGION_SHADOW_EMIT);
         emit.shadow(want_shadow && !dead, s, so, sd, contrib, kind == WF_KIND_SHADOW_DIST ? dist_sq : -(float)(li + 1u), kind);
     }
+
+    // ---- fork: the children of a frame at the last-but-one level are LEAVES; they fly beside the walk, not in its chain
+    // The reference's depth-first order constrains rays whose subtree draws.  A child that enters at level == depth hits a
+    // surface that spawns nothing (iters == 0) in a scene without translucency: it draws nothing, the walk needs nothing back
+    // from it, and all it does is add to the fixed-point Accum, where order does not matter.  So a hit at depth - 1 makes ALL
+    // its children here, with the draws in the reference's order (direction index of a diffuse child, then the survival draw),
+    // marks the survivors as leaves and retires its frame - never saved, never reloaded, no round spent waiting per leaf.
+    // The leaf rays of the pass are made in as few executions of the ray block as possible: the survivors leave a one-word
+    // descriptor (lobe, source lane, direction index) at their rank in the wave's frame columns, and lane k makes survivor k
+    // from the source lane's frame - which is in LDS, and stays as it is until the walk below loads another.
+    if constexpr (FORKS) {
+        const unsigned int n_child = P.reflection_samples + P.spec_samples;            // wave-uniform trip count: the appends stay converged
+        const bool forks = emit.may_fork && live && !leaf && mode == M_NEXT_CHILD && level == depth - 1 && n_child != 0u;
+        if (__ballot(forks) != 0ull) {
+            constexpr int STRIDE = Emit::COL_STRIDE;
+            const unsigned int lane = lane_id();
+            int * const my_col = emit.col;
+            int * const wave_cols = my_col - lane;                                         // lane 0's column; lane k's is wave_cols + k
+            const unsigned int s_all = s;
+            for (unsigned int g0 = 0; g0 < n_child; g0 += (unsigned int)WF_FORK_GROUP) {
+                const unsigned int g1 = g0 + (unsigned int)WF_FORK_GROUP < n_child ? g0 + (unsigned int)WF_FORK_GROUP : n_child;
+                unsigned int made = 0;                                                     // wave-uniform: survivors of this group
+                for (unsigned int c = g0; c < g1; ++c) {
+                    bool flies = false;
+                    int desc = 0;
+                    if (forks) {
+                        emit.region(PRT_REGION_WALK_LOOP);
+                        emit.region(PRT_REGION_WALK_NEXT_CHILD);
+                        emit.region(PRT_REGION_WALK_ENTER);
+                        const bool diffuse = c < P.reflection_samples;                      // raytracer.cpp:516-535: the diffuse children, then the specular ones
+                        const unsigned int sel = diffuse ? (unsigned int)(rng_next<RING>(rng, ring, ring_stride) % 1024ull) : c - P.reflection_samples;
+                        flies = !(rng_float01<RING>(rng, ring, ring_stride) < 0.5f);        // TraceRayColor's entry at level depth >= 1 (raytracer.cpp:415-420)
+                        desc = (int)((diffuse ? 0u : 0x80000000u) | lane << 24 | (sel & 0xFFFFFFu));
+                    }
+                    const unsigned long long m = __ballot(flies);
+                    if (flies) {
+                        const unsigned int r = made + __builtin_amdgcn_mbcnt_hi((unsigned int)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)m, 0u));
+                        wave_cols[(WFL_KD + (int)(r >> 6)) * STRIDE + (int)(r & 63u)] = desc;
+                    }
+                    made += (unsigned int)__popcll(m);
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                for (unsigned int q0 = 0; q0 < made; q0 += 64u) {
+                    const bool have = q0 + lane < made;
+                    const int desc = have ? my_col[(WFL_KD + (int)(q0 >> 6)) * STRIDE] : 0;
+                    const unsigned int src = ((unsigned int)desc >> 24) & 63u;
+                    const unsigned int s_src = (unsigned int)__shfl((int)s_all, (int)src);
+                    f3 lo = mk3(0, 0, 0), ld = mk3(0, 0, 1), lT = mk3(0, 0, 0);
+                    if (have) {
+                        emit.region(PRT_REGION_LEAF_RAY);
+                        // the child's ray exactly as the walk's child-ray block below makes it, from the same frame fields
+                        const int * const sf = wave_cols + src;
+                        const bool diffuse = desc >= 0;
+                        const unsigned int sel = (unsigned int)desc & 0xFFFFFFu;
+                        const f3 s_hit_n = mk3(as_f(sf[WFL_HIT_N * STRIDE]), as_f(sf[(WFL_HIT_N + 1) * STRIDE]), as_f(sf[(WFL_HIT_N + 2) * STRIDE]));
+                        const f3 s_ray_d = mk3(as_f(sf[WFL_RAY_D * STRIDE]), as_f(sf[(WFL_RAY_D + 1) * STRIDE]), as_f(sf[(WFL_RAY_D + 2) * STRIDE]));
+                        const f3 s_T_in = mk3(as_f(sf[WFL_T_IN * STRIDE]), as_f(sf[(WFL_T_IN + 1) * STRIDE]), as_f(sf[(WFL_T_IN + 2) * STRIDE]));
+                        const float s_w_diffuse = as_f(sf[WFL_W_DIFFUSE * STRIDE]);
+                        const int s_mat = sf[WFL_MAT * STRIDE];
+                        const DevMaterial fm = tb.materials[s_mat];
+                        const float4 ts = diffuse ? tb.diffuse[sel] : sc.spec_dirs[(size_t)s_mat * sc.spec_samples + sel];
+                        ld = tangent_to_world(s_hit_n, mk3(ts.x, ts.y, ts.z));
+                        const float cw = diffuse ? ref_max(0.0f, dot3(s_hit_n, ld)) : ref_max(0.0f, dot3(ld, s_ray_d * -1.0f));
+                        const f3 fkd = mk3(fm.diffuse[0], fm.diffuse[1], fm.diffuse[2]);
+                        const f3 fks = mk3(fm.specular[0], fm.specular[1], fm.specular[2]);
+                        const f3 lobe = diffuse ? fkd * s_w_diffuse : fks;
+                        lT = s_T_in * (lobe * cw);
+                        lo = mk3(as_f(sf[WFL_HIT_P * STRIDE]), as_f(sf[(WFL_HIT_P + 1) * STRIDE]), as_f(sf[(WFL_HIT_P + 2) * STRIDE]));
+                    }
+                    emit.closest(have, s_src, lo, ld, lT, depth, (unsigned int)WF_PENDING_LEAF_BIT, false);
+                }
+                emit.leaves(made);
+                __builtin_amdgcn_wave_barrier();                                           // the next group's descriptors go where these were read
+            }
+            if (forks) {
+                // the step that finds no child left: the frame is retired, the walk resumes the deepest parked frame
+                emit.region(PRT_REGION_WALK_LOOP);
+                emit.region(PRT_REGION_WALK_NEXT_CHILD);
+                f.stage = WF_STAGE_DONE;
+                mode = M_RETURN_UP;
+            }
+        }
+    }
+    if (leaf) mode = M_DONE;
 
     // ---- step 2: walk the bounce tree in depth-first order until the next ray or the end of the sample ----
     // The three steps follow each other in ONE pass of the loop (not one step per pass): a lane's own sequence of steps is
@@ -625,6 +732,7 @@ PRT_D void shade_entry_lds(const DevScene & sc, const DevParams & P, const WaveB
 template <int BLOCK>
 struct QueueEmit {
     enum { KEEPS_RNG = 0 };           // fixed spp: a sample that has ended never draws again
+    enum { FORKS = 0 };               // one closest-hit ray per sample in flight, as the header of this file says
     PRT_D void region(int) const {}   // (k_pool's COUNT builds count shade_entry_on's regions through their emitter)
     const WaveBuffers & B;
     int nxt;

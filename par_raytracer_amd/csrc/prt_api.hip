@@ -41,6 +41,9 @@ using namespace prt;
 #ifndef PRT_ADAPT_WAVES
 #define PRT_ADAPT_WAVES 4         // waves per SIMD of the untextured adaptive kernel (128 VGPRs)
 #endif
+#ifndef PRT_POOL_FORK_DEFAULT
+#define PRT_POOL_FORK_DEFAULT 1   // leaf rays fly beside the bounce walk (kernels_pool.h FORKS) when the option POOL_FORK is not set
+#endif
 #ifndef PRT_POOL_SHARED_DEFAULT
 #define PRT_POOL_SHARED_DEFAULT 1 // block-shared pools (kernels_pool.h) for fixed-spp renders when the option POOL_SHARED is not set
 #endif
@@ -629,7 +632,20 @@ int launch_pool(prt_ctx * ctx, bool count, const DevCamera & cam, DevParams P, u
     const unsigned int units = shared ? grid : waves;
     if (shared) cap *= (unsigned int)(BLOCK / 64);
     const unsigned int n_lights = std::max(1u, ctx->scene.light_count);
-    const unsigned int scap = cap * n_lights;
+    // Leaf rays beside the walk (kernels_pool.h FORKS; options POOL_FORK, POOL_FORK_ROOM): the kernels of opaque untextured
+    // fixed-spp renders.  Their lists get room / 8 of the capacity on top of it - `cap` stays the bound on entries with a walk in
+    // progress - and a shade pass forks only when the next list holds its worst case.  No room, or a bounce tree whose bounds
+    // would not fit the fields of the block's reservation word (PCTL_FORK_RES): lcap = cap, and nothing forks.
+    constexpr bool FORKS = !ADAPT && !TEX && RINGMEM == 0;
+    unsigned int lcap = cap;
+    if (FORKS && (opt.pool_fork >= 0 ? opt.pool_fork != 0 : PRT_POOL_FORK_DEFAULT != 0)) {
+        const unsigned long long eighths = (unsigned long long)std::max(0ll, std::min(64ll, opt.pool_fork_room >= 0 ? opt.pool_fork_room : 8ll));
+        const unsigned int per = shared ? (unsigned int)(BLOCK / 64) : 1u;          // the adopting launch divides a shared pool's lists by this
+        const unsigned long long l = cap + (unsigned long long)cap * eighths / 8ull / per * per;
+        const unsigned long long widest = 1ull + P.reflection_samples + P.spec_samples;
+        if (l <= (1ull << 17) && l * widest < (1ull << 20)) lcap = (unsigned int)l;
+    }
+    const unsigned int scap = lcap * n_lights;
 
     prt_ctx::ChainWs & w = ctx->chain[0];
     const size_t N = n_samples;
@@ -637,7 +653,7 @@ int launch_pool(prt_ctx * ctx, bool count, const DevCamera & cam, DevParams P, u
     const unsigned int fr4 = TEX ? 7u : (RING && RINGMEM == 1) ? 5u : 4u;       // kernels_wave.h wframe_save
     HIP_TRY(ctx, w.f4.ensure((size_t)levels * fr4 * N));
     HIP_TRY(ctx, w.rng.ensure(RING ? 2 * N : N));
-    HIP_TRY(ctx, ctx->pool_f4.ensure((size_t)units * (7u * (size_t)cap + 3u * (size_t)scap)));
+    HIP_TRY(ctx, ctx->pool_f4.ensure((size_t)units * (7u * (size_t)lcap + 3u * (size_t)scap)));
     // [0] sample counter, [1] parked closest-hit / finalise entries, [2] parked shadow rays, [3] the adopting launch's counter
     HIP_TRY(ctx, ctx->wf_counts.ensure(16));          // zeroed by k_pool_store_args below
     // Park lists: sized for what scenes with coincident geometry need in practice, never for the worst case (every sample's
@@ -652,7 +668,9 @@ int launch_pool(prt_ctx * ctx, bool count, const DevCamera & cam, DevParams P, u
         hits_per_sample += level_nodes;
     }
     const size_t worst_spark = N * n_lights * std::min<size_t>(hits_per_sample, 1u << 20);
-    const size_t park_cap = std::min<size_t>(ctx->pool_park_cap, N + (ADAPT ? N : 0)), spark_cap = std::min<size_t>(ctx->pool_spark_cap, worst_spark);
+    // (forking kernels: besides its one ray with a walk in progress a sample can have every leaf of its bounce tree parked)
+    const size_t park_worst = N + (ADAPT ? N : 0) + (lcap > cap ? N * std::min<size_t>(level_nodes, 1u << 20) : 0);
+    const size_t park_cap = std::min<size_t>(ctx->pool_park_cap, park_worst), spark_cap = std::min<size_t>(ctx->pool_spark_cap, worst_spark);
     HIP_TRY(ctx, ctx->pool_park.ensure(3 * (park_cap + spark_cap)));
     // the EXACT launch's lanes continue their LDS stack columns in memory; k_pool_parked_shadows has full-height columns
     const unsigned int grid2 = exact_only ? grid : std::max(1u, std::min(grid, (unsigned int)ctx->cu_count));
@@ -679,10 +697,11 @@ int launch_pool(prt_ctx * ctx, bool count, const DevCamera & cam, DevParams P, u
     PoolBuffers Q;
     memset(&Q, 0, sizeof(Q));
     Q.cq = ctx->pool_f4.p;
-    Q.hits = Q.cq + (size_t)units * 6u * cap;
-    Q.sq = Q.hits + (size_t)units * cap;
+    Q.hits = Q.cq + (size_t)units * 6u * lcap;
+    Q.sq = Q.hits + (size_t)units * lcap;
     Q.head = ctx->wf_counts.p;
     Q.cap = cap;
+    Q.lcap = lcap;
     Q.scap = scap;
     Q.park = ctx->pool_park.p;
     Q.spark = ctx->pool_park.p + 3 * park_cap;

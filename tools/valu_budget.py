@@ -51,6 +51,9 @@ TIMES_OF = {
     "shade.pass.miss": "shade_miss", "shade.pass.radiance_store": "radiance_store", "shade.pass.light": "shadow_block",
     "shade.pass.shadow_emit": "shade_pass", "shade.pass.walk.loop": "walk_loop", "shade.pass.walk.next_child": "walk_next_child",
     "shade.pass.walk.enter": "walk_enter", "shade.pass.walk.return_up": "walk_return_up", "shade.pass.walk.child_ray": "walk_child_ray", "shade.pass.outputs_emit": "shade_pass",
+    # the fork step (forking kernels only): its test, draws and descriptor writes by the pass - an upper bound, a pass that does
+    # not fork skips them -, its ray block by its own counter
+    "shade.pass.fork": "shade_pass", "shade.pass.fork.leaf_ray": "leaf_ray",
 }
 
 
@@ -98,9 +101,10 @@ def regions(root):
         "if (__popcll(__ballot(true)) < leave_below) break;",
         "// ---- shade: every closest hit of the pool", "for (unsigned int b0 = b_first; b0 < n_c; b0 += ULANES)",
         "// ---- start ahead:", "// ---- counters: one atomic per workgroup"])
-    w_on, w_step1, w_miss, w_hit, w_store, w_shadow, w_light, w_dead, w_walk, w_child, w_enter, w_up, w_out, w_ray, w_emit = _lines_of(wave, [
+    w_on, w_step1, w_miss, w_hit, w_store, w_shadow, w_light, w_dead, w_fork, w_leaf_ray, w_leaf_ray_end, w_walk, w_child, w_enter, w_up, w_out, w_ray, w_emit = _lines_of(wave, [
         "PRT_D void shade_entry_on(", "// ---- step 1: the hit", "if (hit.tri < 0) {", "} else {", "write the record back",
         "// ---- shadow rays of this hit", "if (want_shadow) {", "// A shadow ray whose radiance-if-unoccluded is exactly zero",
+        "// ---- fork: the children of a frame", "emit.region(PRT_REGION_LEAF_RAY);", "emit.closest(have, s_src,",
         "// ---- step 2: walk the bounce tree", "if (mode == M_NEXT_CHILD) {", "if (mode == M_ENTER) {", "if (mode == M_RETURN_UP) {",
         "// ---- outputs", "// ---- the child that flies", "// ---- append the next ray"])
     t_step, t_descend, t_pop, t_leaf, t_tris, t_tris_end = _lines_of(trav, [
@@ -139,8 +143,10 @@ def regions(root):
                 return "shade.pass.shadow_emit"          # (the loop over the lights: every lane of the pass)
             if ln < w_dead:
                 return "shade.pass.light"
-            if ln < w_walk:
+            if ln < w_fork:
                 return "shade.pass.shadow_emit"
+            if ln < w_walk:
+                return "shade.pass.fork.leaf_ray" if w_leaf_ray <= ln < w_leaf_ray_end else "shade.pass.fork"
             if ln < w_child:
                 return "shade.pass.walk.loop"
             if ln < w_enter:
