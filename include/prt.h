@@ -409,7 +409,12 @@ int prt_trace_rays_backward_device(prt_ctx * ctx, const prt_ray_batch * batch, c
  * A point with a non-finite component, or with max_dist2 negative or NaN, is a miss; it is not an error and does not affect
  * the other points.  A miss: dist2 = FLT_MAX, point and bw zeros, group = -1, vertex0 = 0xFFFFFFFF (the ray queries'
  * convention); a scene of 0 triangles makes every point a miss.  max_dist2 = +inf is "no limit", 0 finds points on the surface.
- * A triangle whose d2 overflows to inf is no candidate, so a point more than 2^64 away from every triangle misses without a radius.
+ * SCALE.  The walk's tests run on (p - a, ab, ac) x 2^-k, k = the exponent of the largest |component| of the three vectors, and
+ * d2 is scaled back by two exact products: v, w and the region are free of scale, and the answer at scale 2^e is 2^e times
+ * the answer at scale 1 for every scene the upload accepts (|coordinate| < 1e18).  What bounds the range is d2 itself:
+ * a triangle whose d2 overflows to inf (true d2 >= 2^128) is no candidate, so a point more than 2^64 away from every triangle
+ * misses without a radius; a d2 below 2^-126 is reported as a subnormal float or 0.  Inside those bounds no valid point misses.
+ * A point farther than 2^31 edge lengths from a triangle may take another region of it than the real-valued walk.
  * A zero-area triangle is a candidate exactly when the function returns finite values for the point: in its vertex and edge
  * regions, not where the interior branch divides by its zero area.
  * The walk culls boxes by their distance to p, padded by 2^-16 x max(scene extent, max |finite point component| of the batch);
@@ -502,7 +507,9 @@ int prt_closest_points_backward_device(prt_ctx * ctx, const prt_point_batch * ba
  *     s = Dot(e, N)    signed_dist = s < 0 ? -sqrtf(d2) : sqrtf(d2)
  * with n = Normalize(cross(ab, ac)) of a triangle's record.  NaN, s == 0 and d2 == 0 give the non-negative branch.  Positive is
  * the side cross(ab, ac) points to - the side PRT_QUERY_CLOSEST calls front-facing.  A miss has signed_dist = FLT_MAX and
- * feature = 255.
+ * feature = 255.  Only the sign of s is read, and s, n and the angles are evaluated on edges and e scaled by the power of two of
+ * their largest component (csrc/dev_signed.h): the sign does not depend on the scale of the scene, within the range of d2
+ * that prt_closest_points states (d2 rounded to 0 gives +0).
  * Vertices are the entries of `positions`, identified by their index in idx_positions; an edge is an unordered pair of position
  * indices; the triangles of all groups count.  Two positions with equal coordinates but different indices are different
  * vertices, and an edge between them is a boundary edge: welding is the caller's business.

@@ -5,7 +5,9 @@
 // three vertex regions, the three edge regions, then the interior - on the 48-byte record's own a, ab, ac (bp and cp are formed
 // as ap - ab and ap - ac: the record is the only input), in plain float32 and the expression order written below, compiled like
 // tri_geom without contraction: host and device give the same bits.  It yields the barycentrics (v, w) of the nearest point
-// q = (a + ab * v) + ac * w and d2 = Dot(p - q, p - q).  Both sides of a triangle count; there is no facing test.  A triangle
+// q = (a + ab * v) + ac * w and d2 = Dot(p - q, p - q).  The tests and d2 are evaluated on the vectors times an exact power of
+// two (THE SCALE, below): the same bits at ordinary scale, and right from 2^-45 to 2^58, where the unscaled products left the
+// float32 range.  Both sides of a triangle count; there is no facing test.  A triangle
 // whose d2, v or w is not finite is not a candidate (a zero-area record with collinear corners divides by zero in the interior
 // branch: it drops out instead of poisoning the point).
 // The answer for p: among the triangles with finite d2 <= max_dist2 (FLT_MAX when no radius is given) the one with the
@@ -49,15 +51,40 @@ enum { CLOSEST_VERTEX_A = 0, CLOSEST_VERTEX_B = 1, CLOSEST_EDGE_AB = 2, CLOSEST_
 // (dev_closest_grad.h).
 struct ClosestTerms { f3 ap, bp, cp; float d1, d2, d3, d4, d5, d6, va, vb, vc; };
 
+// THE SCALE of a record and a point ("Scale").  The areas va, vb, vc are products of four lengths: with
+// edges above 2^31 or below 2^-31 they leave the float32 range, although v, w and the region depend on ratios of lengths alone.
+// So the walk runs on (p - a, ab, ac) x 2^-k, k = the exponent of the largest |component| of the three vectors: the largest
+// component then lies in [1, 2), and the four-fold products within 2^-126 .. 2^11 unless one vector is below 2^-31 of another.
+// A product with a power of two is exact (the one exception: a component below 2^-126 x 2^k, which no longer matters to the
+// largest one), so v, w, the region and - after the two exact products that undo the scale - d2 and the terms are the bits of the
+// unscaled walk wherever that one stayed in range.  k is clamped to -126 .. 126 so that both powers are normal floats.
+struct Pow2 { float down, up; };                         // 2^-k and 2^k
+
+PRT_HD Pow2 pow2_of(float m) {
+    unsigned int be = (__builtin_bit_cast(unsigned int, m) >> 23) & 0xFFu;
+    be = be < 1u ? 1u : (be > 253u ? 253u : be);
+    Pow2 s;
+    s.down = __builtin_bit_cast(float, (254u - be) << 23);
+    s.up = __builtin_bit_cast(float, be << 23);
+    return s;
+}
+
+PRT_HD float abs_max3(f3 a) { return __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(a.x), __builtin_fabsf(a.y)), __builtin_fabsf(a.z)); }
+
+PRT_HD Pow2 closest_scale(f3 ap, f3 ab, f3 ac) { return pow2_of(__builtin_fmaxf(__builtin_fmaxf(abs_max3(ap), abs_max3(ab)), abs_max3(ac))); }
+
 // Ericson 5.1.5 on (a, ab, ac): v, w, d2 and the region (CLOSEST_*) whose branch produced them.  Host and device: the gradient's
-// step and its host harness recompute the region with it.
+// step and its host harness recompute the region with it.  The tests run on the scaled vectors; q is formed from the record
+// itself (closest_point_of), e = p - q is scaled, squared and scaled back; the terms come back in the record's own units.
 PRT_HD int closest_region_walk(f3 p, f3 a, f3 ab, f3 ac, float & d2, float & v, float & w, ClosestTerms & t) {
-    const f3 ap = p - a;
-    const float d1 = dot3(ab, ap), d2_ = dot3(ac, ap);
-    const f3 bp = ap - ab;
-    const float d3 = dot3(ab, bp), d4 = dot3(ac, bp);
-    const f3 cp = ap - ac;
-    const float d5 = dot3(ab, cp), d6 = dot3(ac, cp);
+    const f3 ap0 = p - a;
+    const Pow2 k = closest_scale(ap0, ab, ac);
+    const f3 ap = ap0 * k.down, sab = ab * k.down, sac = ac * k.down;
+    const float d1 = dot3(sab, ap), d2_ = dot3(sac, ap);
+    const f3 bp = ap - sab;
+    const float d3 = dot3(sab, bp), d4 = dot3(sac, bp);
+    const f3 cp = ap - sac;
+    const float d5 = dot3(sab, cp), d6 = dot3(sac, cp);
     const float vc = d1 * d4 - d3 * d2_;
     const float vb = d5 * d2_ - d1 * d6;
     const float va = d3 * d6 - d5 * d4;
@@ -78,10 +105,12 @@ PRT_HD int closest_region_walk(f3 p, f3 a, f3 ab, f3 ac, float & d2, float & v, 
         region = CLOSEST_INTERIOR;
     }
     const f3 q = (a + ab * v) + ac * w;
-    const f3 e = p - q;
-    d2 = dot3(e, e);
-    t.ap = ap; t.bp = bp; t.cp = cp;
-    t.d1 = d1; t.d2 = d2_; t.d3 = d3; t.d4 = d4; t.d5 = d5; t.d6 = d6; t.va = va; t.vb = vb; t.vc = vc;
+    const f3 e = (p - q) * k.down;
+    d2 = (dot3(e, e) * k.up) * k.up;
+    const float u2 = k.up * k.up;                        // the terms of the gradient: inf above 2^64, where it is not defined
+    t.ap = ap0; t.bp = bp * k.up; t.cp = cp * k.up;
+    t.d1 = d1 * u2; t.d2 = d2_ * u2; t.d3 = d3 * u2; t.d4 = d4 * u2; t.d5 = d5 * u2; t.d6 = d6 * u2;
+    t.va = (va * u2) * u2; t.vb = (vb * u2) * u2; t.vc = (vc * u2) * u2;
     return region;
 }
 

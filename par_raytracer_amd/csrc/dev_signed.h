@@ -6,10 +6,11 @@
 //
 // THE DEFINITION (include/prt.h).  For the winner (leaf slot, d2) of a point p: R = the region of
 // closest_region_walk on the slot's 48-byte record, q = closest_point_of, e = p - q, and
-//     N = cross(ab, ac), unnormalised                     R = interior
+//     N = cross(ab, ac) x 2^-2k, unnormalised             R = interior
 //     N = the edge's accumulator x 2^-32                  R = an edge
 //     N = the vertex's accumulator x 2^-32                R = a vertex
-//     s = dot3(e, N);  signed_dist = s < 0 ? -sqrtf(d2) : sqrtf(d2)         (NaN, s == 0, d2 == 0: the non-negative branch)
+//     s = dot3(e x 2^-k, N)                               k: the walk's scale (closest_scale) - only the sign of s is read
+//     signed_dist = s < 0 ? -sqrtf(d2) : sqrtf(d2)         (NaN, s == 0, d2 == 0: the non-negative branch)
 // THE ACCUMULATORS.  Every triangle record (a, ab, ac) gives n = normalize3(cross(ab, ac)) and its three interior angles; the
 // vertex accumulator of corner k gets angle_k x n, the accumulator of each of its three edges gets n; a triangle whose n or
 // angles are not all finite gives nothing.  Each component is rounded once to a multiple of 2^-32 (signed_to_fixed) and added
@@ -55,7 +56,12 @@ PRT_HD float signed_angle(f3 u, f3 v) { return signed_acos(dot3(u, v) / sqrtf(do
 PRT_HD bool signed_finite(float x) { return x - x == 0.0f; }            // false for NaN and +-inf
 
 // One record's contributions: the unit normal and the interior angles at a, b, c.  False: the triangle contributes nothing.
-PRT_HD bool signed_triangle_terms(f3 ab, f3 ac, f3 & n, float * alpha) {
+// Both are free of scale, and both square an area (length_sq of the cross product, dot3(u, u) * dot3(v, v)): they are computed on
+// (ab, ac) x 2^-k, k = the exponent of the largest |component| of the two edges (pow2_of, dev_closest.h) - the same bits wherever
+// the unscaled products stayed in range.
+PRT_HD bool signed_triangle_terms(f3 ab0, f3 ac0, f3 & n, float * alpha) {
+    const Pow2 k = pow2_of(__builtin_fmaxf(abs_max3(ab0), abs_max3(ac0)));
+    const f3 ab = ab0 * k.down, ac = ac0 * k.down;
     n = normalize3(cross3(ab, ac));
     const f3 bc = ac - ab;
     alpha[0] = signed_angle(ab, ac);
@@ -82,7 +88,7 @@ PRT_HD void signed_triangle_fixed(f3 n, const float * alpha, long long * vq, lon
 // The column of adj that a vertex or edge region reads: CLOSEST_VERTEX_A, _B, EDGE_AB, VERTEX_C, EDGE_AC, EDGE_BC -> 0, 1, 3, 2, 4, 5.
 PRT_HD unsigned int signed_adj_column(int region) { return (0x542310u >> (4u * (unsigned int)region)) & 7u; }
 
-// N of the definition for leaf slot `slot` in region R.
+// N of the definition for leaf slot `slot` in region R; (ab, ac): the record's edges x 2^-k.
 PRT_D f3 signed_normal_of(const SignedTables & T, unsigned int slot, int region, f3 ab, f3 ac) {
     if (region == CLOSEST_INTERIOR) return cross3(ab, ac);
     const unsigned int col = signed_adj_column(region);
@@ -96,11 +102,12 @@ PRT_D float signed_of_winner(const SignedTables & T, unsigned int slot, f3 p, f3
     float d2r, v, w;
     ClosestTerms t;
     const int region = closest_region_walk(p, a, ab, ac, d2r, v, w, t);
-    const f3 e = p - closest_point_of(a, ab, ac, v, w);
-    const float s = dot3(e, signed_normal_of(T, slot, region, ab, ac));
+    const Pow2 k = closest_scale(t.ap, ab, ac);
+    const f3 e = (p - closest_point_of(a, ab, ac, v, w)) * k.down;
+    const float s = dot3(e, signed_normal_of(T, slot, region, ab * k.down, ac * k.down));
     const float d = sqrtf(d2);
     feature = (unsigned int)region;
-    return s < 0.0f ? -d : d;
+    return (s < 0.0f && d2 > 0.0f) ? -d : d;              // (d2 rounded to 0 below 2^-149 while s, on the scaled e, is not: +0, never -0)
 }
 
 }  // namespace prt

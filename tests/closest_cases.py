@@ -440,3 +440,70 @@ def far_tail_scene():
     mesh = height_field(32, 1)
     pts, kind = recipe_points(mesh, 1024, 9)
     return mesh, np.ascontiguousarray(pts[kind == KIND_NEAR])
+
+
+# ---- the scale sweep: float64 truth at every scale (tests/test_closest_cases_host.py and tests/test_signed_host.py prove it on the
+# harnesses, tests/test_gpu_closest_schedules.py and tests/test_gpu_signed.py assert it on the device's own answers)
+
+SWEEP_EXPONENTS = (-45, -34, -30, 0, 31, 34, 40, 58)
+SWEEP_POINTS = 1024
+SWEEP_CLOSED = ("cube", "l_prism", "torus")              # signed_cases.MESHES: the signed sweep, and with "height_field" the unsigned one
+
+
+def sweep_mesh(name):
+    import signed_cases
+    return height_field(16, 2) if name == "height_field" else signed_cases.mesh_of(name)
+
+
+def sweep_points(name):
+    """The SWEEP_POINTS recipe points of a sweep mesh at 2^0: the signed recipe on the closed meshes, the closest recipe on the
+    height field."""
+    import signed_cases
+    if name == "height_field":
+        return recipe_points(sweep_mesh(name), SWEEP_POINTS, SCALE_SEED)[0]
+    return signed_cases.recipe_points(sweep_mesh(name), SWEEP_POINTS, signed_cases.SEEDS[name])
+
+
+def true_distance(mesh, points):
+    """The float64 minimum over all triangles of the yardstick's distance, per point."""
+    a, b, c = corners(mesh, np.arange(mesh[1].size // 3))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        dist, v, w, _ = yardstick(np.asarray(points, np.float64)[:, None, :], a[None], b[None], c[None])
+    return np.where(np.isfinite(dist) & np.isfinite(v) & np.isfinite(w), dist, np.inf).min(1)
+
+
+def sweep_keep(best, e):
+    """The points whose true squared distance times 2^2e is a normal float32, or exactly 0."""
+    d2 = (np.asarray(best, np.float64) * 2.0 ** e) ** 2
+    return (best == 0) | ((d2 > 2.0 ** -126) & (d2 < 2.0 ** 127))
+
+
+def sweep_case(mesh, points, best, e):
+    """(mesh x 2^e, kept points x 2^e, keep): both scaled exactly (asserted), every squared edge length a normal float32."""
+    keep = sweep_keep(best, e)
+    big = scaled(mesh, e)
+    tri = big[0].astype(np.float64)[big[1].reshape(-1, 3).astype(np.int64)]
+    edge2 = np.concatenate([((tri[:, i] - tri[:, j]) ** 2).sum(1) for i, j in ((0, 1), (0, 2), (1, 2))])
+    edge2 = edge2[edge2 > 0]
+    assert edge2.min() > 2.0 ** -126 and edge2.max() < 2.0 ** 127, e
+    pts = np.ldexp(points[keep], e).astype(np.float32)
+    assert np.array_equal(np.ldexp(pts.astype(np.float64), -e), points[keep].astype(np.float64)) and np.all(np.isfinite(pts))
+    return big, np.ascontiguousarray(pts), keep
+
+
+def assert_sweep_answers(answers, mesh, points, best, e, limit_units, what):
+    """Conditions a and b of the sweep on the five closest-point fields of `answers` (for mesh x 2^e and points x 2^e; mesh, points
+    and the float64 minimum `best` are the unscaled ones): no point misses; the float64 yardstick's distance to the reported
+    triangle is within limit_units x 2^-23 M of `best` (M: the largest |coordinate| of the point and the three corners), and
+    sqrt(dist2) x 2^-e is within the same limit of that distance.  Returns the two largest errors in those units."""
+    group, vertex0 = np.asarray(answers["group"]), np.asarray(answers["vertex0"])
+    missed = np.nonzero(group < 0)[0]
+    assert missed.size == 0, "%s: %d of %d valid points miss, first %d" % (what, missed.size, len(group), missed[0])
+    a, b, c = corners(mesh, input_triangle(mesh, group, vertex0))
+    answered = yardstick(points, a, b, c)[0]
+    unit = 2.0 ** -23 * np.max(np.abs(np.concatenate([points, a, b, c], axis=1)), axis=1).astype(np.float64)
+    excess = (answered - best) / unit
+    root = np.abs(np.ldexp(np.sqrt(np.asarray(answers["dist2"], np.float64)), -e) - answered) / unit
+    assert excess.max() <= limit_units, "%s: the reported triangle is %.3g units farther than the nearest (point %d)" % (what, excess.max(), excess.argmax())
+    assert root.max() <= limit_units, "%s: sqrt(dist2) is %.3g units off the distance to the reported triangle (point %d)" % (what, root.max(), root.argmax())
+    return float(excess.max()), float(root.max())

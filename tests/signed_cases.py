@@ -98,11 +98,17 @@ def mesh_of(name):
     return MESHES[name]() if name in MESHES else scene_mesh(name)
 
 
+SHEAR_MIRROR = np.array([[-1.25, 0.0, 0.0], [0.5, 0.75, 0.0], [-0.25, 0.125, 1.5]], np.float32)
+
+
 def sheared_mirror(mesh):
     """The mesh sheared and mirrored in x (float32): the winding stays, so every normal - and every sign - flips."""
     p, idx, runs = mesh
-    m = np.array([[-1.25, 0.0, 0.0], [0.5, 0.75, 0.0], [-0.25, 0.125, 1.5]], np.float32)
-    return np.ascontiguousarray((p @ m).astype(np.float32)), idx, runs
+    return sheared_mirror_points(p), idx, runs
+
+
+def sheared_mirror_points(points):
+    return np.ascontiguousarray((points @ SHEAR_MIRROR).astype(np.float32))
 
 
 # ---- the analytic inside tests (float64, of float32 points)
@@ -303,3 +309,105 @@ def assert_same_bits(got, expect, what, fields=FIELDS):
 def to_numpy(res):
     """A signed_distance result with torch tensors -> numpy arrays (vertex0 back to uint32)."""
     return K.to_numpy({k: v for k, v in res.items()})
+
+
+# ---- the scale sweep (closest_cases.SWEEP_EXPONENTS): conditions c and d on the unscaled mesh
+
+ANGLE_GATE = 8.0 * 2.0 ** -24 / np.sin(0.015) + 2.0 ** -20            # DESIGN.md section 4.12; argued in tests/test_signed_host.py
+OFF_SURFACE = 1e-4                                                    # x extent: closer points' signs are rounding noise
+INSIDE = {"cube": inside_cube, "l_prism": inside_l_prism}
+
+
+def assert_sweep_signs(signed_distance, name, mesh, points, ref_sd, what):
+    """Condition c: the sign is the float64 reference's on the unscaled mesh for every point at least OFF_SURFACE extents off the
+    surface, and on the cube and the L-prism the analytic inside test's.  Returns the number of points checked."""
+    negative = np.asarray(signed_distance) < 0
+    checked = np.abs(ref_sd) >= OFF_SURFACE * K.mesh_extent(mesh)[2]
+    wrong = (negative != (ref_sd < 0)) & checked
+    assert not wrong.any(), "%s: %d of %d checked signs differ from the float64 reference, first %d" % (what, wrong.sum(), checked.sum(), np.nonzero(wrong)[0][0])
+    if name in INSIDE:
+        wrong = (negative != INSIDE[name](points)) & checked
+        assert not wrong.any(), "%s: %d of %d checked signs differ from the analytic inside test" % (what, wrong.sum(), checked.sum())
+    return int(checked.sum())
+
+
+def assert_sweep_angles(angles, mesh, what):
+    """Condition d: every non-degenerate triangle has its three angles, each within ANGLE_GATE of float64."""
+    alpha, keep = mesh_angle_cosines(mesh)
+    got = np.asarray(angles, np.float64)
+    assert np.all(np.isfinite(got[keep])), "%s: %d non-degenerate triangles without angles" % (what, (~np.isfinite(got[keep]).all(1)).sum())
+    err = float(np.abs(got[keep] - alpha[keep]).max())
+    assert err <= ANGLE_GATE, "%s: angle error %.3e" % (what, err)
+    return err
+
+
+# ---- the topologies the definition speaks of (DESIGN.md section 4.12): boundary edges, unwelded vertices, edges of three triangles,
+# accumulators that cancel, records that contribute nothing, positions nobody uses, several groups.  TOPOLOGY_POINTS recipe points each.
+
+TOPOLOGY_POINTS = 1024
+
+
+def open_sheet():
+    """height_field(16, 2): 512 triangles, the rim's edges have one triangle each."""
+    return K.height_field(16, 2)
+
+
+def unwelded(mesh):
+    """Every triangle owns its three positions: equal coordinates under different indices, every edge a boundary edge."""
+    p, idx, runs = mesh
+    return np.ascontiguousarray(p[idx]), np.arange(idx.size, dtype=np.uint32), runs.copy()
+
+
+def non_manifold():
+    """Three quads around the edge (0, 0, 0) - (0, 0, 1), at 0, 100 and 230 degrees: 8 positions, 6 triangles, one edge of six
+    triangle sides."""
+    p = [[0, 0, 0], [0, 0, 1]]
+    tri = []
+    for k, deg in enumerate((0.0, 100.0, 230.0)):
+        c, s = np.cos(np.radians(deg)), np.sin(np.radians(deg))
+        p += [[c, s, 0], [c, s, 1]]
+        lo, hi = 2 + 2 * k, 3 + 2 * k
+        tri += [list(np.roll([0, lo, hi], k)), list(np.roll([0, hi, 1], k))]     # the shared edge is ab, ca or bc: a quad each
+    return _mesh(np.array(p, np.float32), tri)
+
+
+def back_to_back():
+    """height_field(8, 5) and its copy with reversed winding on the same indices: every accumulator cancels to exactly 0."""
+    p, idx, runs = K.height_field(8, 5)
+    tri = idx.reshape(-1, 3)
+    return _mesh(p, np.concatenate([tri, tri[:, [0, 2, 1]]]))
+
+
+def degenerate_cube():
+    return K.with_degenerates(cube(), 3)
+
+
+def unreferenced_and_repeated():
+    """The cube, three positions that no triangle uses (one of them far away) and a triangle (a, a, b) on the diagonal 0 - 7."""
+    p, idx, runs = cube()
+    p = np.concatenate([[[9.0, 9.0, 9.0]], p, [[0.5, 0.5, 0.5], [-3.0, 0.25, 0.75]]]).astype(np.float32)
+    tri = np.concatenate([idx.reshape(-1, 3).astype(np.int64) + 1, [[1, 1, 8]]])
+    return _mesh(p, tri)
+
+
+def multi_group(mesh, seed=8):
+    """The mesh's triangles shuffled and split over three groups that lie in the index buffer in the order 2, 0, 1."""
+    p, idx, runs = mesh
+    tri = idx.reshape(-1, 3)[np.random.default_rng(seed).permutation(idx.size // 3)]
+    third = 3 * (len(tri) // 3)
+    first = [0, third, 2 * third, 3 * len(tri)]
+    order = (2, 0, 1)
+    return p, np.ascontiguousarray(tri.reshape(-1)), np.array([[first[k], first[k + 1] - first[k]] for k in order], np.uint32)
+
+
+TOPOLOGIES = {"open": open_sheet, "unwelded": lambda: unwelded(cube()), "non_manifold": non_manifold, "back_to_back": back_to_back,
+              "degenerate": degenerate_cube, "unreferenced": unreferenced_and_repeated, "multi_group": lambda: multi_group(torus())}
+TOPOLOGY_SEEDS = {name: 330 + i for i, name in enumerate(TOPOLOGIES)}
+
+
+def topology_case(name):
+    """(mesh, its TOPOLOGY_POINTS recipe points); multi_group: the points of the one-group torus, whose sums it must repeat."""
+    mesh = TOPOLOGIES[name]()
+    if name == "multi_group":
+        return mesh, recipe_points(torus(), TOPOLOGY_POINTS, SEEDS["torus"])
+    return mesh, recipe_points(mesh, TOPOLOGY_POINTS, TOPOLOGY_SEEDS[name])

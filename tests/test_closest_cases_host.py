@@ -187,3 +187,60 @@ def test_sanitized_harness_on_the_new_cases(workdir):
     results = K.run_harness(exe, [K.case(cases[name][0], cases[name][1][:256], stack_cap=cap) for name, cap in picked], workdir)
     assert all(r["mismatches"] == 0 for r in results)
     assert int(results[0]["listed"].sum()) > 0
+    # the scale sweep: the exponent arithmetic of pow2_of at both ends of its clamp and in between
+    sweep = []
+    for name in SWEEP_MESHES:
+        mesh, pts = K.sweep_mesh(name), K.sweep_points(name)[:256]
+        best = K.true_distance(mesh, pts)
+        sweep += [K.sweep_case(mesh, pts, best, e)[:2] for e in K.SWEEP_EXPONENTS]
+    tiny = (np.ldexp(K.sweep_mesh("cube")[0], -140).astype(np.float32),) + K.sweep_mesh("cube")[1:]          # subnormal coordinates: k clamps at -126
+    sweep.append((tiny, np.ldexp(K.sweep_points("cube")[:256], -140).astype(np.float32)))
+    results = K.run_harness(exe, [K.case(mesh, pts, stack_cap=2) for mesh, pts in sweep], workdir)
+    assert all(r["mismatches"] == 0 for r in results) and all(np.all(r["brute"]["group"] >= 0) for r in results[:-1])
+
+
+# ---- float64 truth at every scale (closest_cases.SWEEP_EXPONENTS)
+
+SWEEP_MESHES = K.SWEEP_CLOSED + ("height_field",)
+
+
+@pytest.fixture(scope="module")
+def sweep_truth():
+    """name -> (mesh, points, float64 minimum distance), unscaled."""
+    out = {}
+    for name in SWEEP_MESHES:
+        mesh, pts = K.sweep_mesh(name), K.sweep_points(name)
+        out[name] = (mesh, pts, K.true_distance(mesh, pts))
+    return out
+
+
+def test_the_sweeps_filter_keeps_seven_eighths_of_every_batch(sweep_truth):
+    for name, (mesh, pts, best) in sweep_truth.items():
+        shares = {e: float(K.sweep_keep(best, e).mean()) for e in K.SWEEP_EXPONENTS}
+        print(name, "kept:", ", ".join("2^%d %.4f" % (e, s) for e, s in shares.items()))
+        assert min(shares.values()) >= 7.0 / 8.0 and shares[0] == 1.0, (name, shares)
+        assert shares[58] < 1.0, name + ": no far point is dropped at 2^58"
+
+
+@pytest.mark.parametrize("width", [4, 8])
+def test_closest_points_against_float64_at_every_scale(workdir, harness, sweep_truth, width):
+    """Conditions a and b of the sweep on the brute force, the walk's bits against it, and how many answers are not the exact
+    2^e multiple of the 2^0 answer (reported)."""
+    keys, cases = [], []
+    for name, (mesh, pts, best) in sweep_truth.items():
+        for e in K.SWEEP_EXPONENTS:
+            big, big_pts, keep = K.sweep_case(mesh, pts, best, e)
+            keys.append((name, e, keep))
+            cases.append(K.case(big, big_pts, stack_cap=2))
+    results = dict(((name, e), (keep, r)) for (name, e, keep), r in zip(keys, K.run_harness(harness(width), cases, workdir)))
+    for (name, e), (keep, r) in results.items():
+        mesh, pts, best = sweep_truth[name]
+        what = "%d-wide %s x 2^%d" % (width, name, e)
+        assert r["mismatches"] == 0, what
+        K.assert_same_bits(r["walk"], r["brute"], what)
+        excess, root = K.assert_sweep_answers(r["brute"], mesh, pts[keep], best[keep], e, LIMIT_UNITS, what)
+        base = results[name, 0][1]["brute"]
+        inexact = int((np.ldexp(base["dist2"][keep].astype(np.float64), 2 * e) != r["brute"]["dist2"]).sum() +
+                      np.any(base["bw"][keep] != r["brute"]["bw"], axis=1).sum())
+        print("%s: %d points, excess %.3f and sqrt(d2) %.3f units (limit %.3f), %d listed at cap 2, %d answers not 2^e x the 2^0 answer" % (
+            what, int(keep.sum()), excess, root, LIMIT_UNITS, int(r["listed"].sum()), inexact))

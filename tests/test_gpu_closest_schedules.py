@@ -5,8 +5,8 @@ tests/closest_host_harness.cpp on the batch's unique points; tests/test_closest_
 varies is the batch (its length, its order, whole waves and chunks of one kind of point, more points than one pass of each grid,
 a far point that only k_closest_pad's second stride pass sees), the schedule (KEEP_MIN, NODE_MIN, CHUNK_MIN, TRACE_BLOCKS_PER_CU,
 the counting kernels), the LDS stack (STACK_CAP: points that overflow it are walked again by k_closest_exact, with their radius),
-the requested fields, and the scene (zero-area records, identical stacked records, scales from 2^-70 to 2^58, offsets to 1e6, a
-refitted tree, the 8-wide library).
+the requested fields, and the scene (zero-area records, identical stacked records, scales from 2^-70 to 2^58 - eight of them
+against float64 as well - offsets to 1e6, a refitted tree, the 8-wide library).
 
 Every comparison is assert_same_bits on all requested fields over every point of the batch, through the host entry point (numpy)
 and the device entry point (torch).  Before each of them a spoil batch of the same length, radii and fields runs through the same
@@ -227,6 +227,34 @@ def scale_and_degenerates(orc, name, width):
     return int((expect["group"] < 0).sum())
 
 
+def scale_sweep(orc, name, width):
+    """One mesh of the float64 sweep (K.SWEEP_EXPONENTS) on contexts of its own, one per builder, uploaded once per exponent: the
+    harness's bits at the default stack and at STACK_CAP=2 through both entry points, and conditions a and b on the harness's and
+    on the device's own answers."""
+    from par_raytracer_amd import api
+    mesh, pts = K.sweep_mesh(name), K.sweep_points(name)
+    best = K.true_distance(mesh, pts)
+    cases = [K.sweep_case(mesh, pts, best, e) for e in K.SWEEP_EXPONENTS]
+    expects = [x["brute"] for x in K.run_harness(orc.exe, [K.case(big, big_pts) for big, big_pts, keep in cases], orc.dir)]
+    made = {builder: api.Renderer(0) for builder in ("sah", "lbvh")}
+    try:
+        for builder, r in made.items():
+            r.set_option("BVH_BUILDER", builder)
+            for e, (big, big_pts, keep), expect in zip(K.SWEEP_EXPONENTS, cases, expects):
+                what = "%d-wide %s x 2^%d / %s" % (width, name, e, builder)
+                assert keep.mean() >= 7.0 / 8.0, what
+                K.assert_sweep_answers(expect, mesh, pts[keep], best[keep], e, LIMIT_UNITS, what + ", brute force")
+                r.upload(K.flat_desc(big))
+                for cap in (None, 2):
+                    with options(r, STACK_CAP=cap):
+                        check(r, big_pts, None, expect, "%s / STACK_CAP=%s" % (what, cap))
+                        for torch_path in (False, True):
+                            K.assert_sweep_answers(query(r, big_pts, None, torch_path), mesh, pts[keep], best[keep], e, LIMIT_UNITS, what + ", device")
+    finally:
+        for r in made.values():
+            r.close()
+
+
 # ---- a. around the wave size
 
 @pytest.mark.gpu
@@ -353,6 +381,16 @@ def test_scales_offsets_and_degenerate_records(oracle, name):
     assert (misses > 0) == (name in ("2^58", "2^62"))       # d2 overflows for the far points: misses without a radius
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", K.SWEEP_CLOSED + ("height_field",))
+def test_float64_truth_at_every_scale(oracle, name):
+    """2^-45 to 2^58: no valid point misses and the answer is within LIMIT_UNITS of the float64 minimum over all triangles - on
+    the device's own answers, which are also the harness's bits (tests/test_closest_cases_host.py proves the cases)."""
+    t0 = time.perf_counter()
+    scale_sweep(oracle, name, 4)
+    print("%s: %d exponents, %.2f s" % (name, len(K.SWEEP_EXPONENTS), time.perf_counter() - t0))
+
+
 # ---- i. a moved scene on the slow path
 
 @pytest.mark.gpu
@@ -403,6 +441,7 @@ steps = [lambda: S.whole_waves_of_one_kind(get, orc), lambda: S.invalid_points_o
          lambda: S.overflow_with_every_lane_kept(get, orc), lambda: S.long_list(get, orc),
          lambda: S.past_one_pass(get, orc, None, 2), lambda: S.past_one_pass(get, orc, 1, 2), lambda: S.field_subsets(get, orc)]
 steps += [lambda name=name: S.scale_and_degenerates(orc, name, 8) for name in K.scale_meshes()]
+steps += [lambda name=name: S.scale_sweep(orc, name, 8) for name in K.SWEEP_CLOSED + ("height_field",)]
 for i, step in enumerate(steps):
     step()
     print("step", i, "ok", flush=True)

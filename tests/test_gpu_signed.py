@@ -1,7 +1,8 @@
 """prt_signed_distance on the GPU against the brute force of tests/signed_host_harness.cpp (the definition with the PRT_HD functions of
 csrc/dev_signed.h and integer accumulators, built here with g++): signed_distance, feature and the five closest fields bit for bit,
 through the host entry point (numpy) and the device entry point (torch), on the SAH tree, the LBVH tree, the 8-wide library, the
-stack overflow path and a refitted tree; permutations, contention at a vertex of 200 triangles, radii, invalid points, the empty
+stack overflow path and a refitted tree; eight scales from 2^-45 to 2^58 against float64; open, unwelded, non-manifold, cancelling,
+degenerate and multi-group meshes, each moved and moved back; permutations, contention at a vertex of 200 triangles, radii, invalid points, the empty
 scene, the errors, and signed_distance_differentiable."""
 from __future__ import annotations
 
@@ -120,12 +121,115 @@ def test_meshes_equal_the_brute_force(renderers, reference, name, builder):
         assert set(np.unique(expect["feature"])) >= set(range(7)), "every region occurs"
 
 
+def signed_sweep(exe, directory, name, what):
+    """One closed mesh of the float64 sweep (K.SWEEP_EXPONENTS) on contexts of its own, one per builder, uploaded once per exponent:
+    the harness's bits on all seven fields at the default stack and at STACK_CAP=2 through both entry points, and conditions a, b
+    and c on the harness's and on the device's own answers (tests/test_signed_host.py proves the cases)."""
+    import torch
+    from par_raytracer_amd import api
+    from test_closest_host import LIMIT_UNITS
+    mesh, pts = K.sweep_mesh(name), K.sweep_points(name)
+    best = K.true_distance(mesh, pts)
+    ref_sd = S.reference(mesh, pts)[0]
+    cases = [K.sweep_case(mesh, pts, best, e) for e in K.SWEEP_EXPONENTS]
+    expects = S.run_harness(exe, [S.case(big, big_pts) for big, big_pts, keep in cases], directory)
+
+    def conditions(res, keep, e, who):
+        K.assert_sweep_answers(res, mesh, pts[keep], best[keep], e, LIMIT_UNITS, who)
+        assert S.assert_sweep_signs(res["signed_distance"], name, mesh, pts[keep], ref_sd[keep], who) >= 0.9 * keep.sum()
+    made = {builder: api.Renderer(0) for builder in ("sah", "lbvh")}
+    try:
+        for builder, r in made.items():
+            r.set_option("BVH_BUILDER", builder)
+            dev = torch.device("cuda", r.device_id)
+            for e, (big, big_pts, keep), expect in zip(K.SWEEP_EXPONENTS, cases, expects):
+                who = "%s x 2^%d / %s / %s" % (name, e, builder, what)
+                assert keep.mean() >= 7.0 / 8.0, who
+                conditions(expect, keep, e, who + ", brute force")
+                S.assert_sweep_angles(expect["angles"], mesh, who)
+                r.upload(S.flat_desc(big))
+                for cap in (None, 2):
+                    r.set_option("STACK_CAP", cap)
+                    both_paths(r, big_pts, "%s / STACK_CAP=%s" % (who, cap), expect)
+                    conditions(r.signed_distance(big_pts), keep, e, who + ", device (numpy)")
+                    conditions(S.to_numpy(r.signed_distance(torch.from_numpy(big_pts).to(dev))), keep, e, who + ", device (torch)")
+                r.set_option("STACK_CAP", None)
+    finally:
+        for r in made.values():
+            r.close()
+
+
+def topology_round_trip(exe, directory, name, builders, what):
+    """One mesh of S.TOPOLOGIES: the harness's bits on all seven fields through both entry points, then after an update_geometry
+    to the sheared mirror image and after one back, each time on the moved context and on a fresh upload."""
+    from par_raytracer_amd import api
+    mesh, pts = S.topology_case(name)
+    moved, pts_moved = S.sheared_mirror(mesh), S.sheared_mirror_points(pts)
+    here, there = S.run_harness(exe, [S.case(mesh, pts), S.case(moved, pts_moved)], directory)
+    for builder in builders:
+        r = api.Renderer(0)
+        try:
+            if builder != "sah":
+                r.set_option("BVH_BUILDER", builder)
+            r.upload(S.flat_desc(mesh))
+            both_paths(r, pts, "%s / %s / %s" % (name, builder, what), here)
+            for at, at_pts, expect, step in ((moved, pts_moved, there, "moved"), (mesh, pts, here, "moved back")):
+                r.update_geometry(at[0])
+                both_paths(r, at_pts, "%s / %s / %s, %s" % (name, builder, what, step), expect)
+                fresh = api.Renderer(0)
+                try:
+                    if builder != "sah":
+                        fresh.set_option("BVH_BUILDER", builder)
+                    fresh.upload(S.flat_desc(at))
+                    S.assert_same_bits(fresh.signed_distance(at_pts), expect, "%s / %s / %s, %s, fresh upload" % (name, builder, what, step))
+                finally:
+                    fresh.close()
+        finally:
+            r.close()
+    return here
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(S.TOPOLOGIES))
+def test_topologies_equal_the_brute_force(workdir, name):
+    """Boundary edges, unwelded vertices, an edge of three triangles, accumulators that cancel, zero-area records that win ties,
+    unused positions and three shuffled groups (tests/test_signed_host.py proves the cases and what their signs mean)."""
+    expect = topology_round_trip(S.build_harness(workdir), workdir, name, ("sah", "lbvh"), "4-wide")
+    if name == "back_to_back":
+        assert not np.any(expect["signed_distance"][expect["feature"] <= 5] < 0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", K.SWEEP_CLOSED)
+def test_float64_truth_at_every_scale(workdir, name):
+    signed_sweep(S.build_harness(workdir), workdir, name, "4-wide")
+
+
+@pytest.mark.gpu
+def test_the_bounds_of_dist2(brute):
+    """The cube x 2^58 with its whole batch (the far points' dist2 overflows: misses) and x 2^-70 (dist2 subnormal or 0: +0, never
+    -0) - the harness's bits, which tests/test_signed_host.py holds against the unscaled cube."""
+    from par_raytracer_amd import api
+    mesh, pts = K.sweep_mesh("cube"), K.sweep_points("cube")
+    for e in (58, -70):
+        big, big_pts = K.scaled(mesh, e), np.ldexp(pts, e).astype(np.float32)
+        expect = brute(big, big_pts)
+        assert (expect["group"] < 0).any() == (e == 58) and not np.any(np.signbit(expect["signed_distance"][expect["dist2"] == 0]))
+        r = api.Renderer(0)
+        try:
+            r.upload(S.flat_desc(big))
+            both_paths(r, big_pts, "cube x 2^%d" % e, expect)
+        finally:
+            r.close()
+
+
 CHILD = r"""
 import os, sys, tempfile
 sys.path.insert(0, %(root)r); sys.path.insert(0, os.path.join(%(root)r, "tests")); sys.path.insert(0, os.path.join(%(root)r, "oracle"))
 import numpy as np
 import signed_cases as S
-from test_gpu_signed import NAMES, both_paths, upload
+import closest_cases as K
+from test_gpu_signed import NAMES, both_paths, signed_sweep, topology_round_trip, upload
 from par_raytracer_amd import api, capi
 lib = capi.hip_lib()
 assert os.path.basename(lib._name) == "libprt_hip_bvh8.so" and not (lib.prt_build_flags() & capi.BUILD_BVH4)
@@ -140,6 +244,12 @@ for name, res in zip(NAMES, results):
     both_paths(r, points[name], name + " / 8-wide", res)
     print(name, "equal", flush=True)
     r.close()
+for name in S.TOPOLOGIES:
+    topology_round_trip(exe, d, name, ("sah",), "8-wide")
+    print(name, "topology ok", flush=True)
+for name in K.SWEEP_CLOSED:
+    signed_sweep(exe, d, name, "8-wide")
+    print(name, "sweep ok", flush=True)
 print("bvh8 signed distance ok")
 """
 
@@ -209,8 +319,7 @@ def test_moved_scene_equals_a_fresh_upload_and_the_brute_force(brute, reference)
     from par_raytracer_amd import api
     mesh, pts, before = reference("torus")
     moved = S.sheared_mirror(mesh)
-    m = np.array([[-1.25, 0.0, 0.0], [0.5, 0.75, 0.0], [-0.25, 0.125, 1.5]], np.float32)
-    pts_moved = np.ascontiguousarray((pts @ m).astype(np.float32))
+    pts_moved = S.sheared_mirror_points(pts)
     expect = brute(moved, pts_moved)
     r, fresh = api.Renderer(0), api.Renderer(0)
     try:

@@ -139,3 +139,181 @@ def test_harness_under_the_sanitizers(workdir):
     assert np.all(out[1]["feature"][::7] == 255)
     plain = S.run_harness(S.build_harness(workdir), [S.case(mesh, pts)], workdir)[0]
     S.assert_same_bits(out[0], plain, "sanitized and plain harness")
+    # the scale sweep (the exponent arithmetic of pow2_of, up to both ends of its clamp) and the topologies
+    cases = []
+    for name in K.SWEEP_CLOSED:
+        m, p = K.sweep_mesh(name), K.sweep_points(name)[:256]
+        best = K.true_distance(m, p)
+        cases += [S.case(*K.sweep_case(m, p, best, e)[:2]) for e in K.SWEEP_EXPONENTS]
+    cases.append(S.case((np.ldexp(S.cube()[0], -140).astype(np.float32),) + S.cube()[1:], np.ldexp(K.sweep_points("cube")[:256], -140).astype(np.float32)))
+    cases.append(S.case((np.ldexp(S.cube()[0], 126).astype(np.float32),) + S.cube()[1:], np.ldexp(K.sweep_points("cube")[:256], 100).astype(np.float32)))
+    n_sweep = len(cases) - 2
+    for name in S.TOPOLOGIES:
+        m, p = S.topology_case(name)
+        cases.append(S.case(m, p[:256]))
+    out = S.run_harness(exe, cases, workdir)
+    assert all(np.all(res["group"] >= 0) for res in out[:n_sweep])
+
+
+# ---- float64 truth at every scale (closest_cases.SWEEP_EXPONENTS)
+
+@pytest.fixture(scope="module")
+def sweep(workdir):
+    """(name, e) -> (mesh, kept points, float64 minimum, reference signed distance and region - all unscaled - and the harness's
+    answers on mesh x 2^e and points x 2^e), and name -> the share of the batch that the filter keeps per exponent."""
+    exe = S.build_harness(workdir)
+    keys, cases, truth, shares = [], [], {}, {}
+    for name in K.SWEEP_CLOSED:
+        mesh, pts = K.sweep_mesh(name), K.sweep_points(name)
+        best = K.true_distance(mesh, pts)
+        ref_sd, ref_region, _ = S.reference(mesh, pts)
+        for e in K.SWEEP_EXPONENTS:
+            big, big_pts, keep = K.sweep_case(mesh, pts, best, e)
+            keys.append((name, e))
+            cases.append(S.case(big, big_pts))
+            truth[name, e] = (mesh, pts[keep], best[keep], ref_sd[keep], ref_region[keep])
+            shares.setdefault(name, {})[e] = float(keep.mean())
+    out = S.run_harness(exe, cases, workdir)
+    return {k: truth[k] + (res,) for k, res in zip(keys, out)}, shares
+
+
+def test_the_sweeps_filter_keeps_seven_eighths_of_every_batch(sweep):
+    for name, per in sweep[1].items():
+        print(name, "kept:", ", ".join("2^%d %.4f" % (e, s) for e, s in per.items()))
+        assert min(per.values()) >= 7.0 / 8.0, (name, per)
+        assert per[0] == 1.0, (name, per)                     # the 2^0 batch holds every other batch's points
+
+
+@pytest.mark.parametrize("name", K.SWEEP_CLOSED)
+def test_signed_distance_against_float64_at_every_scale(sweep, name):
+    """Conditions a to d of the sweep on the harness, and the two reported counts (e)."""
+    from test_closest_host import LIMIT_UNITS
+    base = sweep[0][name, 0][5]
+    for e in K.SWEEP_EXPONENTS:
+        mesh, pts, best, ref_sd, ref_region, res = sweep[0][name, e]
+        what = "%s x 2^%d" % (name, e)
+        excess, root = K.assert_sweep_answers(res, mesh, pts, best, e, LIMIT_UNITS, what)
+        checked = S.assert_sweep_signs(res["signed_distance"], name, mesh, pts, ref_sd, what)
+        angle = S.assert_sweep_angles(res["angles"], mesh, what)
+        assert np.array_equal(np.abs(res["signed_distance"]), np.sqrt(res["dist2"])), what
+        # e: reported only.  The 2^0 batch holds every point of the others (the filter keeps all of it), in the same order
+        at = np.nonzero(K.sweep_keep(sweep[0][name, 0][2], e))[0]
+        inexact = int((np.ldexp(base["signed_distance"][at].astype(np.float64), e) != res["signed_distance"]).sum() +
+                      (base["feature"][at] != res["feature"]).sum()) if len(at) == len(pts) else -1
+        print("%s: %d points, %d signs checked, excess %.3f and sqrt(d2) %.3f units (limit %.3f), angle error %.2e, %d regions other than "
+              "float64's, %d answers not 2^e x the 2^0 answer" % (what, len(pts), checked, excess, root, LIMIT_UNITS, angle,
+                                                                  int((res["feature"] != ref_region).sum()), inexact))
+
+
+# ---- the topologies of the definition (signed_cases.TOPOLOGIES)
+
+@pytest.fixture(scope="module")
+def topologies(workdir):
+    """name -> (mesh, points, harness answers); also "torus" on multi_group's points and "cube" on degenerate's."""
+    exe = S.build_harness(workdir)
+    cases = {name: S.topology_case(name) for name in S.TOPOLOGIES}
+    cases["torus"] = (S.torus(), cases["multi_group"][1])
+    cases["cube"] = (S.cube(), cases["degenerate"][1])
+    out = S.run_harness(exe, [S.case(mesh, pts) for mesh, pts in cases.values()], workdir)
+    return {name: cases[name] + (res,) for name, res in zip(cases, out)}
+
+
+def edge_uses(mesh):
+    """How many triangles use each undirected edge of position indices (zero-length edges (a, a) left out)."""
+    tri = mesh[1].reshape(-1, 3).astype(np.int64)
+    pairs = np.sort(np.concatenate([tri[:, [0, 1]], tri[:, [0, 2]], tri[:, [1, 2]]]), axis=1)
+    return np.unique(pairs[pairs[:, 0] != pairs[:, 1]], axis=0, return_counts=True)[1]
+
+
+def test_topologies_are_what_their_names_say():
+    for name in S.TOPOLOGIES:
+        mesh = S.TOPOLOGIES[name]()
+        assert mesh[1].size // 3 <= 2000 and mesh[2][:, 1].sum() == mesh[1].size, name
+    uses = edge_uses(S.open_sheet())
+    assert (uses == 1).sum() == 4 * 16 and set(uses) == {1, 2}, "the rim's edges have one triangle"
+    p, idx, runs = S.unwelded(S.cube())
+    assert len(p) == 36 and np.all(edge_uses((p, idx, runs)) == 1) and len(np.unique(p, axis=0)) == 8
+    assert sorted(edge_uses(S.non_manifold())) == [1] * 9 + [2] * 3 + [3]
+    p, idx, runs = S.back_to_back()
+    tri = idx.reshape(-1, 3)
+    assert np.array_equal(tri[128:], tri[:128][:, [0, 2, 1]]) and np.all(edge_uses((p, idx, runs)) % 2 == 0)
+    p, idx, runs = S.unreferenced_and_repeated()
+    assert sorted(set(range(len(p))) - set(idx.tolist())) == [0, 9, 10] and idx.reshape(-1, 3)[-1].tolist() == [1, 1, 8]
+    p, idx, runs = S.multi_group(S.torus())
+    assert runs[:, 0].tolist() == [384 * 3, 0, 192 * 3] and np.all(runs[:, 1] == 192 * 3)
+    key = lambda t: sorted(map(tuple, t.reshape(-1, 3).tolist()))       # noqa: E731
+    assert key(idx) == key(S.torus()[1]) and np.array_equal(p, S.torus()[0])
+
+
+def test_every_region_occurs_on_every_topology(topologies):
+    """Every region code in every batch - but one: on with_degenerates(cube) edge bc never wins.  Its 128 zero-area records
+    (a, b, midpoint) and (a, a, b) on random vertex pairs cover all 28 pairs of the cube's 8 vertices (asserted), so on every edge of
+    the cube a record of group 0 ties with the real triangles, wins by group order, and names the edge ab or ac."""
+    for name in S.TOPOLOGIES:
+        mesh, pts, res = topologies[name]
+        seen = set(np.unique(res["feature"]))
+        print(name, "points per region:", np.bincount(res["feature"], minlength=7).tolist(), "negative:", int((res["signed_distance"] < 0).sum()))
+        assert len(pts) == S.TOPOLOGY_POINTS and np.all(res["group"] >= 0)
+        assert seen >= set(range(7)) - ({5} if name == "degenerate" else set()), (name, seen)
+        assert np.array_equal(np.abs(res["signed_distance"]), np.sqrt(res["dist2"])), name
+    mesh = S.degenerate_cube()
+    flat = mesh[1].reshape(-1, 3)[:2 * K.DEGENERATE_PER_FORM]
+    pairs = {tuple(sorted((int(t[0]), int(t[1]) if t[1] != t[0] else int(t[2])))) for t in flat}
+    assert len(pairs) == 28
+
+
+def test_signs_on_the_topologies(topologies):
+    """open, non_manifold, unwelded, unreferenced, multi_group: the float64 reference's sign at every point 1e-4 extents off the
+    surface.  back_to_back: the accumulators cancel to exactly 0, so no vertex or edge answer is negative; an interior answer is
+    signed by the winner's own cross product - and the two copies of a triangle round d2 differently (ab and ac change places), so
+    which copy wins, and with it the interior sign, is decided by the last bit of d2: the sign is the winner's side, no more.  multi_group: the one-group torus's signed_distance bits.
+    degenerate: how many signs differ from the plain cube's analytic inside test - a property of the definition that
+    DESIGN.md section 4.12 records, not a gate."""
+    for name in ("open", "non_manifold", "unwelded", "unreferenced", "multi_group"):
+        mesh, pts, res = topologies[name]
+        ref_sd = S.reference(mesh, pts)[0]
+        checked = S.assert_sweep_signs(res["signed_distance"], name, mesh, pts, ref_sd, name)
+        assert checked >= 0.95 * len(pts), (name, checked)
+    mesh, pts, res = topologies["back_to_back"]
+    edge = res["feature"] <= 5
+    assert edge.sum() > 200 and not np.any(res["signed_distance"][edge] < 0) and not np.any(np.signbit(res["signed_distance"][edge]))
+    tri = K.input_triangle(mesh, res["group"], res["vertex0"])
+    print("back_to_back: %d of %d answers name a reversed copy" % ((tri >= mesh[1].size // 6).sum(), len(tri)))
+    a, b, c = (x.astype(np.float64) for x in K.corners(mesh, tri))
+    side = ((pts - res["point"].astype(np.float64)) * np.cross(b - a, c - a)).sum(1)
+    inner = ~edge & (np.sqrt(res["dist2"]) >= S.OFF_SURFACE * K.mesh_extent(mesh)[2])
+    assert inner.sum() > 500 and np.array_equal(res["signed_distance"][inner] < 0, side[inner] < 0)
+    assert (res["signed_distance"][inner] < 0).sum() > 100
+    S.assert_same_bits(topologies["multi_group"][2], topologies["torus"][2], "three shuffled groups and one", ("dist2", "signed_distance"))
+    mesh, pts, res = topologies["degenerate"]
+    inside = S.inside_cube(pts)
+    assert not np.any((topologies["cube"][2]["signed_distance"] < 0) != inside)
+    changed = (res["signed_distance"] < 0) != inside
+    print("with_degenerates(cube): %d of %d points take another sign than the plain cube's inside test (%d answers name a zero-area record, "
+          "%d triangles contribute nothing)" % (changed.sum(), len(pts), (res["group"] == 0).sum(), np.isnan(res["angles"]).any(1).sum()))
+    assert np.all(inside[changed]) and not np.any(res["signed_distance"][res["group"] == 0] < 0), "a zero-area record has no normal: never negative"
+
+
+def test_signed_distance_at_the_bounds_of_dist2(workdir):
+    """The documented range is that of dist2 (include/prt.h).  Above: the cube x 2^58 with its whole batch - the points whose true
+    dist2 reaches 2^128 miss (FLT_MAX, feature 255), the others keep their sign.  Below: the cube x 2^-70 - nearly every dist2 is
+    subnormal or 0, signed_distance is +-sqrtf of it, +0 where it is 0, and the sign of every point whose dist2 is still a
+    positive float is the unscaled cube's."""
+    exe = S.build_harness(workdir)
+    mesh, pts = K.sweep_mesh("cube"), K.sweep_points("cube")
+    best = K.true_distance(mesh, pts)
+    ref_sd = S.reference(mesh, pts)[0]
+    up, down = (S.case(K.scaled(mesh, e), np.ldexp(pts, e).astype(np.float32)) for e in (58, -70))
+    big, small = S.run_harness(exe, [up, down], workdir)
+    over = (best * 2.0 ** 58) ** 2 >= 2.0 ** 128
+    margin = np.abs(np.log2(np.maximum(best, 1e-300)) - 6.0) > 0.01           # not within rounding of the bound 2^64 / 2^58
+    missed = big["group"] < 0
+    assert over.sum() > 16 and np.array_equal(missed[margin], over[margin])
+    assert np.all(big["signed_distance"][missed] == S.FLT_MAX) and np.all(big["feature"][missed] == 255)
+    S.assert_sweep_signs(big["signed_distance"][~missed], "cube", mesh, pts[~missed], ref_sd[~missed], "cube x 2^58, every point that hits")
+    tiny = small["dist2"] < np.float32(2.0 ** -126)                         # all but the far points: subnormal, or rounded to 0
+    assert np.all(small["group"] >= 0) and tiny.sum() > 800 and (tiny & (small["dist2"] > 0)).sum() > 200
+    assert np.array_equal(np.abs(small["signed_distance"]), np.sqrt(small["dist2"]))
+    zero = small["dist2"] == 0
+    assert not np.any(np.signbit(small["signed_distance"][zero]))
+    S.assert_sweep_signs(small["signed_distance"][~zero], "cube", mesh, pts[~zero], ref_sd[~zero], "cube x 2^-70, dist2 > 0")
