@@ -542,6 +542,94 @@ int prt_signed_distance(prt_ctx * ctx, const prt_point_batch * batch, const prt_
 int prt_signed_distance_device(prt_ctx * ctx, const prt_point_batch * batch, const prt_signed_buffers * out, uint32_t flags,
                                prt_counters * counters);
 
+/* ---- surface samples: points on the uploaded mesh, drawn uniformly by area -------------------------------------------------------
+ * The other side of a chamfer loss (mesh -> scan; prt_closest_points is scan -> mesh), mesh-to-mesh and Hausdorff estimates (sample
+ * one mesh, prt_closest_points on the other), area-weighted surface integrals, seeds for rays.  One call draws `count` points on the
+ * scene as it lies on the device now (after any number of prt_update_geometry calls).
+ * THE DEFINITION (csrc/dev_sample.h).  Everything is a pure function of (the records as they lie on the
+ * device, seed, sample index j): the same bits for every tree (SAH, LBVH, 8-wide, refitted), launch shape, split of a batch into
+ * calls and run, and the bits a brute force on the host gives with the same functions.
+ *   Triangle order   input order: triangle t is index triple t of idx_positions (group g's triangles start at first_index / 3),
+ *                    not the order of the tree's leaves.
+ *   Weight           of a triangle record (a, ab = b - a, ac = c - a): k = the exponent of the largest |component| of ab and ac,
+ *                    A = sqrtf(length_sq(cross(ab x 2^-k, ac x 2^-k))) in float32 without contraction; the weight is the real number
+ *                    A x 2^(2k), twice the area, held exactly in a double.  A triangle whose A is zero or not finite has weight 0
+ *                    and is never drawn.
+ *   Fixed point      E: 2^(E-1) <= the largest weight < 2^E; L: the smallest integer with triangle count <= 2^L;
+ *                    unit_exponent = E + L - 62 (the rule of prt_trace_rays_backward's unit_exponent);
+ *                    W_t = (uint64)rint(weight_t x 2^-unit_exponent); C_t = W_0 + ... + W_t; T = C_(n-1) < 2^62.  The sums are
+ *                    integers: every scan order gives the same C.  With L = 20 the largest triangle keeps 42 bits, so float32's 24
+ *                    bits survive for triangles down to 2^-18 of the largest area; a smaller triangle's weight loses low bits, and
+ *                    one below 2^-(62 - L) of the largest rounds to weight 0.
+ *   Sample j         j = first + i < 2^48.  The generator is seeded with prt_sample_key(seed, j >> 16, j & 0xFFFF) (prt_key.h: the
+ *                    key's packed word is j itself) and makes three draws: r0, the raw 64 bits; u1, u2 = the next two as floats in
+ *                    [0, 1].  x = the high 64 bits of r0 x T; the triangle is the smallest t with C_t > x (zero-weight triangles
+ *                    are skipped by construction).  v = u1, w = u2, and if v + w > 1.0f both are mirrored: v = 1 - v, w = 1 - w.
+ *                    bw = (fmaxf(0, (1 - v) - w), v, w); point = (a + ab v) + ac w; normal = Normalize(cross(ab, ac)) on the
+ *                    edges x 2^-k - the expression PRT_QUERY_CLOSEST uses for prt_hit_buffers.normal, free of the scene's scale;
+ *                    group, vertex0 = the triangle's reference, as prt_hit_buffers reports it.
+ *   Miss             T == 0 (no triangles, or none with an area) makes every sample a miss: zeros in point, bw and normal,
+ *                    group = -1, vertex0 = 0xFFFFFFFF.  It is not an error.
+ * SCALE.  At scale 2^e group, vertex0, bw, normal, total_weight and live_triangles are the bits of scale 1, point is 2^e times the
+ * point of scale 1 and unit_exponent moves by 2e, for every scene the upload accepts (|coordinate| < 1e18) whose edges' squared
+ * lengths are normal floats after the per-triangle scaling.
+ * NOT MODELLED.  The choice of the triangle is not differentiated: prt_sample_surface_backward has no gradient through the area
+ * weights - the stance the other gradients take on silhouettes and regions.
+ * prt_sample_info: device_ms = the call's device time, table_ms = the part of it spent rebuilding the prefix sums (0 when nothing
+ * was rebuilt); area = 0.5 x total_weight x 2^unit_exponent; total_weight = T; live_triangles = the triangles with W_t > 0.
+ * TABLES.  The first sampling call after an upload builds the input triangle -> leaf table (4 B per triangle); the first sampling
+ * call after an upload or after a successful prt_update_geometry[_device] rebuilds the weights and their prefix sums on the device
+ * from the records as they lie there (16 B per triangle and 8 B per 256 triangles of scratch; four launches on the context's stream,
+ * no lane waits for another workgroup) and reads 24 bytes back.  Like the leaf table they are not in prt_scene_info.device_bytes
+ * and are freed by the next upload.
+ * Errors: -1 NULL request or buffers, first + count > 2^48; -2 no scene; -10 a HIP call failed.  count == 0 writes nothing
+ * (info, if given, is zeroed: no table is built for it) and returns 0.  Stream contract of prt_trace_rays_device.  The call leaves
+ * the render stats and the counters alone. */
+typedef struct prt_sample_request { uint64_t seed; uint64_t first; uint32_t count; } prt_sample_request;
+/* Every pointer may be NULL: that field is not written. */
+typedef struct prt_sample_buffers {
+    float * point;                 /* x3 */
+    float * bw;                    /* x3: (1 - v - w, v, w), as prt_hit_buffers.bw */
+    float * normal;                /* x3: unit, the side cross(ab, ac) points to */
+    uint32_t * vertex0;            /* as prt_hit_buffers.vertex0; 0xFFFFFFFF on a miss */
+    int32_t * group;               /* as prt_hit_buffers.group; -1 on a miss */
+} prt_sample_buffers;
+typedef struct prt_sample_info { double device_ms; double table_ms; double area; uint64_t total_weight;
+                                 int32_t unit_exponent; uint32_t live_triangles; } prt_sample_info;
+/* Host pointers (buffers); info may be NULL. */
+int prt_sample_surface(prt_ctx * ctx, const prt_sample_request * request, const prt_sample_buffers * out, prt_sample_info * info);
+/* Device pointers on the context's device (hipMalloc'ed or torch tensors' data_ptr). */
+int prt_sample_surface_device(prt_ctx * ctx, const prt_sample_request * request, const prt_sample_buffers * out, prt_sample_info * info);
+
+/* ---- gradients of surface samples: how point and normal change with the vertices ------------------------------------------------
+ * Closes the loop for the mesh -> scan side of a chamfer loss: prt_update_geometry moves the mesh, prt_sample_surface draws points
+ * on it, and this call turns the gradients of a loss with respect to the samples' points and normals into gradients with respect
+ * to the vertex positions.  What is differentiated is, on the triangle (a, b, c) the forward call REPORTED (group, vertex0 ->
+ * corners idx_positions[first_index + vertex0 + 0..2]) and with the sample's barycentrics bw held fixed (csrc/dev_sample_grad.h):
+ *     point = bw0 a + bw1 b + bw2 c          dL/da += g bw0, dL/db += g bw1, dL/dc += g bw2
+ *     normal = n = N / |N|, N = cross(ab, ac)   gN = (g - n (n.g)) / |N|, dL/dab = ac x gN, dL/dac = gN x ab, dL/da = -(dL/dab + dL/dac)
+ * (the normal term on the edges x 2^-k, as the forward call forms n).
+ *   count, group, vertex0, bw   the forward call's count and outputs.  group < 0 is a miss and contributes nothing.
+ *   positions      the vertex positions the forward call saw; position_count must equal the upload's
+ *   gout           dL/dpoint, dL/dnormal (count x 3); a NULL array, or gout NULL, means zero
+ *   gin_positions  position_count x 3, summed over the samples, OVERWRITTEN (not accumulated into); NULL = not computed
+ * A sample is SKIPPED - nothing added - when its triangle has no finite normal while gout->normal is given, or when any of its 9
+ * gradient components is not finite (a NaN vertex, a NaN in bw or gout, an overflow).
+ * Determinism, prt_grad_info (hit_rays = samples that contributed, skipped_rays = referenced samples that were skipped), the errors
+ * (-1 NULL group, vertex0, bw or positions with count > 0; a position_count that differs from the upload's; an invalid reference,
+ * found BEFORE any output is written; -2 no scene; -10 a HIP call failed), count == 0, the stream contract and what the call leaves
+ * alone are prt_trace_rays_backward's, word for word; the calls share their device buffers.  The option QGRAD_MERGE governs all
+ * three (same bits either way). */
+typedef struct prt_sample_grads { const float * point; const float * normal; } prt_sample_grads;   /* dL/doutputs; NULL = zero */
+/* Host pointers (group, vertex0, bw, positions, gout's arrays, gin_positions); info may be NULL. */
+int prt_sample_surface_backward(prt_ctx * ctx, uint32_t count, const int32_t * group, const uint32_t * vertex0, const float * bw,
+                                const float * positions, uint32_t position_count, const prt_sample_grads * gout, float * gin_positions,
+                                prt_grad_info * info);
+/* The same with device pointers on the context's device (hipMalloc'ed or torch tensors' data_ptr). */
+int prt_sample_surface_backward_device(prt_ctx * ctx, uint32_t count, const int32_t * group, const uint32_t * vertex0, const float * bw,
+                                       const float * positions, uint32_t position_count, const prt_sample_grads * gout, float * gin_positions,
+                                       prt_grad_info * info);
+
 /* ---- several devices behind one handle --------------------------------------------------------------------------------
  * SURVEY.md 8(b)'s prt_create(const int * device_ids, int n_dev): what the host mirror's Render() uses for n GPUs, in place
  * of the reference's one-rank-per-core partition + MPI_Gather (main.cpp:311-347).  The scene is replicated (as every MPI rank

@@ -551,6 +551,73 @@ class Renderer:
         out["info"] = info
         return out
 
+    # (name, components per sample, numpy dtype) of prt_sample_buffers' fields
+    SAMPLE_FIELDS = (("point", 3, np.float32), ("bw", 3, np.float32), ("normal", 3, np.float32), ("vertex0", 1, np.uint32),
+                     ("group", 1, np.int32))
+
+    def sample_surface(self, count: int, *, seed: int = 0, first: int = 0, fields: Optional[Sequence[str]] = None, out: str = "numpy") -> dict:
+        """`count` points on the uploaded surface, drawn uniformly by area (prt_sample_surface, include/prt.h): samples
+        first .. first + count - 1 of `seed`, a pure function of (scene as it lies on the device, seed, sample index).
+
+        fields: any of point, bw, normal, vertex0, group (default all).  out: "numpy" (host entry point, numpy results) or
+        "torch" (device entry point, tensors on this context's device; vertex0 carries its bits as int32).  Returns
+        {field: array} plus "info" (PrtSampleInfo: area, total_weight, unit_exponent, live_triangles, device_ms, table_ms)."""
+        spec = {name: (k, dt) for name, k, dt in self.SAMPLE_FIELDS}
+        if fields is None:
+            fields = tuple(spec)
+        for f in fields:
+            if f not in spec:
+                raise ValueError("unknown sample field %r" % (f,))
+        if out not in ("numpy", "torch"):
+            raise ValueError("out must be 'numpy' or 'torch', not %r" % (out,))
+        n = int(count)
+        if n < 0 or n >= 1 << 32 or int(first) < 0 or int(seed) < 0:
+            raise ValueError("count must be in 0 .. 2^32 - 1, first and seed non-negative")
+        if out == "torch":
+            import torch
+            like = torch.empty(0, device="cuda:%d" % self.device_id)
+        else:
+            like = np.empty(0, np.float32)
+        _check, empty, ptr, sync, suffix = self._arrays(like)
+        res = {f: empty((n, spec[f][0]) if spec[f][0] > 1 else (n,), spec[f][1]) for f in fields}
+        sync()
+        name = "prt_sample_surface" + suffix
+        rq = capi.PrtSampleRequest(int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), n)
+        sb = capi.PrtSampleBuffers(*[ptr(res[f]) if f in res else None for f, _, _ in self.SAMPLE_FIELDS])
+        info = capi.PrtSampleInfo()
+        self._check(getattr(self._lib, name)(self._ctx, C.byref(rq), C.byref(sb), C.byref(info)), name)
+        res["info"] = info
+        return res
+
+    def sample_surface_backward(self, group, vertex0, bw, positions, *, grad_point=None, grad_normal=None) -> dict:
+        """Gradients of surface samples (prt_sample_surface_backward, include/prt.h): from dL/dpoint and dL/dnormal of n samples
+        (None = zero) to dL/dpositions, summed over the samples - the same bits for every order of the samples.
+
+        group, vertex0, bw: the forward sample_surface call's outputs (vertex0 uint32, or int32 holding the same bits);
+        positions: float32 (P, 3), the vertices that call saw.  numpy arrays go to the host entry point, torch tensors on this
+        context's device to the device entry point (decided by `group`).  Returns {"positions": array, "info": PrtGradInfo}."""
+        check, empty, ptr, sync, suffix = self._arrays(group)
+        name = "prt_sample_surface_backward" + suffix
+        if getattr(group, "ndim", 0) != 1:
+            raise ValueError("group must have shape (n,)")
+        n = int(group.shape[0])
+        if getattr(positions, "ndim", 0) != 2:
+            raise ValueError("positions must have shape (P, 3)")
+        n_pos = int(positions.shape[0])
+        group = check(group, "group", (n,), (np.int32,))
+        vertex0 = check(vertex0, "vertex0", (n,), (np.int32, np.uint32))
+        bw = check(bw, "bw", (n, 3))
+        positions = check(positions, "positions", (n_pos, 3))
+        gouts = [None if g is None else check(g, what, (n, 3)) for g, what in ((grad_point, "grad_point"), (grad_normal, "grad_normal"))]
+        out = {"positions": empty((n_pos, 3))}
+        sync()
+        go = capi.PrtSampleGrads(*[ptr(g) for g in gouts])
+        info = PrtGradInfo()
+        self._check(getattr(self._lib, name)(self._ctx, n, ptr(group), ptr(vertex0), ptr(bw), ptr(positions), n_pos, C.byref(go),
+                                             ptr(out["positions"]), C.byref(info)), name)
+        out["info"] = info
+        return out
+
     def update_geometry(self, positions, normals=None, tangents=None, spheres=None, sphere_group=None) -> PrtUpdateInfo:
         """Move the uploaded scene's vertices in place and refit the tree on the device (prt_update_geometry, include/prt.h):
         afterwards renders and queries give the bits a fresh upload of the moved scene would.

@@ -14,12 +14,17 @@ each point reported; a change of region or of the winning triangle is not modell
 `signed_distance_differentiable` puts the sign of Renderer.signed_distance on the distance of `closest_points_differentiable`: a
 signed distance whose gradient is that of the unsigned distance times the sign.  A gradient of the sign itself is not modelled.
 
+`sample_surface_differentiable` ties Renderer.update_geometry, Renderer.sample_surface and Renderer.sample_surface_backward together:
+points drawn uniformly by area on the mesh - the mesh -> scan side of a chamfer loss - whose positions and normals are
+differentiable with respect to the vertex positions.  The choice of the triangle is not differentiated.
+
 torch is imported when a function is first called: importing the package stays torch-free.
 """
 from __future__ import annotations
 
 _FUNCTION = None
 _POINT_FUNCTION = None
+_SAMPLE_FUNCTION = None
 
 
 def _function():
@@ -143,3 +148,47 @@ def signed_distance_differentiable(renderer, positions, points, *, max_dist=None
     dist = torch.where(live, torch.where(live, dist2, torch.ones_like(dist2)).sqrt(), torch.zeros_like(dist2))
     g = torch.where(signed < 0, -dist, dist)
     return signed + (g - g.detach())                     # the library's bits, the gradient of sign x sqrt(dist2)
+
+
+def _sample_function():
+    global _SAMPLE_FUNCTION
+    if _SAMPLE_FUNCTION is not None:
+        return _SAMPLE_FUNCTION
+    import torch
+
+    class SampleSurface(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, renderer, positions, count, seed, first, update_geometry):
+            p = positions.detach().contiguous()
+            if update_geometry:
+                renderer.update_geometry(p)
+            res = renderer.sample_surface(count, seed=seed, first=first, out="torch")
+            ctx.renderer = renderer
+            ctx.set_materialize_grads(False)              # an output the loss does not use arrives as None = zero, and is not read
+            ctx.save_for_backward(p, res["bw"], res["group"], res["vertex0"])
+            ctx.mark_non_differentiable(res["bw"], res["group"], res["vertex0"])
+            return res["point"], res["normal"], res["bw"], res["group"], res["vertex0"]
+
+        @staticmethod
+        def backward(ctx, g_point, g_normal, _g_bw, _g_group, _g_vertex0):
+            p, bw, group, vertex0 = ctx.saved_tensors
+            if not ctx.needs_input_grad[1]:
+                return (None,) * 6
+            grads = [None if g is None else g.contiguous() for g in (g_point, g_normal)]
+            res = ctx.renderer.sample_surface_backward(group, vertex0, bw, p, grad_point=grads[0], grad_normal=grads[1])
+            return (None, res["positions"], None, None, None, None)
+
+    _SAMPLE_FUNCTION = SampleSurface
+    return _SAMPLE_FUNCTION
+
+
+def sample_surface_differentiable(renderer, positions, count, *, seed, first: int = 0, update_geometry: bool = True):
+    """`count` points drawn uniformly by area on the renderer's scene with its vertices at `positions` (Renderer.sample_surface).
+
+    positions (P, 3): a float32 torch tensor on the renderer's device.  With update_geometry (the default) the scene's vertices
+    are first moved to `positions` (Renderer.update_geometry: P must be the uploaded scene's count); without it `positions` must
+    be what the scene holds already.  Returns (point, normal, bw, group, vertex0) as Renderer.sample_surface(out="torch") does;
+    point and normal are differentiable with respect to positions - each sample moves with its triangle, at fixed barycentrics -,
+    bw, group and vertex0 are not.  The choice of the triangle is not differentiated: there is no gradient through the area
+    weights.  A miss (a scene without area) has zeros and zero gradient."""
+    return _sample_function().apply(renderer, positions, int(count), int(seed), int(first), bool(update_geometry))

@@ -154,6 +154,26 @@ class PrtGradInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class PrtSampleRequest(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("first", C.c_uint64), ("count", C.c_uint32)]
+
+
+class PrtSampleBuffers(C.Structure):
+    _fields_ = [("point", C.c_void_p), ("bw", C.c_void_p), ("normal", C.c_void_p), ("vertex0", C.c_void_p), ("group", C.c_void_p)]
+
+
+class PrtSampleInfo(C.Structure):
+    _fields_ = [("device_ms", C.c_double), ("table_ms", C.c_double), ("area", C.c_double), ("total_weight", C.c_uint64),
+                ("unit_exponent", C.c_int32), ("live_triangles", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class PrtSampleGrads(C.Structure):
+    _fields_ = [("point", C.c_void_p), ("normal", C.c_void_p)]
+
+
 QUERY_CLOSEST, QUERY_OCCLUDED = 0, 1
 PIPELINE_DEFAULT, PIPELINE_MEGAKERNEL, PIPELINE_WAVEFRONT, PIPELINE_PERSISTENT, PIPELINE_POOL = 0, 1, 2, 3, 4
 FLAG_COUNT_VISITS = 0x100
@@ -170,7 +190,9 @@ PRT_SYMBOLS = ["prt_create", "prt_destroy", "prt_last_error", "prt_abi_version",
                "prt_trace_rays_backward", "prt_trace_rays_backward_device",
                "prt_closest_points", "prt_closest_points_device",
                "prt_closest_points_backward", "prt_closest_points_backward_device",
-               "prt_signed_distance", "prt_signed_distance_device"]
+               "prt_signed_distance", "prt_signed_distance_device",
+               "prt_sample_surface", "prt_sample_surface_device",
+               "prt_sample_surface_backward", "prt_sample_surface_backward_device"]
 # PRT_REGION_* of include/prt.h, in index order (tests/test_host_side.py's header check keeps the symbol list in step; the
 # region test compares this list with the header's enum)
 REGION_NAMES = ["round", "topup", "topup_pass", "trace_outer", "refill", "walk_pass", "node_step", "node_descend", "node_pop", "node_push", "leaf",
@@ -275,6 +297,12 @@ def hip_lib() -> C.CDLL:
             lib.prt_signed_distance.argtypes = [C.c_void_p, C.POINTER(PrtPointBatch), C.POINTER(PrtSignedBuffers), C.c_uint32,
                                                 C.POINTER(PrtCounters)]
             lib.prt_signed_distance_device.argtypes = lib.prt_signed_distance.argtypes
+        if hasattr(lib, "prt_sample_surface"):         # (absent from a PRT_HIP_LIB build of an earlier commit)
+            lib.prt_sample_surface.argtypes = [C.c_void_p, C.POINTER(PrtSampleRequest), C.POINTER(PrtSampleBuffers), C.POINTER(PrtSampleInfo)]
+            lib.prt_sample_surface_device.argtypes = lib.prt_sample_surface.argtypes
+            lib.prt_sample_surface_backward.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                        C.POINTER(PrtSampleGrads), C.c_void_p, C.POINTER(PrtGradInfo)]
+            lib.prt_sample_surface_backward_device.argtypes = lib.prt_sample_surface_backward.argtypes
         _hip = lib
     return _hip
 

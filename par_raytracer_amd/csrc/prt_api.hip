@@ -35,6 +35,8 @@
 #include "kernels_closest.h"
 #include "kernels_closest_grad.h"
 #include "kernels_signed.h"
+#include "kernels_sample.h"
+#include "kernels_sample_grad.h"
 
 using namespace prt;
 
@@ -219,6 +221,17 @@ struct prt_ctx {
     DevBuf<unsigned int> sg_adj;          // leaf slot -> three position indices, three edge ids (24 B per triangle)
     DevBuf<long long> sg_acc;             // (position_count + sg_edge_count) x 3 fixed-point accumulators (24 B each)
     uint32_t sg_edge_count = 0;
+    // surface samples (prt_sample_surface, dev_sample.h).  The input triangle -> leaf slot table is topology: the inverse of
+    // q_tri_order, built by the first sampling call after an upload (4 B per triangle).  The weights and their prefix sums are
+    // geometry: rebuilt on the device (kernels_sample.h) by the first sampling call after an upload or a prt_update_geometry
+    // (8 B per triangle of sums, 8 B per triangle of weights and 8 B per tile of scratch).  Like q_leaf_map not in
+    // prt_scene_info.device_bytes, freed by the next upload.
+    uint64_t sm_generation = 0;           // of the records sm_prefix was built from; 0 = never
+    DevBuf<unsigned int> sm_slot_of_input;
+    DevBuf<double> sm_weight;
+    DevBuf<unsigned long long> sm_prefix, sm_tile_sum, sm_words;
+    unsigned long long sm_host_words[SAMPLE_WORDS] = {};   // the table's control words as last read back
+    unsigned long long sm_read_words[SAMPLE_WORDS] = {};   // ... and where a rebuild's copy of them lands (it outlives a failed call)
 };
 
 namespace {
@@ -1992,6 +2005,161 @@ int closest_points(prt_ctx * ctx, const prt_point_batch * batch, const prt_signe
     return 0;
 }
 
+// ---- surface samples (prt_sample_surface, kernels_sample.h) ------------------------------------------------------------------------
+
+unsigned int sample_fields(const prt_sample_buffers * o) {
+    return (o->point ? SF_POINT : 0) | (o->bw ? SF_BW : 0) | (o->normal ? SF_NORMAL : 0) | (o->vertex0 ? SF_VERTEX0 : 0) | (o->group ? SF_GROUP : 0);
+}
+
+// The tables of prt_sample_surface into T: the input -> slot table once per upload, the prefix sums once per geometry generation
+// (four launches on the context's stream, between ev[2] and ev[3]; their control words travel to sm_read_words behind them, valid
+// after the caller's synchronisation).  *rebuilt says whether they ran.
+int ensure_sample_table(prt_ctx * ctx, SampleTable & T, bool * rebuilt) {
+    const uint32_t n_tris = ctx->scene.tri_count;
+    *rebuilt = false;
+    if (ctx->q_tri_order.size() != n_tris) { ctx->error = "prt_sample_surface: the scene's leaf order is not available"; return -2; }
+    if (!ctx->sm_slot_of_input.p) {
+        std::vector<unsigned int> slot_of_input(n_tris);
+        for (uint32_t slot = 0; slot < n_tris; ++slot) {
+            if (ctx->q_tri_order[slot] >= n_tris) { ctx->error = "prt_sample_surface: the scene's leaf order is not a permutation"; return -2; }
+            slot_of_input[ctx->q_tri_order[slot]] = slot;
+        }
+        hipError_t e = ctx->sm_slot_of_input.upload(slot_of_input);
+        if (e == hipSuccess) e = hipDeviceSynchronize();          // the upload went through the null stream
+        if (e != hipSuccess) {
+            ctx->sm_slot_of_input.release();
+            ctx->error = std::string("prt_sample_surface: table upload: ") + hipGetErrorString(e);
+            return -10;
+        }
+        ctx->sm_generation = 0;
+    }
+    const unsigned int n_tiles = (n_tris + (unsigned int)SAMPLE_TILE - 1u) / (unsigned int)SAMPLE_TILE;
+    HIP_TRY(ctx, ctx->sm_weight.ensure(n_tris));
+    HIP_TRY(ctx, ctx->sm_prefix.ensure(n_tris));
+    HIP_TRY(ctx, ctx->sm_tile_sum.ensure(n_tiles));
+    HIP_TRY(ctx, ctx->sm_words.ensure(SAMPLE_WORDS));
+    T.tris = ctx->tris.p;
+    T.slot_of_input = ctx->sm_slot_of_input.p;
+    T.weight = ctx->sm_weight.p;
+    T.C = ctx->sm_prefix.p;
+    T.tile_sum = ctx->sm_tile_sum.p;
+    T.words = ctx->sm_words.p;
+    T.n_tris = n_tris;
+    T.n_tiles = n_tiles;
+    if (ctx->sm_generation == ctx->geom_generation) return 0;
+    hipStream_t stream = ctx->stream;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev[2], stream));
+    HIP_TRY(ctx, hipMemsetAsync(T.words, 0, SAMPLE_WORDS * sizeof(unsigned long long), stream));
+    if (n_tris) {
+        const unsigned int cap = (unsigned int)std::max(1, ctx->cu_count) * 8u;
+        const unsigned int lanes_grid = std::max(1u, std::min(n_tiles, cap));
+        hipLaunchKernelGGL(k_sample_weights, dim3(lanes_grid), dim3(256), 0, stream, T);
+        HIP_TRY(ctx, hipGetLastError());
+        hipLaunchKernelGGL(k_sample_tiles, dim3(lanes_grid), dim3(SAMPLE_TILE), 0, stream, T);
+        HIP_TRY(ctx, hipGetLastError());
+        hipLaunchKernelGGL(k_sample_totals, dim3(1), dim3(SAMPLE_TILE), 0, stream, T);
+        HIP_TRY(ctx, hipGetLastError());
+        hipLaunchKernelGGL(k_sample_offsets, dim3(lanes_grid), dim3(256), 0, stream, T);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev[3], stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->sm_read_words, T.words, SAMPLE_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    *rebuilt = true;
+    return 0;
+}
+
+// prt_sample_surface and prt_sample_surface_device: `device` says where the buffers live.
+int sample_surface(prt_ctx * ctx, const prt_sample_request * rq, const prt_sample_buffers * out, prt_sample_info * info, bool device) {
+    if (!ctx) return -1;
+    if (info) memset(info, 0, sizeof(*info));
+    if (!rq || !out) { ctx->error = "prt_sample_surface: null request or buffers"; return -1; }
+    if (rq->first > (1ull << 48) || (unsigned long long)rq->count > (1ull << 48) - rq->first) {
+        ctx->error = "prt_sample_surface: first + count exceeds 2^48 (the sample index is the key's packed word)";
+        return -1;
+    }
+    if (!ctx->has_scene) { ctx->error = "prt_sample_surface: no scene uploaded"; return -2; }
+    if (rq->count == 0) return 0;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (const int rc = ensure_leaf_map(ctx, "prt_sample_surface")) return rc;
+    hipStream_t stream = ctx->stream;
+    const size_t n = rq->count;
+    const unsigned int fields = sample_fields(out);
+    SampleArgs A;
+    memset(&A, 0, sizeof(A));
+    A.seed = rq->seed; A.first = rq->first; A.count = rq->count;
+    A.point = out->point; A.bw = out->bw; A.normal = out->normal; A.vertex0 = out->vertex0; A.group = out->group;
+    StageList io;
+    if (!device) {
+        io.out(&A.point, 12 * n, fields & SF_POINT); io.out(&A.bw, 12 * n, fields & SF_BW); io.out(&A.normal, 12 * n, fields & SF_NORMAL);
+        io.out(&A.vertex0, 4 * n, fields & SF_VERTEX0); io.out(&A.group, 4 * n, fields & SF_GROUP);
+        HIP_TRY(ctx, io.carve(ctx->q_io));
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev[0], stream));
+    SampleTable T;
+    memset(&T, 0, sizeof(T));
+    bool rebuilt = false;
+    if (const int rc = ensure_sample_table(ctx, T, &rebuilt)) return rc;
+    hipLaunchKernelGGL(k_sample, dim3(grad_grid(ctx, rq->count)), dim3(256), 0, stream, T, A, ctx->q_leaf_map.p, fields);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->ev[1], stream));
+    if (!device) HIP_TRY(ctx, io.download(stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    if (rebuilt) {
+        memcpy(ctx->sm_host_words, ctx->sm_read_words, sizeof(ctx->sm_host_words));
+        ctx->sm_generation = ctx->geom_generation;
+    }
+    if (info) {
+        float ms = 0.0f, tms = 0.0f;
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+        if (rebuilt) HIP_TRY(ctx, hipEventElapsedTime(&tms, ctx->ev[2], ctx->ev[3]));
+        info->device_ms = ms;
+        info->table_ms = tms;
+        info->total_weight = ctx->sm_host_words[SAMPLE_W_TOTAL];
+        info->unit_exponent = sample_unit_exponent(ctx->sm_host_words[SAMPLE_W_MAX], ctx->scene.tri_count);
+        info->live_triangles = (uint32_t)ctx->sm_host_words[SAMPLE_W_LIVE];
+        info->area = 0.5 * (double)info->total_weight * qgrad_pow2(info->unit_exponent);
+    }
+    return 0;
+}
+
+// What prt_sample_surface_backward supplies to grad_backward (RayGrad, PointGrad).
+struct SampleGrad {
+    typedef SGradArgs Args;
+    struct Batch { uint32_t count; };
+    Batch batch;
+    const Batch * b;
+    const int32_t * group;
+    const uint32_t * vertex0;
+    const float * bw;
+    const float * positions;
+    const prt_sample_grads * gout;
+    float * gin_positions;
+    static const char * required() { return "null group, vertex0, bw or positions"; }
+    static const char * items() { return "samples"; }
+    bool complete() const { return group && vertex0 && bw && positions; }
+    float * want_positions() const { return gin_positions; }
+    void fill(SGradArgs & A) const {
+        A.group = group; A.vertex0 = vertex0; A.bw = bw; A.positions = positions;
+        if (gout) { A.g_point = gout->point; A.g_normal = gout->normal; }
+    }
+    float ** g_positions(SGradArgs &, float ** own) const { return own; }      // SGradArgs has none: k_qgrad_resolve gets it
+    void stage(StageList & l, SGradArgs & A, float ** g_pos, size_t n, size_t np) const {
+        l.in(&A.group, 4 * n); l.in(&A.vertex0, 4 * n); l.in(&A.bw, 12 * n); l.in(&A.positions, 4 * np);
+        l.in(&A.g_point, 12 * n); l.in(&A.g_normal, 12 * n);
+        l.out(g_pos, 4 * np, *g_pos != nullptr);
+    }
+    static bool scatter_writes(const SGradArgs &) { return false; }            // no per-sample gradient: the draws have no inputs
+    static void (*scan())(SGradArgs) { return k_sgrad_scan; }
+    static void (*scatter(bool merge))(SGradArgs) { return merge ? k_sgrad_scatter<true> : k_sgrad_scatter<false>; }
+};
+
+int sample_surface_backward(prt_ctx * ctx, uint32_t count, const int32_t * group, const uint32_t * vertex0, const float * bw, const float * positions,
+                            uint32_t position_count, const prt_sample_grads * gout, float * gin_positions, prt_grad_info * info, bool device) {
+    SampleGrad q = { { count }, nullptr, group, vertex0, bw, positions, gout, gin_positions };
+    q.b = &q.batch;
+    return grad_backward(ctx, "prt_sample_surface_backward", q, position_count, info, device);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2102,6 +2270,7 @@ void prt_destroy(prt_ctx * ctx) {
     ctx->q_leaf_map.release(); ctx->q_slot_of_rank.release(); ctx->q_work.release(); ctx->q_slow.release(); ctx->q_exact_stack.release(); ctx->q_io.release(); ctx->q_occ.release();
     ctx->rf_table.release(); ctx->rf_boxes.release(); ctx->rf_bounds.release(); ctx->rf_in.release();
     ctx->qg_idx.release(); ctx->qg_runs.release(); ctx->qg_acc.release(); ctx->qg_words.release(); ctx->qg_io.release();
+    ctx->sm_slot_of_input.release(); ctx->sm_weight.release(); ctx->sm_prefix.release(); ctx->sm_tile_sum.release(); ctx->sm_words.release();
     for (int c = 0; c < PRT_MAX_CHAINS; ++c) {
         prt_ctx::ChainWs & w = ctx->chain[c];
         w.f4.release(); w.rng.release(); w.counts.release(); w.overflow.release(); w.slow_stack.release();
@@ -2165,6 +2334,8 @@ int prt_upload_scene(prt_ctx * ctx, const prt_scene_desc * s) {
     ctx->qg_idx.release(); ctx->qg_runs.release(); ctx->qg_acc.release();
     ctx->sg_adj.release(); ctx->sg_acc.release();
     ctx->sg_edge_count = 0;
+    ctx->sm_slot_of_input.release(); ctx->sm_weight.release(); ctx->sm_prefix.release(); ctx->sm_tile_sum.release();
+    ctx->sm_generation = 0;
     ctx->rf_idx_positions.clear();
     ctx->rf_idx_normals.clear();
     ctx->rf_level_first.clear();
@@ -2583,6 +2754,34 @@ int prt_closest_points_backward_device(prt_ctx * ctx, const prt_point_batch * ba
     PRT_API_TRY
     return grad_backward(ctx, "prt_closest_points_backward", PointGrad{ batch, group, vertex0, positions, gout, gin }, position_count, info, true);
     PRT_API_CATCH_RC(ctx, "prt_closest_points_backward_device")
+}
+
+int prt_sample_surface(prt_ctx * ctx, const prt_sample_request * request, const prt_sample_buffers * out, prt_sample_info * info) {
+    PRT_API_TRY
+    return sample_surface(ctx, request, out, info, false);
+    PRT_API_CATCH_RC(ctx, "prt_sample_surface")
+}
+
+int prt_sample_surface_device(prt_ctx * ctx, const prt_sample_request * request, const prt_sample_buffers * out, prt_sample_info * info) {
+    PRT_API_TRY
+    return sample_surface(ctx, request, out, info, true);
+    PRT_API_CATCH_RC(ctx, "prt_sample_surface_device")
+}
+
+int prt_sample_surface_backward(prt_ctx * ctx, uint32_t count, const int32_t * group, const uint32_t * vertex0, const float * bw,
+                                const float * positions, uint32_t position_count, const prt_sample_grads * gout, float * gin_positions,
+                                prt_grad_info * info) {
+    PRT_API_TRY
+    return sample_surface_backward(ctx, count, group, vertex0, bw, positions, position_count, gout, gin_positions, info, false);
+    PRT_API_CATCH_RC(ctx, "prt_sample_surface_backward")
+}
+
+int prt_sample_surface_backward_device(prt_ctx * ctx, uint32_t count, const int32_t * group, const uint32_t * vertex0, const float * bw,
+                                       const float * positions, uint32_t position_count, const prt_sample_grads * gout, float * gin_positions,
+                                       prt_grad_info * info) {
+    PRT_API_TRY
+    return sample_surface_backward(ctx, count, group, vertex0, bw, positions, position_count, gout, gin_positions, info, true);
+    PRT_API_CATCH_RC(ctx, "prt_sample_surface_backward_device")
 }
 
 // The geometric check of bvh_check.cpp on the tree as it lies on the device NOW (after any number of updates), against the
