@@ -630,6 +630,68 @@ int prt_sample_surface_backward_device(prt_ctx * ctx, uint32_t count, const int3
                                        const float * positions, uint32_t position_count, const prt_sample_grads * gout, float * gin_positions,
                                        prt_grad_info * info);
 
+/* ---- hemisphere visibility: which fraction of a cosine lobe around a point is unoccluded ---------------------------------------
+ * Ambient occlusion, sky-view factor, an unshadowed-irradiance weight.  For `count` points with their normals - the (point, normal)
+ * pairs prt_sample_surface and PRT_QUERY_CLOSEST emit, or any others: the query refers to no triangle - the call casts `samples`
+ * rays per point and counts those that PRT_QUERY_OCCLUDED answers 0.  The rays exist on the device only, in registers: 24 bytes
+ * per POINT go in, 4 to 20 bytes per point come out.
+ * THE DEFINITION (csrc/dev_hemi.h).  Point i of a call has the global index j = first + i (j < 2^32);
+ * sample s runs over 0 .. samples - 1, 1 <= samples <= 65535.  For each (j, s):
+ *     rng_seed(prt_sample_key(seed, (uint32)j, s));  k = rng_next<false>() % 1024      (prt_key.h, the reference's generator)
+ *     ts  = diffuse_dirs[k]      the reference's 1024-direction cosine lobe (the Hammersley set of GetDiffuseReflectionRay,
+ *                                csrc/hammersley.h), the table prt_upload_scene builds
+ *     dir = tangent_to_world(normal_i, ts.xyz)      (raytracer.cpp:306-312; the normal is used AS GIVEN)
+ *     ray = (origin point_i, direction dir, ray_bias, tmax = max_dist[i])
+ *   The normal       must be unit length, as the reference assumes.  This is not checked: a non-unit normal skews the lobe, and the
+ *                    call is still the composition below.
+ *   max_dist         NULL = no limit.
+ *   unoccluded[i]    the number of s for which PRT_QUERY_OCCLUDED answers 0 for that ray: the rule above under "batched ray
+ *                    queries" - tested against FLT_MAX, t < tmax, front-facing triangles only - word for word, including a
+ *                    max_dist that is 0, negative or NaN (nothing occludes), +inf, and rays that are a miss by definition (they
+ *                    count as unoccluded).  Single-sided: a point inside an outward-wound closed mesh sees back faces only and
+ *                    is unoccluded.
+ *   visibility[i]    (float)unoccluded[i] / (float)samples, one IEEE float32 division.
+ *   bent[i] (x3)     the mean unoccluded direction: per component c, B_c = the sum over the unoccluded samples of
+ *                    (int64)rint((double)dir_c x 2^32) (0 for a component that is not finite, which only a ray that is a miss by
+ *                    definition has); bent_c = (float)(((double)B_c x 2^-32) / (double)samples).  The sums are integers.
+ *   Invalid point    a component of point_i or normal_i is not finite, or the normal is all zeros: no ray is cast,
+ *                    unoccluded = 0xFFFFFFFF, visibility and bent are zeros.  It is not an error and does not touch the other
+ *                    points.
+ *   0 triangles      every valid point has unoccluded = samples.
+ * The whole answer is a pure function of (the scene as it lies on the device, point, normal, seed, j, samples, ray_bias, max_dist):
+ * the same bits for every tree (SAH, LBVH, 8-wide, refitted), schedule, run and split of a batch into calls (`first` makes a batch
+ * splittable, as in prt_sample_surface), and the count equals what prt_trace_rays(PRT_QUERY_OCCLUDED) says ray by ray.  No gradient
+ * belongs to it: visibility is piecewise constant in everything.
+ * PASSES.  The call works in passes of whole points with at most HEMI_PASS_ITEMS (an option; default 2^24, at least one point)
+ * rays each; its scratch is 5 bytes per ray of a pass (the slow list and one flag byte), whatever count x samples is.
+ * Counters: prt_trace_rays'; ray_count = rays cast (valid points x samples), node_visits / tri_tests with PRT_FLAG_COUNT_VISITS,
+ * render_ms, trace_kernel_ms, pipeline = 0.  The render stats are left alone.
+ * Errors: -1 NULL batch or buffers, NULL points or normals with count > 0, samples outside 1..65535, first + count > 2^32; -2 no
+ * scene; -10 a HIP call failed.  count == 0 writes nothing (counters, if given, are zeroed) and returns 0.  Stream contract of
+ * prt_trace_rays_device. */
+typedef struct prt_hemi_batch {
+    const float * points;          /* count x 3 */
+    const float * normals;         /* count x 3, unit length */
+    const float * max_dist;        /* count, or NULL = no limit */
+    uint32_t count;
+    uint32_t samples;              /* 1..65535 rays per point */
+    uint64_t seed;
+    uint64_t first;                /* the global index of point 0; first + count <= 2^32 */
+    float ray_bias;
+} prt_hemi_batch;
+/* Every pointer may be NULL: that field is not written. */
+typedef struct prt_hemi_buffers {
+    uint32_t * unoccluded;         /* 0 .. samples; 0xFFFFFFFF for an invalid point */
+    float * visibility;
+    float * bent;                  /* x3 */
+} prt_hemi_buffers;
+/* Host pointers (batch and buffers); counters may be NULL. */
+int prt_hemisphere_visibility(prt_ctx * ctx, const prt_hemi_batch * batch, const prt_hemi_buffers * out, uint32_t flags,
+                              prt_counters * counters);
+/* Device pointers on the context's device (hipMalloc'ed or torch tensors' data_ptr). */
+int prt_hemisphere_visibility_device(prt_ctx * ctx, const prt_hemi_batch * batch, const prt_hemi_buffers * out, uint32_t flags,
+                                     prt_counters * counters);
+
 /* ---- several devices behind one handle --------------------------------------------------------------------------------
  * SURVEY.md 8(b)'s prt_create(const int * device_ids, int n_dev): what the host mirror's Render() uses for n GPUs, in place
  * of the reference's one-rank-per-core partition + MPI_Gather (main.cpp:311-347).  The scene is replicated (as every MPI rank

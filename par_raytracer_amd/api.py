@@ -589,6 +589,46 @@ class Renderer:
         res["info"] = info
         return res
 
+    # (name, components per point, numpy dtype) of prt_hemi_buffers' fields
+    HEMI_FIELDS = (("unoccluded", 1, np.uint32), ("visibility", 1, np.float32), ("bent", 3, np.float32))
+
+    def hemisphere_visibility(self, points, normals, *, samples: int = 64, seed: int = 0, first: int = 0, max_dist=None,
+                              ray_bias: float = 0.0, fields: Optional[Sequence[str]] = None, count_visits: bool = False) -> dict:
+        """Which part of a cosine lobe around n points' normals is unoccluded (prt_hemisphere_visibility, include/prt.h).
+
+        points, normals: float32 (n, 3), contiguous, the normals unit length - numpy arrays (host entry point, numpy results) or
+        torch tensors on this context's device (device entry point, tensors on that device).  samples rays are cast per point,
+        drawn from the reference's 1024-direction lobe by (seed, first + i, s); max_dist: None, or float32 (n,), the rays' reach.
+        fields: any of unoccluded (uint32, int32 in torch: the rays nothing occludes, 0xFFFFFFFF for an invalid point), visibility
+        (unoccluded / samples) and bent (n, 3: the mean unoccluded direction); default all.  Returns {field: array} plus "counters"
+        (PrtCounters)."""
+        spec = {name: (k, dt) for name, k, dt in self.HEMI_FIELDS}
+        if fields is None:
+            fields = tuple(spec)
+        for f in fields:
+            if f not in spec:
+                raise ValueError("unknown hemisphere-visibility field %r" % (f,))
+        check, empty, ptr, sync, suffix = self._arrays(points)
+        points = check(points, "points", (None, 3))
+        n = int(points.shape[0])
+        normals = check(normals, "normals", (n, 3))
+        if max_dist is not None:
+            max_dist = check(max_dist, "max_dist", (n,))
+        out = {f: empty((n, spec[f][0]) if spec[f][0] > 1 else (n,), spec[f][1]) for f in fields}
+        sync()
+        if not 0 <= int(samples) < 1 << 32 or not 0 <= int(first) < 1 << 64 or int(seed) < 0:
+            raise ValueError("samples must be in 0 .. 2^32 - 1, first in 0 .. 2^64 - 1 and seed non-negative")
+        # what the C types hold goes to the library as given: its refusals (samples, first + count) are the check
+        batch = capi.PrtHemiBatch(ptr(points), ptr(normals), ptr(max_dist), n, int(samples), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first),
+                                  float(ray_bias))
+        hb = capi.PrtHemiBuffers(*[ptr(out[name]) if name in out else None for name, _, _ in self.HEMI_FIELDS])
+        counters = PrtCounters()
+        flags = capi.FLAG_COUNT_VISITS if count_visits else 0
+        name = "prt_hemisphere_visibility" + suffix
+        self._check(getattr(self._lib, name)(self._ctx, C.byref(batch), C.byref(hb), flags, C.byref(counters)), name)
+        out["counters"] = counters
+        return out
+
     def sample_surface_backward(self, group, vertex0, bw, positions, *, grad_point=None, grad_normal=None) -> dict:
         """Gradients of surface samples (prt_sample_surface_backward, include/prt.h): from dL/dpoint and dL/dnormal of n samples
         (None = zero) to dL/dpositions, summed over the samples - the same bits for every order of the samples.

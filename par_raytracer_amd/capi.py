@@ -174,6 +174,15 @@ class PrtSampleGrads(C.Structure):
     _fields_ = [("point", C.c_void_p), ("normal", C.c_void_p)]
 
 
+class PrtHemiBatch(C.Structure):
+    _fields_ = [("points", C.c_void_p), ("normals", C.c_void_p), ("max_dist", C.c_void_p), ("count", C.c_uint32), ("samples", C.c_uint32),
+                ("seed", C.c_uint64), ("first", C.c_uint64), ("ray_bias", C.c_float)]
+
+
+class PrtHemiBuffers(C.Structure):
+    _fields_ = [("unoccluded", C.c_void_p), ("visibility", C.c_void_p), ("bent", C.c_void_p)]
+
+
 QUERY_CLOSEST, QUERY_OCCLUDED = 0, 1
 PIPELINE_DEFAULT, PIPELINE_MEGAKERNEL, PIPELINE_WAVEFRONT, PIPELINE_PERSISTENT, PIPELINE_POOL = 0, 1, 2, 3, 4
 FLAG_COUNT_VISITS = 0x100
@@ -192,7 +201,8 @@ PRT_SYMBOLS = ["prt_create", "prt_destroy", "prt_last_error", "prt_abi_version",
                "prt_closest_points_backward", "prt_closest_points_backward_device",
                "prt_signed_distance", "prt_signed_distance_device",
                "prt_sample_surface", "prt_sample_surface_device",
-               "prt_sample_surface_backward", "prt_sample_surface_backward_device"]
+               "prt_sample_surface_backward", "prt_sample_surface_backward_device",
+               "prt_hemisphere_visibility", "prt_hemisphere_visibility_device"]
 # PRT_REGION_* of include/prt.h, in index order (tests/test_host_side.py's header check keeps the symbol list in step; the
 # region test compares this list with the header's enum)
 REGION_NAMES = ["round", "topup", "topup_pass", "trace_outer", "refill", "walk_pass", "node_step", "node_descend", "node_pop", "node_push", "leaf",
@@ -303,6 +313,10 @@ def hip_lib() -> C.CDLL:
             lib.prt_sample_surface_backward.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                                         C.POINTER(PrtSampleGrads), C.c_void_p, C.POINTER(PrtGradInfo)]
             lib.prt_sample_surface_backward_device.argtypes = lib.prt_sample_surface_backward.argtypes
+        if hasattr(lib, "prt_hemisphere_visibility"):  # (absent from a PRT_HIP_LIB build of an earlier commit)
+            lib.prt_hemisphere_visibility.argtypes = [C.c_void_p, C.POINTER(PrtHemiBatch), C.POINTER(PrtHemiBuffers), C.c_uint32,
+                                                      C.POINTER(PrtCounters)]
+            lib.prt_hemisphere_visibility_device.argtypes = lib.prt_hemisphere_visibility.argtypes
         _hip = lib
     return _hip
 

@@ -171,51 +171,6 @@ __global__ __launch_bounds__(BLOCK, 6) void k_query(DevScene sc, QueryArgs A, co
     if (COUNT) trace_stats_flush<true>(ctr, st);
 }
 
-// Any hit below tmax on a stack that cannot overflow (trace_ray's walk with the best hit started at tmax).
-template <class STK, bool COUNT>
-PRT_D HitRec query_any_below(const DevScene & sc, f3 o, f3 d, float tmax, float pad, const STK & stk, TraceStats & st) {
-    TravRay r;
-    trav_start<true>(r, o, d, TRACE_ANY, pad, stk);
-    r.best.t = tmax;
-    for (;;) {
-        while (trav_walking(r)) trav_node_step<STK, COUNT>(sc, r, stk, st, pad);
-        if (trav_done(r)) break;
-        if (trav_leaf<STK, COUNT>(sc, r, stk, st)) break;                   // found its occluder
-    }
-    return r.best;
-}
-
-// OCCLUDED for an origin far from the scene (query_far): there the triangle test's t carries a rounding error (ap = o - a is
-// large and cancels in Dot(ap, n)) that can exceed the box pad, so a box culled against tmax could hold a triangle whose
-// computed t is below tmax.  This walk culls boxes by geometry only and applies the rule itself to every triangle the ray's
-// line meets: IntersectRayTriangle against FLT_MAX and t < tmax.
-template <class STK, bool COUNT>
-PRT_D HitRec query_any_unculled(const DevScene & sc, f3 o, f3 d, float tmax, float pad, const STK & stk, TraceStats & st) {
-    TravRay r;
-    trav_start<true>(r, o, d, TRACE_ANY, pad, stk);
-    r.best.t = __uint_as_float(0x7F800000u);
-    const f3 qp = o - (o + d);                                              // raytracer.cpp:88-89
-    HitRec h = hit_miss();
-    for (;;) {
-        while (trav_walking(r)) trav_node_step<STK, COUNT>(sc, r, stk, st, pad);
-        if (trav_done(r)) break;
-        unsigned int first, count;
-        trav_leaf_range(r, first, count);
-        for (unsigned int i = 0; i < count; ++i) {
-            const float4 * tp = sc.tris + 3 * (size_t)(first + i);
-            const float4 r0 = tp[0], r1 = tp[1], r2 = tp[2];
-            float t, dd, v, w;
-            if (COUNT) st.tris++;
-            if (!tri_geom(o, qp, mk3(r0.x, r0.y, r0.z), mk3(r0.w, r1.x, r1.y), mk3(r1.z, r1.w, r2.x), mk3(r2.y, r2.z, r2.w), t, dd, v, w)) continue;
-            if (t > 3.402823466e+38f * dd) continue;                        // raytracer.cpp:104 against FLT_MAX
-            const float th = t * (1.0f / dd);
-            if (th < tmax) { h.t = th; h.tri = (int)(first + i); return h; }
-        }
-        trav_leaf_next(r, stk);
-    }
-    return h;
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // Slow path of k_query (exact_list_walk).
 template <int MODE, bool COUNT>

@@ -37,6 +37,8 @@
 #include "kernels_signed.h"
 #include "kernels_sample.h"
 #include "kernels_sample_grad.h"
+#include "kernels_hemi.h"
+#include "hammersley.h"
 
 using namespace prt;
 
@@ -192,6 +194,7 @@ struct prt_ctx {
     DevBuf<int> q_exact_stack;
     DevBuf<float> q_io;                   // host entry point: the batch and the requested fields on the device
     DevBuf<unsigned char> q_occ;
+    DevBuf<unsigned char> q_hemi_flags;   // prt_hemisphere_visibility: one byte per item of a pass
     // geometry updates (prt_update_geometry, kernels_refit.h).  The upload keeps, on the host, the index buffers and the first
     // node of every tree level; the first update builds the leaf slot -> vertex indices table from them (24 B per triangle; like
     // q_leaf_map not in prt_scene_info.device_bytes, freed by the next upload).  The table and the scratch boxes are reused by
@@ -243,31 +246,6 @@ f3 ld3(const float * p) { return mk3(p[0], p[1], p[2]); }
 // Every stack area - the LDS columns, their spill columns, the exact kernels' full-height global columns - is sized here.
 size_t stack_dwords(size_t entries, size_t lanes) { return entries * lanes * (size_t)STACK_ENTRY_INTS; }
 
-
-// raytracer.cpp:273-288 on the host.
-float radical_inverse_vdc(uint32_t bits) {
-    bits = (bits << 16u) | (bits >> 16u);
-    bits = ((bits & 0x55555555u) << 1u) | ((bits & 0xAAAAAAAAu) >> 1u);
-    bits = ((bits & 0x33333333u) << 2u) | ((bits & 0xCCCCCCCCu) >> 2u);
-    bits = ((bits & 0x0F0F0F0Fu) << 4u) | ((bits & 0xF0F0F0F0u) >> 4u);
-    bits = ((bits & 0x00FF00FFu) << 8u) | ((bits & 0xFF00FF00u) >> 8u);
-    return (float)(bits * 2.3283064365386963e-10);
-}
-
-const float kPi32 = 3.1415927f;
-
-// Tangent-space direction of GetDiffuseReflectionRay for Xi = Hammersley(i, 1024) (raytracer.cpp:322-328).
-// Host libm: the same cosf / sinf the reference's CPU path calls.
-float4 diffuse_tangent_dir(uint32_t i) {
-    float xi_x = (float)i / (float)1024u;
-    float xi_y = radical_inverse_vdc(i);
-    float phi = xi_y * 2.0f * kPi32;
-    float cp = cosf(phi);
-    float sp = sinf(phi);
-    float ct = sqrtf(1.0f - xi_x);
-    float st = sqrtf(1.0f - ct * ct);
-    return make_float4(cp * st, sp * st, ct, 0.0f);
-}
 
 // ImportanceSamplePhong(Hammersley(samp, count), e) (raytracer.cpp:290-300).
 float4 phong_tangent_dir(uint32_t samp, uint32_t count, float e) {
@@ -1364,6 +1342,12 @@ struct PointWalk {
     int verdict(prt_ctx *, const DevCounters &) const { return 0; }
 };
 
+// The items a batch's walk hands out - the slow list holds as many at the most: the batch's rays or points, unless the query
+// makes several items of each (prt_hemisphere_visibility: a pass's points x samples).
+template <typename Args>
+size_t batch_items(const Args & A) { return A.count; }
+size_t batch_items(const HemiArgs & A) { return (size_t)A.count * A.samples; }
+
 // One batch on the device: A's inputs and outputs are device pointers; pad_max < 0 asks the pad kernel for the inputs' extent.
 // Synchronous (returns after the context's stream has drained).  The work words, the slow list and the exact stacks are shared by
 // all queries (a context runs one call at a time).
@@ -1380,7 +1364,7 @@ int run_batch(prt_ctx * ctx, const Walk & q, typename Walk::Args A, unsigned int
     A.exact_stack = ctx->q_exact_stack.p;
     A.exact_stack_stride = (unsigned int)exact_lanes;
     HIP_TRY(ctx, ctx->q_work.ensure(BATCH_WORDS));
-    HIP_TRY(ctx, ctx->q_slow.ensure(A.count));
+    HIP_TRY(ctx, ctx->q_slow.ensure(batch_items(A)));
     HIP_TRY(ctx, ctx->counters.ensure(1));
     A.work = ctx->q_work.p;
     A.slow = ctx->q_slow.p;
@@ -2005,6 +1989,132 @@ int closest_points(prt_ctx * ctx, const prt_point_batch * batch, const prt_signe
     return 0;
 }
 
+// ---- hemisphere visibility (prt_hemisphere_visibility, kernels_hemi.h) ----------------------------------------------------------
+
+unsigned int hemi_fields(const prt_hemi_buffers * o) {
+    return (o->unoccluded ? HF_UNOCCLUDED : 0) | (o->visibility ? HF_VISIBILITY : 0) | (o->bent ? HF_BENT : 0);
+}
+
+// What prt_hemisphere_visibility supplies to run_batch, one pass of whole points at a time.
+struct HemiWalk {
+    typedef HemiArgs Args;
+    static const char * name() { return "prt_hemisphere_visibility"; }
+    int prepare(prt_ctx * ctx, HemiArgs & A) const {
+        A.replay_beyond = 64.0f * ctx->scene_abs_max;
+        A.scene_max = ctx->scene_abs_max;
+        HIP_TRY(ctx, ctx->q_hemi_flags.ensure(batch_items(A)));
+        A.flags = ctx->q_hemi_flags.p;
+        return 0;
+    }
+    int tables(prt_ctx *, HemiArgs &, unsigned int) const { return 0; }
+    static void (*pad_kernel())(HemiArgs) { return k_hemi_pad; }
+    // The walk on its persistent grid, the exact kernel for the items it set aside, then the reduction of the pass's flags.
+    template <typename Fast, typename Exact>
+    static int walk(prt_ctx * ctx, Fast fast, Exact exact, const HemiArgs & A, unsigned int fields) {
+        constexpr int BLOCK = 256;
+        const size_t lds = stack_dwords(A.stack_lds_entries, BLOCK) * sizeof(int);
+        const TraceRule rule = trace_rule(ctx, fast, lds);
+        const TraceGrid g = trace_grid(ctx, rule.per_cu, rule.chunk_min, (unsigned int)batch_items(A));
+        hipLaunchKernelGGL(fast, dim3(g.grid), dim3(BLOCK), lds, ctx->stream, ctx->scene, A, rule.keep_min, rule.node_min, g.chunk, ctx->counters.p);
+        HIP_TRY(ctx, hipGetLastError());
+        hipLaunchKernelGGL(exact, dim3(64), dim3(256), 0, ctx->stream, ctx->scene, A, ctx->counters.p);      // A.exact_stack holds 64 * 256 columns
+        HIP_TRY(ctx, hipGetLastError());
+        const bool wave = A.samples >= (unsigned int)HEMI_WAVE_SAMPLES, bent = (fields & HF_BENT) != 0;
+        const unsigned int cap = (unsigned int)std::max(1, ctx->cu_count) * 8u;
+        const unsigned int want = wave ? (A.count + 3u) / 4u : (A.count + 255u) / 256u;
+        const unsigned int grid = std::max(1u, std::min(want, cap));
+        void (*reduce)(DevScene, HemiArgs, unsigned int, DevCounters *) =
+            wave ? (bent ? k_hemi_reduce<true, true> : k_hemi_reduce<true, false>) : (bent ? k_hemi_reduce<false, true> : k_hemi_reduce<false, false>);
+        hipLaunchKernelGGL(reduce, dim3(grid), dim3(256), 0, ctx->stream, ctx->scene, A, fields, ctx->counters.p);
+        HIP_TRY(ctx, hipGetLastError());
+        return 0;
+    }
+    int launch(prt_ctx * ctx, const HemiArgs & A, unsigned int fields, bool count) const {
+        return count ? walk(ctx, k_hemi<256, true>, k_hemi_exact<true>, A, fields) : walk(ctx, k_hemi<256, false>, k_hemi_exact<false>, A, fields);
+    }
+    int verdict(prt_ctx *, const DevCounters &) const { return 0; }
+};
+
+// The checks both entry points share; 1 = nothing to do (count 0: counters zeroed), 0 = go on, < 0 = error.
+int hemi_check(prt_ctx * ctx, const prt_hemi_batch * b, const prt_hemi_buffers * o, prt_counters * counters) {
+    if (!ctx) return -1;
+    if (!b || !o) { ctx->error = "prt_hemisphere_visibility: null batch or buffers"; return -1; }
+    if (b->count && (!b->points || !b->normals)) { ctx->error = "prt_hemisphere_visibility: null points or normals"; return -1; }
+    if (b->samples < 1 || b->samples > 65535) {
+        ctx->error = "prt_hemisphere_visibility: samples must be in 1..65535 (prt_key.h packs the sample in 16 bits)";
+        return -1;
+    }
+    if (b->first > (1ull << 32) || (unsigned long long)b->count > (1ull << 32) - b->first) {
+        ctx->error = "prt_hemisphere_visibility: first + count exceeds 2^32 (the point index is the key's pixel word)";
+        return -1;
+    }
+    if (!ctx->has_scene) { ctx->error = "prt_hemisphere_visibility: no scene uploaded"; return -2; }
+    if (b->count == 0) {
+        if (counters) memset(counters, 0, sizeof(*counters));
+        return 1;
+    }
+    return 0;
+}
+
+// prt_hemisphere_visibility and prt_hemisphere_visibility_device after hemi_check: `device` says where the arrays live.  The call
+// runs in passes of whole points (option HEMI_PASS_ITEMS items each at the most): the slow list and the flags are sized for a
+// pass, whatever count x samples is.
+int hemisphere_visibility(prt_ctx * ctx, const prt_hemi_batch * b, const prt_hemi_buffers * o, uint32_t flags, prt_counters * counters, bool device) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t n = b->count;
+    const unsigned int fields = hemi_fields(o);
+    HemiArgs A;
+    memset(&A, 0, sizeof(A));
+    A.points = b->points; A.normals = b->normals; A.max_dist = b->max_dist;
+    A.samples = b->samples; A.seed = b->seed; A.ray_bias = b->ray_bias;
+    A.unoccluded = o->unoccluded; A.visibility = o->visibility; A.bent = o->bent;
+    A.pad_max = -1.0f;                                     // the points' extent is reduced on the device (k_hemi_pad)
+    hipStream_t stream = ctx->stream;
+    StageList io;
+    if (!device) {
+        io.in(&A.points, 12 * n); io.in(&A.normals, 12 * n); io.in(&A.max_dist, 4 * n);
+        io.out(&A.unoccluded, 4 * n, fields & HF_UNOCCLUDED); io.out(&A.visibility, 4 * n, fields & HF_VISIBILITY); io.out(&A.bent, 12 * n, fields & HF_BENT);
+        HIP_TRY(ctx, io.carve(ctx->q_io));
+        // batch_pad's extent from the valid points, on the host (k_hemi_pad's rule and hemi_pad's sum; work[BATCH_W_EXTENT] stays 0)
+        float extent = 0.0f;
+        for (size_t i = 0; i < n; ++i) {
+            const f3 p = ld3(b->points + 3 * i), nr = ld3(b->normals + 3 * i);
+            if (hemi_point_valid(p, nr)) extent = std::max(extent, std::max(std::max(fabsf(p.x), fabsf(p.y)), fabsf(p.z)));
+        }
+        A.pad_max = std::max(ctx->scene_abs_max, extent + fabsf(b->ray_bias));
+        if (!(A.pad_max >= 0.0f)) A.pad_max = ctx->scene_abs_max;          // a NaN bias: every ray is a miss by definition
+        HIP_TRY(ctx, io.upload(stream));
+    }
+    const long long want_items = ctx->opt.hemi_pass_items >= 0 ? ctx->opt.hemi_pass_items : (1ll << 24);
+    const size_t pass_points = hemi_pass_points((unsigned long long)want_items, b->samples);
+    prt_counters total;
+    memset(&total, 0, sizeof(total));
+    for (size_t at = 0; at < n; at += pass_points) {
+        HemiArgs P = A;
+        P.points += 3 * at; P.normals += 3 * at;
+        if (P.max_dist) P.max_dist += at;
+        if (P.unoccluded) P.unoccluded += at;
+        if (P.visibility) P.visibility += at;
+        if (P.bent) P.bent += 3 * at;
+        P.count = (unsigned int)std::min(pass_points, n - at);
+        P.first = (unsigned int)(b->first + at);
+        prt_counters c;
+        if (const int rc = run_batch(ctx, HemiWalk(), P, fields, (flags & PRT_FLAG_COUNT_VISITS) != 0, &c)) return rc;
+        total.ray_count += ctx->host_counters->ray_count;                   // k_hemi_reduce: the pass's valid points x samples
+        total.node_visits += c.node_visits;
+        total.tri_tests += c.tri_tests;
+        total.render_ms += c.render_ms;
+        total.trace_kernel_ms += c.trace_kernel_ms;
+        total.trace_kernel_launches += 3;
+    }
+    if (!device) {
+        HIP_TRY(ctx, io.download(stream));
+        HIP_TRY(ctx, hipStreamSynchronize(stream));
+    }
+    if (counters) *counters = total;
+    return 0;
+}
+
 // ---- surface samples (prt_sample_surface, kernels_sample.h) ------------------------------------------------------------------------
 
 unsigned int sample_fields(const prt_sample_buffers * o) {
@@ -2267,7 +2377,7 @@ void prt_destroy(prt_ctx * ctx) {
     ctx->sample_rgb.release(); ctx->frame_out.release(); ctx->counters.release(); ctx->ring_ws.release(); ctx->pixel_list.release(); ctx->wf_counts.release(); ctx->stack_spill.release(); ctx->pool_f4.release(); ctx->pool_park.release(); ctx->pool_fin.release(); ctx->pool_args.release(); ctx->adapt_f4.release(); ctx->wave_times.release();
     ctx->textures.release(); ctx->texels.release(); ctx->srgb_lut.release(); ctx->tri_uv.release(); ctx->tri_tan.release();
     ctx->ref_spheres.release();
-    ctx->q_leaf_map.release(); ctx->q_slot_of_rank.release(); ctx->q_work.release(); ctx->q_slow.release(); ctx->q_exact_stack.release(); ctx->q_io.release(); ctx->q_occ.release();
+    ctx->q_leaf_map.release(); ctx->q_slot_of_rank.release(); ctx->q_work.release(); ctx->q_slow.release(); ctx->q_exact_stack.release(); ctx->q_io.release(); ctx->q_occ.release(); ctx->q_hemi_flags.release();
     ctx->rf_table.release(); ctx->rf_boxes.release(); ctx->rf_bounds.release(); ctx->rf_in.release();
     ctx->qg_idx.release(); ctx->qg_runs.release(); ctx->qg_acc.release(); ctx->qg_words.release(); ctx->qg_io.release();
     ctx->sm_slot_of_input.release(); ctx->sm_weight.release(); ctx->sm_prefix.release(); ctx->sm_tile_sum.release(); ctx->sm_words.release();
@@ -2711,6 +2821,24 @@ int prt_signed_distance(prt_ctx * ctx, const prt_point_batch * batch, const prt_
     if (chk) return chk > 0 ? 0 : chk;
     return closest_points(ctx, batch, *out, signed_fields(out), flags, counters, false);
     PRT_API_CATCH_RC(ctx, "prt_signed_distance")
+}
+
+int prt_hemisphere_visibility_device(prt_ctx * ctx, const prt_hemi_batch * batch, const prt_hemi_buffers * out, uint32_t flags,
+                                     prt_counters * counters) {
+    PRT_API_TRY
+    const int chk = hemi_check(ctx, batch, out, counters);
+    if (chk) return chk > 0 ? 0 : chk;
+    return hemisphere_visibility(ctx, batch, out, flags, counters, true);
+    PRT_API_CATCH_RC(ctx, "prt_hemisphere_visibility_device")
+}
+
+int prt_hemisphere_visibility(prt_ctx * ctx, const prt_hemi_batch * batch, const prt_hemi_buffers * out, uint32_t flags,
+                              prt_counters * counters) {
+    PRT_API_TRY
+    const int chk = hemi_check(ctx, batch, out, counters);
+    if (chk) return chk > 0 ? 0 : chk;
+    return hemisphere_visibility(ctx, batch, out, flags, counters, false);
+    PRT_API_CATCH_RC(ctx, "prt_hemisphere_visibility")
 }
 
 int prt_update_geometry(prt_ctx * ctx, const prt_geometry_update * update, prt_update_info * info) {

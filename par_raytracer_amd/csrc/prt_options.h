@@ -47,6 +47,7 @@ struct PrtOptions {
     long long pool_shared_cap = -1;         // ... slots per WAVE of a shared pool before the x4 (experiments)
     long long pass_samples = -1, pass_mb = -1, stack_cap = -1, no_tiles = 0;
     long long qgrad_merge = -1;             // prt_trace_rays_backward and prt_closest_points_backward (both scatter kernels): 1 = lanes of a wave on one triangle merge their adds, 0 = every lane adds; -1 = the default (same bits)
+    long long hemi_pass_items = -1;         // prt_hemisphere_visibility: items (points x samples) of one pass at the most; whole points, at least one (default 2^24)
     long long reserve_cus = 0;              // creation only: compute units the context's streams leave free
     long long reserve_pattern = 2;          // creation only: which bits of the CU mask are cleared - 2 = every (n / k)-th (k = 8: one compute unit per XCD),
                                             // experiments: 0 = the last k, 1 = the first k, 3 = none (profiles/r03_cu_mask.txt)
@@ -71,7 +72,7 @@ inline const OptEntry * option_table(size_t * n) {
         { "POOL_PARK_CAP", &PrtOptions::pool_park_cap, nullptr }, { "POOL_SHARED", &PrtOptions::pool_shared, nullptr }, { "POOL_FORK", &PrtOptions::pool_fork, nullptr }, { "POOL_FORK_ROOM", &PrtOptions::pool_fork_room, nullptr }, { "POOL_FAIR", &PrtOptions::pool_fair, nullptr }, { "POOL_GUIDED", &PrtOptions::pool_guided, nullptr }, { "POOL_GUIDED_MIN", &PrtOptions::pool_guided_min, nullptr }, { "WORK_REVERSE", &PrtOptions::work_reverse, nullptr }, { "WORK_SCATTER", &PrtOptions::work_scatter, nullptr },
         { "POOL_SHARED_CAP", &PrtOptions::pool_shared_cap, nullptr }, { "PASS_SAMPLES", &PrtOptions::pass_samples, nullptr },
         { "PASS_MB", &PrtOptions::pass_mb, nullptr }, { "STACK_CAP", &PrtOptions::stack_cap, nullptr }, { "NO_TILES", &PrtOptions::no_tiles, nullptr },
-        { "QGRAD_MERGE", &PrtOptions::qgrad_merge, nullptr },
+        { "QGRAD_MERGE", &PrtOptions::qgrad_merge, nullptr }, { "HEMI_PASS_ITEMS", &PrtOptions::hemi_pass_items, nullptr },
         { "RESERVE_CUS", &PrtOptions::reserve_cus, nullptr }, { "RESERVE_PATTERN", &PrtOptions::reserve_pattern, nullptr }, { "LEAF_MAX", &PrtOptions::leaf_max, nullptr },
         { "SAH_BINS", nullptr, &BvhBuildOptions::sah_bins }, { "SAH_SWEEP", nullptr, &BvhBuildOptions::sah_sweep },
         { "LBVH_PLAIN", nullptr, &BvhBuildOptions::lbvh_plain }, { "LBVH_CLUSTER", nullptr, &BvhBuildOptions::lbvh_cluster },
