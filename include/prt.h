@@ -741,6 +741,32 @@ typedef struct prt_scene_info {
 } prt_scene_info;
 int prt_get_scene_info(const prt_ctx * ctx, prt_scene_info * info);
 
+/* Shadow trees.  The triangle test is single-sided and all shadow rays of a directional light share one direction, so which
+ * triangles such a ray can hit at all is fixed at upload.  prt_upload_scene builds, for each of the first
+ * PRT_MAX_SHADOW_TREES directional lights whose possible occluders are at most SHADOW_TREE_RATIO hundredths (default 75) of
+ * the scene's triangles, a second tree over just those, behind the scene's in the same device arrays; the light's any-hit
+ * shadow rays start there.  Images, ray_count and shaded_hits are the same bits either way; node_visits and tri_tests fall.
+ * Option SHADOW_TREES (default 1) is read by every render call: 0 starts every ray at the scene's root.  A render call also
+ * does so by itself when its |ray_bias| or its camera position lies outside what the upload's bound assumed (|ray_bias| <=
+ * the scene's largest |coordinate|, camera within 4 x that on every axis).
+ * STALE AFTER prt_update_geometry: the trees are of the uploaded geometry, in membership and in boxes.  After an update the
+ * context starts every shadow ray at the scene's root (`active` = 0 below) until the next prt_upload_scene.
+ * prt_get_shadow_trees writes up to `cap` entries, one per light of the scene in light order, and returns the number of
+ * lights (or -1 / -2 like prt_get_scene_info).  prt_scene_info.bvh_node_count and triangle_count never include the trees;
+ * device_bytes does. */
+enum { PRT_MAX_SHADOW_TREES = 4 };
+typedef struct prt_shadow_tree_info {
+    uint32_t built;                /* 1: the light has a tree (directional, within the ratio and the arrays' caps) */
+    uint32_t active;               /* 1: renders use it - built, and not stale; (SHADOW_TREES and the per-call guard come on top) */
+    uint32_t triangle_count;       /* possible occluders (also counted when no tree was built for a directional light) */
+    uint32_t node_count;
+    uint32_t root;                 /* node index the light's shadow rays start at; 0 when not built */
+    uint32_t stack_bound;
+    uint64_t device_bytes;         /* nodes + triangle records of this tree */
+    double build_ms;               /* classification + build */
+} prt_shadow_tree_info;
+int prt_get_shadow_trees(const prt_ctx * ctx, prt_shadow_tree_info * out, uint32_t cap);
+
 /* Diagnostics of the context's last render call made with PRT_FLAG_COUNT_VISITS (bench.py's roofline block):
  * wave-level step counts - lane utilisation of a loop = lane-level count / (64 x wave-level count) -, where the waves of the
  * pool pipeline spent their time, and how many rays took the slow path (near-tied hits, include/prt.h "Determinism"). */

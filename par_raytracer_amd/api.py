@@ -237,6 +237,15 @@ class Renderer:
         self._check(self._lib.prt_get_scene_info(self._ctx, C.byref(info)), "prt_get_scene_info")
         return info
 
+    def shadow_trees(self) -> list:
+        """One capi.PrtShadowTreeInfo per light of the uploaded scene (include/prt.h "Shadow trees")."""
+        n = self._lib.prt_get_shadow_trees(self._ctx, None, 0)
+        if n < 0:
+            self._check(n, "prt_get_shadow_trees")
+        out = (capi.PrtShadowTreeInfo * max(1, n))()
+        self._check(min(0, self._lib.prt_get_shadow_trees(self._ctx, out, n)), "prt_get_shadow_trees")
+        return [out[i] for i in range(n)]
+
     def render_stats(self) -> "capi.PrtRenderStats":
         """Diagnostics of the last render made with FLAG_COUNT_VISITS (lane utilisation, phase times, parked rays)."""
         st = capi.PrtRenderStats()

@@ -568,6 +568,106 @@ void build_bvh_wide(int width, const float * verts, uint32_t n_tris, uint32_t le
     finish_wide(b, n_tris, width, out);
 }
 
+// ---- shadow trees (bvh_build.h).  The bound, with u = 2^-24, D = max |d_k|, M = origin_max, N1 = |n_x| + |n_y| + |n_z|:
+//   the device forms qp_k = fl(o_k - fl(o_k + d_k)) = -d_k + e_k with |e_k| <= u (M + 2 D) (1 + u) =: E, and
+//   dd = fl(Dot(qp, n)) <= Sum qp_k n_k + g3 Sum |qp_k n_k| <= -d.n + N1 (E + g3 (D + E)), g3 = 3 u / (1 - 3 u) < 4 u,
+// so dd <= 0 is certain where d.n >= N1 (E + 4 u (D + E)).  d.n is taken in double (the products are exact, the two sums
+// cost 2^-52 D N1) and the margin is raised by 2^-20 of itself for its own rounding.  N1 and D are kept inside ranges where
+// no product of the float expression can overflow, and where an underflow (or a flushed subnormal, 2^-126 a term) is far
+// below the margin: N1 in [2^-60, 2^60], D in [2^-20, 2^20], M <= 2^60.
+bool shadow_tri_excluded(const float n[3], const float d[3], double origin_max) {
+    const double u = 5.9604644775390625e-8, lo60 = 8.673617379884035e-19, hi60 = 1152921504606846976.0;
+    const double D = std::max(std::max(fabs((double)d[0]), fabs((double)d[1])), fabs((double)d[2]));
+    const double N1 = fabs((double)n[0]) + fabs((double)n[1]) + fabs((double)n[2]);
+    if (!(N1 >= lo60 && N1 <= hi60)) return false;                         // zero area, tiny, huge or not finite: kept
+    if (!(D >= 9.5367431640625e-7 && D <= 1048576.0)) return false;
+    if (!(origin_max >= 0.0 && origin_max <= hi60)) return false;
+    const double E = u * (origin_max + 2.0 * D) * (1.0 + u);
+    const double margin = N1 * (E + 4.0 * u * (D + E) + D * 8.881784197001252e-16) * (1.0 + 9.5367431640625e-7);
+    const double dn = (double)d[0] * (double)n[0] + (double)d[1] * (double)n[1] + (double)d[2] * (double)n[2];
+    return dn >= margin;
+}
+
+void shadow_occluders(const float * normals, uint32_t n_tris, const float d[3], double origin_max, std::vector<uint32_t> * ids) {
+    ids->clear();
+    for (uint32_t t = 0; t < n_tris; ++t)
+        if (!shadow_tri_excluded(normals + 3 * (size_t)t, d, origin_max)) ids->push_back(t);
+}
+
+void make_empty_bvh(int width, BvhWide * out) {
+    if (width != 4 && width != 8) throw std::invalid_argument("make_empty_bvh: width must be 4 or 8");
+    *out = BvhWide();
+    const bool eight = width == 8;
+    const uint32_t one = 127u << 23;                                       // grid step 2^0
+    out->node_dwords = eight ? BVH8_NODE_DWORDS : BVH4_NODE_DWORDS;
+    out->nodes.assign(out->node_dwords, 0u);
+    uint32_t * d = out->nodes.data();
+    if (eight) {
+        d[3] = d[6] = d[7] = one;                                          // no mask bit, no count bit
+        d[4] = 1u;                                                         // child_base, tri_base: nothing follows
+        for (int k = 8; k < 14; ++k) d[k] = 0xFFFFFFFFu;                   // lo = 255 > hi = 0 in every slot
+    } else {
+        d[3] = d[14] = d[15] = one;
+        d[4] = d[5] = d[6] = 0xFFFFFFFFu;
+        for (int k = 0; k < 4; ++k) d[10 + k] = (uint32_t)~(int32_t)0;     // the dummy record at slot n_tris = 0
+    }
+    out->node_count = 1;
+    out->max_depth = 1;
+    out->stack_bound = eight ? 3 : 5;
+}
+
+void rebase_bvh_nodes(const BvhWide & sub, uint32_t node_base, uint32_t tri_base, uint32_t * dst) {
+    memcpy(dst, sub.nodes.data(), sub.nodes.size() * sizeof(uint32_t));
+    for (uint32_t ni = 0; ni < sub.node_count; ++ni) {
+        uint32_t * d = dst + (size_t)ni * sub.node_dwords;
+        if (sub.node_dwords == BVH8_NODE_DWORDS) {
+            d[4] += node_base;
+            d[5] += tri_base;
+            continue;
+        }
+        for (int k = 0; k < 4; ++k) {
+            const int32_t link = (int32_t)d[10 + k];
+            if (link >= 0) { d[10 + k] = (uint32_t)link + node_base; continue; }
+            const uint32_t leaf = (uint32_t)~link;
+            d[10 + k] = (uint32_t)~(int32_t)((((leaf >> 2) + tri_base) << 2) | (leaf & 3u));
+        }
+    }
+}
+
+const char * append_shadow_tree(const ShadowTreeBuild & how, const float * verts, const float * normals, uint32_t n_tris, const float d[3], double origin_max,
+                                std::vector<uint32_t> * node_words, uint32_t node_base, uint32_t rec_base,
+                                std::vector<uint32_t> * rec_tri, ShadowTreeResult * r, BvhWide * built) {
+    *r = ShadowTreeResult();
+    *built = BvhWide();
+    rec_tri->clear();
+    std::vector<uint32_t> ids;
+    shadow_occluders(normals, n_tris, d, origin_max, &ids);
+    const uint32_t m = (uint32_t)ids.size();
+    r->triangle_count = m;
+    if ((uint64_t)m * 100u > (uint64_t)n_tris * how.ratio_percent) return nullptr;              // too few left out to pay
+    BvhWide sub;
+    if (m) {
+        std::vector<float> sub_verts((size_t)m * 9);
+        for (uint32_t i = 0; i < m; ++i) memcpy(&sub_verts[(size_t)i * 9], verts + (size_t)ids[i] * 9, 36);
+        build_bvh_wide(how.width, sub_verts.data(), m, how.leaf_max, how.threads, &sub, how.trav_cost, how.opt);
+    } else {
+        make_empty_bvh(how.width, &sub);
+    }
+    if ((uint64_t)node_base + sub.node_count >= (1u << 26) || (uint64_t)rec_base + m + 1u >= (1u << 26)) return nullptr;
+    if (node_words->size() != (size_t)node_base * sub.node_dwords) return "shadow tree: the node array does not end at node_base";
+    node_words->resize(((size_t)node_base + sub.node_count) * sub.node_dwords);
+    rebase_bvh_nodes(sub, node_base, rec_base, &(*node_words)[(size_t)node_base * sub.node_dwords]);
+    for (uint32_t slot = 0; slot < m; ++slot) rec_tri->push_back(ids[sub.tri_order[slot]]);
+    rec_tri->push_back(0xFFFFFFFFu);
+    r->built = 1;
+    r->node_count = sub.node_count;
+    r->root = node_base;
+    r->stack_bound = sub.stack_bound;
+    built->nodes.swap(sub.nodes); built->tri_order.swap(sub.tri_order);
+    built->node_dwords = sub.node_dwords; built->node_count = sub.node_count; built->max_depth = sub.max_depth; built->stack_bound = sub.stack_bound;
+    return nullptr;
+}
+
 // Back end for a tree built elsewhere (the GPU LBVH builder, bvh_lbvh.hip): a binary radix tree over the triangles in
 // sorted order.  Internal node i has children left[i] / right[i] (>= 0: internal node, < 0: ~sorted position of a
 // single triangle), covers sorted positions [first[i], last[i]] and has box node_box[6 i .. 6 i + 5] (lo xyz, hi xyz);

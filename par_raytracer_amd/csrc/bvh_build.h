@@ -58,6 +58,47 @@ void build_bvh_wide_from_radix_tree(int width, uint32_t n_tris, uint32_t leaf_ma
                                     const uint32_t * first, const uint32_t * last, const float * node_box, const float * leaf_box,
                                     const uint32_t * sorted_ids, BvhWide * out, const BvhBuildOptions * opt = nullptr);
 
+// ---- shadow trees: per directional light, a second tree over the triangles that its shadow rays can hit at all.
+//
+// The triangle test is single-sided: it leaves at dd = Dot(qp, n) <= 0 with qp = o - (o + d) and n = Cross(ab, ac) as stored
+// in the record (dev_trace_common.h tri_test).  All shadow rays of a directional light share d, so a triangle whose dd is
+// <= 0 for EVERY origin a render can produce is never hit by them and need not be walked (DESIGN.md section 2 has the
+// derivation of the bound below).
+//
+// shadow_tri_excluded: true when the triangle whose record holds the normal n - the three floats as the uploader STORED them,
+// nothing is computed again here - may be left out of the tree of the light whose rays have direction d (the kernels'
+// `facing * -1.0f`), for origins with |o_k| <= origin_max on every axis.  Conservative: false for anything it cannot prove -
+// a normal that is not finite, is tiny or huge (the float products could under- or overflow), a direction outside
+// [2^-20, 2^20], an origin_max that is not finite.
+bool shadow_tri_excluded(const float n[3], const float d[3], double origin_max);
+// The input triangles that stay: ids ascending.  normals: 3 floats per input triangle, the record normals.
+void shadow_occluders(const float * normals, uint32_t n_tris, const float d[3], double origin_max, std::vector<uint32_t> * ids);
+// A tree without triangles: one node whose slots are all empty (its 4-wide links name the dummy record at slot 0).
+void make_empty_bvh(int width, BvhWide * out);
+// Copies sub's nodes to dst (sub.nodes.size() dwords) with every node index moved by node_base and every triangle slot by
+// tri_base: the tree as it reads when it lies behind another in the same arrays, rooted at node_base.
+void rebase_bvh_nodes(const BvhWide & sub, uint32_t node_base, uint32_t tri_base, uint32_t * dst);
+
+// One light's tree, whole: classify, decide by size, build with the ordinary back end (an empty set: make_empty_bvh) and
+// append the nodes - rebased to (node_base, rec_base), the arrays' fill so far - to node_words.  `built` gets the tree as the
+// back end made it, before the move: the caller puts it through validate_bvh_links (bvh_check.cpp), over
+// r->triangle_count triangles, before anything is uploaded.  rec_tri gets
+// the input triangle of every record the caller must append to the record array, in order; the last is 0xFFFFFFFF, the
+// tree's own all-zero dummy record.  Not built (r->built = 0, nothing appended): more occluders than ratio_percent hundredths
+// of the scene, or an array would pass 2^26 entries (the traversal's 32-bit byte offsets).  Returns NULL, or what is wrong
+// with its arguments.
+struct ShadowTreeBuild {
+    int width = 4;
+    uint32_t leaf_max = 4, threads = 1, ratio_percent = 75;
+    float trav_cost = 1.0f;
+    const BvhBuildOptions * opt = nullptr;
+};
+struct ShadowTreeResult { uint32_t built = 0, triangle_count = 0, node_count = 0, root = 0, stack_bound = 0; };
+// verts: 9 floats per input triangle (the boxes); normals: 3 per input triangle, the stored record normals (the classification).
+const char * append_shadow_tree(const ShadowTreeBuild & how, const float * verts, const float * normals, uint32_t n_tris, const float d[3], double origin_max,
+                                std::vector<uint32_t> * node_words, uint32_t node_base, uint32_t rec_base,
+                                std::vector<uint32_t> * rec_tri, ShadowTreeResult * r, BvhWide * built);
+
 // bvh_check.cpp.  Every address the traversal kernels will form from the tree, checked on the host before the tree is
 // uploaded: a message naming the first node link or triangle range outside the arrays, or NULL.  O(nodes), links only.
 const char * validate_bvh_links(const BvhWide & bvh, uint32_t n_tris);

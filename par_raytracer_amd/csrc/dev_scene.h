@@ -19,6 +19,10 @@
 //                (a.xyz, ab.x) (ab.yz, ac.xy) (ac.z, n.xyz)   with ab = b-a, ac = c-a, n = Cross(ab, ac)
 //              computed on the host with the reference's float expressions (raytracer.cpp:85-91), so the
 //              device test consumes the same bits the CPU test would compute per call
+//   shadow trees  behind the scene's nodes and triangle records (and the all-zero dummy record), in the same two arrays:
+//              per directional light one more tree over copies of the records of the triangles its shadow rays can
+//              hit, links rebased to the arrays' bases, each with a dummy record of its own.  Only any-hit shadow
+//              rays ever enter them (DevLight::pad); tri_count, node_count and every other table describe the scene's tree
 //   shade      64 B per triangle = 4 x float4, same order: the three vertex normals, the geometric normal
 //              n (again) and the material index - ONE gather per shaded hit, not per test
 //   tri_rank   u32 per triangle: position in the reference's own visit order (sphere tree DFS with c1
@@ -63,8 +67,14 @@ struct DevLight {             // 48 B
     float position[3];
     float falloff;
     float facing[3];
+    // an int, bit for bit: the node at which this light's any-hit shadow rays start.  0 = the scene's tree.  A directional
+    // light may have a tree of its own behind the scene's, in the same `nodes` / `tris` arrays: the triangles that can occlude
+    // at all - the triangle test is single-sided and all of the light's shadow rays share one direction, so every other
+    // triangle fails `dd <= 0` whatever the origin (bvh_build.h shadow_tri_excluded).  The context
+    // keeps a second copy of the table with every root at 0 behind the first (option SHADOW_TREES, stale trees).
     float pad;
 };
+PRT_D int light_shadow_root(const DevLight & L) { return __float_as_int(L.pad); }
 
 struct DevScene {
     const float4 * nodes;

@@ -4,7 +4,7 @@
 //               round 3; 1 - 2 % behind the 4-wide tree on the headline frame, ahead on deep bounce trees: profiles/r03_ab_bvh8.txt)
 // Both implement one interface, and everything below the #include is written against it once:
 //   TravRay; LdsStack<BLOCK>, LdsSpillStack<BLOCK>, GlobalStack; StackEntry, STACK_ENTRY_INTS, BVH_NODE_BYTES
-//   trav_idle(r), trav_init(r, o, d, kind, pad, stk)                          no ray / a ray at the root
+//   trav_idle(r), trav_init(r, o, d, kind, pad, stk, root = 0)                no ray / a ray at the root of a tree
 //   trav_start<ANY_LENGTH>(r, o, d, kind, pad, stk)                           the same, for directions of any length (below)
 //   trav_walking(r), trav_done(r)                                             wants a node step / ended; neither: holds a leaf
 //   trav_node_step<STK, COUNT>(sc, r, stk, st, pad), trav_leaf<STK, COUNT>(sc, r, stk, st)
@@ -37,7 +37,7 @@ namespace prt {
 //     than it could be and never sooner: conservative.  Unit directions are walked as they are.
 // The triangle tests see the caller's direction, bit for bit.  trav_start<false> is trav_init.
 template <bool ANY_LENGTH, class STK>
-PRT_D void trav_start(TravRay & r, f3 o, f3 d, int kind, float pad, const STK & stk) {
+PRT_D void trav_start(TravRay & r, f3 o, f3 d, int kind, float pad, const STK & stk, int root = 0) {
     if (ANY_LENGTH) {
         f3 w = (o + d) - o;
         if (w.x == 0.0f && w.y == 0.0f && w.z == 0.0f) w = d;
@@ -51,11 +51,11 @@ PRT_D void trav_start(TravRay & r, f3 o, f3 d, int kind, float pad, const STK & 
         if (fabsf(w.x) < tiny) w.x = copysignf(tiny, w.x);
         if (fabsf(w.y) < tiny) w.y = copysignf(tiny, w.y);
         if (fabsf(w.z) < tiny) w.z = copysignf(tiny, w.z);
-        trav_init(r, o, w, kind, pad, stk);
+        trav_init(r, o, w, kind, pad, stk, root);
         r.d = d;
         return;
     }
-    trav_init(r, o, d, kind, pad, stk);
+    trav_init(r, o, d, kind, pad, stk, root);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -139,11 +139,12 @@ PRT_D HitRec resolve_near_ties(const DevScene & sc, f3 o, f3 d, float pad, float
 // Whole-ray traversal, "while-while" (Aila & Laine): every lane first walks internal nodes until it holds a leaf (or runs out
 // of work), and only then does the wave run the triangle code.  With 64 lanes a fused node-or-leaf loop would execute the (4x
 // longer) leaf body in almost every iteration.  Near ties are decided on the spot: this is the form for the slow paths, on a
-// stack that cannot overflow.  ANY_LENGTH: the queries' form (trav_start).
+// stack that cannot overflow.  ANY_LENGTH: the queries' form (trav_start).  root: where an any-hit ray starts (a closest-hit
+// ray's near ties are replayed over the scene's tree: it always starts at 0).
 template <class STK, bool COUNT, bool ANY_LENGTH = false>
-PRT_D HitRec trace_ray(const DevScene & sc, f3 o, f3 d, int kind, float pad, const STK & stk, TraceStats & st) {
+PRT_D HitRec trace_ray(const DevScene & sc, f3 o, f3 d, int kind, float pad, const STK & stk, TraceStats & st, int root = 0) {
     TravRay r;
-    trav_start<ANY_LENGTH>(r, o, d, kind, pad, stk);
+    trav_start<ANY_LENGTH>(r, o, d, kind, pad, stk, root);
     for (;;) {
         while (trav_walking(r)) trav_node_step<STK, COUNT>(sc, r, stk, st, pad);
         if (trav_done(r)) break;

@@ -118,7 +118,7 @@ PRT_D void trav_push(TravRay & r, const STK & stk, int link) {
 }
 
 template <class STK>
-PRT_D void trav_init(TravRay & r, f3 o, f3 d, int kind, float pad, const STK & stk) {
+PRT_D void trav_init(TravRay & r, f3 o, f3 d, int kind, float pad, const STK & stk, int root = 0) {
     r.o = o;
     r.d = d;
     // direction components are clamped away from 0 so no inf/NaN enters the box test
@@ -135,7 +135,7 @@ PRT_D void trav_init(TravRay & r, f3 o, f3 d, int kind, float pad, const STK & s
     r.kind = kind;
     stk.push(0, TRAV_SENTINEL);
     r.sp = 1;
-    r.node = 0;
+    r.node = root;              // 0: the scene's tree; a directional light's shadow rays may start at that light's occluder tree (dev_scene.h)
 }
 
 PRT_D void cswap(float & ka, float & kb, int & la, int & lb) {

@@ -133,7 +133,7 @@ template <class STK> PRT_D bool trav_needs_slow_path(const TravRay & r, const ST
 }
 
 template <class STK>
-PRT_D void trav_init(TravRay & r, f3 o, f3 d, int kind, float pad, const STK & stk) {
+PRT_D void trav_init(TravRay & r, f3 o, f3 d, int kind, float pad, const STK & stk, int root = 0) {
     r.o = o;
     r.d = d;
     // direction components are clamped away from 0 so no inf/NaN enters the box test
@@ -151,7 +151,7 @@ PRT_D void trav_init(TravRay & r, f3 o, f3 d, int kind, float pad, const STK & s
     r.kind = kind | oct << 4;
     stk.put(0, make_int2(TRAV_SENTINEL, 0));
     r.sp = 1;
-    r.node = 0;
+    r.node = root;              // 0: the scene's tree; a directional light's shadow rays may start at that light's occluder tree (dev_scene.h)
     r.tbase = 0u;
     r.tbits = 0u;
 }

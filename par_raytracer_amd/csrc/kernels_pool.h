@@ -528,7 +528,9 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
                             if (payload.w < 0.0f) {          // shadow_entry_dir (kernels_wave.h), spelled out: the helper changes this kernel's code
                                 const DevLight & L = lights[(unsigned int)(-payload.w) - 1u];
                                 const f3 lv = mk3(L.facing[0], L.facing[1], L.facing[2]) * -1.0f;   // raytracer.cpp:240
-                                rd = make_float4(lv.x, lv.y, lv.z, 0.0f);
+                                // the node this ray starts at - the light's shadow tree, dev_scene.h - rides in the direction's idle
+                                // fourth word: a variable of its own made the deep-bounce variant spill the payload inside the walk
+                                rd = make_float4(lv.x, lv.y, lv.z, L.pad);
                                 kind = WF_KIND_SHADOW_ANY;
                             } else {
                                 rd = sq_d[j];
@@ -538,7 +540,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
                         sample = as_i(ro.w);
                         const f3 d = mk3(rd.x, rd.y, rd.z);
                         const f3 ob = mk3(ro.x, ro.y, ro.z) + d * P.ray_bias;          // raytracer.cpp:163
-                        trav_init(r, ob, d, kind == WF_KIND_SHADOW_ANY ? TRACE_ANY : TRACE_CLOSEST, P.box_pad, stack);
+                        trav_init(r, ob, d, kind == WF_KIND_SHADOW_ANY ? TRACE_ANY : TRACE_CLOSEST, P.box_pad, stack, kind == WF_KIND_SHADOW_ANY ? as_i(rd.w) : 0);
                         ray = (int)idx;
                     }
                     next += take;
@@ -1006,7 +1008,8 @@ __global__ __launch_bounds__(256) void k_pool_parked_shadows(const PoolArgs * ar
         const int sample = as_i(ro.w);
         const f3 d = mk3(rd.x, rd.y, rd.z);
         const f3 ob = mk3(ro.x, ro.y, ro.z) + d * P.ray_bias;                   // raytracer.cpp:163
-        const HitRec h = trace_ray<GlobalStack, COUNT>(sc, ob, d, pay.w < 0.0f ? TRACE_ANY : TRACE_CLOSEST, P.box_pad, slow, st);
+        const int root = pay.w < 0.0f ? light_shadow_root(sc.lights[(unsigned int)(-pay.w) - 1u]) : 0;
+        const HitRec h = trace_ray<GlobalStack, COUNT>(sc, ob, d, pay.w < 0.0f ? TRACE_ANY : TRACE_CLOSEST, P.box_pad, slow, st, root);
         if (shadow_lit(h, pay.w)) accum_add(A.B.accum + sample, mk3(pay.x, pay.y, pay.z));
     }
     if (COUNT) trace_stats_flush<false>(ctr, st);

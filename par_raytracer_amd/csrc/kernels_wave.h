@@ -104,15 +104,18 @@ PRT_D unsigned int block_append(unsigned int * counter, bool pred, unsigned int 
 }
 
 // A shadow list entry's direction and kind: a directional light's direction is a per-light constant (payload.w < 0: light
-// number -w - 1, raytracer.cpp:240), a point light's travels with the ray.
-PRT_D float4 shadow_entry_dir(const DevLight * lights, float4 payload, const float4 * sq_d, unsigned int j, int & kind) {
+// number -w - 1, raytracer.cpp:240), a point light's travels with the ray.  root: the node the ray starts at - the directional
+// light's occluder tree (light_shadow_root), the scene's tree for every other ray.
+PRT_D float4 shadow_entry_dir(const DevLight * lights, float4 payload, const float4 * sq_d, unsigned int j, int & kind, int & root) {
     if (payload.w < 0.0f) {
         const DevLight & L = lights[(unsigned int)(-payload.w) - 1u];
         const f3 lv = mk3(L.facing[0], L.facing[1], L.facing[2]) * -1.0f;
         kind = WF_KIND_SHADOW_ANY;
+        root = light_shadow_root(L);
         return make_float4(lv.x, lv.y, lv.z, 0.0f);
     }
     kind = WF_KIND_SHADOW_DIST;
+    root = 0;
     return sq_d[j];
 }
 // A shadow ray's verdict.  w < 0: directional light (boolean only, raytracer.cpp:385); otherwise the point light's inverted
@@ -143,7 +146,7 @@ __global__ __launch_bounds__(256) void k_raygen(DevCamera cam, DevParams P, Wave
 // raytracer.cpp:163), its sample, and a shadow ray's payload (a closest-hit ray leaves `payload` as it is).
 struct TraceEntry {
     f3 ob, d;
-    int kind, sample;
+    int kind, sample, root;
 };
 PRT_D TraceEntry trace_entry(const DevScene & sc, const DevParams & P, const WaveBuffers & B, int cur, unsigned int n_closest,
                              unsigned int idx, float4 & payload) {
@@ -153,11 +156,12 @@ PRT_D TraceEntry trace_entry(const DevScene & sc, const DevParams & P, const Wav
         ro = B.rq_o[cur][idx];
         rd = B.rq_d[cur][idx];
         e.kind = WF_KIND_CLOSEST;
+        e.root = 0;
     } else {
         const unsigned int j = idx - n_closest;
         ro = B.sq_o[j];
         payload = B.sq_c[j];
-        rd = shadow_entry_dir(sc.lights, payload, B.sq_d, j, e.kind);
+        rd = shadow_entry_dir(sc.lights, payload, B.sq_d, j, e.kind, e.root);
     }
     e.sample = as_i(ro.w);
     e.d = mk3(rd.x, rd.y, rd.z);
@@ -183,7 +187,7 @@ struct TraceJob : RaySteps<BLOCK, COUNT> {
     PRT_D bool start(unsigned int idx, TravRay & r, const LdsStack<BLOCK> & stack) {
         const TraceEntry e = trace_entry(this->sc, P, B, cur, n_closest, idx, payload);
         sample = e.sample;
-        trav_init(r, e.ob, e.d, trace_entry_mode(e), this->pad, stack);
+        trav_init(r, e.ob, e.d, trace_entry_mode(e), this->pad, stack, e.root);
         return true;
     }
     PRT_D void finish(unsigned int idx, const TravRay & r, const LdsStack<BLOCK> & stack) const {
@@ -222,7 +226,7 @@ __global__ __launch_bounds__(256) void k_trace_exact(DevScene sc, DevParams P, W
     exact_list_walk<COUNT>(B.overflow, B.counts[3], P.exact_stack, P.exact_stack_stride, ctr, [&](unsigned int idx, const GlobalStack & slow, TraceStats & st) {
         float4 payload = make_float4(0, 0, 0, 0);
         const TraceEntry e = trace_entry(sc, P, B, cur, n_closest, idx, payload);
-        const HitRec best = trace_ray<GlobalStack, COUNT>(sc, e.ob, e.d, trace_entry_mode(e), P.box_pad, slow, st);
+        const HitRec best = trace_ray<GlobalStack, COUNT>(sc, e.ob, e.d, trace_entry_mode(e), P.box_pad, slow, st, e.root);
         trace_entry_emit(B, n_closest, idx, best, payload, e.sample);
     });
 }

@@ -126,7 +126,14 @@ struct prt_ctx {
     DevBuf<float4> nodes, tris, shade, diffuse_dirs, spec_dirs;
     DevBuf<unsigned int> tri_rank;
     DevBuf<DevMaterial> materials;
-    DevBuf<DevLight> lights;
+    DevBuf<DevLight> lights;              // two copies of the table, light_stride apart: shadow-tree roots in DevLight::pad, then every root at 0
+    unsigned int light_stride = 1;
+    // shadow trees (include/prt.h): one entry per light; fresh = of the geometry on the device (an update makes them stale);
+    // origin_max = the |coordinate| of a shadow ray's origin that the exclusion bound covers (bvh_build.h), and what a
+    // render call's |ray_bias| and camera position may be for its shadow rays to stay inside it
+    std::vector<prt_shadow_tree_info> shadow_info;
+    bool shadow_trees_fresh = false;
+    float shadow_bias_max = 0.0f, shadow_cam_max = 0.0f;
     DevScene scene;
     prt_scene_info info;
     float scene_abs_max = 0.0f;
@@ -848,6 +855,13 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
     P.pixel_list = px.d_pixel_list;
     const PrtOptions & opt = ctx->opt;
     ctx->scene.tie_widen_max = (unsigned int)std::max(0ll, std::min(64ll, opt.tie_widen_max));
+    {
+        // which copy of the light table: the shadow-tree roots, or every root at 0 - the option, trees of an older geometry, or a
+        // call whose shadow-ray origins the upload's exclusion bound does not cover (include/prt.h "Shadow trees")
+        bool trees = opt.shadow_trees != 0 && ctx->shadow_trees_fresh && fabsf(params->ray_bias) <= ctx->shadow_bias_max;
+        for (int a = 0; a < 3; ++a) trees = trees && fabsf(cam_in->position[a]) <= ctx->shadow_cam_max;
+        ctx->scene.lights = ctx->lights.p + (trees ? 0u : ctx->light_stride);
+    }
     P.elide_dead_shadow_rays = opt.trace_dead_shadow_rays ? 0u : 1u;
     // tiled work order: sets made of full-width rows only (a whole frame or a range that starts at a row, row-block shards)
     P.tile_pixels = 0;
@@ -1710,6 +1724,10 @@ int update_geometry(prt_ctx * ctx, const prt_geometry_update * u, prt_update_inf
     ctx->scene.ref_spheres = ref_spheres.empty() ? nullptr : ctx->ref_spheres.p;      // spheres of the old geometry are never kept
     ctx->info.device_bytes = ctx->info.device_bytes - old_sphere_bytes + (ref_spheres.empty() ? 0 : ctx->ref_spheres.bytes());
     ctx->scene_abs_max = abs_max;
+    // the shadow trees are of the uploaded geometry, in membership and in boxes: every shadow ray starts at the scene's root
+    // until the next upload (render_pixels_once)
+    ctx->shadow_trees_fresh = false;
+    for (prt_shadow_tree_info & si : ctx->shadow_info) si.active = 0;
     ctx->tuned.clear();                                           // a refitted tree may change which pipeline wins a try-out
     ctx->geom_generation++;                                       // the pseudonormals of prt_signed_distance are of the old records
     if (info) { info->device_ms = ms; info->abs_max = abs_max; }
@@ -2528,14 +2546,21 @@ int prt_upload_scene(prt_ctx * ctx, const prt_scene_desc * s) {
     std::vector<float4> tri_uv(textured ? (size_t)n_rec * 2 : 0, make_float4(0, 0, 0, 0));
     std::vector<float4> tri_tan(bumped ? (size_t)n_rec * 3 : 0, make_float4(0, 0, 0, 0));
     float abs_max = 0.0f;
-    for (uint32_t slot = 0; slot < n_tris; ++slot) {
-        const uint32_t t = bvh.tri_order[slot];
+    // input triangle t's 48-byte record at `slot` of the record array; returns n
+    auto put_tri_record = [&](uint32_t t, size_t slot) {
         const f3 a = ld3(&verts[(size_t)t * 9]), b = ld3(&verts[(size_t)t * 9 + 3]), c = ld3(&verts[(size_t)t * 9 + 6]);
         const f3 ab = b - a, ac = c - a;                          // raytracer.cpp:85-86
         const f3 n = cross3(ab, ac);                              // raytracer.cpp:91
-        tris[(size_t)slot * 3 + 0] = make_float4(a.x, a.y, a.z, ab.x);
-        tris[(size_t)slot * 3 + 1] = make_float4(ab.y, ab.z, ac.x, ac.y);
-        tris[(size_t)slot * 3 + 2] = make_float4(ac.z, n.x, n.y, n.z);
+        tris[slot * 3 + 0] = make_float4(a.x, a.y, a.z, ab.x);
+        tris[slot * 3 + 1] = make_float4(ab.y, ab.z, ac.x, ac.y);
+        tris[slot * 3 + 2] = make_float4(ac.z, n.x, n.y, n.z);
+        return n;
+    };
+    std::vector<float> rec_normals((size_t)n_tris * 3);          // per INPUT triangle: n as its record holds it (the shadow trees classify by it)
+    for (uint32_t slot = 0; slot < n_tris; ++slot) {
+        const uint32_t t = bvh.tri_order[slot];
+        const f3 n = put_tri_record(t, slot);
+        { const float4 stored = tris[(size_t)slot * 3 + 2]; rec_normals[(size_t)t * 3] = stored.y; rec_normals[(size_t)t * 3 + 1] = stored.z; rec_normals[(size_t)t * 3 + 2] = stored.w; }
         const float * n0 = s->normals + 3 * (size_t)s->idx_normals[3 * t + 0];
         const float * n1 = s->normals + 3 * (size_t)s->idx_normals[3 * t + 1];
         const float * n2 = s->normals + 3 * (size_t)s->idx_normals[3 * t + 2];
@@ -2586,7 +2611,8 @@ int prt_upload_scene(prt_ctx * ctx, const prt_scene_desc * s) {
         tex_fill_srgb_lut(lut);
     }
     ctx->kat_textures = dev_tex;
-    std::vector<DevLight> lights(std::max(1u, s->light_count));
+    const uint32_t light_stride = std::max(1u, s->light_count);
+    std::vector<DevLight> lights(2 * (size_t)light_stride);       // [0, stride): shadow-tree roots in pad; [stride, 2 stride): every root 0
     memset(lights.data(), 0, lights.size() * sizeof(DevLight));
     for (uint32_t l = 0; l < s->light_count; ++l) {
         const prt_light & pl = s->lights[l];
@@ -2600,9 +2626,52 @@ int prt_upload_scene(prt_ctx * ctx, const prt_scene_desc * s) {
     std::vector<float4> ddirs(1024);
     for (uint32_t i = 0; i < 1024; ++i) ddirs[i] = diffuse_tangent_dir(i);
 
-    std::vector<float4> nodes4(bvh.nodes.size() / 4);
-    memcpy(nodes4.data(), bvh.nodes.data(), bvh.nodes.size() * sizeof(uint32_t));
-    ctx->stack_bound = bvh.stack_bound;
+    // ---- shadow trees (include/prt.h, bvh_build.h): behind the scene's nodes and records, links rebased
+    std::vector<uint32_t> node_words(bvh.nodes);
+    uint32_t all_nodes = bvh.node_count, all_recs = n_rec;
+    // (the context learns of all this only once every tree is built and checked: a failed upload leaves it describing nothing new)
+    unsigned int stack_bound = bvh.stack_bound;
+    std::vector<prt_shadow_tree_info> shadow_info(s->light_count, prt_shadow_tree_info());
+    // origins the bound covers: a shadow ray starts at (hit + n * bias) + d * bias; the hit is taken to lie within 16 extents of
+    // the origin for a camera within 4 and a bias of at most one extent; render_pixels_once holds a call to that
+    const double shadow_origin_max = 32.0 * (double)abs_max;
+    uint32_t shadow_trees = 0;
+    for (uint32_t l = 0; l < s->light_count && abs_max > 0.0f; ++l) {
+        if (s->lights[l].type != 0 || shadow_trees >= (uint32_t)PRT_MAX_SHADOW_TREES) continue;
+        prt_shadow_tree_info & si = shadow_info[l];
+        const auto ts = std::chrono::steady_clock::now();
+        const float dir[3] = { lights[l].facing[0] * -1.0f, lights[l].facing[1] * -1.0f, lights[l].facing[2] * -1.0f };   // as the kernels form it
+        ShadowTreeBuild sb;
+        sb.width = BVH_WIDTH; sb.leaf_max = leaf_max; sb.threads = std::min(hw, 16u); sb.trav_cost = trav_cost; sb.opt = &ctx->opt.bvh;
+        sb.ratio_percent = (uint32_t)std::max(0ll, std::min(100ll, ctx->opt.shadow_tree_ratio));
+        ShadowTreeResult sr;
+        std::vector<uint32_t> rec_tri;
+        BvhWide sub;
+        const char * bad = append_shadow_tree(sb, verts.data(), rec_normals.data(), n_tris, dir, shadow_origin_max, &node_words, all_nodes, all_recs, &rec_tri, &sr, &sub);
+        if (!bad && sr.built) bad = validate_bvh_links(sub, sr.triangle_count);
+        if (bad) { ctx->error = std::string("prt_upload_scene: the builder produced a broken shadow tree - ") + bad; return -9; }
+        si.triangle_count = sr.triangle_count;
+        si.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ts).count();
+        if (!sr.built) continue;
+        tris.resize(((size_t)all_recs + rec_tri.size()) * 3, make_float4(0, 0, 0, 0));
+        for (size_t i = 0; i < rec_tri.size(); ++i)
+            if (rec_tri[i] != 0xFFFFFFFFu) put_tri_record(rec_tri[i], (size_t)all_recs + i);         // (the tree's own dummy record stays all-zero)
+        si.built = si.active = 1;
+        si.node_count = sr.node_count;
+        si.root = sr.root;
+        si.stack_bound = sr.stack_bound;
+        si.device_bytes = (uint64_t)sr.node_count * BVH_NODE_BYTES + (uint64_t)rec_tri.size() * 48u;
+        const int root = (int)sr.root;
+        memcpy(&lights[l].pad, &root, 4);
+        all_nodes += sr.node_count;
+        all_recs += (uint32_t)rec_tri.size();
+        stack_bound = std::max(stack_bound, sr.stack_bound);
+        shadow_trees++;
+    }
+    for (uint32_t l = 0; l < light_stride; ++l) { lights[light_stride + l] = lights[l]; lights[light_stride + l].pad = 0.0f; }
+
+    std::vector<float4> nodes4(node_words.size() / 4);
+    memcpy(nodes4.data(), node_words.data(), node_words.size() * sizeof(uint32_t));
 
     HIP_TRY(ctx, ctx->nodes.upload(nodes4));
     HIP_TRY(ctx, ctx->tris.upload(tris));
@@ -2646,6 +2715,13 @@ int prt_upload_scene(prt_ctx * ctx, const prt_scene_desc * s) {
     if (rc) return rc;
 
     ctx->scene_abs_max = abs_max;
+    // the trees, the two light tables and the bound's limits: only now that all of it lies on the device
+    ctx->stack_bound = stack_bound;
+    ctx->shadow_info.swap(shadow_info);
+    ctx->shadow_bias_max = abs_max;
+    ctx->shadow_cam_max = 4.0f * abs_max;
+    ctx->light_stride = light_stride;
+    ctx->shadow_trees_fresh = true;
     prt_scene_info & info = ctx->info;
     info.triangle_count = n_tris;
     info.bvh_node_count = bvh.node_count;
@@ -2683,6 +2759,15 @@ int prt_get_scene_info(const prt_ctx * ctx, prt_scene_info * info) {
     *info = ctx->info;
     return 0;
     PRT_API_CATCH_RC(nullptr, "prt_get_scene_info")
+}
+
+int prt_get_shadow_trees(const prt_ctx * ctx, prt_shadow_tree_info * out, uint32_t cap) {
+    PRT_API_TRY
+    if (!ctx || (!out && cap)) return -1;
+    if (!ctx->has_scene) return -2;
+    for (size_t l = 0; l < ctx->shadow_info.size() && l < cap; ++l) out[l] = ctx->shadow_info[l];
+    return (int)ctx->shadow_info.size();
+    PRT_API_CATCH_RC(nullptr, "prt_get_shadow_trees")
 }
 
 int prt_render_device(prt_ctx * ctx, const prt_camera * cam, const prt_params * params, uint32_t width, uint32_t height,
@@ -3145,6 +3230,8 @@ prt_ctx * clone_context(prt_ctx * src) {
     c->any_translucent = src->any_translucent; c->point_lights = src->point_lights; c->textured = src->textured;
     c->kat_textures = src->kat_textures;
     c->stack_bound = src->stack_bound;
+    c->light_stride = src->light_stride; c->shadow_info = src->shadow_info; c->shadow_trees_fresh = src->shadow_trees_fresh;
+    c->shadow_bias_max = src->shadow_bias_max; c->shadow_cam_max = src->shadow_cam_max;
     c->pool_park_cap = src->pool_park_cap; c->pool_spark_cap = src->pool_spark_cap;
     c->has_scene = src->has_scene;
     c->scene_epoch = 1;
@@ -3342,6 +3429,7 @@ int prt_multi_update_geometry(prt_multi * m, const prt_geometry_update * update)
             c->ref_spheres.borrow(src->ref_spheres);              // the update may have allocated or enlarged it
             c->scene.ref_spheres = src->scene.ref_spheres;
             c->scene_abs_max = src->scene_abs_max;
+            c->shadow_trees_fresh = src->shadow_trees_fresh; c->shadow_info = src->shadow_info;
             c->info = src->info;
             c->has_scene = src->has_scene;
             c->tuned.clear();

@@ -8,6 +8,8 @@
 // Input file: u32 n_tris, 9 floats per triangle, then camera position (3 floats), facing (3), fov (1).
 // Rays: primary rays of a 480 x 270 lattice of the 1920 x 1080 frame; from every hit a shadow ray towards the reference's
 // default light (main.cpp:522-524) and one cosine-distributed bounce ray with its own shadow ray - the ray mix of depth 2.
+// Shadow trees (bvh_build.h): a second 4-wide tree over the light's possible occluders alone, and the shadow rays the device
+// really traces - those whose surface faces the light - through both trees: visits, tests and hit / miss mismatches.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -212,6 +214,33 @@ int main(int argc, char ** argv) {
     const V3 right = norm(cross(fwd, V3{ 0, 1, 0 })), up = norm(cross(right, fwd));
     const V3 light = norm(V3{ 1, -1.5, 0.25 }) * -1.0;
 
+    // the light's possible occluders and their tree (origins within 32 x the scene's largest |coordinate|, as the upload assumes)
+    float abs_max = 0.0f;
+    for (float v : g_verts) abs_max = std::max(abs_max, std::fabs(v));
+    const float lightf[3] = { (float)light.x, (float)light.y, (float)light.z };
+    std::vector<uint32_t> occ_ids;
+    std::vector<float> rec_normals((size_t)n_tris * 3);       // the record normals: Cross(b - a, c - a) in float (prt_upload_scene)
+    for (uint32_t t = 0; t < n_tris; ++t) {
+        const float * v = &g_verts[(size_t)t * 9];
+        const float ab[3] = { v[3] - v[0], v[4] - v[1], v[5] - v[2] }, ac[3] = { v[6] - v[0], v[7] - v[1], v[8] - v[2] };
+        rec_normals[(size_t)t * 3 + 0] = ab[1] * ac[2] - ac[1] * ab[2];
+        rec_normals[(size_t)t * 3 + 1] = ab[2] * ac[0] - ac[2] * ab[0];
+        rec_normals[(size_t)t * 3 + 2] = ab[0] * ac[1] - ac[0] * ab[1];
+    }
+    shadow_occluders(rec_normals.data(), n_tris, lightf, 32.0 * abs_max, &occ_ids);
+    std::vector<float> occ_verts(occ_ids.size() * 9);
+    for (size_t i = 0; i < occ_ids.size(); ++i) memcpy(&occ_verts[i * 9], &g_verts[(size_t)occ_ids[i] * 9], 36);
+    Bvh4Result bocc;
+    if (occ_ids.empty()) make_empty_bvh(4, &bocc); else build_bvh_wide(4, occ_verts.data(), (uint32_t)occ_ids.size(), 4, 8, &bocc);
+    for (uint32_t & t : bocc.tri_order) t = occ_ids[t];          // leaf slot -> input triangle of the whole scene
+    Stats s_full, s_occ;
+    uint64_t occ_mismatches = 0;
+    auto price_shadow = [&](const Ray & r, V3 n) {
+        if (dot(n, light) <= 0) return;                           // the device counts such a ray and does not trace it (dead: no radiance)
+        const Hit a = trace4(b4, r, s_full), b = trace4(bocc, r, s_occ);
+        if ((a.tri < 0) != (b.tri < 0)) occ_mismatches++;
+    };
+
     Stats s4[3], s8d[3], s8a[3];            // primary, shadow, bounce
     uint64_t mismatches = 0;
     uint64_t rng = 0x9E3779B97F4A7C15ull;
@@ -235,6 +264,7 @@ int main(int argc, char ** argv) {
             const V3 n = norm(cross(b - a, c - a));
             const V3 p = r.o + r.d * h.t + n * bias;
             trace_all(Ray{ p, light, true }, 1);
+            price_shadow(Ray{ p, light, true }, n);
             // cosine-distributed bounce
             const double u1 = rnd(), u2 = rnd(), ct = std::sqrt(1 - u1), stn = std::sqrt(u1), ph = 2 * M_PI * u2;
             const V3 upv = std::fabs(n.z) < 0.9999 ? V3{ 0, 0, 1 } : V3{ 1, 0, 0 };
@@ -246,6 +276,7 @@ int main(int argc, char ** argv) {
             const V3 a2{ v2[0], v2[1], v2[2] }, b2{ v2[3], v2[4], v2[5] }, c2{ v2[6], v2[7], v2[8] };
             const V3 n2 = norm(cross(b2 - a2, c2 - a2));
             trace_all(Ray{ br.o + br.d * bh.t + n2 * bias, light, true }, 1);
+            price_shadow(Ray{ br.o + br.d * bh.t + n2 * bias, light, true }, n2);
         }
     const char * cls[3] = { "primary", "shadow (any hit)", "bounce" };
     for (int k = 0; k < 3; ++k) {
@@ -265,5 +296,9 @@ int main(int argc, char ** argv) {
     report("8-wide, one axis per node (80 B)", t8a, b8.node_count, 80, b8.max_depth);
     report("8-wide, sorted by entry distance", t8d, b8.node_count, 80, b8.max_depth);
     printf("hit / miss or distance mismatches between the two trees: %llu\n", (unsigned long long)mismatches);
-    return mismatches ? 1 : 0;
+    printf("-- shadow trees: possible occluders %zu of %u; traced shadow rays: %llu\n", occ_ids.size(), n_tris, (unsigned long long)s_full.rays);
+    report("4-wide, the scene's tree", s_full, b4.node_count, 64, b4.max_depth);
+    report("4-wide, the light's occluders", s_occ, bocc.node_count, 64, bocc.max_depth);
+    printf("hit / miss mismatches between the scene's tree and the light's: %llu\n", (unsigned long long)occ_mismatches);
+    return mismatches || occ_mismatches ? 1 : 0;
 }
