@@ -692,6 +692,57 @@ int prt_hemisphere_visibility(prt_ctx * ctx, const prt_hemi_batch * batch, const
 int prt_hemisphere_visibility_device(prt_ctx * ctx, const prt_hemi_batch * batch, const prt_hemi_buffers * out, uint32_t flags,
                                      prt_counters * counters);
 
+/* ---- radiance along the caller's rays: TraceRayColor on rays that are not a pinhole pixel's -------------------------------------
+ * Panoramic, fisheye, orthographic and lens-distorted cameras, light probes and irradiance gathering at the points
+ * prt_sample_surface emits, re-shading the rays of a geometry loop: everything prt_render computes behind its camera ray - lights,
+ * shadow rays, textures, alpha maps, the Russian-roulette bounce tree (raytracer.cpp:413-577) - along rays the caller made.
+ * par_raytracer_amd/cameras.py has ray makers.
+ * THE DEFINITION (csrc/kernels_rays.h).  Output i of a call has the global index first + i; it owns
+ * params->spp rays, ray e = i * spp + s being its sample s (so origins and directions are count x spp x 3 floats).  For each (i, s):
+ *     rng = rng_seed(prt_sample_key(params->seed, (uint32)(first + i), s))       the key prt_render gives sample s of pixel first + i
+ *     with PRT_RAYS_CAMERA_STREAM: two NextFloat11 draws are made and dropped - those RenderPixel spends on the jitter
+ *         (main.cpp:238) - so the stream goes on exactly where prt_render's does; without the flag the ray's first draw is the
+ *         bounce tree's first
+ *     radiance(e) = TraceRayColor(Ray(origin_e, direction_e), params->bounce_depth, rng)      the ray AS GIVEN: no normalisation
+ *   rgba_out[i] = (the mean of radiance over the spp rays, 1), computed as prt_render computes a pixel: the pipeline's throughput
+ *   form, the fixed-point sample accumulators, the same resolve.  params means what it means to prt_render (ray_bias,
+ *   reflection_samples, spec_samples, bounce_depth, background_color, spp, seed); there is no image, so no width or height.
+ *   Composition: the rays RenderPixel makes for the pixels [p0, p0 + n) of a frame, with PRT_RAYS_CAMERA_STREAM and first = p0,
+ *   give prt_render's pixels bit for bit, on either of its pipelines, with the same ray_count.
+ * The answer is a pure function of (the scene as it lies on the device, ray, params, seed, first + i, s, flags): the same bits for
+ * every tree (SAH, LBVH, 8-wide, refitted), for every value of the options STACK_CAP, CHAINS, PASS_SAMPLES and SHADOW_TREES, and for
+ * every split of a batch into calls (`first` makes a batch splittable, as in prt_sample_surface).
+ * DOMAIN.  A ray is inside the domain when every component of its origin, direction and biased origin (origin + direction x
+ * ray_bias) is finite; |Dot(d, d) - 1| <= 2^-18 in float arithmetic - the unit directions for which the device's walk is the
+ * reference's sphere-tree TraceRay (see "ray queries"); and every |origin component| <= 64 x the scene's largest |coordinate|.
+ * The whole batch is checked on the device before anything is rendered, as prt_update_geometry checks its coordinates: if any
+ * ray is outside the call returns -1, prt_last_error gives their number and the first one's index, and nothing is written.  A
+ * renderer cannot give a pixel whose ray it refuses a colour that means anything, and a batch with a hole is not the image the
+ * caller asked for.  (Shadow trees are used while every |origin component| stays within the bound a camera position has to stay
+ * within - "Shadow trees" below; the image is the same bits either way.)
+ * PIPELINE.  The call runs on the wavefront pipeline: params->pipeline may be PRT_PIPELINE_DEFAULT or PRT_PIPELINE_WAVEFRONT, with
+ * or without PRT_FLAG_COUNT_VISITS; PRT_FLAG_TRYOUT is ignored; PRT_PIPELINE_POOL and adaptive sampling (max_spp > spp) are refused.
+ * Counters: prt_render's - ray_count = TraceRay calls, shaded_hits, node_visits / tri_tests with PRT_FLAG_COUNT_VISITS, render_ms
+ * (the check included), trace_kernel_ms, pipeline = PRT_PIPELINE_WAVEFRONT; the render stats are updated as a wavefront render's.
+ * Errors: -1 NULL batch or params, NULL arrays or output with count > 0, spp outside 1..65535, bounce_depth > 16, first + count >
+ * 2^32, an unknown flag, PRT_PIPELINE_POOL or another pipeline, max_spp > spp, a ray outside the domain; -2 no scene; -8 and -10
+ * as in prt_render.  count == 0 writes nothing (counters, if given, are zeroed) and returns 0.  Stream contract of
+ * prt_render_device. */
+enum { PRT_RAYS_CAMERA_STREAM = 1 };
+typedef struct prt_radiance_batch {
+    const float * origins;         /* count x spp x 3 */
+    const float * directions;      /* count x spp x 3, unit length (see DOMAIN) */
+    uint32_t count;                /* outputs; rays = count x params->spp */
+    uint32_t flags;                /* PRT_RAYS_* */
+    uint64_t first;                /* the global index of output 0; first + count <= 2^32 */
+} prt_radiance_batch;
+/* Host pointers (batch arrays and rgba_out: count x 4 floats); counters may be NULL. */
+int prt_render_rays(prt_ctx * ctx, const prt_radiance_batch * batch, const prt_params * params, float * rgba_out,
+                    prt_counters * counters);
+/* Device pointers on the context's device (hipMalloc'ed or torch tensors' data_ptr); d_rgba_out 16-byte aligned. */
+int prt_render_rays_device(prt_ctx * ctx, const prt_radiance_batch * batch, const prt_params * params, void * d_rgba_out,
+                           prt_counters * counters);
+
 /* ---- several devices behind one handle --------------------------------------------------------------------------------
  * SURVEY.md 8(b)'s prt_create(const int * device_ids, int n_dev): what the host mirror's Render() uses for n GPUs, in place
  * of the reference's one-rank-per-core partition + MPI_Gather (main.cpp:311-347).  The scene is replicated (as every MPI rank

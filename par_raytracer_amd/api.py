@@ -638,6 +638,39 @@ class Renderer:
         out["counters"] = counters
         return out
 
+    def render_rays(self, origins, directions, params: PrtParams, *, first: int = 0, camera_stream: bool = False):
+        """The radiance TraceRayColor returns along the caller's rays (prt_render_rays, include/prt.h): lights, shadow rays,
+        textures, alpha maps and the bounce tree, for rays that are no pinhole pixel's.  par_raytracer_amd.cameras makes rays.
+
+        origins, directions: float32, contiguous, (count, spp, 3) or (count * spp, 3) with spp = params.spp - numpy arrays (host
+        entry point, a numpy result) or torch tensors on this context's device (device entry point, a tensor on that device).  Ray
+        i * spp + s is sample s of output first + i and draws from the stream prt_render gives sample s of pixel first + i;
+        camera_stream first drops the two draws RenderPixel spends on the jitter.  The directions must be unit length and are used
+        as given; a ray outside the domain makes the library refuse the whole batch.  Returns (rgba (count, 4), PrtCounters)."""
+        spp = int(params.spp)
+        check, empty, ptr, sync, suffix = self._arrays(origins)
+        if len(origins.shape) == 3:
+            origins = check(origins, "origins", (None, spp, 3))
+            count = int(origins.shape[0])
+            directions = check(directions, "directions", (count, spp, 3))
+        else:
+            origins = check(origins, "origins", (None, 3))
+            rays = int(origins.shape[0])
+            if spp < 1 or rays % spp:
+                raise ValueError("origins holds %d rays, not a multiple of params.spp = %d" % (rays, spp))
+            count = rays // spp
+            directions = check(directions, "directions", (rays, 3))
+        if not 0 <= int(first) < 1 << 64:
+            raise ValueError("first must be in 0 .. 2^64 - 1")
+        out = empty((count, 4))
+        sync()
+        # what the C types hold goes to the library as given: its refusals (spp, first + count, the domain) are the check
+        batch = capi.PrtRadianceBatch(ptr(origins), ptr(directions), count, capi.RAYS_CAMERA_STREAM if camera_stream else 0, int(first))
+        counters = PrtCounters()
+        name = "prt_render_rays" + suffix
+        self._check(getattr(self._lib, name)(self._ctx, C.byref(batch), C.byref(params), ptr(out), C.byref(counters)), name)
+        return out, counters
+
     def sample_surface_backward(self, group, vertex0, bw, positions, *, grad_point=None, grad_normal=None) -> dict:
         """Gradients of surface samples (prt_sample_surface_backward, include/prt.h): from dL/dpoint and dL/dnormal of n samples
         (None = zero) to dL/dpositions, summed over the samples - the same bits for every order of the samples.

@@ -38,6 +38,7 @@
 #include "kernels_sample.h"
 #include "kernels_sample_grad.h"
 #include "kernels_hemi.h"
+#include "kernels_rays.h"
 #include "hammersley.h"
 
 using namespace prt;
@@ -202,6 +203,7 @@ struct prt_ctx {
     DevBuf<float> q_io;                   // host entry point: the batch and the requested fields on the device
     DevBuf<unsigned char> q_occ;
     DevBuf<unsigned char> q_hemi_flags;   // prt_hemisphere_visibility: one byte per item of a pass
+    DevBuf<unsigned long long> rays_words;  // prt_render_rays: k_rays_check's three words
     // geometry updates (prt_update_geometry, kernels_refit.h).  The upload keeps, on the host, the index buffers and the first
     // node of every tree level; the first update builds the leaf slot -> vertex indices table from them (24 B per triangle; like
     // q_leaf_map not in prt_scene_info.device_bytes, freed by the next upload).  The table and the scratch boxes are reused by
@@ -350,6 +352,12 @@ struct PixelSet {
     const unsigned int * d_pixel_list;         // explicit list (device pointer) or NULL
 };
 
+// prt_render_rays: the caller's rays take the camera's place as the source of the primary rays (kernels_rays.h).
+struct RaySource {
+    RaysArgs A;                                // the arrays on the device; the call's k_rays_check has passed them
+    float origin_abs_max;                      // ... and reduced the largest |origin component|
+};
+
 // The wavefront pipeline (kernels_wave.h): raygen, then rounds of {persistent trace, shade} until no ray is
 // left.  Queue sizes come back to the host once per round (8 bytes, pinned): they size the next launches, end
 // the loop and sum to ray_count (every queued ray is one TraceRay call, raytracer.cpp:161).
@@ -492,8 +500,9 @@ int chain_finish_round(prt_ctx * ctx, Chain & c) {
     return 0;
 }
 
-int render_wavefront(prt_ctx * ctx, const DevCamera & cam, const DevParams & P, bool ring, bool count_visits,
-                     unsigned int n_samples, size_t lds, unsigned long long * ray_count, float * trace_ms, unsigned int * launches) {
+// rays: the primary rays come from the caller's arrays, not from cam; the pass's first sample is ray `ray_base` of them.
+int render_wavefront(prt_ctx * ctx, const DevCamera & cam, const RaySource * rays, unsigned long long ray_base, const DevParams & P, bool ring,
+                     bool count_visits, unsigned int n_samples, size_t lds, unsigned long long * ray_count, float * trace_ms, unsigned int * launches) {
     constexpr int BLOCK = 256;
     WaveTuning t;
     t.lds = lds;
@@ -533,7 +542,10 @@ int render_wavefront(prt_ctx * ctx, const DevCamera & cam, const DevParams & P, 
         }
         const unsigned int gen_grid = (chain[c].B.n_samples + 255) / 256;
         if (gen_grid) {
-            if (ring) hipLaunchKernelGGL(k_raygen<true>, dim3(gen_grid), dim3(256), 0, st, cam, chain[c].P, chain[c].B);
+            const unsigned long long chain_base = ray_base + chain[c].B.sample_base;      // in the caller's arrays
+            if (rays && ring) hipLaunchKernelGGL(k_raygen_rays<true>, dim3(gen_grid), dim3(256), 0, st, rays->A, chain[c].P, chain[c].B, chain_base);
+            else if (rays) hipLaunchKernelGGL(k_raygen_rays<false>, dim3(gen_grid), dim3(256), 0, st, rays->A, chain[c].P, chain[c].B, chain_base);
+            else if (ring) hipLaunchKernelGGL(k_raygen<true>, dim3(gen_grid), dim3(256), 0, st, cam, chain[c].P, chain[c].B);
             else hipLaunchKernelGGL(k_raygen<false>, dim3(gen_grid), dim3(256), 0, st, cam, chain[c].P, chain[c].B);
             HIP_TRY(ctx, hipGetLastError());
         }
@@ -802,11 +814,13 @@ int render_pixels(prt_ctx * ctx, const prt_camera * cam_in, const prt_params * p
                   const PixelSet & px, float4 * d_out, prt_counters * counters);
 
 // Renders the pixel set into d_out (device, float4 per pixel, packed in local pixel order).  Synchronous.
+// rays (prt_render_rays): output i of the set is the mean over the caller's rays i * spp .. of it, not a pixel of cam_in (null);
+// wavefront pipeline, fixed spp, item order = ray order.
 int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_params * params, uint32_t width, uint32_t height,
-                       const PixelSet & px, float4 * d_out, prt_counters * counters, bool * park_overflow) {
+                       const PixelSet & px, float4 * d_out, prt_counters * counters, bool * park_overflow, const RaySource * rays = nullptr) {
     *park_overflow = false;
     if (!ctx->has_scene) { ctx->error = "prt_render: no scene uploaded"; return -2; }
-    if (!cam_in || !params || !width || !height) { ctx->error = "prt_render: null camera / params or empty image"; return -1; }
+    if ((!cam_in && !rays) || !params || !width || !height) { ctx->error = "prt_render: null camera / params or empty image"; return -1; }
     if (params->spp == 0 || params->spp > 65535) { ctx->error = "prt_render: spp must be in 1..65535 (prt_key.h packs the sample in 16 bits)"; return -1; }
     if (params->bounce_depth > 16) { ctx->error = "prt_render: bounce_depth > 16 not supported"; return -1; }
     if ((uint64_t)width * height >= (1ull << 32)) { ctx->error = "prt_render: image has 2^32 pixels or more"; return -1; }
@@ -825,12 +839,15 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
     }
 
     DevCamera cam;
-    cam.position = ld3(cam_in->position);
-    cam.forward = ld3(cam_in->forward);
-    cam.right_scaled = ld3(cam_in->right) * cam_in->tan_a2 * cam_in->aspect;      // main.cpp:170
-    cam.up_scaled = ld3(cam_in->up) * cam_in->tan_a2;                              // main.cpp:171
-    cam.inv_width = cam_in->inv_width;
-    cam.inv_height = cam_in->inv_height;
+    memset(&cam, 0, sizeof(cam));
+    if (!rays) {
+        cam.position = ld3(cam_in->position);
+        cam.forward = ld3(cam_in->forward);
+        cam.right_scaled = ld3(cam_in->right) * cam_in->tan_a2 * cam_in->aspect;      // main.cpp:170
+        cam.up_scaled = ld3(cam_in->up) * cam_in->tan_a2;                              // main.cpp:171
+        cam.inv_width = cam_in->inv_width;
+        cam.inv_height = cam_in->inv_height;
+    }
 
     DevParams P;
     P.ray_bias = params->ray_bias;
@@ -845,8 +862,10 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
     P.variance_threshold = params->variance_threshold > 0.0f ? params->variance_threshold : 0.01f;    // main.cpp:254
     P.width = width;
     P.height = height;
+    // (where the primary rays start: the camera position, or the largest |origin component| of the caller's rays)
     float extent = ctx->scene_abs_max;
-    for (int a = 0; a < 3; ++a) extent = std::max(extent, fabsf(cam_in->position[a]));
+    if (rays) extent = std::max(extent, rays->origin_abs_max);
+    else for (int a = 0; a < 3; ++a) extent = std::max(extent, fabsf(cam_in->position[a]));
     P.box_pad = extent * (1.0f / 65536.0f);
     P.first_pixel = px.first_pixel;
     P.shard_block_rows = std::max(1u, px.block_rows);
@@ -859,18 +878,19 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
         // which copy of the light table: the shadow-tree roots, or every root at 0 - the option, trees of an older geometry, or a
         // call whose shadow-ray origins the upload's exclusion bound does not cover (include/prt.h "Shadow trees")
         bool trees = opt.shadow_trees != 0 && ctx->shadow_trees_fresh && fabsf(params->ray_bias) <= ctx->shadow_bias_max;
-        for (int a = 0; a < 3; ++a) trees = trees && fabsf(cam_in->position[a]) <= ctx->shadow_cam_max;
+        if (rays) trees = trees && rays->origin_abs_max <= ctx->shadow_cam_max;
+        else for (int a = 0; a < 3; ++a) trees = trees && fabsf(cam_in->position[a]) <= ctx->shadow_cam_max;
         ctx->scene.lights = ctx->lights.p + (trees ? 0u : ctx->light_stride);
     }
     P.elide_dead_shadow_rays = opt.trace_dead_shadow_rays ? 0u : 1u;
     // tiled work order: sets made of full-width rows only (a whole frame or a range that starts at a row, row-block shards)
     P.tile_pixels = 0;
-    if (!px.d_pixel_list && width % 8u == 0u && !opt.no_tiles) {
+    if (!rays && !px.d_pixel_list && width % 8u == 0u && !opt.no_tiles) {
         const bool rows = px.nranks > 1 ? std::max(1u, px.block_rows) % 8u == 0u : px.first_pixel % width == 0u;
         if (rows) P.tile_pixels = px.n_pixels / (8u * width) * (8u * width);
     }
 
-    P.work_reverse_n = (opt.work_reverse > 0 && !px.d_pixel_list) ? px.n_pixels : 0u;
+    P.work_reverse_n = (opt.work_reverse > 0 && !px.d_pixel_list && !rays) ? px.n_pixels : 0u;
     P.work_scatter_n = 0; P.work_scatter_mul = 1;
     if (opt.work_scatter > 0 && !px.d_pixel_list && P.tile_pixels >= 64u) {
         // a multiplier near n / golden ratio spreads consecutive chunks far apart; coprime to n, and (n - 1) * mul must fit 32 bits
@@ -1050,11 +1070,11 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
                            : launch_pool<PRT_POOL_BLOCK, PRT_DEEP_WAVES, false, true, false, false, 1>(ctx, count_visits, cam, P, n_samples, stack_entries);
             launches += 1;
         } else {
-            unsigned long long rays = 0;
+            unsigned long long n_rays = 0;
             float tms = 0.0f;
             unsigned int nl = 0;
-            rc = render_wavefront(ctx, cam, P, ring, count_visits, n_samples, lds, &rays, &tms, &nl);
-            host_ray_count += rays;
+            rc = render_wavefront(ctx, cam, rays, (unsigned long long)p0 * P.spp, P, ring, count_visits, n_samples, lds, &n_rays, &tms, &nl);
+            host_ray_count += n_rays;
             trace_ms_accum += tms;
             launches += nl;
         }
@@ -2133,6 +2153,99 @@ int hemisphere_visibility(prt_ctx * ctx, const prt_hemi_batch * b, const prt_hem
     return 0;
 }
 
+// ---- radiance along the caller's rays (prt_render_rays, kernels_rays.h) -----------------------------------------------------------
+
+// The checks both entry points share; 1 = nothing to do (count 0: counters zeroed), 0 = go on, < 0 = error.
+int rays_check(prt_ctx * ctx, const prt_radiance_batch * b, const prt_params * params, const void * out, prt_counters * counters) {
+    if (!ctx) return -1;
+    if (!b || !params) { ctx->error = "prt_render_rays: null batch or params"; return -1; }
+    if (b->count && (!b->origins || !b->directions || !out)) { ctx->error = "prt_render_rays: null origins, directions or output"; return -1; }
+    if (b->flags & ~(uint32_t)PRT_RAYS_CAMERA_STREAM) { ctx->error = "prt_render_rays: unknown flag"; return -1; }
+    if (params->spp == 0 || params->spp > 65535) { ctx->error = "prt_render_rays: spp must be in 1..65535 (prt_key.h packs the sample in 16 bits)"; return -1; }
+    if (params->bounce_depth > 16) { ctx->error = "prt_render_rays: bounce_depth > 16 not supported"; return -1; }
+    if (b->first > (1ull << 32) || (unsigned long long)b->count > (1ull << 32) - b->first) {
+        ctx->error = "prt_render_rays: first + count exceeds 2^32 (the output index is the key's pixel word)";
+        return -1;
+    }
+    if (params->max_spp > params->spp) { ctx->error = "prt_render_rays: adaptive sampling (max_spp > spp) is not supported for caller rays"; return -1; }
+    const unsigned int pipeline = params->pipeline & PRT_PIPELINE_MASK;
+    if (pipeline != PRT_PIPELINE_DEFAULT && pipeline != PRT_PIPELINE_WAVEFRONT) {
+        ctx->error = "prt_render_rays: runs on PRT_PIPELINE_WAVEFRONT (or DEFAULT) only";
+        return -1;
+    }
+    if (!ctx->has_scene) { ctx->error = "prt_render_rays: no scene uploaded"; return -2; }
+    if (b->count == 0) {
+        if (counters) memset(counters, 0, sizeof(*counters));
+        return 1;
+    }
+    return 0;
+}
+
+// prt_render_rays and prt_render_rays_device after rays_check: `device` says where the arrays live.  The domain check comes before
+// anything is rendered or written; the render itself is render_pixels_once with the rays in the camera's place.
+int render_rays(prt_ctx * ctx, const prt_radiance_batch * b, const prt_params * params, float4 * out, prt_counters * counters, bool device) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    const size_t n = b->count;
+    const unsigned long long n_rays = (unsigned long long)n * params->spp;
+    RaySource src;
+    memset(&src, 0, sizeof(src));
+    RaysArgs & A = src.A;
+    A.origins = b->origins; A.directions = b->directions;
+    A.n_rays = n_rays;
+    A.ray_bias = params->ray_bias;
+    A.origin_max = 64.0f * ctx->scene_abs_max;
+    A.first = (unsigned int)b->first;
+    A.camera_stream = (b->flags & PRT_RAYS_CAMERA_STREAM) ? 1u : 0u;
+    StageList io;
+    if (!device) {
+        io.out(&out, 16 * n, true);                        // first in the slab: k_resolve stores float4
+        io.in(&A.origins, 12 * (size_t)n_rays); io.in(&A.directions, 12 * (size_t)n_rays);
+        HIP_TRY(ctx, io.carve(ctx->q_io));
+        HIP_TRY(ctx, io.upload(stream));
+    }
+    HIP_TRY(ctx, ctx->rays_words.ensure(RAYS_WORDS));
+    A.words = ctx->rays_words.p;
+
+    // ---- the domain, before anything is rendered
+    HIP_TRY(ctx, hipEventRecord(ctx->ev[2], stream));
+    HIP_TRY(ctx, hipMemsetAsync(A.words, 0, RAYS_W_FIRST * sizeof(unsigned long long), stream));
+    HIP_TRY(ctx, hipMemsetAsync(A.words + RAYS_W_FIRST, 0xFF, sizeof(unsigned long long), stream));
+    {
+        const unsigned long long want = (n_rays + 255ull) / 256ull;
+        const unsigned int grid = (unsigned int)std::max(1ull, std::min(want, (unsigned long long)std::max(1, ctx->cu_count) * 8ull));
+        hipLaunchKernelGGL(k_rays_check, dim3(grid), dim3(256), 0, stream, A);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev[3], stream));
+    unsigned long long words[RAYS_WORDS] = { 0ull, 0ull, 0ull };
+    HIP_TRY(ctx, hipMemcpyAsync(words, A.words, sizeof(words), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    if (words[RAYS_W_OUTSIDE]) {
+        char msg[256];
+        snprintf(msg, sizeof(msg), "prt_render_rays: %llu of %llu rays lie outside the domain (a component that is not finite, a direction that is not "
+                 "unit length, an origin beyond 64 x the scene's extent); the first is ray %llu", words[RAYS_W_OUTSIDE], n_rays, words[RAYS_W_FIRST]);
+        ctx->error = msg;
+        return -1;
+    }
+    float check_ms = 0.0f;
+    HIP_TRY(ctx, hipEventElapsedTime(&check_ms, ctx->ev[2], ctx->ev[3]));
+    const unsigned int extent_bits = (unsigned int)words[RAYS_W_EXTENT];
+    memcpy(&src.origin_abs_max, &extent_bits, 4);
+
+    prt_params pp = *params;
+    pp.pipeline = PRT_PIPELINE_WAVEFRONT | (params->pipeline & PRT_FLAG_COUNT_VISITS);
+    const PixelSet px = { b->count, (uint32_t)b->first, 1, 0, 1, nullptr };
+    bool park_overflow = false;            // the pool pipeline's
+    if (const int rc = render_pixels_once(ctx, nullptr, &pp, 1, 1, px, out, counters, &park_overflow, &src)) return rc;
+    if (counters) counters->render_ms += check_ms;
+    if (!device) {
+        HIP_TRY(ctx, io.download(stream));
+        HIP_TRY(ctx, hipStreamSynchronize(stream));
+    }
+    return 0;
+}
+
 // ---- surface samples (prt_sample_surface, kernels_sample.h) ------------------------------------------------------------------------
 
 unsigned int sample_fields(const prt_sample_buffers * o) {
@@ -2924,6 +3037,22 @@ int prt_hemisphere_visibility(prt_ctx * ctx, const prt_hemi_batch * batch, const
     if (chk) return chk > 0 ? 0 : chk;
     return hemisphere_visibility(ctx, batch, out, flags, counters, false);
     PRT_API_CATCH_RC(ctx, "prt_hemisphere_visibility")
+}
+
+int prt_render_rays_device(prt_ctx * ctx, const prt_radiance_batch * batch, const prt_params * params, void * d_rgba_out, prt_counters * counters) {
+    PRT_API_TRY
+    const int chk = rays_check(ctx, batch, params, d_rgba_out, counters);
+    if (chk) return chk < 0 ? chk : 0;
+    return render_rays(ctx, batch, params, (float4 *)d_rgba_out, counters, true);
+    PRT_API_CATCH_RC(ctx, "prt_render_rays_device")
+}
+
+int prt_render_rays(prt_ctx * ctx, const prt_radiance_batch * batch, const prt_params * params, float * rgba_out, prt_counters * counters) {
+    PRT_API_TRY
+    const int chk = rays_check(ctx, batch, params, rgba_out, counters);
+    if (chk) return chk < 0 ? chk : 0;
+    return render_rays(ctx, batch, params, (float4 *)rgba_out, counters, false);
+    PRT_API_CATCH_RC(ctx, "prt_render_rays")
 }
 
 int prt_update_geometry(prt_ctx * ctx, const prt_geometry_update * update, prt_update_info * info) {
