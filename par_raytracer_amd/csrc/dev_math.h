@@ -36,6 +36,16 @@ PRT_HD f3 normalize3(f3 a) {
     if (length_sq == 0.0f) return a;
     return a / sqrtf(length_sq);
 }
+// The 48-byte triangle record of DevScene::tris (dev_scene.h): a, ab = b - a, ac = c - a and n = Cross(ab, ac), packed into three
+// float4.  The upload, the refit kernel and the tests' host harnesses all write it through here; returns n.
+PRT_HD f3 tri_record(f3 a, f3 b, f3 c, float4 * rec) {
+    const f3 ab = b - a, ac = c - a;                              // raytracer.cpp:85-86
+    const f3 n = cross3(ab, ac);                                  // raytracer.cpp:91
+    rec[0] = make_float4(a.x, a.y, a.z, ab.x);
+    rec[1] = make_float4(ab.y, ab.z, ac.x, ac.y);
+    rec[2] = make_float4(ac.z, n.x, n.y, n.z);
+    return n;
+}
 PRT_HD float ref_max(float a, float b) { return a > b ? a : b; }
 PRT_HD float ref_min(float a, float b) { return a < b ? a : b; }
 

@@ -62,12 +62,7 @@ __global__ __launch_bounds__(256) void k_refit_records(RefitArgs A) {
                 n12 = *reinterpret_cast<const uint2 *>(t + 4);
     const float * pa = A.positions + 3 * (size_t)i01.x, * pb = A.positions + 3 * (size_t)i01.y, * pc = A.positions + 3 * (size_t)i2n0.x;
     const f3 a = mk3(pa[0], pa[1], pa[2]), b = mk3(pb[0], pb[1], pb[2]), c = mk3(pc[0], pc[1], pc[2]);
-    const f3 ab = b - a, ac = c - a;                              // raytracer.cpp:85-86
-    const f3 n = cross3(ab, ac);                                  // raytracer.cpp:91
-    float4 * tr = A.tris + 3 * (size_t)slot;
-    tr[0] = make_float4(a.x, a.y, a.z, ab.x);
-    tr[1] = make_float4(ab.y, ab.z, ac.x, ac.y);
-    tr[2] = make_float4(ac.z, n.x, n.y, n.z);
+    const f3 n = tri_record(a, b, c, A.tris + 3 * (size_t)slot);
     float4 * sh = A.shade + 4 * (size_t)slot;
     if (A.normals) {
         const float * n0 = A.normals + 3 * (size_t)i2n0.y, * n1 = A.normals + 3 * (size_t)n12.x, * n2 = A.normals + 3 * (size_t)n12.y;

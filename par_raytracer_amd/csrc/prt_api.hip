@@ -2661,13 +2661,7 @@ int prt_upload_scene(prt_ctx * ctx, const prt_scene_desc * s) {
     float abs_max = 0.0f;
     // input triangle t's 48-byte record at `slot` of the record array; returns n
     auto put_tri_record = [&](uint32_t t, size_t slot) {
-        const f3 a = ld3(&verts[(size_t)t * 9]), b = ld3(&verts[(size_t)t * 9 + 3]), c = ld3(&verts[(size_t)t * 9 + 6]);
-        const f3 ab = b - a, ac = c - a;                          // raytracer.cpp:85-86
-        const f3 n = cross3(ab, ac);                              // raytracer.cpp:91
-        tris[slot * 3 + 0] = make_float4(a.x, a.y, a.z, ab.x);
-        tris[slot * 3 + 1] = make_float4(ab.y, ab.z, ac.x, ac.y);
-        tris[slot * 3 + 2] = make_float4(ac.z, n.x, n.y, n.z);
-        return n;
+        return tri_record(ld3(&verts[(size_t)t * 9]), ld3(&verts[(size_t)t * 9 + 3]), ld3(&verts[(size_t)t * 9 + 6]), &tris[slot * 3]);
     };
     std::vector<float> rec_normals((size_t)n_tris * 3);          // per INPUT triangle: n as its record holds it (the shadow trees classify by it)
     for (uint32_t slot = 0; slot < n_tris; ++slot) {

@@ -4,13 +4,12 @@ tests/closest_host_harness.cpp (the walk of csrc/dev_closest.h and a brute force
 at a time on the host) and the case builders of the schedule tests (pure numpy, seeded)."""
 from __future__ import annotations
 
-import os
 import struct
-import subprocess
 
 import numpy as np
 
-from query_grad_cases import ROOT, bits, flat_desc, one_triangle, scene_mesh       # noqa: F401  (re-exported)
+import harness
+from query_grad_cases import bits, flat_desc, one_triangle, scene_mesh       # noqa: F401  (re-exported)
 
 FIXTURES = ("cornell_box", "icosphere_l3", "coincident", "terrain_64")
 RECIPE_POINTS = 2048
@@ -122,19 +121,8 @@ def input_triangle(mesh, group, vertex0):
 # ---- the host harness
 
 def build_harness(directory, sanitize=False, bvh8=False):
-    exe = os.path.join(str(directory), "closest_host" + ("8" if bvh8 else "") + ("_san" if sanitize else ""))
-    csrc = os.path.join(ROOT, "par_raytracer_amd", "csrc")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-pthread"]
-    if bvh8:
-        cmd += ["-DPRT_BVH8"]
-    if sanitize:
-        # the sanitizer runtimes are linked statically: the program then starts whatever else the environment loads ahead of it
-        cmd += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan"]
-    cmd += ["-I" + os.path.join(ROOT, "tests", "hip_shim"), "-I" + csrc, os.path.join(ROOT, "tests", "closest_host_harness.cpp"),
-            os.path.join(csrc, "bvh_build.cpp"), "-o", exe]
-    build = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    assert build.returncode == 0, build.stdout.decode()
-    return exe
+    return harness.build("closest_host_harness.cpp", directory, "closest_host" + ("8" if bvh8 else "") + ("_san" if sanitize else ""),
+                         sanitize=sanitize, bvh8=bvh8, sources=("bvh_build.cpp",))
 
 
 def case(mesh, points, max_dist2=None, pair_tri=None, stack_cap=None):
@@ -146,7 +134,7 @@ def run_harness(exe, cases, directory):
     """Every case through the harness in one run.  Per case a dict: walked cases - mismatches, tie_points, node_visits, tri_tests,
     "brute" and "walk" ({field: array}), with a stack cap also stack_cap (the cap in effect: clamped to 2..40 and to the tree's
     stack_bound) and listed (u32 per point: the capped walk dropped a push); pair cases - d2, v, w, ok."""
-    fin, fout = os.path.join(str(directory), "closest_cases.bin"), os.path.join(str(directory), "closest_results.bin")
+    fin, fout = harness.case_files(directory, "closest_cases.bin", "closest_results.bin")
     with open(fin, "wb") as f:
         f.write(struct.pack("<I", len(cases)))
         for c in cases:
@@ -157,62 +145,38 @@ def run_harness(exe, cases, directory):
             f.write(struct.pack("<6I", n, p.shape[0], idx.size, runs.shape[0], flags, cap or 0))
             f.write(c["points"].tobytes())
             if c["max_dist2"] is not None:
-                f.write(np.ascontiguousarray(c["max_dist2"], np.float32).tobytes())
+                harness.put(f, (c["max_dist2"], np.float32))
             if c["pair_tri"] is not None:
-                f.write(np.ascontiguousarray(c["pair_tri"], np.uint32).tobytes())
-            for arr, dt in ((p, np.float32), (idx, np.uint32), (runs, np.uint32)):
-                f.write(np.ascontiguousarray(arr, dt).tobytes())
-    run = subprocess.run([exe, fin, fout], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    assert run.returncode == 0, run.stdout.decode()[-4000:]
-    blob = open(fout, "rb").read()
-    at, out = 0, []
-
-    def take(count, dt):
-        nonlocal at
-        a = np.frombuffer(blob, dt, count, at).copy()
-        at += a.nbytes
-        return a
+                harness.put(f, (c["pair_tri"], np.uint32))
+            harness.put(f, (p, np.float32), (idx, np.uint32), (runs, np.uint32))
+    harness.run(exe, fin, fout)
+    r, out = harness.Reader.of_file(fout), []
     for c in cases:
         n = c["points"].shape[0]
-        mism, ties, nodes, tris = struct.unpack_from("<iIQQ", blob, at)
-        at += 24
+        mism, ties, nodes, tris = r.unpack("<iIQQ")
         if c["pair_tri"] is not None:
-            out.append(dict(d2=take(n, np.float32), v=take(n, np.float32), w=take(n, np.float32), ok=take(n, np.uint32)))
+            out.append(dict(d2=r.take(n, np.float32), v=r.take(n, np.float32), w=r.take(n, np.float32), ok=r.take(n, np.uint32)))
             continue
-        r = dict(mismatches=mism, tie_points=ties, node_visits=nodes, tri_tests=tris)
+        res = dict(mismatches=mism, tie_points=ties, node_visits=nodes, tri_tests=tris)
         for which in ("brute", "walk"):
-            r[which] = dict(dist2=take(n, np.float32), point=take(3 * n, np.float32).reshape(n, 3), bw=take(3 * n, np.float32).reshape(n, 3),
-                            vertex0=take(n, np.uint32), group=take(n, np.int32))
+            res[which] = dict(dist2=r.take(n, np.float32), point=r.take(3 * n, np.float32, (n, 3)), bw=r.take(3 * n, np.float32, (n, 3)),
+                              vertex0=r.take(n, np.uint32), group=r.take(n, np.int32))
         if c.get("stack_cap") is not None:
-            r["stack_cap"] = int(take(1, np.uint32)[0])
-            r["listed"] = take(n, np.uint32)
-        out.append(r)
-    assert at == len(blob)
+            res["stack_cap"] = int(r.take(1, np.uint32)[0])
+            res["listed"] = r.take(n, np.uint32)
+        out.append(res)
+    r.done()
     return out
 
 
 def assert_same_bits(got, expect, what, fields=FIELDS):
     """Every field of `got` ({field: numpy array}) equals `expect` bit for bit."""
-    for k in fields:
-        g = np.ascontiguousarray(got[k])
-        g = g.view(np.uint32) if g.dtype != np.uint32 else g
-        e = np.ascontiguousarray(expect[k])
-        e = e.view(np.uint32) if e.dtype != np.uint32 else e
-        bad = np.nonzero(np.any((g != e).reshape(len(e), -1), axis=1))[0]
-        assert bad.size == 0, "%s: field %s differs on %d of %d points, first %d: got %r, expected %r" % (
-            what, k, bad.size, len(e), bad[0], got[k][bad[0]], expect[k][bad[0]])
+    harness.assert_same_bits(got, expect, what, fields)
 
 
 def to_numpy(res):
     """A closest_points result with torch tensors -> numpy arrays (vertex0 back to uint32)."""
-    out = {}
-    for k, v in res.items():
-        if k == "counters":
-            out[k] = v
-        else:
-            a = v.cpu().numpy() if hasattr(v, "cpu") else v
-            out[k] = a.view(np.uint32) if k == "vertex0" else a
-    return out
+    return harness.to_numpy(res, ("vertex0",))
 
 
 # ---- case builders of the schedule tests (tests/test_closest_cases_host.py proves them, tests/test_gpu_closest_schedules.py runs them)

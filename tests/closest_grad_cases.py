@@ -4,15 +4,14 @@ the per-region function of csrc/dev_closest_grad.h, in float64 and float32, each
 points only) and the case builders both suites use (pure numpy, seeded)."""
 from __future__ import annotations
 
-import os
 import struct
-import subprocess
 
 import numpy as np
 
 import closest_cases as C
+import harness
 import query_grad_cases as Q
-from query_grad_cases import ROOT, bits, flat_desc, one_triangle, scene_mesh       # noqa: F401  (re-exported)
+from query_grad_cases import bits, flat_desc, one_triangle, scene_mesh       # noqa: F401  (re-exported)
 
 GRADS = ("positions", "points")
 GOUT_KEYS = ("dist2", "point", "bw")
@@ -27,16 +26,7 @@ REGION_NAMES = ("vertex a", "vertex b", "edge ab", "vertex c", "edge ac", "edge 
 # ---- the host harness
 
 def build_harness(directory, sanitize):
-    exe = os.path.join(str(directory), "closest_grad_host" + ("_san" if sanitize else ""))
-    csrc = os.path.join(ROOT, "par_raytracer_amd", "csrc")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-pthread"]
-    if sanitize:
-        # the sanitizer runtimes are linked statically: the program then starts whatever else the environment loads ahead of it
-        cmd += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan"]
-    cmd += ["-I" + os.path.join(ROOT, "tests", "hip_shim"), "-I" + csrc, os.path.join(ROOT, "tests", "closest_grad_host_harness.cpp"), "-o", exe]
-    build = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    assert build.returncode == 0, build.stdout.decode()
-    return exe
+    return harness.build("closest_grad_host_harness.cpp", directory, "closest_grad_host" + ("_san" if sanitize else ""), sanitize=sanitize)
 
 
 def case(mesh, points, group, vertex0, gout=None, merge=False):
@@ -48,7 +38,7 @@ def run_harness(exe, cases, directory):
     """Every case through the harness in one run; returns per case a dict: rc, hit_rays, skipped_rays, invalid, unit_exponent,
     max_contribution, positions and points (the output buffers as the call left them: the sentinel SENTINEL everywhere after a
     refusal) and - rc 0 - contrib (n, 9), region (n,)."""
-    fin, fout = os.path.join(str(directory), "cg_cases.bin"), os.path.join(str(directory), "cg_results.bin")
+    fin, fout = harness.case_files(directory, "cg_cases.bin", "cg_results.bin")
     with open(fin, "wb") as f:
         f.write(struct.pack("<I", len(cases)))
         for c in cases:
@@ -56,30 +46,21 @@ def run_harness(exe, cases, directory):
             n = len(c["group"])
             flags = sum(1 << i for i, k in enumerate(GOUT_KEYS) if c["gout"].get(k) is not None) | (16 if c["merge"] else 0)
             f.write(struct.pack("<5I", n, p.shape[0], idx.size, runs.shape[0], flags))
-            for arr, dt in ((c["points"], np.float32), (c["group"], np.int32), (c["vertex0"], np.uint32), (p, np.float32), (idx, np.uint32),
-                            (runs, np.uint32)):
-                f.write(np.ascontiguousarray(arr, dt).tobytes())
-            for k in GOUT_KEYS:
-                if c["gout"].get(k) is not None:
-                    f.write(np.ascontiguousarray(c["gout"][k], np.float32).tobytes())
-    run = subprocess.run([exe, fin, fout], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
-    assert run.returncode == 0, run.stdout.decode()[-4000:]
-    blob = open(fout, "rb").read()
-    at, out = 0, []
+            harness.put(f, (c["points"], np.float32), (c["group"], np.int32), (c["vertex0"], np.uint32), (p, np.float32), (idx, np.uint32),
+                        (runs, np.uint32), *((c["gout"][k], np.float32) for k in GOUT_KEYS if c["gout"].get(k) is not None))
+    harness.run(exe, fin, fout, timeout=300)
+    blob, out = harness.Reader.of_file(fout), []
     for c in cases:
-        rc, hit, skipped, invalid, unit, m = struct.unpack_from("<iIIIif", blob, at)
-        at += 24
+        rc, hit, skipped, invalid, unit, m = blob.unpack("<iIIIif")
         r = dict(rc=rc, hit_rays=hit, skipped_rays=skipped, invalid=invalid, unit_exponent=unit, max_contribution=np.float32(m))
         n, n_pos = len(c["group"]), c["mesh"][0].shape[0]
         fields = (("positions", (n_pos, 3), np.float32), ("points", (n, 3), np.float32))       # written on a refusal too
         if rc == 0:
             fields += (("contrib", (n, 9), np.float32), ("region", (n,), np.int32))
         for k, shape, dt in fields:
-            size = int(np.prod(shape))
-            r[k] = np.frombuffer(blob, dt, size, at).reshape(shape).copy()
-            at += 4 * size
+            r[k] = blob.take(np.prod(shape), dt, shape)
         out.append(r)
-    assert at == len(blob)
+    blob.done()
     return out
 
 

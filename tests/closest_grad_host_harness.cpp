@@ -27,8 +27,6 @@
 
 #include <hip/hip_runtime.h>            // tests/hip_shim: one lane at a time
 using std::isfinite;
-struct uint2 { unsigned int x, y; };
-static inline uint2 make_uint2(unsigned int x, unsigned int y) { uint2 r = { x, y }; return r; }
 // what the kernels need beyond the shim.  A wave of one lane: the other 63 hold what an idle lane holds in the kernels'
 // reductions - 0, the neutral element of their sums and of their maximum over non-negative floats.
 static inline float __shfl_xor(float, int) { return 0.0f; }
@@ -38,19 +36,9 @@ static inline unsigned int __float_as_uint(float f) { unsigned int v; memcpy(&v,
 static inline unsigned int atomicMax(unsigned int * p, unsigned int v) { unsigned int o = *p; if (v > o) *p = v; return o; }
 
 #include "kernels_closest_grad.h"
+#include "harness_io.h"
 
 using namespace prt;
-
-template <class T>
-static std::vector<T> rd(FILE * f, size_t n) {
-    std::vector<T> v(n);
-    if (n && fread(v.data(), sizeof(T), n, f) != n) { fprintf(stderr, "closest_grad_host_harness: short input\n"); exit(2); }
-    return v;
-}
-template <class T>
-static void wr(FILE * f, const T * p, size_t n) {
-    if (n && fwrite(p, sizeof(T), n, f) != n) { fprintf(stderr, "closest_grad_host_harness: short write\n"); exit(2); }
-}
 
 template <class K, class ARGS>
 static void launch(K kernel, unsigned int grid, const ARGS & A) {
@@ -61,9 +49,8 @@ static void launch(K kernel, unsigned int grid, const ARGS & A) {
 }
 
 int main(int argc, char ** argv) {
-    if (argc != 3) { fprintf(stderr, "usage: %s cases.bin results.bin\n", argv[0]); return 2; }
-    FILE * in = fopen(argv[1], "rb"), * out = fopen(argv[2], "wb");
-    if (!in || !out) { fprintf(stderr, "closest_grad_host_harness: cannot open the files\n"); return 2; }
+    FILE * in, * out;
+    if (!open_in_out(argc, argv, "closest_grad_host", &in, &out)) return 2;
     const unsigned int n_cases = rd<unsigned int>(in, 1)[0];
     for (unsigned int cs = 0; cs < n_cases; ++cs) {
         const std::vector<unsigned int> h = rd<unsigned int>(in, 5);

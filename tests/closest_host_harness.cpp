@@ -26,25 +26,12 @@
 
 #include <hip/hip_runtime.h>            // tests/hip_shim: one lane at a time
 using std::isfinite;
-struct uint2 { unsigned int x, y; };
-static inline uint2 make_uint2(unsigned int x, unsigned int y) { uint2 r = { x, y }; return r; }
 
 #include "dev_closest.h"
-#include "bvh_build.h"
-#include "prt_options.h"
+#include "harness_io.h"
+#include "harness_mesh.h"
 
 using namespace prt;
-
-template <class T>
-static std::vector<T> rd(FILE * f, size_t n) {
-    std::vector<T> v(n);
-    if (n && fread(v.data(), sizeof(T), n, f) != n) { fprintf(stderr, "closest_host: short read\n"); exit(2); }
-    return v;
-}
-template <class T>
-static void wr(FILE * f, const std::vector<T> & v) {
-    if (!v.empty() && fwrite(v.data(), sizeof(T), v.size(), f) != v.size()) { fprintf(stderr, "closest_host: short write\n"); exit(2); }
-}
 
 struct Answers {
     std::vector<float> dist2, point, bw;
@@ -91,9 +78,8 @@ static bool lane_lists_point(const DevScene & sc, f3 p, float max_d2, float pad,
 }
 
 int main(int argc, char ** argv) {
-    if (argc < 3) { fprintf(stderr, "usage: closest_host cases.bin results.bin\n"); return 2; }
-    FILE * fin = fopen(argv[1], "rb"), * fout = fopen(argv[2], "wb");
-    if (!fin || !fout) { fprintf(stderr, "closest_host: cannot open the files\n"); return 2; }
+    FILE * fin, * fout;
+    if (!open_in_out(argc, argv, "closest_host", &fin, &fout)) return 2;
     const uint32_t n_cases = rd<uint32_t>(fin, 1)[0];
     for (uint32_t ci = 0; ci < n_cases; ++ci) {
         const std::vector<uint32_t> hd = rd<uint32_t>(fin, 6);
@@ -105,10 +91,8 @@ int main(int argc, char ** argv) {
         const std::vector<uint32_t> idx = rd<uint32_t>(fin, n_idx);
         const std::vector<uint32_t> runs = rd<uint32_t>(fin, 2 * (size_t)n_groups);
 
-        std::vector<float> verts(9 * (size_t)n_tris);
+        const std::vector<float> verts = mesh::unindexed(pos, idx);
         float abs_max = 0.0f;
-        for (uint32_t t = 0; t < n_tris; ++t)
-            for (int c = 0; c < 3; ++c) memcpy(&verts[9 * (size_t)t + 3 * c], &pos[3 * (size_t)idx[3 * t + c]], 12);
         for (float v : verts) abs_max = std::max(abs_max, fabsf(v));
         uint64_t header[3] = { 0, 0, 0 };
 
@@ -126,36 +110,14 @@ int main(int argc, char ** argv) {
         }
 
         BvhWide bvh;
-#if !defined(PRT_BVH8)
-        build_bvh_wide(4, verts.data(), n_tris, 4, 2, &bvh);
-#else
-        BvhBuildOptions bopt;
-        build_bvh_wide(8, verts.data(), n_tris, 4, 2, &bvh, 1.0f, &bopt);
-#endif
-        // device records and the leaf table, as prt_upload_scene and the queries lay them out
-        std::vector<float4> tris((size_t)(n_tris + 1) * 3, make_float4(0, 0, 0, 0));
-        std::vector<uint2> of_input(n_tris, make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu)), leaf_map((size_t)n_tris + 1, make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu));
-        for (uint32_t g = 0; g < n_groups; ++g)
-            for (uint32_t k = 0; k < runs[2 * g + 1] / 3; ++k) of_input[runs[2 * g] / 3 + k] = make_uint2(g, 3u * k);
-        for (uint32_t slot = 0; slot < n_tris; ++slot) {
-            const float * v = &verts[(size_t)bvh.tri_order[slot] * 9];
-            const f3 a = mk3(v[0], v[1], v[2]), b = mk3(v[3], v[4], v[5]), c = mk3(v[6], v[7], v[8]);
-            const f3 ab = b - a, ac = c - a, nn = cross3(ab, ac);
-            tris[(size_t)slot * 3 + 0] = make_float4(a.x, a.y, a.z, ab.x);
-            tris[(size_t)slot * 3 + 1] = make_float4(ab.y, ab.z, ac.x, ac.y);
-            tris[(size_t)slot * 3 + 2] = make_float4(ac.z, nn.x, nn.y, nn.z);
-            leaf_map[slot] = of_input[bvh.tri_order[slot]];
-        }
-        DevScene sc;
-        memset(&sc, 0, sizeof(sc));
-        sc.nodes = reinterpret_cast<const float4 *>(bvh.nodes.data());
-        sc.tris = tris.data();
-        sc.tri_count = n_tris;
-        sc.node_count = bvh.node_count;
-        std::vector<int> stack_mem((size_t)(bvh.stack_bound + 2) * STACK_ENTRY_INTS, 0);
-        GlobalStack stk;
-        stk.attach(stack_mem.data(), 0, 1);
-        TraceStats st;
+        mesh::build_tree(verts, n_tris, &bvh);
+        // device records and the leaf table, in the tree's leaf order
+        const std::vector<float4> tris = mesh::records(verts, n_tris, bvh.tri_order.data());
+        const std::vector<uint2> leaf_map = mesh::leaf_map(runs, n_groups, n_tris, bvh.tri_order.data());
+        mesh::Walk lane(bvh, tris, n_tris);
+        const DevScene & sc = lane.sc;
+        GlobalStack & stk = lane.stk;
+        TraceStats & st = lane.st;
 
         float extent = abs_max;                               // the pad's rule: 2^-16 x max(scene, finite points of the batch)
         for (uint32_t i = 0; i < n; ++i) {

@@ -9,13 +9,12 @@ import ctypes
 import ctypes.util
 import os
 import struct
-import subprocess
 
 import numpy as np
 
 import closest_cases as K
+import harness
 import signed_cases as S
-from closest_cases import ROOT
 
 FIELDS = ("unoccluded", "visibility", "bent")
 INVALID = np.uint32(0xFFFFFFFF)
@@ -23,14 +22,7 @@ RAY_BIAS = np.float32(1e-3)
 
 
 def build_harness(directory, bvh8=False):
-    exe = os.path.join(str(directory), "hemi_host" + ("_bvh8" if bvh8 else ""))
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off"] + (["-DPRT_BVH8"] if bvh8 else [])
-    cmd += ["-I" + os.path.join(ROOT, "tests", "hip_shim"), "-I" + os.path.join(ROOT, "par_raytracer_amd", "csrc"),
-            os.path.join(ROOT, "tests", "hemi_host_harness.cpp"), os.path.join(ROOT, "par_raytracer_amd", "csrc", "bvh_build.cpp"),
-            "-pthread", "-o", exe]
-    build = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    assert build.returncode == 0, build.stdout.decode()
-    return exe
+    return harness.build("hemi_host_harness.cpp", directory, "hemi_host" + ("_bvh8" if bvh8 else ""), bvh8=bvh8, sources=("bvh_build.cpp",))
 
 
 def case(mesh, points, normals, samples, seed=0, first=0, ray_bias=RAY_BIAS, max_dist=None):
@@ -46,7 +38,7 @@ def case(mesh, points, normals, samples, seed=0, first=0, ray_bias=RAY_BIAS, max
 def run_harness(exe, cases, directory, tag="hemi"):
     """Every case through the harness in one run.  Per case a dict: per ray "k" (n, samples), "dirs" (n, samples, 3), "brute" and
     "walk" (n, samples: 1 = unoccluded); per point the three FIELDS and "sums" (n, 3 int64); "cast" = the rays cast."""
-    fin, fout = os.path.join(str(directory), tag + "_cases.bin"), os.path.join(str(directory), tag + "_results.bin")
+    fin, fout = harness.case_files(directory, tag + "_cases.bin", tag + "_results.bin")
     with open(fin, "wb") as f:
         f.write(struct.pack("<I", len(cases)))
         for c in cases:
@@ -54,59 +46,40 @@ def run_harness(exe, cases, directory, tag="hemi"):
             n = c["points"].shape[0]
             f.write(struct.pack("<8I", p.shape[0], idx.size, n, c["samples"], 1 if c["max_dist"] is not None else 0, 0, 0, 0))
             f.write(struct.pack("<2Q2f", c["seed"], c["first"], float(c["ray_bias"]), 0.0))
-            f.write(np.ascontiguousarray(p, np.float32).tobytes() + np.ascontiguousarray(idx, np.uint32).tobytes())
+            harness.put(f, (p, np.float32), (idx, np.uint32))
             f.write(c["points"].tobytes() + c["normals"].tobytes())
             if c["max_dist"] is not None:
                 f.write(c["max_dist"].tobytes())
-    run = subprocess.run([exe, fin, fout], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    assert run.returncode == 0, run.stdout.decode()[-4000:]
-    blob = open(fout, "rb").read()
-    at, out = 0, []
-
-    def take(count, dt):
-        nonlocal at
-        a = np.frombuffer(blob, dt, count, at).copy()
-        at += a.nbytes
-        return a
+    harness.run(exe, fin, fout)
+    r, out = harness.Reader.of_file(fout), []
     for c in cases:
         n, s = c["points"].shape[0], c["samples"]
-        res = dict(k=take(n * s, np.uint32).reshape(n, s), dirs=take(3 * n * s, np.float32).reshape(n, s, 3),
-                   brute=take(n * s, np.uint8).reshape(n, s), walk=take(n * s, np.uint8).reshape(n, s),
-                   unoccluded=take(n, np.uint32), visibility=take(n, np.float32), bent=take(3 * n, np.float32).reshape(n, 3),
-                   sums=take(3 * n, np.int64).reshape(n, 3), cast=int(take(1, np.uint64)[0]))
-        out.append(res)
-    assert at == len(blob)
+        out.append(dict(k=r.take(n * s, np.uint32, (n, s)), dirs=r.take(3 * n * s, np.float32, (n, s, 3)),
+                        brute=r.take(n * s, np.uint8, (n, s)), walk=r.take(n * s, np.uint8, (n, s)),
+                        unoccluded=r.take(n, np.uint32), visibility=r.take(n, np.float32), bent=r.take(3 * n, np.float32, (n, 3)),
+                        sums=r.take(3 * n, np.int64, (n, 3)), cast=r.unpack("<Q")[0]))
+    r.done()
     return out
 
 
 def harness_table(exe, directory):
     """The 1024 entries of DevScene::diffuse_dirs as csrc/hammersley.h computes them with the host's libm: (1024, 4) float32."""
     fout = os.path.join(str(directory), "hemi_table.bin")
-    run = subprocess.run([exe, "--table", fout], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    assert run.returncode == 0, run.stdout.decode()[-4000:]
-    return np.frombuffer(open(fout, "rb").read(), np.float32).reshape(1024, 4).copy()
+    harness.run(exe, "--table", fout)
+    r = harness.Reader.of_file(fout)
+    table = r.take(4096, np.float32, (1024, 4))
+    r.done()
+    return table
 
 
 def assert_same_bits(got, expect, what, fields=FIELDS):
     """Every field of `got` ({field: numpy array}) equals `expect` bit for bit."""
-    for f in fields:
-        a, b = np.ascontiguousarray(got[f]), np.ascontiguousarray(expect[f])
-        assert a.shape == b.shape and a.dtype.itemsize == b.dtype.itemsize, (what, f, a.shape, b.shape, a.dtype, b.dtype)
-        same = a.view(np.uint32) == b.view(np.uint32)
-        assert same.all(), "%s: %s differs at %d of %d entries, first %r: %r != %r" % (
-            what, f, (~same).sum(), same.size, np.argwhere(~same)[0].tolist(), a[tuple(np.argwhere(~same)[0])], b[tuple(np.argwhere(~same)[0])])
+    harness.assert_same_bits(got, expect, what, fields)
 
 
 def to_numpy(res):
     """A hemisphere_visibility result with torch tensors -> numpy arrays (unoccluded back to uint32)."""
-    out = {}
-    for k, v in res.items():
-        if k == "counters":
-            out[k] = v
-        else:
-            a = v.cpu().numpy() if hasattr(v, "cpu") else v
-            out[k] = a.view(np.uint32) if k == "unoccluded" else a
-    return out
+    return harness.to_numpy(res, ("unoccluded",))
 
 
 # ---- the definition's pieces in plain numpy (uint64 arithmetic wraps)

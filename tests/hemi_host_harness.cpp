@@ -31,21 +31,10 @@ using std::isfinite;
 
 #include "dev_hemi.h"
 #include "hammersley.h"
-#include "bvh_build.h"
-#include "prt_options.h"
+#include "harness_io.h"
+#include "harness_mesh.h"
 
 using namespace prt;
-
-template <class T>
-static std::vector<T> rd(FILE * f, size_t n) {
-    std::vector<T> v(n);
-    if (n && fread(v.data(), sizeof(T), n, f) != n) { fprintf(stderr, "hemi_host: short read\n"); exit(2); }
-    return v;
-}
-template <class T>
-static void wr(FILE * f, const std::vector<T> & v) {
-    if (!v.empty() && fwrite(v.data(), sizeof(T), v.size(), f) != v.size()) { fprintf(stderr, "hemi_host: short write\n"); exit(2); }
-}
 
 int main(int argc, char ** argv) {
     std::vector<float4> table(1024);
@@ -57,8 +46,8 @@ int main(int argc, char ** argv) {
         return fclose(f) ? 2 : 0;
     }
     if (argc != 3) { fprintf(stderr, "usage: hemi_host in.bin out.bin | hemi_host --table out.bin\n"); return 2; }
-    FILE * fin = fopen(argv[1], "rb"), * fout = fopen(argv[2], "wb");
-    if (!fin || !fout) { fprintf(stderr, "hemi_host: cannot open the files\n"); return 2; }
+    FILE * fin, * fout;
+    if (!open_in_out(argc, argv, "hemi_host", &fin, &fout)) return 2;
     const uint32_t n_cases = rd<uint32_t>(fin, 1)[0];
     unsigned long long mismatches = 0;
     for (uint32_t ci = 0; ci < n_cases; ++ci) {
@@ -73,50 +62,22 @@ int main(int argc, char ** argv) {
         const std::vector<float> points = rd<float>(fin, 3 * (size_t)n_points), normals = rd<float>(fin, 3 * (size_t)n_points);
         const std::vector<float> max_dist = rd<float>(fin, (hd[4] & 1u) ? n_points : 0);
 
-        // the tree, and the records as prt_upload_scene lays them out: `brute` in input order, `tris` in the tree's leaf order
-        std::vector<float> verts(9 * (size_t)n_tris);
-        for (uint32_t t = 0; t < n_tris; ++t)
-            for (int c = 0; c < 3; ++c) memcpy(&verts[9 * (size_t)t + 3 * c], &pos[3 * (size_t)idx[3 * (size_t)t + c]], 12);
+        // the tree, and the records: `brute` in input order, `tris` in the tree's leaf order
+        const std::vector<float> verts = mesh::unindexed(pos, idx);
         BvhWide bvh;
-        if (n_tris) {
-#if !defined(PRT_BVH8)
-            build_bvh_wide(4, verts.data(), n_tris, 4, 2, &bvh);
-#else
-            BvhBuildOptions bopt;
-            build_bvh_wide(8, verts.data(), n_tris, 4, 2, &bvh, 1.0f, &bopt);
-#endif
-        }
-        auto records = [&](bool leaf_order) {
-            std::vector<float4> rec((size_t)(n_tris + 1) * 3, make_float4(0, 0, 0, 0));
-            for (uint32_t slot = 0; slot < n_tris; ++slot) {
-                const float * v = &verts[(size_t)(leaf_order ? bvh.tri_order[slot] : slot) * 9];
-                const f3 a = mk3(v[0], v[1], v[2]), b = mk3(v[3], v[4], v[5]), c = mk3(v[6], v[7], v[8]);
-                const f3 ab = b - a, ac = c - a, n = cross3(ab, ac);
-                rec[(size_t)slot * 3 + 0] = make_float4(a.x, a.y, a.z, ab.x);
-                rec[(size_t)slot * 3 + 1] = make_float4(ab.y, ab.z, ac.x, ac.y);
-                rec[(size_t)slot * 3 + 2] = make_float4(ac.z, n.x, n.y, n.z);
-            }
-            return rec;
-        };
-        const std::vector<float4> brute = records(false), tris = records(true);
+        if (n_tris) mesh::build_tree(verts, n_tris, &bvh);
+        const std::vector<float4> brute = mesh::records(verts, n_tris, nullptr), tris = mesh::records(verts, n_tris, bvh.tri_order.data());
         std::vector<unsigned int> rank(n_tris + 1, 0);
         for (uint32_t slot = 0; slot < n_tris; ++slot) rank[slot] = bvh.tri_order[slot];
         unsigned long long unresolved = 0;
-        DevScene sc;
-        memset(&sc, 0, sizeof(sc));
-        sc.nodes = reinterpret_cast<const float4 *>(bvh.nodes.data());
-        sc.tris = tris.data();
+        mesh::Walk lane(bvh, tris, n_tris);
+        DevScene & sc = lane.sc;
         sc.tri_rank = rank.data();
-        sc.tri_count = n_tris;
-        sc.node_count = bvh.node_count;
         sc.tie_widen_max = 8;
         sc.near_tie_unresolved = &unresolved;
         sc.diffuse_dirs = table.data();
-        std::vector<int> stack_mem((size_t)(bvh.stack_bound + 2) * STACK_ENTRY_INTS, 0);
-        GlobalStack stk;
-        stk.attach(stack_mem.data(), 0, 1);
-        TraceStats st;
-        memset(&st, 0, sizeof(st));
+        GlobalStack & stk = lane.stk;
+        TraceStats & st = lane.st;
 
         // the pad and the routing thresholds, as the host entry point computes them
         float scene_max = 0.0f, extent = 0.0f;

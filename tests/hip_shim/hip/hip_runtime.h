@@ -1,6 +1,6 @@
-// Host stand-in for <hip/hip_runtime.h>: just enough of the HIP device vocabulary to compile the traversal headers
-// (par_raytracer_amd/csrc/dev_trace*.h) with g++ and run them one "lane" at a time.  Test infrastructure only
-// (tests/trace_host_harness.cpp); the product never sees this file.
+// Host stand-in for <hip/hip_runtime.h>: just enough of the HIP device vocabulary to compile the device headers and kernels
+// (par_raytracer_amd/csrc/dev_*.h, kernels_*.h) with g++ and run them one "lane" at a time.  Test infrastructure only: every
+// tests/*_host_harness.cpp is built against it (tests/harness.py holds the recipe); the product never sees this file.
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -17,9 +17,11 @@
 struct float4 { float x, y, z, w; };
 struct uint4 { unsigned int x, y, z, w; };
 struct int2 { int x, y; };
+struct uint2 { unsigned int x, y; };
 struct ulonglong2 { unsigned long long x, y; };
 static inline float4 make_float4(float x, float y, float z, float w) { float4 r = { x, y, z, w }; return r; }
 static inline int2 make_int2(int x, int y) { int2 r = { x, y }; return r; }
+static inline uint2 make_uint2(unsigned int x, unsigned int y) { uint2 r = { x, y }; return r; }
 static inline ulonglong2 make_ulonglong2(unsigned long long x, unsigned long long y) { ulonglong2 r = { x, y }; return r; }
 struct dim3_shim { unsigned int x, y, z; };
 static dim3_shim threadIdx = { 0, 0, 0 }, blockIdx = { 0, 0, 0 }, blockDim = { 1, 1, 1 }, gridDim = { 1, 1, 1 };

@@ -15,13 +15,12 @@ owns vertices 3 t .. 3 t + 2."""
 from __future__ import annotations
 
 import bisect
-import os
 import struct
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import harness
+
 QMAX = 2097151                                   # 2^21 - 1: the Morton grid per axis
 TREE_ARRAYS = ("sorted_keys", "sorted_ids", "left", "right", "first", "last", "leaf_box", "node_box")
 
@@ -391,17 +390,8 @@ BACKENDS = (("plain", 1, -1), ("cluster4", 0, 4), ("cluster64", 0, -1), ("cluste
 
 
 def build_backend_harness(directory, sanitize=True):
-    exe = os.path.join(str(directory), "lbvh_backend" + ("_san" if sanitize else ""))
-    csrc = os.path.join(ROOT, "par_raytracer_amd", "csrc")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-pthread"]
-    if sanitize:
-        # the sanitizer runtimes are linked statically: the program then starts whatever else the environment loads ahead of it
-        cmd += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan"]
-    cmd += ["-I" + csrc, os.path.join(ROOT, "tests", "lbvh_backend_harness.cpp"), os.path.join(csrc, "bvh_build.cpp"),
-            os.path.join(csrc, "bvh_check.cpp"), "-o", exe]
-    build = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    assert build.returncode == 0, build.stdout.decode()
-    return exe
+    return harness.build("lbvh_backend_harness.cpp", directory, "lbvh_backend" + ("_san" if sanitize else ""), sanitize=sanitize,
+                         sources=("bvh_build.cpp", "bvh_check.cpp"))
 
 
 def write_trees(path, names):
@@ -413,6 +403,5 @@ def write_trees(path, names):
         for name in names:
             r, v = case_reference(name), verts9(case(name))
             f.write(struct.pack("<I", len(name)) + name.encode() + struct.pack("<I", v.shape[0]))
-            for arr, dt in ((v, np.float32), (r["left"], np.int32), (r["right"], np.int32), (r["first"], np.uint32), (r["last"], np.uint32),
-                            (r["node_box"], np.float32), (r["leaf_box"], np.float32), (r["sorted_ids"], np.uint32)):
-                f.write(np.ascontiguousarray(arr, dt).tobytes())
+            harness.put(f, (v, np.float32), (r["left"], np.int32), (r["right"], np.int32), (r["first"], np.uint32), (r["last"], np.uint32),
+                        (r["node_box"], np.float32), (r["leaf_box"], np.float32), (r["sorted_ids"], np.uint32))

@@ -2,13 +2,12 @@
 CPU autograd of the hit arithmetic, in float64 and float32) and the runner of tests/query_grad_host_harness.cpp."""
 from __future__ import annotations
 
-import os
 import struct
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import harness
+
 GRADS = ("positions", "origins", "directions")
 FLOOR = 2.0 ** -22          # four float32 ulps of an array's largest entry
 
@@ -154,16 +153,7 @@ def check_against_yardstick(mesh, o, d, group, vertex0, ray_bias, gout, ours, wh
 # ---- the host harness
 
 def build_harness(directory, sanitize):
-    exe = os.path.join(str(directory), "query_grad_host")
-    csrc = os.path.join(ROOT, "par_raytracer_amd", "csrc")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-pthread"]
-    if sanitize:
-        # the sanitizer runtimes are linked statically: the program then starts whatever else the environment loads ahead of it
-        cmd += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan"]
-    cmd += ["-I" + os.path.join(ROOT, "tests", "hip_shim"), "-I" + csrc, os.path.join(ROOT, "tests", "query_grad_host_harness.cpp"), "-o", exe]
-    build = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    assert build.returncode == 0, build.stdout.decode()
-    return exe
+    return harness.build("query_grad_host_harness.cpp", directory, "query_grad_host", sanitize=sanitize)
 
 
 def case(mesh, o, d, group, vertex0, ray_bias=0.0, gout=None, merge=False):
@@ -173,7 +163,7 @@ def case(mesh, o, d, group, vertex0, ray_bias=0.0, gout=None, merge=False):
 def run_harness(exe, cases, directory):
     """Every case through the harness in one run; returns per case a dict: rc, hit_rays, skipped_rays, invalid, unit_exponent,
     max_contribution and - rc 0 - positions, origins, directions, contrib (n, 9)."""
-    fin, fout = os.path.join(str(directory), "cases.bin"), os.path.join(str(directory), "results.bin")
+    fin, fout = harness.case_files(directory, "cases.bin", "results.bin")
     with open(fin, "wb") as f:
         f.write(struct.pack("<I", len(cases)))
         for c in cases:
@@ -182,28 +172,19 @@ def run_harness(exe, cases, directory):
             keys = ("t", "bw", "position", "normal")
             flags = sum(1 << i for i, k in enumerate(keys) if c["gout"].get(k) is not None) | (16 if c["merge"] else 0)
             f.write(struct.pack("<5If", n, p.shape[0], idx.size, runs.shape[0], flags, c["ray_bias"]))
-            for arr, dt in ((c["o"], np.float32), (c["d"], np.float32), (c["group"], np.int32), (c["vertex0"], np.uint32), (p, np.float32),
-                            (idx, np.uint32), (runs, np.uint32)):
-                f.write(np.ascontiguousarray(arr, dt).tobytes())
-            for k in keys:
-                if c["gout"].get(k) is not None:
-                    f.write(np.ascontiguousarray(c["gout"][k], np.float32).tobytes())
-    run = subprocess.run([exe, fin, fout], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
-    assert run.returncode == 0, run.stdout.decode()[-4000:]
-    blob = open(fout, "rb").read()
-    at, out = 0, []
+            harness.put(f, (c["o"], np.float32), (c["d"], np.float32), (c["group"], np.int32), (c["vertex0"], np.uint32), (p, np.float32),
+                        (idx, np.uint32), (runs, np.uint32), *((c["gout"][k], np.float32) for k in keys if c["gout"].get(k) is not None))
+    harness.run(exe, fin, fout, timeout=300)
+    blob, out = harness.Reader.of_file(fout), []
     for c in cases:
-        rc, hit, skipped, invalid, unit, m = struct.unpack_from("<iIIIif", blob, at)
-        at += 24
+        rc, hit, skipped, invalid, unit, m = blob.unpack("<iIIIif")
         r = dict(rc=rc, hit_rays=hit, skipped_rays=skipped, invalid=invalid, unit_exponent=unit, max_contribution=np.float32(m))
         if rc == 0:
             n, n_pos = len(c["group"]), c["mesh"][0].shape[0]
             for k, shape in (("positions", (n_pos, 3)), ("origins", (n, 3)), ("directions", (n, 3)), ("contrib", (n, 9))):
-                size = int(np.prod(shape))
-                r[k] = np.frombuffer(blob, np.float32, size, at).reshape(shape).copy()
-                at += 4 * size
+                r[k] = blob.take(np.prod(shape), np.float32, shape)
         out.append(r)
-    assert at == len(blob)
+    blob.done()
     return out
 
 

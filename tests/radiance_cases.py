@@ -12,12 +12,12 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import subprocess
 import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import harness
+
 SCENES = ("cornell_box", "many_materials", "coincident", "textured_gallery")
 # RGB against the harness: what tests/test_gpu_parity.py applies against the reference (README "Parity")
 TOL = 1e-4
@@ -30,11 +30,7 @@ def harness_lib() -> C.CDLL:
     """tests/radiance_oracle_harness.cpp compiled with g++ (once per process)."""
     global _LIB
     if _LIB is None:
-        so = os.path.join(tempfile.mkdtemp(prefix="prt_radiance_oracle_"), "radiance_oracle.so")
-        cmd = ["g++", "-O2", "-std=c++14", "-fPIC", "-shared", "-ffp-contract=off", "-fno-strict-aliasing", "-pthread",
-               "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "radiance_oracle_harness.cpp"), "-o", so]
-        subprocess.run(cmd, check=True)
-        lib = C.CDLL(so)
+        lib = C.CDLL(harness.build_shared("radiance_oracle_harness.cpp", tempfile.mkdtemp(prefix="prt_radiance_oracle_"), "radiance_oracle.so"))
         lib.prt_radiance_oracle_batch.restype = C.c_int
         lib.prt_radiance_oracle_batch.argtypes = [C.c_void_p] * 4 + [C.c_uint32, C.c_uint64, C.c_int] + [C.c_void_p] * 5 + [C.c_int]
         lib.prt_radiance_camera_rays.restype = C.c_int

@@ -16,8 +16,6 @@
 
 #include <hip/hip_runtime.h>            // tests/hip_shim: one lane at a time
 // what kernels_refit.h needs beyond the shim (a wave of one lane: a shuffle returns the lane's own value)
-struct uint2 { unsigned int x, y; };
-static inline uint2 make_uint2(unsigned int x, unsigned int y) { uint2 r = { x, y }; return r; }
 static inline uint4 make_uint4(unsigned int x, unsigned int y, unsigned int z, unsigned int w) { uint4 r = { x, y, z, w }; return r; }
 static inline float __shfl_xor(float v, int) { return v; }
 static inline int __shfl_xor(int v, int) { return v; }
@@ -122,6 +120,7 @@ static void kernels_on_the_host() {
     }
     blockIdx.x = 0;
     uint32_t record_bad = 0;
+    // the records written out on purpose, not through tri_record (dev_math.h): the kernel calls it, so this is its test
     for (uint32_t slot = 0; slot < n_tris; ++slot) {              // prt_upload_scene's loop, on the moved positions
         const uint32_t t = bvh.tri_order[slot];
         const float * pa = &moved[3 * ip[3 * t]], * pb = &moved[3 * ip[3 * t + 1]], * pc = &moved[3 * ip[3 * t + 2]];

@@ -4,15 +4,13 @@ and csrc/dev_sample_grad.h), the meshes of tests/signed_cases.py and tests/close
 kernels care about, and float64 numpy yardsticks: the area, the gradient, the statistic's gate."""
 from __future__ import annotations
 
-import os
 import struct
-import subprocess
 
 import numpy as np
 
 import closest_cases as K
+import harness
 import signed_cases as S
-from closest_cases import ROOT
 
 FIELDS = ("point", "bw", "normal", "vertex0", "group")
 INFO = ("area", "total_weight", "unit_exponent", "live_triangles")
@@ -25,16 +23,7 @@ TOTALS_PASS = SAMPLE_TILE * SAMPLE_TILE
 
 
 def build_harness(directory, sanitize=False):
-    exe = os.path.join(str(directory), "sample_host" + ("_san" if sanitize else ""))
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off"]
-    if sanitize:
-        # the sanitizer runtimes are linked statically: the program then starts whatever else the environment loads ahead of it
-        cmd += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan"]
-    cmd += ["-I" + os.path.join(ROOT, "tests", "hip_shim"), "-I" + os.path.join(ROOT, "par_raytracer_amd", "csrc"),
-            os.path.join(ROOT, "tests", "sample_host_harness.cpp"), "-o", exe]
-    build = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    assert build.returncode == 0, build.stdout.decode()
-    return exe
+    return harness.build("sample_host_harness.cpp", directory, "sample_host" + ("_san" if sanitize else ""), sanitize=sanitize)
 
 
 def request(seed, first, count):
@@ -55,14 +44,13 @@ def run_harness(exe, cases, directory, tag="sample"):
     """Every case through the harness in one run.  Per case a dict: the four INFO entries, "W" (uint64 per input triangle),
     "samples" (per request {field: array}) and "grads" (per gradient call rc, hit, skipped, invalid, unit_exponent,
     max_contribution, positions)."""
-    fin, fout = os.path.join(str(directory), tag + "_cases.bin"), os.path.join(str(directory), tag + "_results.bin")
+    fin, fout = harness.case_files(directory, tag + "_cases.bin", tag + "_results.bin")
     with open(fin, "wb") as f:
         f.write(struct.pack("<I", len(cases)))
         for c in cases:
             p, idx, runs = c["mesh"]
             f.write(struct.pack("<6I", p.shape[0], idx.size, runs.shape[0], len(c["requests"]), len(c["grads"]), 0))
-            for arr, dt in ((p, np.float32), (idx, np.uint32), (runs, np.uint32)):
-                f.write(np.ascontiguousarray(arr, dt).tobytes())
+            harness.put(f, (p, np.float32), (idx, np.uint32), (runs, np.uint32))
             for seed, first, count in c["requests"]:
                 f.write(struct.pack("<3Q", seed, first, count))
             for g in c["grads"]:
@@ -72,46 +60,37 @@ def run_harness(exe, cases, directory, tag="sample"):
                 for key in ("grad_point", "grad_normal"):
                     if g[key] is not None:
                         f.write(g[key].tobytes())
-    run = subprocess.run([exe, fin, fout], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    assert run.returncode == 0, run.stdout.decode()[-4000:]
-    blob = open(fout, "rb").read()
-    at, out = 0, []
-
-    def take(count, dt):
-        nonlocal at
-        a = np.frombuffer(blob, dt, count, at).copy()
-        at += a.nbytes
-        return a
+    harness.run(exe, fin, fout)
+    r, out = harness.Reader.of_file(fout), []
     for c in cases:
         n_pos, n_tris = c["mesh"][0].shape[0], c["mesh"][1].size // 3
-        res = dict(area=float(take(1, np.float64)[0]), total_weight=int(take(1, np.uint64)[0]), unit_exponent=int(take(1, np.int32)[0]),
-                   live_triangles=int(take(1, np.uint32)[0]), W=take(n_tris, np.uint64), samples=[], grads=[])
+        area, total, unit, live = r.unpack("<dQiI")
+        res = dict(area=area, total_weight=total, unit_exponent=unit, live_triangles=live, W=r.take(n_tris, np.uint64), samples=[], grads=[])
         for _seed, _first, n in c["requests"]:
-            res["samples"].append(dict(point=take(3 * n, np.float32).reshape(n, 3), bw=take(3 * n, np.float32).reshape(n, 3),
-                                       normal=take(3 * n, np.float32).reshape(n, 3), vertex0=take(n, np.uint32), group=take(n, np.int32)))
+            res["samples"].append(dict(point=r.take(3 * n, np.float32, (n, 3)), bw=r.take(3 * n, np.float32, (n, 3)),
+                                       normal=r.take(3 * n, np.float32, (n, 3)), vertex0=r.take(n, np.uint32), group=r.take(n, np.int32)))
         for _g in c["grads"]:
-            head = take(5, np.int32)
-            res["grads"].append(dict(rc=int(head[0]), hit=int(head[1]), skipped=int(head[2]), invalid=int(head[3]), unit_exponent=int(head[4]),
-                                     max_contribution=float(take(1, np.float32)[0]), positions=take(3 * n_pos, np.float32).reshape(n_pos, 3)))
+            rc, hit, skipped, invalid, unit, m = r.unpack("<5if")
+            res["grads"].append(dict(rc=rc, hit=hit, skipped=skipped, invalid=invalid, unit_exponent=unit, max_contribution=m,
+                                     positions=r.take(3 * n_pos, np.float32, (n_pos, 3))))
         out.append(res)
-    assert at == len(blob)
+    r.done()
     return out
 
 
 def run_pick(exe, lists, directory):
     """lists: [(weights, r0 values)] of Python integers -> per list the int64 array of the triangles picked (-1: a miss)."""
-    fin, fout = os.path.join(str(directory), "pick_lists.bin"), os.path.join(str(directory), "pick_out.bin")
+    fin, fout = harness.case_files(directory, "pick_lists.bin", "pick_out.bin")
     with open(fin, "wb") as f:
         f.write(struct.pack("<I", len(lists)))
         for w, r in lists:
             f.write(struct.pack("<2I", len(w), len(r)))
             f.write(np.array(w, np.uint64).tobytes() + np.array(r, np.uint64).tobytes())
-    run = subprocess.run([exe, "--pick", fin, fout], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    assert run.returncode == 0, run.stdout.decode()[-4000:]
-    blob = np.frombuffer(open(fout, "rb").read(), np.int64)
-    assert blob.size == sum(len(r) for _, r in lists)
-    ends = np.cumsum([len(r) for _, r in lists])
-    return [blob[e - len(r):e].copy() for e, (_, r) in zip(ends, lists)]
+    harness.run(exe, "--pick", fin, fout)
+    blob = harness.Reader.of_file(fout)
+    out = [blob.take(len(r), np.int64) for _, r in lists]
+    blob.done()
+    return out
 
 
 def pick_by_integers(weights, r0):
@@ -143,19 +122,12 @@ def boundary_draws(weights):
 
 def assert_same_bits(got, expect, what, fields=FIELDS):
     """Every field of `got` ({field: numpy array}) equals `expect` bit for bit."""
-    K.assert_same_bits(got, expect, what, fields)
+    harness.assert_same_bits(got, expect, what, fields)
 
 
 def to_numpy(res):
     """A sample_surface result with torch tensors -> numpy arrays (vertex0 back to uint32)."""
-    out = {}
-    for k, v in res.items():
-        if k == "info":
-            out[k] = v
-        else:
-            a = v.cpu().numpy() if hasattr(v, "cpu") else v
-            out[k] = a.view(np.uint32) if k == "vertex0" else a
-    return out
+    return harness.to_numpy(res, ("vertex0",))
 
 
 def assert_all_miss(res, what, fields=FIELDS):

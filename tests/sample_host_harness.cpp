@@ -31,8 +31,6 @@
 
 #include <hip/hip_runtime.h>            // tests/hip_shim: one lane at a time
 using std::isfinite;
-struct uint2 { unsigned int x, y; };
-static inline uint2 make_uint2(unsigned int x, unsigned int y) { uint2 r = { x, y }; return r; }
 // what the kernels need beyond the shim.  A wave of one lane: the other 63 hold the neutral element of the reductions.
 static inline float __shfl_xor(float, int) { return 0.0f; }
 static inline int __shfl_xor(int, int) { return 0; }
@@ -41,21 +39,10 @@ static inline unsigned int __float_as_uint(float f) { unsigned int v; memcpy(&v,
 static inline unsigned int atomicMax(unsigned int * p, unsigned int v) { unsigned int o = *p; if (v > o) *p = v; return o; }
 
 #include "kernels_sample_grad.h"
+#include "harness_io.h"
+#include "harness_mesh.h"
 
 using namespace prt;
-
-template <class T>
-static std::vector<T> rd(FILE * f, size_t n) {
-    std::vector<T> v(n);
-    if (n && fread(v.data(), sizeof(T), n, f) != n) { fprintf(stderr, "sample_host: short read\n"); exit(2); }
-    return v;
-}
-template <class T>
-static void wr(FILE * f, const T * p, size_t n) {
-    if (n && fwrite(p, sizeof(T), n, f) != n) { fprintf(stderr, "sample_host: short write\n"); exit(2); }
-}
-template <class T>
-static void wr(FILE * f, const std::vector<T> & v) { wr(f, v.data(), v.size()); }
 
 template <class K, class ARGS>
 static void launch(K kernel, unsigned int grid, const ARGS & A) {
@@ -84,8 +71,8 @@ static int pick_mode(FILE * fin, FILE * fout) {
 int main(int argc, char ** argv) {
     const bool pick = argc == 4 && !strcmp(argv[1], "--pick");
     if (argc != 3 && !pick) { fprintf(stderr, "usage: sample_host [--pick] in.bin out.bin\n"); return 2; }
-    FILE * fin = fopen(argv[argc - 2], "rb"), * fout = fopen(argv[argc - 1], "wb");
-    if (!fin || !fout) { fprintf(stderr, "sample_host: cannot open the files\n"); return 2; }
+    FILE * fin, * fout;
+    if (!open_in_out(argc, argv, "sample_host", &fin, &fout)) return 2;
     if (pick) {
         const int rc = pick_mode(fin, fout);
         fclose(fin);
@@ -100,19 +87,8 @@ int main(int argc, char ** argv) {
         const std::vector<uint32_t> runs = rd<uint32_t>(fin, 2 * (size_t)n_groups);
 
         // the records (slot = input triangle) and the leaf table
-        std::vector<float4> tris((size_t)(n_tris + 1) * 3, make_float4(0, 0, 0, 0));
-        std::vector<uint2> leaf_map((size_t)n_tris + 1, make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu));
-        for (uint32_t g = 0; g < n_groups; ++g)
-            for (uint32_t k = 0; k < runs[2 * g + 1] / 3; ++k) leaf_map[runs[2 * g] / 3 + k] = make_uint2(g, 3u * k);
-        for (uint32_t t = 0; t < n_tris; ++t) {
-            const uint32_t * vi = &idx[3 * (size_t)t];
-            const f3 a = mk3(pos[3 * vi[0]], pos[3 * vi[0] + 1], pos[3 * vi[0] + 2]), b = mk3(pos[3 * vi[1]], pos[3 * vi[1] + 1], pos[3 * vi[1] + 2]),
-                     c = mk3(pos[3 * vi[2]], pos[3 * vi[2] + 1], pos[3 * vi[2] + 2]);
-            const f3 ab = b - a, ac = c - a, nn = cross3(ab, ac);
-            tris[(size_t)t * 3 + 0] = make_float4(a.x, a.y, a.z, ab.x);
-            tris[(size_t)t * 3 + 1] = make_float4(ab.y, ab.z, ac.x, ac.y);
-            tris[(size_t)t * 3 + 2] = make_float4(ac.z, nn.x, nn.y, nn.z);
-        }
+        const std::vector<float4> tris = mesh::records(mesh::unindexed(pos, idx), n_tris, nullptr);
+        const std::vector<uint2> leaf_map = mesh::leaf_map(runs, n_groups, n_tris, nullptr);
         // the table: what k_sample_weights .. k_sample_offsets build, in input order
         std::vector<double> weight(n_tris);
         unsigned long long max_bits = 0;

@@ -20,9 +20,7 @@
 #include <cstring>
 #include <vector>
 
-#include "dev_trace.h"
-#include "bvh_build.h"
-#include "prt_options.h"
+#include "harness_mesh.h"
 #include "harness_scene.h"
 
 using namespace prt;
@@ -33,12 +31,8 @@ enum { WIDTH = 8 };
 enum { WIDTH = 4 };
 #endif
 
-static void put_record(std::vector<float4> & tris, size_t slot, const float * v) {           // prt_upload_scene's expressions
-    const f3 a = mk3(v[0], v[1], v[2]), b = mk3(v[3], v[4], v[5]), c = mk3(v[6], v[7], v[8]);
-    const f3 ab = b - a, ac = c - a, n = cross3(ab, ac);
-    tris[slot * 3 + 0] = make_float4(a.x, a.y, a.z, ab.x);
-    tris[slot * 3 + 1] = make_float4(ab.y, ab.z, ac.x, ac.y);
-    tris[slot * 3 + 2] = make_float4(ac.z, n.x, n.y, n.z);
+static void put_record(std::vector<float4> & tris, size_t slot, const float * v) {           // prt_upload_scene's own function
+    tri_record(mk3(v[0], v[1], v[2]), mk3(v[3], v[4], v[5]), mk3(v[6], v[7], v[8]), &tris[slot * 3]);
 }
 
 static float abs_max_of(const std::vector<float> & v) { float m = 0.0f; for (float x : v) m = fmaxf(m, fabsf(x)); return m; }
@@ -98,8 +92,7 @@ static void upload(Scene & S, const char * name, const std::vector<f3> & dirs, u
     S.n_tris = (uint32_t)(S.verts.size() / 9);
     BvhBuildOptions bopt;
     build_bvh_wide(WIDTH, S.verts.data(), S.n_tris, 4, 2, &S.bvh, 1.0f, &bopt);
-    S.tris.assign((size_t)(S.n_tris + 1) * 3, make_float4(0, 0, 0, 0));
-    for (uint32_t slot = 0; slot < S.n_tris; ++slot) put_record(S.tris, slot, &S.verts[(size_t)S.bvh.tri_order[slot] * 9]);
+    S.tris = mesh::records(S.verts, S.n_tris, S.bvh.tri_order.data());
     S.node_words = S.bvh.nodes;
     S.all_nodes = S.bvh.node_count;
     S.all_recs = S.n_tris + 1;
@@ -147,15 +140,9 @@ static void upload(Scene & S, const char * name, const std::vector<f3> & dirs, u
 // Shadow rays as a render starts them (kernels_wave.h shade_entry_on): from a point of the surface, off along the normal and the
 // light by the bias.  Hit / miss of the light's tree, of the scene's tree and of a loop over every triangle.
 static void brute(const Scene & S, const char * name, int n_rays) {
-    DevScene sc;
-    memset(&sc, 0, sizeof(sc));
-    sc.nodes = reinterpret_cast<const float4 *>(S.node_words.data());
-    sc.tris = S.tris.data();
-    sc.tri_count = S.n_tris;
-    sc.node_count = S.bvh.node_count;
-    std::vector<int> stack_mem((size_t)(S.stack_bound + 2) * STACK_ENTRY_INTS, 0);
-    GlobalStack stk;
-    stk.attach(stack_mem.data(), 0, 1);
+    mesh::Walk lane(S.node_words.data(), S.bvh.node_count, S.tris, S.n_tris, S.stack_bound);
+    const DevScene & sc = lane.sc;
+    GlobalStack & stk = lane.stk;
     const float A = abs_max_of(S.verts), pad = A * (1.0f / 65536.0f), bias = 1e-3f;
     for (size_t l = 0; l < S.trees.size(); ++l) {
         const Scene::Tree & T = S.trees[l];

@@ -4,13 +4,13 @@ arccos, the analytic inside tests, and the runner of tests/signed_host_harness.c
 the PRT_HD functions of csrc/dev_signed.h and integer accumulators)."""
 from __future__ import annotations
 
-import os
-import subprocess
+import struct
 
 import numpy as np
 
 import closest_cases as K
-from closest_cases import ROOT, bits, flat_desc, scene_mesh                       # noqa: F401  (re-exported)
+import harness
+from closest_cases import bits, flat_desc, scene_mesh                       # noqa: F401  (re-exported)
 
 POINTS = 2048
 FIELDS = K.FIELDS + ("signed_distance", "feature")
@@ -232,16 +232,7 @@ def mesh_angle_cosines(mesh):
 # ---- the host harness
 
 def build_harness(directory, sanitize=False):
-    exe = os.path.join(str(directory), "signed_host" + ("_san" if sanitize else ""))
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off"]
-    if sanitize:
-        # the sanitizer runtimes are linked statically: the program then starts whatever else the environment loads ahead of it
-        cmd += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan"]
-    cmd += ["-I" + os.path.join(ROOT, "tests", "hip_shim"), "-I" + os.path.join(ROOT, "par_raytracer_amd", "csrc"),
-            os.path.join(ROOT, "tests", "signed_host_harness.cpp"), "-o", exe]
-    build = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    assert build.returncode == 0, build.stdout.decode()
-    return exe
+    return harness.build("signed_host_harness.cpp", directory, "signed_host" + ("_san" if sanitize else ""), sanitize=sanitize)
 
 
 def case(mesh, points, max_dist2=None):
@@ -258,8 +249,7 @@ def sweep(x):
 def run_harness(exe, cases, directory):
     """Every case through the harness in one run.  Per case a dict {field: array} of the seven fields plus "angles" (n_tris, 3); a
     sweep gives {"acos": array}."""
-    import struct
-    fin, fout = os.path.join(str(directory), "signed_cases.bin"), os.path.join(str(directory), "signed_results.bin")
+    fin, fout = harness.case_files(directory, "signed_cases.bin", "signed_results.bin")
     with open(fin, "wb") as f:
         f.write(struct.pack("<I", len(cases)))
         for c in cases:
@@ -272,43 +262,30 @@ def run_harness(exe, cases, directory):
             f.write(struct.pack("<5I", n, p.shape[0], idx.size, runs.shape[0], 1 if c["max_dist2"] is not None else 0))
             f.write(c["points"].tobytes())
             if c["max_dist2"] is not None:
-                f.write(np.ascontiguousarray(c["max_dist2"], np.float32).tobytes())
-            for arr, dt in ((p, np.float32), (idx, np.uint32), (runs, np.uint32)):
-                f.write(np.ascontiguousarray(arr, dt).tobytes())
-    run = subprocess.run([exe, fin, fout], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    assert run.returncode == 0, run.stdout.decode()[-4000:]
-    blob = open(fout, "rb").read()
-    at, out = 0, []
-
-    def take(count, dt):
-        nonlocal at
-        a = np.frombuffer(blob, dt, count, at).copy()
-        at += a.nbytes
-        return a
+                harness.put(f, (c["max_dist2"], np.float32))
+            harness.put(f, (p, np.float32), (idx, np.uint32), (runs, np.uint32))
+    harness.run(exe, fin, fout)
+    r, out = harness.Reader.of_file(fout), []
     for c in cases:
         if "sweep" in c:
-            out.append(dict(acos=take(c["sweep"].size, np.float32)))
+            out.append(dict(acos=r.take(c["sweep"].size, np.float32)))
             continue
         n, n_tris = c["points"].shape[0], c["mesh"][1].size // 3
-        out.append(dict(dist2=take(n, np.float32), point=take(3 * n, np.float32).reshape(n, 3), bw=take(3 * n, np.float32).reshape(n, 3),
-                        vertex0=take(n, np.uint32), group=take(n, np.int32), signed_distance=take(n, np.float32),
-                        feature=take(n, np.uint8), angles=take(3 * n_tris, np.float32).reshape(n_tris, 3)))
-    assert at == len(blob)
+        out.append(dict(dist2=r.take(n, np.float32), point=r.take(3 * n, np.float32, (n, 3)), bw=r.take(3 * n, np.float32, (n, 3)),
+                        vertex0=r.take(n, np.uint32), group=r.take(n, np.int32), signed_distance=r.take(n, np.float32),
+                        feature=r.take(n, np.uint8), angles=r.take(3 * n_tris, np.float32, (n_tris, 3))))
+    r.done()
     return out
 
 
 def assert_same_bits(got, expect, what, fields=FIELDS):
-    """Every field of `got` equals `expect` bit for bit (feature: byte for byte)."""
-    K.assert_same_bits(got, expect, what, tuple(f for f in fields if f != "feature"))
-    if "feature" in fields:
-        g, e = np.asarray(got["feature"]), np.asarray(expect["feature"])
-        bad = np.nonzero(g != e)[0]
-        assert bad.size == 0, "%s: feature differs on %d of %d points, first %d: got %d, expected %d" % (what, bad.size, len(e), bad[0], g[bad[0]], e[bad[0]])
+    """Every field of `got` equals `expect` bit for bit."""
+    harness.assert_same_bits(got, expect, what, fields)
 
 
 def to_numpy(res):
     """A signed_distance result with torch tensors -> numpy arrays (vertex0 back to uint32)."""
-    return K.to_numpy({k: v for k, v in res.items()})
+    return K.to_numpy(res)
 
 
 # ---- the scale sweep (closest_cases.SWEEP_EXPONENTS): conditions c and d on the unscaled mesh

@@ -24,28 +24,16 @@
 
 #include <hip/hip_runtime.h>            // tests/hip_shim: one lane at a time
 using std::isfinite;
-struct uint2 { unsigned int x, y; };
-static inline uint2 make_uint2(unsigned int x, unsigned int y) { uint2 r = { x, y }; return r; }
 
 #include "dev_signed.h"
+#include "harness_io.h"
+#include "harness_mesh.h"
 
 using namespace prt;
 
-template <class T>
-static std::vector<T> rd(FILE * f, size_t n) {
-    std::vector<T> v(n);
-    if (n && fread(v.data(), sizeof(T), n, f) != n) { fprintf(stderr, "signed_host: short read\n"); exit(2); }
-    return v;
-}
-template <class T>
-static void wr(FILE * f, const std::vector<T> & v) {
-    if (!v.empty() && fwrite(v.data(), sizeof(T), v.size(), f) != v.size()) { fprintf(stderr, "signed_host: short write\n"); exit(2); }
-}
-
 int main(int argc, char ** argv) {
-    if (argc < 3) { fprintf(stderr, "usage: signed_host cases.bin results.bin\n"); return 2; }
-    FILE * fin = fopen(argv[1], "rb"), * fout = fopen(argv[2], "wb");
-    if (!fin || !fout) { fprintf(stderr, "signed_host: cannot open the files\n"); return 2; }
+    FILE * fin, * fout;
+    if (!open_in_out(argc, argv, "signed_host", &fin, &fout)) return 2;
     const uint32_t n_cases = rd<uint32_t>(fin, 1)[0];
     for (uint32_t ci = 0; ci < n_cases; ++ci) {
         const std::vector<uint32_t> hd = rd<uint32_t>(fin, 5);
@@ -63,20 +51,12 @@ int main(int argc, char ** argv) {
         const std::vector<uint32_t> runs = rd<uint32_t>(fin, 2 * (size_t)n_groups);
 
         // the records (slot = input triangle), the leaf table, the adjacency
-        std::vector<float4> tris((size_t)(n_tris + 1) * 3, make_float4(0, 0, 0, 0));
-        std::vector<uint2> leaf_map((size_t)n_tris + 1, make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu));
-        for (uint32_t g = 0; g < n_groups; ++g)
-            for (uint32_t k = 0; k < runs[2 * g + 1] / 3; ++k) leaf_map[runs[2 * g] / 3 + k] = make_uint2(g, 3u * k);
+        const std::vector<float4> tris = mesh::records(mesh::unindexed(pos, idx), n_tris, nullptr);
+        const std::vector<uint2> leaf_map = mesh::leaf_map(runs, n_groups, n_tris, nullptr);
         std::map<std::pair<uint32_t, uint32_t>, uint32_t> edge_id;
         std::vector<unsigned int> adj(6 * (size_t)n_tris);
         for (uint32_t t = 0; t < n_tris; ++t) {
             const uint32_t * vi = &idx[3 * (size_t)t];
-            const f3 a = mk3(pos[3 * vi[0]], pos[3 * vi[0] + 1], pos[3 * vi[0] + 2]), b = mk3(pos[3 * vi[1]], pos[3 * vi[1] + 1], pos[3 * vi[1] + 2]),
-                     c = mk3(pos[3 * vi[2]], pos[3 * vi[2] + 1], pos[3 * vi[2] + 2]);
-            const f3 ab = b - a, ac = c - a, nn = cross3(ab, ac);
-            tris[(size_t)t * 3 + 0] = make_float4(a.x, a.y, a.z, ab.x);
-            tris[(size_t)t * 3 + 1] = make_float4(ab.y, ab.z, ac.x, ac.y);
-            tris[(size_t)t * 3 + 2] = make_float4(ac.z, nn.x, nn.y, nn.z);
             const uint32_t pair[3][2] = { { vi[0], vi[1] }, { vi[0], vi[2] }, { vi[1], vi[2] } };          // ab, ac, bc
             for (int k = 0; k < 3; ++k) {
                 adj[6 * (size_t)t + k] = vi[k];

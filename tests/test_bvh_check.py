@@ -3,28 +3,20 @@ prt_upload_scene asks before it uploads a tree (the round-3
 behind prt_debug_check_bvh.  tests/bvh_check_harness.cpp, built with g++ from bvh_build.cpp + bvh_check.cpp alone, hands them
 trees of both widths and both collapse rules as the builder made them, and then copies with one edit each; it prints a line per
 tree and the assertions are here.  No GPU library is involved, so the 8-wide checker runs whichever library is loaded."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import harness
+
 LINE = re.compile(r"width (\d) (\w+) (\w+) (good|edit \w+) \| n_tris (\d+) violations (\d+) nodes (\d+) depth (\d+) stack_bound (\d+) "
                   r"leaves (\d+) refs (\d+) \| validate: (.*)")
 
 
 @pytest.fixture(scope="module")
 def trees(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("bvh_check") / "bvh_check")
-    csrc = os.path.join(ROOT, "par_raytracer_amd", "csrc")
-    cmd = ["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-pthread", "-I" + csrc, os.path.join(ROOT, "tests", "bvh_check_harness.cpp"),
-           os.path.join(csrc, "bvh_build.cpp"), os.path.join(csrc, "bvh_check.cpp"), "-o", exe]
-    build = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    assert build.returncode == 0, build.stdout.decode()
-    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
-    out = run.stdout.decode()
-    assert run.returncode == 0, out
+    exe = harness.build("bvh_check_harness.cpp", tmp_path_factory.mktemp("bvh_check"), "bvh_check", sources=("bvh_build.cpp", "bvh_check.cpp"))
+    out = harness.run(exe, timeout=120)
     found = {}
     for line in out.splitlines():
         m = LINE.fullmatch(line)

@@ -13,11 +13,11 @@ harness's build and run."""
 from __future__ import annotations
 
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import harness
 import lbvh_cases as L
 
 SMALL = [n for n in L.case_names() if n != "large"]
@@ -252,9 +252,7 @@ def backend(tmp_path_factory):
     exe = L.build_backend_harness(d, sanitize=True)
     path = str(d / "trees.bin")
     L.write_trees(path, L.case_names())
-    run = subprocess.run([exe, path], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    out = run.stdout.decode()
-    assert run.returncode == 0, out[-4000:]
+    out = harness.run(exe, path)
     found = {}
     for line in out.splitlines():
         m = LINE.fullmatch(line)

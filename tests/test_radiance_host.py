@@ -5,15 +5,14 @@ csrc/kernels_rays.h run lane by lane on the host in a stand-alone program built 
 from __future__ import annotations
 
 import ctypes as C
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import harness
 import radiance_cases as R
-from conftest import ROOT, host_scene, scene_dir
+from conftest import host_scene, scene_dir
 
 F = np.float32
 
@@ -134,18 +133,8 @@ def test_the_other_cameras_make_unit_rays_inside_the_domain():
 def test_the_kernels_run_lane_by_lane_under_the_sanitizers(tmp_path):
     """k_rays_check's three words and k_raygen_rays's queue entries and generators over 3 passes x 2 chains of uneven size, in a
     stand-alone program with its own main: a wrong base is an out-of-bounds access there, not a fault on a card."""
-    exe = str(tmp_path / "rays_host")
-    csrc = os.path.join(ROOT, "par_raytracer_amd", "csrc")
-    # the sanitizer runtimes are linked statically: the program then starts whatever else the environment loads ahead of it
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-static-libasan", "-static-libubsan", "-I" + os.path.join(ROOT, "tests", "hip_shim"), "-I" + csrc,
-           os.path.join(ROOT, "tests", "rays_host_harness.cpp"), "-o", exe]
-    build = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    assert build.returncode == 0, build.stdout.decode()
-    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
-    out = run.stdout.decode()
-    assert run.returncode == 0, out[-4000:]
-    lines = out.splitlines()
+    exe = harness.build("rays_host_harness.cpp", tmp_path, "rays_host", sanitize=True)
+    lines = harness.run(exe, timeout=120).splitlines()
     assert lines[0] == "check | clean_ok 1 bad_ok 1 edge_ok 1 bias_ok 1"
     for cs in (0, 1):
         m = re.fullmatch(r"raygen camera_stream (\d) \| plain bad (\d+) of (\d+) ring bad (\d+) of (\d+)", lines[1 + cs])

@@ -3,13 +3,12 @@ read the children's exact boxes, union them, re-derive the node's power-of-two g
 __host__ __device__ code; tests/refit_host_harness.cpp, a stand-alone program built with g++ (and AddressSanitizer / UBSan,
 through tests/hip_shim) from bvh_build.cpp + bvh_check.cpp + that header, runs it level by level, deepest first, over trees of
 both widths and prints one line per (width, soup, move); the assertions are here.  No GPU library is involved."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import harness
+
 LINE = re.compile(r"width (\d) n (\d+) move (\w+) \| level_ok (\d) levels (\d+) depth (\d+) covered (\d+) nodes (\d+) child_bad (\d+) "
                   r"identical (\d) violations (\d+) refs (\d+) exp_bad (\d+) exp_m100 (\d+) root_e (-?\d+) (-?\d+) (-?\d+) validate (\w+)")
 KERNELS = re.compile(r"kernels width (\d) \| level_ok (\d) bounds_ok (\d) nan_flag (\d+) record_bad (\d+) violations (\d+) refs (\d+) "
@@ -20,17 +19,9 @@ KEYS = ("level_ok", "levels", "depth", "covered", "nodes", "child_bad", "identic
 
 @pytest.fixture(scope="module")
 def refits(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("refit_host") / "refit_host")
-    csrc = os.path.join(ROOT, "par_raytracer_amd", "csrc")
-    # the sanitizer runtimes are linked statically: the program then starts whatever else the environment loads ahead of it
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-static-libasan", "-static-libubsan", "-I" + os.path.join(ROOT, "tests", "hip_shim"), "-I" + csrc, os.path.join(ROOT, "tests", "refit_host_harness.cpp"),
-           os.path.join(csrc, "bvh_build.cpp"), os.path.join(csrc, "bvh_check.cpp"), "-o", exe]
-    build = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    assert build.returncode == 0, build.stdout.decode()
-    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
-    out = run.stdout.decode()
-    assert run.returncode == 0, out[-4000:]
+    exe = harness.build("refit_host_harness.cpp", tmp_path_factory.mktemp("refit_host"), "refit_host", sanitize=True,
+                        sources=("bvh_build.cpp", "bvh_check.cpp"))
+    out = harness.run(exe, timeout=120)
     found = {}
     for line in out.splitlines():
         k = KERNELS.fullmatch(line)
@@ -112,7 +103,7 @@ def test_a_power_of_two_scale_shifts_every_exponent(refits, width, n, move, shif
 def test_null_handles_are_refused_without_a_gpu():
     import ctypes as C
     import sys
-    sys.path.insert(0, ROOT)
+    sys.path.insert(0, harness.ROOT)
     from par_raytracer_amd import capi
     lib = capi.hip_lib()
     u, info, out = capi.PrtGeometryUpdate(), capi.PrtUpdateInfo(), (C.c_uint64 * 6)()

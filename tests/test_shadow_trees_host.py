@@ -11,29 +11,22 @@ scales 2^10 and 2^14 among them, where the rounding of o + d decides who stays; 
 itself with origins at the bound.  The normal is always the one read back out of the record, as the upload classifies it."""
 import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import harness
+from harness import ROOT
+
 WIDTHS = [4, 8]
 
 
 @pytest.fixture(scope="module")
 def lines(tmp_path_factory):
     out = {}
-    csrc = os.path.join(ROOT, "par_raytracer_amd", "csrc")
     for width in WIDTHS:
-        exe = str(tmp_path_factory.mktemp("shadow_trees") / ("st%d" % width))
-        cmd = ["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-pthread", "-I" + os.path.join(ROOT, "tests", "hip_shim"), "-I" + csrc,
-               "-I" + os.path.join(ROOT, "tests")] + (["-DPRT_BVH8"] if width == 8 else []) + [
-               os.path.join(ROOT, "tests", "shadow_trees_host_harness.cpp"), os.path.join(csrc, "bvh_build.cpp"),
-               os.path.join(csrc, "bvh_check.cpp"), "-o", exe]
-        build = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-        assert build.returncode == 0, build.stdout.decode()
-        run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
-        assert run.returncode == 0, run.stdout.decode()
-        out[width] = run.stdout.decode().splitlines()
+        exe = harness.build("shadow_trees_host_harness.cpp", tmp_path_factory.mktemp("shadow_trees"), "st%d" % width, bvh8=width == 8,
+                            sources=("bvh_build.cpp", "bvh_check.cpp"))
+        out[width] = harness.run(exe, timeout=120).splitlines()
     return out
 
 

@@ -7,17 +7,15 @@ a box-test failure here, without a GPU.  The length case on the flat grid fails 
 traversal (trav_init's absolute 1e-30 clamp: 35 of 2,048 rays) and passes through the queries' (trav_start<true>)."""
 from __future__ import annotations
 
-import os
 import re
 import subprocess
 
 import numpy as np
 import pytest
 
+import harness as H                                         # (the fixture below is called harness)
 import trace_cases as T
 import trace_edge_cases as E
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def of_family(family):
@@ -210,14 +208,8 @@ def harness(tmp_path_factory):
 
     def get(flavour):
         if flavour not in made:
-            exe = str(tmp_path_factory.mktemp("edges") / ("trace_host_" + flavour))
-            flags = {"bvh4": [], "bvh8": ["-DPRT_BVH8"]}[flavour]
-            cmd = ["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-pthread", "-I" + os.path.join(ROOT, "tests", "hip_shim"),
-                   "-I" + os.path.join(ROOT, "par_raytracer_amd", "csrc")] + flags + [
-                   os.path.join(ROOT, "tests", "trace_host_harness.cpp"), os.path.join(ROOT, "par_raytracer_amd", "csrc", "bvh_build.cpp"), "-o", exe]
-            build = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-            assert build.returncode == 0, build.stdout.decode()
-            made[flavour] = exe
+            made[flavour] = H.build("trace_host_harness.cpp", tmp_path_factory.mktemp("edges"), "trace_host_" + flavour,
+                                    bvh8=flavour == "bvh8", sources=("bvh_build.cpp",))
         return made[flavour]
     return get
 

@@ -9,11 +9,12 @@ import ctypes as C
 import ctypes.util
 import os
 import struct
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import harness
+from harness import ROOT
+
 F = np.float32
 
 
@@ -242,7 +243,7 @@ def oracle_hits(scene, records):
 
 def run_hit_harness(exe, scenes, records, directory):
     """[(n, 16) float32 per scene]: textured_hit_at of csrc/dev_texture.h on the host, for the same (v, w) records in every scene."""
-    fin, fout = os.path.join(str(directory), "hit_cases.bin"), os.path.join(str(directory), "hit_results.bin")
+    fin, fout = harness.case_files(directory, "hit_cases.bin", "hit_results.bin")
     rec = np.ascontiguousarray(records, F).reshape(-1, 2)
     with open(fin, "wb") as f:
         f.write(struct.pack("<II", 1, len(scenes)))
@@ -258,11 +259,11 @@ def run_hit_harness(exe, scenes, records, directory):
                 f.write(np.ascontiguousarray(a, F).tobytes())
             f.write(struct.pack("<I", len(rec)))
             f.write(rec.tobytes())
-    run = subprocess.run([exe, fin, fout], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    assert run.returncode == 0, run.stdout.decode()[-4000:]
-    blob = np.fromfile(fout, F)
-    assert blob.size == 16 * len(rec) * len(scenes)
-    return list(blob.reshape(len(scenes), len(rec), 16).copy())
+    harness.run(exe, fin, fout)
+    r = harness.Reader.of_file(fout)
+    out = [r.take(16 * len(rec), F, (len(rec), 16)) for _ in scenes]
+    r.done()
+    return out
 
 
 def has_maps(name):
@@ -286,19 +287,13 @@ def assert_same_hits(got, expect, what, compare_uv=True):
 # ---- the host harness
 
 def build_harness(directory):
-    exe = os.path.join(str(directory), "texture_host")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off",
-           "-I" + os.path.join(ROOT, "tests", "hip_shim"), "-I" + os.path.join(ROOT, "par_raytracer_amd", "csrc"),
-           os.path.join(ROOT, "tests", "texture_host_harness.cpp"), "-o", exe]
-    build = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    assert build.returncode == 0, build.stdout.decode()
-    return exe
+    return harness.build("texture_host_harness.cpp", directory, "texture_host")
 
 
 def run_harness(exe, texture_dims, texture_bytes, records, directory):
     """(srgb table (256), samples (n, 5): tex_sample_rgb's x, y, z, tex_sample_r and the fourth channel by tex_channel) of the
     records (n, 3: texture, u, v)."""
-    fin, fout = os.path.join(str(directory), "texture_cases.bin"), os.path.join(str(directory), "texture_results.bin")
+    fin, fout = harness.case_files(directory, "texture_cases.bin", "texture_results.bin")
     dims = np.ascontiguousarray(texture_dims, np.uint32).reshape(-1)
     texels = np.ascontiguousarray(texture_bytes, np.uint8)
     rec = np.ascontiguousarray(records, F).reshape(-1, 3)
@@ -309,15 +304,13 @@ def run_harness(exe, texture_dims, texture_bytes, records, directory):
         f.write(texels.tobytes())
         f.write(struct.pack("<I", len(rec)))
         f.write(rec.tobytes())
-    run = subprocess.run([exe, fin, fout], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    assert run.returncode == 0, run.stdout.decode()[-4000:]
-    blob = np.fromfile(fout, F)
-    assert blob.size == 256 + 5 * len(rec)
-    return blob[:256].copy(), blob[256:].reshape(-1, 5).copy()
+    harness.run(exe, fin, fout)
+    r = harness.Reader.of_file(fout)
+    out = r.take(256, F), r.take(5 * len(rec), F, (-1, 5))
+    r.done()
+    return out
 
 
 def assert_same_bits(got, expect, what):
-    g, e = bits(got), bits(expect)
-    bad = np.nonzero((g != e).reshape(len(g), -1).any(1))[0]
-    assert bad.size == 0, "%s: %d of %d records differ, first %d: got %r, expected %r" % (
-        what, bad.size, len(g), bad[0], np.asarray(got)[bad[0]].tolist(), np.asarray(expect)[bad[0]].tolist())
+    """Two float32 arrays of records, bit for bit."""
+    harness.assert_same_bits({"records": np.asarray(got, F)}, {"records": np.asarray(expect, F)}, what, ("records",))

@@ -22,19 +22,9 @@
 
 #include "tex_upload.h"
 #include "dev_texture.h"
+#include "harness_io.h"
 
 using namespace prt;
-
-template <class T>
-static std::vector<T> rd(FILE * f, size_t n) {
-    std::vector<T> v(n);
-    if (n && fread(v.data(), sizeof(T), n, f) != n) { fprintf(stderr, "texture_host: short read\n"); exit(2); }
-    return v;
-}
-template <class T>
-static void wr(FILE * f, const std::vector<T> & v) {
-    if (!v.empty() && fwrite(v.data(), sizeof(T), v.size(), f) != v.size()) { fprintf(stderr, "texture_host: short write\n"); exit(2); }
-}
 
 // A texture table as the cases file holds it, and what prt_upload_scene makes of it (csrc/tex_upload.h).
 struct Tables {
@@ -120,9 +110,8 @@ static void run_hits(FILE * fin, FILE * fout) {
 }
 
 int main(int argc, char ** argv) {
-    if (argc < 3) { fprintf(stderr, "usage: texture_host cases.bin results.bin\n"); return 2; }
-    FILE * fin = fopen(argv[1], "rb"), * fout = fopen(argv[2], "wb");
-    if (!fin || !fout) { fprintf(stderr, "texture_host: cannot open the files\n"); return 2; }
+    FILE * fin, * fout;
+    if (!open_in_out(argc, argv, "texture_host", &fin, &fout)) return 2;
     const uint32_t mode = rd<uint32_t>(fin, 1)[0];
     if (mode == 1) {
         run_hits(fin, fout);

@@ -13,13 +13,14 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import subprocess
 import sys
 import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import harness
+from harness import ROOT
+
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 FLT_MAX = np.float32(3.4028234663852886e38)
 
@@ -36,12 +37,7 @@ def harness_lib(out_dir: str = None) -> C.CDLL:
     """tests/trace_oracle_harness.cpp compiled with g++ (once per process)."""
     global _LIB
     if _LIB is None:
-        out_dir = out_dir or tempfile.mkdtemp(prefix="prt_trace_oracle_")
-        so = os.path.join(out_dir, "trace_oracle.so")
-        cmd = ["g++", "-O2", "-std=c++14", "-fPIC", "-shared", "-ffp-contract=off", "-fno-strict-aliasing", "-pthread",
-               "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "trace_oracle_harness.cpp"), "-o", so]
-        subprocess.run(cmd, check=True)
-        lib = C.CDLL(so)
+        lib = C.CDLL(harness.build_shared("trace_oracle_harness.cpp", out_dir or tempfile.mkdtemp(prefix="prt_trace_oracle_"), "trace_oracle.so"))
         lib.prt_trace_oracle_batch.restype = C.c_int
         lib.prt_trace_oracle_batch.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_uint32] + [C.c_void_p] * 10 + [C.c_int]
         _LIB = lib

@@ -22,9 +22,7 @@
 #include <cstring>
 #include <vector>
 
-#include "dev_trace.h"
-#include "bvh_build.h"
-#include "prt_options.h"
+#include "harness_mesh.h"
 #include "harness_scene.h"
 
 using namespace prt;
@@ -54,42 +52,20 @@ int main(int argc, char ** argv) {
     const uint32_t n_tris = (uint32_t)(verts.size() / 9);
 
     BvhWide bvh;
-#if !defined(PRT_BVH8)
-    build_bvh_wide(4, verts.data(), n_tris, 4, 2, &bvh);
-#else
-    BvhBuildOptions bopt;
-    build_bvh_wide(8, verts.data(), n_tris, 4, 2, &bvh, 1.0f, &bopt);
-#endif
-    // device records, as prt_upload_scene lays them out
-    std::vector<float4> tris((size_t)(n_tris + 1) * 3, make_float4(0, 0, 0, 0));
+    mesh::build_tree(verts, n_tris, &bvh);
+    const std::vector<float4> tris = mesh::records(verts, n_tris, bvh.tri_order.data());        // device records, in leaf order
     std::vector<unsigned int> rank(n_tris + 1, 0);
-    for (uint32_t slot = 0; slot < n_tris; ++slot) {
-        const float * v = &verts[(size_t)bvh.tri_order[slot] * 9];
-        const f3 a = mk3(v[0], v[1], v[2]), b = mk3(v[3], v[4], v[5]), c = mk3(v[6], v[7], v[8]);
-        const f3 ab = b - a, ac = c - a, n = cross3(ab, ac);
-        tris[(size_t)slot * 3 + 0] = make_float4(a.x, a.y, a.z, ab.x);
-        tris[(size_t)slot * 3 + 1] = make_float4(ab.y, ab.z, ac.x, ac.y);
-        tris[(size_t)slot * 3 + 2] = make_float4(ac.z, n.x, n.y, n.z);
-        rank[slot] = bvh.tri_order[slot];                   // the "reference visit order": input order
-    }
+    for (uint32_t slot = 0; slot < n_tris; ++slot) rank[slot] = bvh.tri_order[slot];            // the "reference visit order": input order
     std::vector<uint32_t> slot_of_rank(n_tris);
     for (uint32_t slot = 0; slot < n_tris; ++slot) slot_of_rank[rank[slot]] = slot;
     unsigned long long unresolved = 0;
-    DevScene sc;
-    memset(&sc, 0, sizeof(sc));
-    sc.nodes = reinterpret_cast<const float4 *>(bvh.nodes.data());
-    sc.tris = tris.data();
+    mesh::Walk lane(bvh, tris, n_tris);
+    DevScene & sc = lane.sc;
     sc.tri_rank = rank.data();
-    sc.tri_count = n_tris;
-    sc.node_count = bvh.node_count;
     sc.tie_widen_max = 8;
     sc.near_tie_unresolved = &unresolved;
-
-    std::vector<int> stack_mem((size_t)(bvh.stack_bound + 2) * STACK_ENTRY_INTS, 0);
-    GlobalStack stk;
-    stk.attach(stack_mem.data(), 0, 1);
-    TraceStats st;
-    memset(&st, 0, sizeof(st));
+    GlobalStack & stk = lane.stk;
+    TraceStats & st = lane.st;
 
     float pad = 16.0f / 65536.0f, scene_max = 0.0f;
     unsigned long long scanned = 0;
