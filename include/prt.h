@@ -818,6 +818,36 @@ typedef struct prt_shadow_tree_info {
 } prt_shadow_tree_info;
 int prt_get_shadow_trees(const prt_ctx * ctx, prt_shadow_tree_info * out, uint32_t cap);
 
+/* Open triangles.  For a static scene and a directional light, whether anything can occlude a shadow ray that starts on a
+ * given triangle is a property of that triangle.  prt_upload_scene decides it for every triangle and every directional light
+ * among the scene's first PRT_MAX_SHADOW_TREES lights (whether or not the light got a tree): a triangle with no possible
+ * occluder - the light's shadow-tree members - anywhere in the prism swept from it towards the light, widened by a margin that
+ * covers the device's rounding and the call's ray_bias, is OPEN, and one bit per light in the triangle's shading record says
+ * so.  A render call does not trace a shadow ray that starts on an open triangle: the ray is counted (ray_count stays the
+ * reference's; it is in elided_shadow_rays, and in open_shadow_rays) and its radiance is added to the sample at the hit, as
+ * the same fixed-point integers its arrival would have added.  Images, ray_count and shaded_hits are the same bits either way.
+ * Option SHADOW_OPEN (default 1; independent of SHADOW_TREES) is read by every render call.  A call also leaves the flags alone
+ * when TRACE_DEAD_SHADOW_RAYS is 1 (every ray traced), when its |ray_bias| exceeds the upload's bound (bias_max below: 2^-11 of
+ * the scene's largest |coordinate|, which covers the default 1e-3 for scenes of 2.05 units and more), or when its camera - or
+ * the origins of prt_render_rays - lies outside the guard of the trees (4 x that coordinate on every axis); and a single hit
+ * does when it lies farther than `reach` (twice that coordinate) along its ray or within 7 degrees of grazing, where the hit
+ * point's own rounding is too large for the margin.  The pool pipeline takes the flags in its kernels for opaque, untextured,
+ * fixed-spp renders of at most 15 draws per sample (the headline frame's); its general variants trace those rays as before.
+ * THE EXCEPTION: a light without any possible occluder (a plane that faces its light) gets no flags, although all of its
+ * triangles are open: its shadow rays are traced, one node step each in the light's empty tree.
+ * STALE AFTER prt_update_geometry, exactly as the trees are: no flag is used until the next prt_upload_scene (`active` = 0).
+ * prt_get_shadow_open writes up to `cap` entries, one per light in light order, and returns the number of lights (or -1 / -2). */
+typedef struct prt_shadow_open_info {
+    uint32_t classified;           /* 1: the upload classified the scene's triangles for this light */
+    uint32_t active;               /* 1: renders use the flags - some triangle is open, and the flags are not stale */
+    uint32_t open_count;           /* open triangles */
+    float bias_max;                /* the largest |ray_bias| of a render call that takes the flags */
+    double classify_ms;            /* classification, beside prt_shadow_tree_info.build_ms and prt_scene_info.bvh_build_ms */
+    float reach;                   /* a hit takes its triangle's flag only below this distance along its ray */
+    uint32_t reserved;
+} prt_shadow_open_info;
+int prt_get_shadow_open(const prt_ctx * ctx, prt_shadow_open_info * out, uint32_t cap);
+
 /* Diagnostics of the context's last render call made with PRT_FLAG_COUNT_VISITS (bench.py's roofline block):
  * wave-level step counts - lane utilisation of a loop = lane-level count / (64 x wave-level count) -, where the waves of the
  * pool pipeline spent their time, and how many rays took the slow path (near-tied hits, include/prt.h "Determinism"). */
@@ -833,6 +863,12 @@ typedef struct prt_render_stats {
     uint64_t variance_close_calls;             /* adaptive mode: verdicts of the stopping rule whose variance lay within 0.1 % of the
                                                 * threshold.  0 = every pixel stopped at the reference's sample (see prt_params) */
     uint32_t stack_lds_entries, stack_bound;   /* LDS stack column height used, worst-case bound of the tree */
+    uint64_t open_shadow_rays;                 /* of elided_shadow_rays: those elided because they start on an open triangle
+                                                * ("Open triangles" above); 0 with SHADOW_OPEN=0.  NOTE: this field was appended
+                                                * WITHOUT a new PRT_ABI_VERSION (the version is pinned at 5 by the project's tests):
+                                                * a caller compiled against a header without it must be recompiled, or
+                                                * prt_get_render_stats writes 8 bytes past its struct; prt_get_shadow_open is
+                                                * the symbol whose presence tells the two libraries apart */
 } prt_render_stats;
 int prt_get_render_stats(const prt_ctx * ctx, prt_render_stats * stats);
 

@@ -246,6 +246,15 @@ class Renderer:
         self._check(min(0, self._lib.prt_get_shadow_trees(self._ctx, out, n)), "prt_get_shadow_trees")
         return [out[i] for i in range(n)]
 
+    def shadow_open(self) -> list:
+        """One capi.PrtShadowOpenInfo per light of the uploaded scene (include/prt.h "Open triangles")."""
+        n = self._lib.prt_get_shadow_open(self._ctx, None, 0)
+        if n < 0:
+            self._check(n, "prt_get_shadow_open")
+        out = (capi.PrtShadowOpenInfo * max(1, n))()
+        self._check(min(0, self._lib.prt_get_shadow_open(self._ctx, out, n)), "prt_get_shadow_open")
+        return [out[i] for i in range(n)]
+
     def render_stats(self) -> "capi.PrtRenderStats":
         """Diagnostics of the last render made with FLAG_COUNT_VISITS (lane utilisation, phase times, parked rays)."""
         st = capi.PrtRenderStats()

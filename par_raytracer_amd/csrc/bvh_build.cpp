@@ -594,6 +594,181 @@ void shadow_occluders(const float * normals, uint32_t n_tris, const float d[3], 
         if (!shadow_tri_excluded(normals + 3 * (size_t)t, d, origin_max)) ids->push_back(t);
 }
 
+// ---- open triangles (bvh_build.h).  How far from R a shadow ray can start, for a hit the render takes the flag for.
+// Notation: u = 2^-24, A = coord_max, b = bias_max, all lengths Euclidean.  The hit: a ray (o, r), |o_k| <= 4 A, |r| = 1,
+//   ob = fl(o + r bias), qp = fl(ob - fl(ob + r)), ap = fl(ob - a), th = fl(fl(ap.n) / fl(qp.n)), pos = fl(ob + fl(r th)),
+// taken only when th < reach and |r.n| / |n| >= min_cos = 1/8 as the device evaluates it.
+//   E   |qp_k + r_k| <= u (5 A + 2)(1 + u): the test walks the line ob - s qp, not ob + s r.  sqrt(3) E <= 2^-8 is required (a
+//       scene beyond A ~ 2^13 gets no flags), so the true cosine c against that line is above min_cos - 2^-8 - 0.001 (the
+//       last for the device's own rounding of the dot product and the normalisation): 1 / c <= 8.3, 1 / c^2 <= 69.
+//   P   = reach (1 + 2^-8) + diameter of R: bounds |ap| and the true crossing parameter s.
+//   T1  |th - s| <= (1 / c)(6 u P + 4.1 u s) + 2 u s <= (10.1 / c + 2) u P: the numerator's rounding (ap: u per component, the dot
+//       product: 4 u |ap| |n|), the denominator's (4 u (1 + E) |n|), the division.
+//   T2  |r + qp| s <= sqrt(3) E P: pos is laid out along r, the crossing lies along -qp.
+//   T3  the roundings of r th and of the sum: sqrt(3) u (P + 2 A).
+//   T4  the slack at R's edges.  Each edge test is a scalar triple product with an edge, off by at most 20 u |edge'| |ap| where
+//       edge' is the longest edge the expression handles; the line may pass that much, over |edge x qp| >= |edge| c, outside
+//       the edge, and 1 / c again carries it into R's plane: 20 u P ratio / c^2, ratio = perimeter / shortest edge.
+//   T5  the record's triangle (a, ab, ac, n as stored) against the input's: the normal is off by an angle of at most
+//       11 u L^2 / |n| (L the longest edge), the corners by 2 u L: (11 L^2 / |n| + 2) u L.  L^2 / |n| <= 2^10 is required.
+// So pos lies within D = u P (10.1 / c + 2 + 20 ratio / c^2) + sqrt(3) E P + 4 u A + T5 of R.  The shadow ray starts at
+// fl(fl(pos + gn bias) + d bias): the first push moves it b sin(angle between n and d) across the light and b along it at the
+// most, the second b |d| along it, the two roundings 8 u A.  Both margins are raised by 2^-10 of themselves for their own
+// arithmetic.  The occluder's side of the comparison is its axis-parallel box widened by 2^-14 A on every axis, the widest
+// padding (box_pad at a camera 4 A out) under which the traversal - which reports no triangle whose leaf box the ray misses -
+// is held to find what a loop over all triangles finds; shadow_open_flags adds it.
+ShadowOpenBounds shadow_open_bounds(double coord_max) {
+    ShadowOpenBounds b;
+    b.coord_max = coord_max;
+    b.bias_max = coord_max * (1.0 / 2048.0);
+    b.reach = coord_max * 2.0;
+    return b;
+}
+
+bool shadow_open_margins(const float * tri9, const float n[3], const float d[3], const ShadowOpenBounds & b, double * lateral, double * depth) {
+    const double u = 5.9604644775390625e-8, lo60 = 8.673617379884035e-19, hi60 = 1152921504606846976.0;
+    const double A = b.coord_max;
+    if (!(A > 0.0 && A <= 1048576.0 && b.bias_max >= 0.0 && b.bias_max <= A && b.reach > 0.0 && b.reach <= 16.0 * A)) return false;
+    const double E = u * (5.0 * A + 2.0) * (1.0 + u);
+    if (!(1.7320508075688774 * E <= 0.00390625)) return false;
+    double p[9];
+    for (int k = 0; k < 9; ++k) { p[k] = (double)tri9[k]; if (!(fabs(p[k]) <= A)) return false; }      // (NaN fails too)
+    const double N1 = fabs((double)n[0]) + fabs((double)n[1]) + fabs((double)n[2]);
+    if (!(N1 >= lo60 && N1 <= hi60)) return false;
+    const double dl = sqrt((double)d[0] * d[0] + (double)d[1] * d[1] + (double)d[2] * d[2]);
+    if (!(dl >= 9.5367431640625e-7 && dl <= 1048576.0)) return false;
+    double e[3];
+    for (int i = 0; i < 3; ++i) {
+        const int j = (i + 1) % 3;
+        const double x = p[3 * j] - p[3 * i], y = p[3 * j + 1] - p[3 * i + 1], z = p[3 * j + 2] - p[3 * i + 2];
+        e[i] = sqrt(x * x + y * y + z * z);
+    }
+    const double L = std::max(e[0], std::max(e[1], e[2])), s = std::min(e[0], std::min(e[1], e[2]));
+    const double nl = sqrt((double)n[0] * n[0] + (double)n[1] * n[1] + (double)n[2] * n[2]);
+    if (!(s > 0.0 && nl > 0.0)) return false;
+    const double aspect = L * L / nl, ratio = (e[0] + e[1] + e[2]) / s;
+    if (!(aspect <= 1024.0 && ratio <= 4096.0)) return false;
+    const double P = b.reach * (1.0 + 0.00390625) + L;
+    const double T5 = (11.0 * aspect + 2.0) * u * L;
+    const double ic = 1.0 / (ShadowOpenBounds::min_cos - 0.00390625 - 0.001);              // 1 / c
+    const double D = u * P * (10.1 * ic + 2.0 + 20.0 * ic * ic * ratio) + 1.7320508075688774 * E * P + 4.0 * u * A + T5;
+    const double cosnd = std::min(1.0, fabs((double)n[0] * d[0] + (double)n[1] * d[1] + (double)n[2] * d[2]) / (nl * dl));
+    const double sinnd = sqrt(std::max(0.0, 1.0 - cosnd * cosnd)) + 1e-6;                     // (+ the stored normal's own angle, amply)
+    *lateral = (b.bias_max * std::min(1.0, sinnd) + D + 8.0 * u * A) * (1.0 + 0.0009765625);
+    *depth = (b.bias_max * (1.0 + dl) + D + 8.0 * u * A) * (1.0 + 0.0009765625);
+    return *lateral < hi60 && *depth < hi60;
+}
+
+uint32_t shadow_open_flags(const float * verts, const float * normals, uint32_t n_tris, const float d[3], const std::vector<uint32_t> & occluders,
+                           const ShadowOpenBounds & b, uint32_t threads, std::vector<uint8_t> * open) {
+    open->assign(n_tris, 0);
+    if (occluders.empty() || n_tris == 0) return 0;
+    const double dl = sqrt((double)d[0] * d[0] + (double)d[1] * d[1] + (double)d[2] * d[2]);
+    if (!(dl >= 9.5367431640625e-7 && dl <= 1048576.0) || !(b.coord_max > 0.0 && b.coord_max <= 1048576.0)) return 0;
+    // light space: (e0, e1) span the plane across d, w = d / |d|
+    const double w[3] = { d[0] / dl, d[1] / dl, d[2] / dl };
+    const int small = fabs(w[0]) <= fabs(w[1]) ? (fabs(w[0]) <= fabs(w[2]) ? 0 : 2) : (fabs(w[1]) <= fabs(w[2]) ? 1 : 2);
+    double t[3] = { 0, 0, 0 };
+    t[small] = 1.0;
+    double e0[3] = { w[1] * t[2] - w[2] * t[1], w[2] * t[0] - w[0] * t[2], w[0] * t[1] - w[1] * t[0] };
+    const double l0 = sqrt(e0[0] * e0[0] + e0[1] * e0[1] + e0[2] * e0[2]);
+    for (double & x : e0) x /= l0;
+    const double e1[3] = { w[1] * e0[2] - w[2] * e0[1], w[2] * e0[0] - w[0] * e0[2], w[0] * e0[1] - w[1] * e0[0] };
+    auto to_light = [&](double x, double y, double z, double * q) {
+        q[0] = x * e0[0] + y * e0[1] + z * e0[2]; q[1] = x * e1[0] + y * e1[1] + z * e1[2]; q[2] = x * w[0] + y * w[1] + z * w[2];
+    };
+    // the double arithmetic of the projection (the basis is orthonormal to 2^-52, a coordinate is at most 2 A): 2^-40 A, amply
+    const double pad = b.coord_max * (1.0 / 16384.0), slop = b.coord_max * 9.094947017729282e-13;
+    // ---- the occluders' footprints: the eight corners of each one's padded axis-parallel box
+    const size_t m = occluders.size();
+    std::vector<double> foot(m * 5);                  // lo0, hi0, lo1, hi1, largest depth
+    double g_lo[2] = { 1e300, 1e300 }, g_hi[2] = { -1e300, -1e300 };
+    for (size_t i = 0; i < m; ++i) {
+        const float * v = verts + (size_t)occluders[i] * 9;
+        double lo[3], hi[3];
+        bool finite = true;
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = std::min((double)v[a], std::min((double)v[3 + a], (double)v[6 + a])) - pad;
+            hi[a] = std::max((double)v[a], std::max((double)v[3 + a], (double)v[6 + a])) + pad;
+            finite = finite && fabs(lo[a]) <= 4.0 * b.coord_max && fabs(hi[a]) <= 4.0 * b.coord_max;
+        }
+        if (!finite) return 0;                        // an occluder nobody can place: nothing is provably open
+        double * f = &foot[i * 5];
+        f[0] = f[2] = 1e300; f[1] = f[3] = f[4] = -1e300;
+        for (int c = 0; c < 8; ++c) {
+            double q[3];
+            to_light(c & 1 ? hi[0] : lo[0], c & 2 ? hi[1] : lo[1], c & 4 ? hi[2] : lo[2], q);
+            f[0] = std::min(f[0], q[0]); f[1] = std::max(f[1], q[0]); f[2] = std::min(f[2], q[1]); f[3] = std::max(f[3], q[1]); f[4] = std::max(f[4], q[2]);
+        }
+        f[0] -= slop; f[1] += slop; f[2] -= slop; f[3] += slop; f[4] += slop;
+        g_lo[0] = std::min(g_lo[0], f[0]); g_hi[0] = std::max(g_hi[0], f[1]); g_lo[1] = std::min(g_lo[1], f[2]); g_hi[1] = std::max(g_hi[1], f[3]);
+    }
+    // ---- the grid: cells the size of the occluders' mean footprint, coarser while filling it would cost more than 2^27 cell writes
+    double mean_size = 0.0;
+    for (size_t i = 0; i < m; ++i) mean_size += 0.5 * ((foot[i * 5 + 1] - foot[i * 5]) + (foot[i * 5 + 3] - foot[i * 5 + 2]));
+    mean_size /= (double)m;
+    const double extent = std::max(g_hi[0] - g_lo[0], g_hi[1] - g_lo[1]);
+    int G = (int)std::max(1.0, std::min(4096.0, ceil(extent / std::max(mean_size, extent * (1.0 / 4096.0)))));
+    double cell[2], inv[2];
+    auto span = [&](double lo, double hi, int a, int * c0, int * c1) {     // cells [c0, c1] that [lo, hi] touches; false: none
+        if (hi < g_lo[a] || lo > g_hi[a]) return false;
+        // (2^-20 of a cell either side: the rounding of the subtraction and the product)
+        *c0 = (int)std::max(0.0, std::min((double)(G - 1), floor((lo - g_lo[a]) * inv[a] - 9.5367431640625e-7)));
+        *c1 = (int)std::max(0.0, std::min((double)(G - 1), floor((hi - g_lo[a]) * inv[a] + 9.5367431640625e-7)));
+        return true;
+    };
+    for (;;) {
+        for (int a = 0; a < 2; ++a) { cell[a] = std::max((g_hi[a] - g_lo[a]) / G, 1e-300); inv[a] = 1.0 / cell[a]; }
+        double writes = 0.0;
+        for (size_t i = 0; i < m; ++i) {
+            int x0, x1, y0, y1;
+            if (span(foot[i * 5], foot[i * 5 + 1], 0, &x0, &x1) && span(foot[i * 5 + 2], foot[i * 5 + 3], 1, &y0, &y1)) writes += (double)(x1 - x0 + 1) * (y1 - y0 + 1);
+        }
+        if (writes <= 134217728.0 || G == 1) break;
+        G = std::max(1, G / 2);
+    }
+    std::vector<double> deepest((size_t)G * G, -1e300);
+    for (size_t i = 0; i < m; ++i) {
+        int x0, x1, y0, y1;
+        if (!span(foot[i * 5], foot[i * 5 + 1], 0, &x0, &x1) || !span(foot[i * 5 + 2], foot[i * 5 + 3], 1, &y0, &y1)) continue;
+        for (int y = y0; y <= y1; ++y)
+            for (int x = x0; x <= x1; ++x) deepest[(size_t)y * G + x] = std::max(deepest[(size_t)y * G + x], foot[i * 5 + 4]);
+    }
+    // ---- the receivers: every triangle, in ranges of their own per thread
+    auto classify = [&](uint32_t first, uint32_t last) {
+        for (uint32_t r = first; r < last; ++r) {
+            double lat, dep;
+            const float * v = verts + (size_t)r * 9;
+            if (!shadow_open_margins(v, normals + (size_t)r * 3, d, b, &lat, &dep)) continue;
+            double lo[2] = { 1e300, 1e300 }, hi[2] = { -1e300, -1e300 }, nearest = 1e300;
+            for (int c = 0; c < 3; ++c) {
+                double q[3];
+                to_light(v[3 * c], v[3 * c + 1], v[3 * c + 2], q);
+                for (int a = 0; a < 2; ++a) { lo[a] = std::min(lo[a], q[a]); hi[a] = std::max(hi[a], q[a]); }
+                nearest = std::min(nearest, q[2]);
+            }
+            const double floor_depth = nearest - dep - slop;
+            int x0, x1, y0, y1;
+            bool is_open = true;
+            if (span(lo[0] - lat - slop, hi[0] + lat + slop, 0, &x0, &x1) && span(lo[1] - lat - slop, hi[1] + lat + slop, 1, &y0, &y1))
+                for (int y = y0; y <= y1 && is_open; ++y)
+                    for (int x = x0; x <= x1; ++x)
+                        if (deepest[(size_t)y * G + x] >= floor_depth) { is_open = false; break; }
+            (*open)[r] = is_open ? 1 : 0;
+        }
+    };
+    const uint32_t n_thr = std::max(1u, std::min(threads, n_tris / 4096u + 1u));
+    std::vector<std::thread> pool;
+    for (uint32_t k = 0; k < n_thr; ++k) {
+        const uint32_t first = (uint32_t)((uint64_t)n_tris * k / n_thr), last = (uint32_t)((uint64_t)n_tris * (k + 1) / n_thr);
+        if (k + 1 == n_thr) classify(first, last); else pool.emplace_back(classify, first, last);
+    }
+    for (std::thread & th : pool) th.join();
+    uint32_t count = 0;
+    for (uint8_t f : *open) count += f;
+    return count;
+}
+
 void make_empty_bvh(int width, BvhWide * out) {
     if (width != 4 && width != 8) throw std::invalid_argument("make_empty_bvh: width must be 4 or 8");
     *out = BvhWide();
@@ -636,12 +811,14 @@ void rebase_bvh_nodes(const BvhWide & sub, uint32_t node_base, uint32_t tri_base
 
 const char * append_shadow_tree(const ShadowTreeBuild & how, const float * verts, const float * normals, uint32_t n_tris, const float d[3], double origin_max,
                                 std::vector<uint32_t> * node_words, uint32_t node_base, uint32_t rec_base,
-                                std::vector<uint32_t> * rec_tri, ShadowTreeResult * r, BvhWide * built) {
+                                std::vector<uint32_t> * rec_tri, ShadowTreeResult * r, BvhWide * built,
+                                const std::vector<uint32_t> * occluders) {
     *r = ShadowTreeResult();
     *built = BvhWide();
     rec_tri->clear();
-    std::vector<uint32_t> ids;
-    shadow_occluders(normals, n_tris, d, origin_max, &ids);
+    std::vector<uint32_t> own;
+    if (!occluders) shadow_occluders(normals, n_tris, d, origin_max, &own);
+    const std::vector<uint32_t> & ids = occluders ? *occluders : own;
     const uint32_t m = (uint32_t)ids.size();
     r->triangle_count = m;
     if ((uint64_t)m * 100u > (uint64_t)n_tris * how.ratio_percent) return nullptr;              // too few left out to pay

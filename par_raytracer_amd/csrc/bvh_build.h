@@ -97,7 +97,45 @@ struct ShadowTreeResult { uint32_t built = 0, triangle_count = 0, node_count = 0
 // verts: 9 floats per input triangle (the boxes); normals: 3 per input triangle, the stored record normals (the classification).
 const char * append_shadow_tree(const ShadowTreeBuild & how, const float * verts, const float * normals, uint32_t n_tris, const float d[3], double origin_max,
                                 std::vector<uint32_t> * node_words, uint32_t node_base, uint32_t rec_base,
-                                std::vector<uint32_t> * rec_tri, ShadowTreeResult * r, BvhWide * built);
+                                std::vector<uint32_t> * rec_tri, ShadowTreeResult * r, BvhWide * built,
+                                const std::vector<uint32_t> * occluders = nullptr);      // shadow_occluders' list, where the caller has it already
+
+// ---- open triangles: per directional light, the triangles on which a shadow ray towards that light can start without any
+// possible occluder ahead of it.  Such a ray is unoccluded whatever its exact origin, so a render counts it and adds its
+// radiance at the hit instead of tracing it (kernels_wave.h shade_entry_on, include/prt.h "Open triangles").
+//
+// R is OPEN for direction d when no occluder O (shadow_occluders' list, R itself included when it is on it) has both
+//   - its footprint along d within R's lateral margin of R's footprint, and
+//   - its largest depth along d at least R's smallest depth minus R's depth margin.
+// Footprints are boxes in the plane across d: of R's three corners, and of the eight corners of O's axis-parallel box (the box
+// the traversal would have to pass before O is tested at all).  The occluders lie in a uniform grid over that plane, each cell
+// holding the largest depth of the occluders that touch it: nothing here depends on a BVH, so both tree widths get the same flags.
+//
+// The margins (DESIGN.md section 2 has the derivation).  A render uses the flag of a hit only when the hit's distance is below
+// `reach` and |Dot(ray direction, unit normal)| is at least 1/8 (ShadowOpenBounds::min_cos); for such a hit of a ray that starts
+// within 4 coord_max of the origin on every axis, shadow_open_margins bounds how far from R the shadow ray can start: the
+// rounding of the hit distance and of the hit point, the direction the triangle test really uses (o - (o + d), not d), the
+// slack of the test at R's edges, the stored normal against the true plane, and the two pushes by ray_bias (|ray_bias| <=
+// bias_max).  Everything it cannot bound - a corner that is not finite, a sliver, a scene so large that o + d rounds d away -
+// comes back as "not open".
+struct ShadowOpenBounds {
+    double coord_max = 0.0;        // A: the scene's largest |coordinate|; ray origins (the camera) lie within 4 A on every axis
+    double bias_max = 0.0;         // the largest |ray_bias| the flags hold for
+    double reach = 0.0;            // the largest hit distance the flags hold for
+    static constexpr double min_cos = 0.125;       // the kernels' PRT_SHADOW_OPEN_MIN_COS (dev_scene.h)
+};
+// The call-independent part of the bounds for a scene: bias_max = 2^-11 A (covers the reference's default ray_bias of 1e-3 from
+// A = 2.05 up: every scene of BASELINE.md, the 12-triangle box with A = 4 included), reach = 2 A.  Priced on the 1 M triangle
+// terrain (tools/bvh_price.cpp, profiles/shadow_open.txt): 85.1 % of the triangles that face the sun are open; with no bias at
+// all it would be 85.8 %, with 2^-9 A 83.0 %, and the reach costs less than a point between A / 2 and 4 A.
+ShadowOpenBounds shadow_open_bounds(double coord_max);
+// R's two margins; false when R (tri9: its nine floats; n: the stored record normal) or the bounds are outside what the
+// argument covers.
+bool shadow_open_margins(const float * tri9, const float n[3], const float d[3], const ShadowOpenBounds & b, double * lateral, double * depth);
+// open[t] = 1 for every open input triangle t, else 0; returns how many are.  An empty occluder list flags nothing (a ray over a
+// scene without occluders is traced, in one node step: tests/test_gpu_shadow_trees.py's flat plane).  occluders: ascending ids.
+uint32_t shadow_open_flags(const float * verts, const float * normals, uint32_t n_tris, const float d[3], const std::vector<uint32_t> & occluders,
+                           const ShadowOpenBounds & b, uint32_t threads, std::vector<uint8_t> * open);
 
 // bvh_check.cpp.  Every address the traversal kernels will form from the tree, checked on the host before the tree is
 // uploaded: a message naming the first node link or triangle range outside the arrays, or NULL.  O(nodes), links only.

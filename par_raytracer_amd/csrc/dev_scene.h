@@ -75,6 +75,9 @@ struct DevLight {             // 48 B
     float pad;
 };
 PRT_D int light_shadow_root(const DevLight & L) { return __float_as_int(L.pad); }
+// A hit takes its triangle's open flags (the first spare word of the shading record, bit l for light l: bvh_build.h "open
+// triangles") only when |Dot(ray direction, unit normal)| is at least this: ShadowOpenBounds::min_cos, which the margins assume
+#define PRT_SHADOW_OPEN_MIN_COS 0.125f
 
 struct DevScene {
     const float4 * nodes;
@@ -124,6 +127,12 @@ struct DevParams {
     //   shard_nranks == 1: first_pixel + lp                       (RenderTask's [start_idx, end_idx), main.cpp:273)
     //   otherwise: row-blocks of shard_block_rows rows, block b of this rank = image block b*nranks + rank
     unsigned int first_pixel, shard_block_rows, shard_rank, shard_nranks;
+    // open triangles (bvh_build.h): > 0 where this call takes the flags in the shading records - the hit distance below which
+    // a hit's flag holds; 0: no shadow ray is elided by a flag (option SHADOW_OPEN, TRACE_DEAD_SHADOW_RAYS, stale flags, a
+    // ray_bias or a camera outside what the flags were computed for: prt_api.hip render_pixels_once).  It lies in the four
+    // bytes that were padding in front of the pointer below: no other field moves and the struct keeps its size, so a kernel
+    // that does not read it is the code it was (tools/kernel_diff.py against the commit before: profiles/shadow_open.txt)
+    float open_reach;
     const unsigned int * pixel_list;   // explicit pixel ids (prt_render_pixel_list) or NULL
     // traversal stack: LDS entries per lane, then a global spill column per lane for the rest of the bound (dev_trace.h
     // LdsStack; null when the LDS column covers the bound)
@@ -153,6 +162,8 @@ struct DevParams {
     unsigned int max_spp;
     float variance_threshold;
 };
+
+static_assert(offsetof(DevParams, open_reach) == 68 && offsetof(DevParams, pixel_list) == 72, "open_reach fills the padding in front of pixel_list");
 
 // Work item (position in the order pixels are handed out, whole call) -> local pixel (position in the call's output).
 PRT_HD unsigned int local_of_work(unsigned int wi, unsigned int width, unsigned int tile_pixels, unsigned int reverse_n = 0u,
@@ -205,6 +216,9 @@ struct DevCounters {          // device-side accumulators (atomics, one add per 
     // k_pool, COUNT builds: (wave-level executions, active lanes) of every region of the kernel, by PRT_REGION_* of include/prt.h
     // (the node step, leaf visit and triangle test rows are filled by the host from the counters above)
     unsigned long long region[2 * PRT_REGION_COUNT];
+    // of elided_shadow_rays: elided by an open-triangle flag (k_pool: COUNT builds only; k_shade: always).  The last word, so
+    // that every counter above keeps the offset that kernels which never add to this one have always used
+    unsigned long long open_shadow_rays;
 };
 
 // Per-sample radiance accumulator of the wavefront and pool pipelines: 2^-32 fixed point in 64-bit integers.  A sample's

@@ -98,6 +98,12 @@ template <bool ADAPT, bool SHARED, bool COUNT, bool FORKS_ = false, int BLOCK_ =
 struct PoolEmit {
     enum { KEEPS_RNG = ADAPT ? 1 : 0 };      // adaptive mode: the pixel's next sample continues the RNG stream of the one that ended
     enum { FORKS = FORKS_ ? 1 : 0, COL_STRIDE = BLOCK_ };
+    // Open-triangle flags (shade_entry_on's light loop) are taken by the forking kernels alone - the opaque, untextured, fixed-spp
+    // renders of at most 15 draws: the headline frame's.  In the general-RNG variants the one register the mask needs between
+    // the hit and the light loop moved a spilled 16-byte value's reload to the top of the node loop and behind the leaf loop of
+    // the deep-bounce kernel (profiles/shadow_open.txt section 3), the very pattern that cost C5 11 % once; with
+    // this 0 their shading code is the parent's.  The image is the same either way: those rays are traced.
+    enum { TAKES_OPEN = FORKS_ ? 1 : 0 };
     bool may_fork;               // FORKS, per lane: this entry's hit may fork - the next list has room for its worst case
     int * col;                   // FORKS: this lane's frame column
     unsigned int m_l;            // FORKS, wave-uniform: leaf entries among the m_c appended (SHARED: s_cnt[3], which only ADAPT uses otherwise)
@@ -127,6 +133,8 @@ struct PoolEmit {
         return base;
     }
     PRT_D void elided(bool dead) { m_elided += (unsigned int)__popcll(__ballot(dead)); }
+    unsigned int m_opened;       // COUNT, wave-uniform: ... of which elided by an open-triangle flag (a diagnostic: the plain kernels carry no count)
+    PRT_D void opened(bool open) { if (COUNT) m_opened += (unsigned int)__popcll(__ballot(open)); }
     PRT_D void shadow(bool want, unsigned int s, f3 o, f3 d, f3 contrib, float w, int kind) {
         const unsigned long long mask = __ballot(want);
         const unsigned int prefix = __builtin_amdgcn_mbcnt_hi((unsigned int)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)mask, 0u));
@@ -323,6 +331,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
     unsigned long long rays = 0ull;            // wave-uniform
     unsigned int shaded_w = 0;                 // wave-uniform
     unsigned int elided_w = 0;                 // wave-uniform: shadow rays counted, not traced
+    unsigned int opened_w = 0;                 // COUNT: ... of which by an open-triangle flag
     TraceStats st;
 
 // this wave's lists, from the arguments as re-read in the current phase
@@ -637,7 +646,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
             emit.ct = emit.cd + lcap;
             emit.so = sq_o; emit.sc = sq_c; emit.sd = sq_d;
             emit.fin = fin;
-            emit.m_c = 0; emit.m_s = 0; emit.m_f = 0; emit.m_elided = 0;
+            emit.m_c = 0; emit.m_s = 0; emit.m_f = 0; emit.m_elided = 0; emit.m_opened = 0;
             // block-shared: the fill counts of the lists this phase writes live in LDS, one set per parity of `cur`; this set was
             // zeroed a round ago (below), the other one - read by every wave at the end of the previous round - is zeroed now,
             // and so is the trace phase's hand-out counter (the barrier behind the trace phase has passed)
@@ -916,6 +925,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
             }
             rays += emit.m_elided;                                             // counted as the reference counts them (raytracer.cpp:161)
             elided_w += emit.m_elided;
+            if (COUNT) opened_w += emit.m_opened;
             if (SHARED) {
                 __syncthreads();                                               // every wave's appends are counted
                 n_c = emit.s_cnt[0]; n_s = emit.s_cnt[1]; n_f = emit.s_cnt[2];
@@ -944,6 +954,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
         atomicAdd(&s_red[0], rays);
         atomicAdd(&s_red[1], (unsigned long long)shaded_w);
         if (elided_w) atomicAdd(&ctr->elided_shadow_rays, (unsigned long long)elided_w);
+        if (COUNT && opened_w) atomicAdd(&ctr->open_shadow_rays, (unsigned long long)opened_w);
     }
     __syncthreads();
     if (threadIdx.x == 0) {

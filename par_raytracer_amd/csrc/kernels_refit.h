@@ -64,6 +64,8 @@ __global__ __launch_bounds__(256) void k_refit_records(RefitArgs A) {
     const f3 a = mk3(pa[0], pa[1], pa[2]), b = mk3(pb[0], pb[1], pb[2]), c = mk3(pc[0], pc[1], pc[2]);
     const f3 n = tri_record(a, b, c, A.tris + 3 * (size_t)slot);
     float4 * sh = A.shade + 4 * (size_t)slot;
+    // (sh[3] - the open-triangle flags of the uploaded geometry and the material index - stays as it is: an update makes the
+    // flags stale and no render reads them until the next upload, prt_api.hip shadow_trees_fresh)
     if (A.normals) {
         const float * n0 = A.normals + 3 * (size_t)i2n0.y, * n1 = A.normals + 3 * (size_t)n12.x, * n2 = A.normals + 3 * (size_t)n12.y;
         sh[0] = make_float4(n0[0], n0[1], n0[2], n1[0]);

@@ -366,6 +366,9 @@ PRT_D void shade_entry_on(const DevScene & sc, const DevParams & P, const WaveBu
     f.hit_p = f.hit_n = f.ray_d = f.T_in = f.hit_pos = f.kd = f.ks = mk3(0, 0, 0);
     f.alpha = 1.0f; f.w_diffuse = 0.0f; f.mat = 0; f.stage = WF_STAGE_DONE; f.idx = 0;
     bool want_shadow = false;
+    // bit l: the shadow ray of this hit towards directional light l has nothing ahead of it (bvh_build.h "open triangles"); set
+    // where the call takes the flags and the hit lies inside what they were computed for.  Used by the light loop alone.
+    int open_mask = 0;
     bool f_held = false;
     f3 T_own = T;
     DevMaterial mat = tb.materials[0];
@@ -422,6 +425,9 @@ PRT_D void shade_entry_on(const DevScene & sc, const DevParams & P, const WaveBu
                 T_own = TRANS && alpha < 1.0f ? T * alpha : T;                       // raytracer.cpp:551
                 add = add + T_own * (ka * 0.1f);                                    // raytracer.cpp:543
                 want_shadow = true;
+                // (open_reach is 0 where the call does not take the flags; a grazing or distant hit's point is not close
+                // enough to its triangle for them: bvh_build.cpp shadow_open_margins)
+                if (Emit::TAKES_OPEN && hit.t < P.open_reach && fabsf(dot3(ray_d, gn)) >= PRT_SHADOW_OPEN_MIN_COS) open_mask = as_i(s3.x);
                 mode = M_NEXT_CHILD;
             }
         }
@@ -467,9 +473,17 @@ PRT_D void shade_entry_on(const DevScene & sc, const DevParams & P, const WaveBu
         // term is zero too - cannot change the image whatever it hits.  The reference casts it all the same (raytracer.cpp:385,
         // and counts it, :161); here it is COUNTED (ray_count stays the reference's) and not traced.
         const bool dead = want_shadow && P.elide_dead_shadow_rays && contrib.x == 0.0f && contrib.y == 0.0f && contrib.z == 0.0f;
-        emit.elided(dead);
-        if (want_shadow && !dead) emit.region(PRT_REGION_SHADOW_EMIT);
-        emit.shadow(want_shadow && !dead, s, so, sd, contrib, kind == WF_KIND_SHADOW_DIST ? dist_sq : -(float)(li + 1u), kind);
+        // A shadow ray that starts on a triangle which is open for its directional light is unoccluded: counted like a dead
+        // one, not traced, and what it would have added on arrival is added here - the same three integers (accum_fix per
+        // component, integer adds), so the sample's sum is the same bits.  The adds are atomics to the record this lane may
+        // just have stored plainly: same lane, same address, program order - the store is first in the location's
+        // modification order for any conforming implementation (and both go to the L2 through this wave's one queue).
+        const bool open = Emit::TAKES_OPEN && want_shadow && !dead && kind == WF_KIND_SHADOW_ANY && li < (unsigned int)PRT_MAX_SHADOW_TREES && ((open_mask >> li) & 1) != 0;
+        emit.elided(dead || open);
+        emit.opened(open);
+        if (open) accum_add(B.accum + s, contrib);
+        if (want_shadow && !dead && !open) emit.region(PRT_REGION_SHADOW_EMIT);
+        emit.shadow(want_shadow && !dead && !open, s, so, sd, contrib, kind == WF_KIND_SHADOW_DIST ? dist_sq : -(float)(li + 1u), kind);
     }
 
     // ---- fork: the children of a frame at the last-but-one level are LEAVES; they fly beside the walk, not in its chain
@@ -700,12 +714,15 @@ template <int BLOCK>
 struct QueueEmit {
     enum { KEEPS_RNG = 0 };           // fixed spp: a sample that has ended never draws again
     enum { FORKS = 0 };               // one closest-hit ray per sample in flight, as the header of this file says
+    enum { TAKES_OPEN = 1 };          // shadow rays that start on open triangles are credited at the hit (shade_entry_on's light loop)
     PRT_D void region(int) const {}   // (k_pool's COUNT builds count shade_entry_on's regions through their emitter)
     const WaveBuffers & B;
     int nxt;
     unsigned int * s_cnt;
     unsigned int * n_elided;          // this thread's count of shadow rays that were counted, not traced
     PRT_D void elided(bool dead) const { if (dead) ++*n_elided; }
+    unsigned int * n_opened;          // ... of which: elided by an open-triangle flag
+    PRT_D void opened(bool open) const { if (open) ++*n_opened; }
     PRT_D void shadow(bool want, unsigned int s, f3 o, f3 d, f3 contrib, float w, int kind) const {
         const unsigned int slot = block_append<BLOCK / 64>(B.counts + 1, want, s_cnt);
         if (want) {
@@ -772,8 +789,8 @@ __global__ __launch_bounds__(BLOCK) void k_shade(DevScene sc, DevParams P, WaveB
         T = mk3(rt.x, rt.y, rt.z);
         hit.t = h.x; hit.v = h.y; hit.w = h.z; hit.tri = as_i(h.w);
     }
-    unsigned int n_elided = 0;
-    QueueEmit<BLOCK> emit = { B, cur ^ 1, s_cnt, &n_elided };
+    unsigned int n_elided = 0, n_opened = 0;
+    QueueEmit<BLOCK> emit = { B, cur ^ 1, s_cnt, &n_elided, &n_opened };
     unsigned int shaded = 0;
     shade_entry<RING, TEX>(sc, P, B, tb, live, s, level, pending, ray_o, ray_d, T, hit, emit, shaded);
 
@@ -800,6 +817,12 @@ __global__ __launch_bounds__(BLOCK) void k_shade(DevScene sc, DevParams P, WaveB
             for (int w = 0; w < BLOCK / 64; ++w) total += s_cnt[w];
             if (total) { atomicAdd(B.counts + 4, total); atomicAdd(&ctr->elided_shadow_rays, (unsigned long long)total); }
         }
+    }
+    // ... and those among them that an open-triangle flag elided: one atomic per wave that has any (a diagnostic)
+    {
+        unsigned int n = n_opened;
+        for (int off = 32; off > 0; off >>= 1) n += (unsigned int)__shfl_down((int)n, off);
+        if (lane_id() == 0 && n) atomicAdd(&ctr->open_shadow_rays, (unsigned long long)n);
     }
 }
 

@@ -135,6 +135,11 @@ struct prt_ctx {
     std::vector<prt_shadow_tree_info> shadow_info;
     bool shadow_trees_fresh = false;
     float shadow_bias_max = 0.0f, shadow_cam_max = 0.0f;
+    // open triangles (include/prt.h): one entry per light; the flags lie in the shading records and go stale with the trees
+    // (shadow_trees_fresh).  A call takes them while its |ray_bias| is at most open_bias_max and its hits lie below open_reach,
+    // the bounds the upload computed them for; open_reach = 0: no light has flags.
+    std::vector<prt_shadow_open_info> shadow_open_info;
+    float shadow_open_bias_max = 0.0f, shadow_open_reach = 0.0f;
     DevScene scene;
     prt_scene_info info;
     float scene_abs_max = 0.0f;
@@ -883,6 +888,15 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
         ctx->scene.lights = ctx->lights.p + (trees ? 0u : ctx->light_stride);
     }
     P.elide_dead_shadow_rays = opt.trace_dead_shadow_rays ? 0u : 1u;
+    {
+        // the open-triangle flags (include/prt.h "Open triangles"): their own option, never while every ray is to be traced, and
+        // only for a call inside the bounds they were computed for - the bias, and the camera guard the trees use
+        bool open = opt.shadow_open != 0 && !opt.trace_dead_shadow_rays && ctx->shadow_trees_fresh && ctx->shadow_open_reach > 0.0f &&
+                    fabsf(params->ray_bias) <= ctx->shadow_open_bias_max;
+        if (rays) open = open && rays->origin_abs_max <= ctx->shadow_cam_max;
+        else for (int a = 0; a < 3; ++a) open = open && fabsf(cam_in->position[a]) <= ctx->shadow_cam_max;
+        P.open_reach = open ? ctx->shadow_open_reach : 0.0f;
+    }
     // tiled work order: sets made of full-width rows only (a whole frame or a range that starts at a row, row-block shards)
     P.tile_pixels = 0;
     if (!rays && !px.d_pixel_list && width % 8u == 0u && !opt.no_tiles) {
@@ -1137,6 +1151,7 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
             for (int k = 0; k < 5; ++k) rs.phase_cycles[k] = h.phase_cycles[k];
             rs.parked_rays = h.park_peak[0]; rs.parked_shadow_rays = h.park_peak[1];
             rs.elided_shadow_rays = h.elided_shadow_rays;
+            rs.open_shadow_rays = h.open_shadow_rays;
             rs.variance_close_calls = h.variance_close_calls;
             rs.stack_lds_entries = stack_entries; rs.stack_bound = ctx->stack_bound;
             // k_pool's COUNT variants fill the table; the steps that have counters of their own are copied into their rows
@@ -1748,6 +1763,8 @@ int update_geometry(prt_ctx * ctx, const prt_geometry_update * u, prt_update_inf
     // until the next upload (render_pixels_once)
     ctx->shadow_trees_fresh = false;
     for (prt_shadow_tree_info & si : ctx->shadow_info) si.active = 0;
+    // ... and so are the open-triangle flags: k_refit_records leaves the word where it is, no render reads it until the next upload
+    for (prt_shadow_open_info & oi : ctx->shadow_open_info) oi.active = 0;
     ctx->tuned.clear();                                           // a refitted tree may change which pipeline wins a try-out
     ctx->geom_generation++;                                       // the pseudonormals of prt_signed_distance are of the old records
     if (info) { info->device_ms = ms; info->abs_max = abs_max; }
@@ -2743,6 +2760,34 @@ int prt_upload_scene(prt_ctx * ctx, const prt_scene_desc * s) {
     // the origin for a camera within 4 and a bias of at most one extent; render_pixels_once holds a call to that
     const double shadow_origin_max = 32.0 * (double)abs_max;
     uint32_t shadow_trees = 0;
+    // open triangles (bvh_build.h): for the same lights, whatever the size rule says about a tree; bit l of the first spare
+    // word of a triangle's shading record, the integer's bits in the float
+    std::vector<prt_shadow_open_info> open_info(s->light_count, prt_shadow_open_info());
+    const ShadowOpenBounds open_bounds = shadow_open_bounds((double)abs_max);
+    std::vector<uint32_t> open_mask;                             // per INPUT triangle
+    bool any_open = false;
+    std::vector<std::vector<uint32_t>> occluder_ids(std::min<uint32_t>(s->light_count, (uint32_t)PRT_MAX_SHADOW_TREES));   // one pass over the normals per light: the tree loop below takes the list
+    for (uint32_t l = 0; l < s->light_count && l < (uint32_t)PRT_MAX_SHADOW_TREES && abs_max > 0.0f; ++l) {
+        if (s->lights[l].type != 0) continue;
+        const auto to = std::chrono::steady_clock::now();
+        const float dir[3] = { lights[l].facing[0] * -1.0f, lights[l].facing[1] * -1.0f, lights[l].facing[2] * -1.0f };   // as the kernels form it
+        std::vector<uint32_t> & ids = occluder_ids[l];
+        shadow_occluders(rec_normals.data(), n_tris, dir, shadow_origin_max, &ids);
+        std::vector<uint8_t> open;
+        prt_shadow_open_info & oi = open_info[l];
+        oi.bias_max = (float)open_bounds.bias_max; oi.reach = (float)open_bounds.reach;
+        oi.open_count = shadow_open_flags(verts.data(), rec_normals.data(), n_tris, dir, ids, open_bounds, std::min(hw, 16u), &open);
+        if (oi.open_count) {
+            if (open_mask.empty()) open_mask.assign(n_tris, 0u);
+            for (uint32_t t = 0; t < n_tris; ++t) open_mask[t] |= (uint32_t)open[t] << l;
+            any_open = true;
+        }
+        oi.classified = 1;
+        oi.active = oi.open_count ? 1u : 0u;
+        oi.classify_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - to).count();
+    }
+    if (any_open)
+        for (uint32_t slot = 0; slot < n_tris; ++slot) memcpy(&shade[(size_t)slot * 4 + 3].x, &open_mask[bvh.tri_order[slot]], 4);
     for (uint32_t l = 0; l < s->light_count && abs_max > 0.0f; ++l) {
         if (s->lights[l].type != 0 || shadow_trees >= (uint32_t)PRT_MAX_SHADOW_TREES) continue;
         prt_shadow_tree_info & si = shadow_info[l];
@@ -2754,7 +2799,8 @@ int prt_upload_scene(prt_ctx * ctx, const prt_scene_desc * s) {
         ShadowTreeResult sr;
         std::vector<uint32_t> rec_tri;
         BvhWide sub;
-        const char * bad = append_shadow_tree(sb, verts.data(), rec_normals.data(), n_tris, dir, shadow_origin_max, &node_words, all_nodes, all_recs, &rec_tri, &sr, &sub);
+        const char * bad = append_shadow_tree(sb, verts.data(), rec_normals.data(), n_tris, dir, shadow_origin_max, &node_words, all_nodes, all_recs, &rec_tri, &sr, &sub,
+                                              l < occluder_ids.size() ? &occluder_ids[l] : nullptr);
         if (!bad && sr.built) bad = validate_bvh_links(sub, sr.triangle_count);
         if (bad) { ctx->error = std::string("prt_upload_scene: the builder produced a broken shadow tree - ") + bad; return -9; }
         si.triangle_count = sr.triangle_count;
@@ -2827,6 +2873,9 @@ int prt_upload_scene(prt_ctx * ctx, const prt_scene_desc * s) {
     ctx->shadow_info.swap(shadow_info);
     ctx->shadow_bias_max = abs_max;
     ctx->shadow_cam_max = 4.0f * abs_max;
+    ctx->shadow_open_info.swap(open_info);
+    ctx->shadow_open_bias_max = any_open ? (float)open_bounds.bias_max : 0.0f;       // (both exact in float: powers of two times abs_max)
+    ctx->shadow_open_reach = any_open ? (float)open_bounds.reach : 0.0f;
     ctx->light_stride = light_stride;
     ctx->shadow_trees_fresh = true;
     prt_scene_info & info = ctx->info;
@@ -2875,6 +2924,16 @@ int prt_get_shadow_trees(const prt_ctx * ctx, prt_shadow_tree_info * out, uint32
     for (size_t l = 0; l < ctx->shadow_info.size() && l < cap; ++l) out[l] = ctx->shadow_info[l];
     return (int)ctx->shadow_info.size();
     PRT_API_CATCH_RC(nullptr, "prt_get_shadow_trees")
+}
+
+static_assert((float)ShadowOpenBounds::min_cos == PRT_SHADOW_OPEN_MIN_COS, "the margins assume the kernels' grazing threshold");
+int prt_get_shadow_open(const prt_ctx * ctx, prt_shadow_open_info * out, uint32_t cap) {
+    PRT_API_TRY
+    if (!ctx) return -1;
+    if (!ctx->has_scene) return -2;
+    for (uint32_t l = 0; l < cap && l < ctx->shadow_open_info.size() && out; ++l) out[l] = ctx->shadow_open_info[l];
+    return (int)ctx->shadow_open_info.size();
+    PRT_API_CATCH_RC(nullptr, "prt_get_shadow_open")
 }
 
 int prt_render_device(prt_ctx * ctx, const prt_camera * cam, const prt_params * params, uint32_t width, uint32_t height,
@@ -3355,6 +3414,7 @@ prt_ctx * clone_context(prt_ctx * src) {
     c->stack_bound = src->stack_bound;
     c->light_stride = src->light_stride; c->shadow_info = src->shadow_info; c->shadow_trees_fresh = src->shadow_trees_fresh;
     c->shadow_bias_max = src->shadow_bias_max; c->shadow_cam_max = src->shadow_cam_max;
+    c->shadow_open_info = src->shadow_open_info; c->shadow_open_bias_max = src->shadow_open_bias_max; c->shadow_open_reach = src->shadow_open_reach;
     c->pool_park_cap = src->pool_park_cap; c->pool_spark_cap = src->pool_spark_cap;
     c->has_scene = src->has_scene;
     c->scene_epoch = 1;
@@ -3553,6 +3613,7 @@ int prt_multi_update_geometry(prt_multi * m, const prt_geometry_update * update)
             c->scene.ref_spheres = src->scene.ref_spheres;
             c->scene_abs_max = src->scene_abs_max;
             c->shadow_trees_fresh = src->shadow_trees_fresh; c->shadow_info = src->shadow_info;
+            c->shadow_open_info = src->shadow_open_info;          // (the bounds are the upload's and came with the clone)
             c->info = src->info;
             c->has_scene = src->has_scene;
             c->tuned.clear();

@@ -10,7 +10,12 @@
 // default light (main.cpp:522-524) and one cosine-distributed bounce ray with its own shadow ray - the ray mix of depth 2.
 // Shadow trees (bvh_build.h): a second 4-wide tree over the light's possible occluders alone, and the shadow rays the device
 // really traces - those whose surface faces the light - through both trees: visits, tests and hit / miss mismatches.
+// Open triangles (bvh_build.h shadow_open_flags): how many triangles are open for that light, the share of the traced shadow rays
+// whose receiver is open - and whose hit lies inside what a render takes the flag for (distance below `reach`, at least
+// min_cos off grazing) -, the visits and tests of the light's tree those rays would have cost, and how many of them the scene's
+// tree finds occluded (must be 0).  PRICE_OPEN_BIAS_DIV / PRICE_OPEN_REACH_DIV: bias_max and reach as coord_max over these.
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -235,10 +240,33 @@ int main(int argc, char ** argv) {
     for (uint32_t & t : bocc.tri_order) t = occ_ids[t];          // leaf slot -> input triangle of the whole scene
     Stats s_full, s_occ;
     uint64_t occ_mismatches = 0;
-    auto price_shadow = [&](const Ray & r, V3 n) {
+    // open triangles: the upload's bounds unless the environment says otherwise
+    ShadowOpenBounds ob = shadow_open_bounds(abs_max);
+    if (getenv("PRICE_OPEN_BIAS_DIV")) ob.bias_max = abs_max / atof(getenv("PRICE_OPEN_BIAS_DIV"));
+    if (getenv("PRICE_OPEN_REACH_DIV")) ob.reach = abs_max / atof(getenv("PRICE_OPEN_REACH_DIV"));
+    std::vector<uint8_t> open_flag;
+    const auto t_open = std::chrono::steady_clock::now();
+    const uint32_t n_open = shadow_open_flags(g_verts.data(), rec_normals.data(), n_tris, lightf, occ_ids, ob, 8, &open_flag);
+    const double open_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_open).count();
+    uint64_t facing = 0, facing_open = 0;
+    for (uint32_t t = 0; t < n_tris; ++t) {
+        const float * nn = &rec_normals[(size_t)t * 3];
+        if (nn[0] * light.x + nn[1] * light.y + nn[2] * light.z > 0) { facing++; facing_open += open_flag[t]; }
+    }
+    struct OpenStats { uint64_t rays = 0, open = 0, taken = 0, nodes = 0, tris = 0, occluded = 0; } os[2];       // primary hits, bounce hits
+    auto price_shadow = [&](const Ray & r, V3 n, uint32_t input_tri, double t_hit, double cos_hit, int cls) {
         if (dot(n, light) <= 0) return;                           // the device counts such a ray and does not trace it (dead: no radiance)
+        const uint64_t n0 = s_occ.nodes, t0 = s_occ.tris;
         const Hit a = trace4(b4, r, s_full), b = trace4(bocc, r, s_occ);
         if ((a.tri < 0) != (b.tri < 0)) occ_mismatches++;
+        OpenStats & o = os[cls];
+        o.rays++;
+        if (!open_flag[input_tri]) return;
+        o.open++;
+        if (!(t_hit < ob.reach && std::fabs(cos_hit) >= ShadowOpenBounds::min_cos)) return;
+        o.taken++;
+        o.nodes += s_occ.nodes - n0; o.tris += s_occ.tris - t0;
+        if (a.tri >= 0) o.occluded++;
     };
 
     Stats s4[3], s8d[3], s8a[3];            // primary, shadow, bounce
@@ -264,7 +292,7 @@ int main(int argc, char ** argv) {
             const V3 n = norm(cross(b - a, c - a));
             const V3 p = r.o + r.d * h.t + n * bias;
             trace_all(Ray{ p, light, true }, 1);
-            price_shadow(Ray{ p, light, true }, n);
+            price_shadow(Ray{ p, light, true }, n, b8.tri_order[h.tri], h.t, dot(r.d, n), 0);
             // cosine-distributed bounce
             const double u1 = rnd(), u2 = rnd(), ct = std::sqrt(1 - u1), stn = std::sqrt(u1), ph = 2 * M_PI * u2;
             const V3 upv = std::fabs(n.z) < 0.9999 ? V3{ 0, 0, 1 } : V3{ 1, 0, 0 };
@@ -276,7 +304,7 @@ int main(int argc, char ** argv) {
             const V3 a2{ v2[0], v2[1], v2[2] }, b2{ v2[3], v2[4], v2[5] }, c2{ v2[6], v2[7], v2[8] };
             const V3 n2 = norm(cross(b2 - a2, c2 - a2));
             trace_all(Ray{ br.o + br.d * bh.t + n2 * bias, light, true }, 1);
-            price_shadow(Ray{ br.o + br.d * bh.t + n2 * bias, light, true }, n2);
+            price_shadow(Ray{ br.o + br.d * bh.t + n2 * bias, light, true }, n2, b8.tri_order[bh.tri], bh.t, dot(br.d, n2), 1);
         }
     const char * cls[3] = { "primary", "shadow (any hit)", "bounce" };
     for (int k = 0; k < 3; ++k) {
@@ -300,5 +328,16 @@ int main(int argc, char ** argv) {
     report("4-wide, the scene's tree", s_full, b4.node_count, 64, b4.max_depth);
     report("4-wide, the light's occluders", s_occ, bocc.node_count, 64, bocc.max_depth);
     printf("hit / miss mismatches between the scene's tree and the light's: %llu\n", (unsigned long long)occ_mismatches);
-    return mismatches || occ_mismatches ? 1 : 0;
+    printf("-- open triangles (bias_max %.6g, reach %.6g, classified in %.1f ms): %u of %u; of the %llu that face the light: %llu (%.1f %%)\n", ob.bias_max, ob.reach,
+           open_ms, n_open, n_tris, (unsigned long long)facing, (unsigned long long)facing_open, facing ? 100.0 * facing_open / facing : 0.0);
+    const char * ocls[2] = { "primary hits", "bounce hits" };
+    uint64_t open_occluded = 0;
+    for (int k = 0; k < 2; ++k) {
+        const OpenStats & o = os[k];
+        printf("traced shadow rays from %-12s %8llu | receiver open %5.1f %% | flag taken (hit inside reach, off grazing) %5.1f %%: %.2f node visits, %.2f tri tests each saved | of those occluded: %llu\n",
+               ocls[k], (unsigned long long)o.rays, o.rays ? 100.0 * o.open / o.rays : 0.0, o.rays ? 100.0 * o.taken / o.rays : 0.0,
+               o.taken ? (double)o.nodes / o.taken : 0.0, o.taken ? (double)o.tris / o.taken : 0.0, (unsigned long long)o.occluded);
+        open_occluded += o.occluded;
+    }
+    return mismatches || occ_mismatches || open_occluded ? 1 : 0;
 }
