@@ -28,13 +28,13 @@ all: hip host oracle
 
 hip: $(PKG)/libprt_hip.so
 $(PKG)/libprt_hip.so: $(HIP_DEPS)
-	$(HIPCC) $(HIP_FLAGS) $(HIP_EXTRA) -o $@ $(HIP_SRCS) $(PKG)/csrc/bvh_build.cpp $(PKG)/csrc/bvh_check.cpp
+	$(HIPCC) $(HIP_FLAGS) $(HIP_EXTRA) -o $@ $(HIP_SRCS) $(PKG)/csrc/bvh_build.cpp $(PKG)/csrc/bvh_check.cpp $(PKG)/csrc/scene_pack.cpp
 
 # Variant library (not built by default; git-ignored like every .so):
 #   hip-bvh8          the 8-wide compressed BVH of round 3 (80 B nodes, no per-step sort) instead of the 4-wide sorted one
 hip-bvh8: $(PKG)/libprt_hip_bvh8.so
 $(PKG)/libprt_hip_bvh8.so: $(HIP_DEPS)
-	$(HIPCC) $(HIP_FLAGS) -DPRT_BVH8 -o $@ $(HIP_SRCS) $(PKG)/csrc/bvh_build.cpp $(PKG)/csrc/bvh_check.cpp
+	$(HIPCC) $(HIP_FLAGS) -DPRT_BVH8 -o $@ $(HIP_SRCS) $(PKG)/csrc/bvh_build.cpp $(PKG)/csrc/bvh_check.cpp $(PKG)/csrc/scene_pack.cpp
 
 host: $(PKG)/libprt_host.so $(PKG)/prt_main
 $(PKG)/libprt_host.so: $(HOST_SRCS) $(HOST_DEPS) $(PKG)/libprt_hip.so

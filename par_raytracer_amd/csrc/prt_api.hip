@@ -1,9 +1,10 @@
 // prt_api.hip - implementation of the C ABI in include/prt.h: context, scene upload, render dispatch.
 //
-// One prt_ctx = one HIP device + one stream + one resident scene.  Upload flattens the scene into the
-// records of dev_scene.h and builds the per-triangle BVH on the host (bvh_build.cpp).  Render launches
-// the selected pipeline on the context's stream; nothing in the render path allocates when the
-// workspace from a previous call is large enough.
+// One prt_ctx = one HIP device + one stream + one resident scene.  Upload builds the per-triangle BVH (bvh_build.cpp on the
+// host, or bvh_lbvh.h on the device), has scene_pack.cpp flatten the scene into the records of dev_scene.h - host code with no
+// HIP call in it -, uploads the arrays and only then commits: the scene is four structs of the context (SceneArrays, SceneDesc,
+// SceneKeep, SceneTables), written together at the end of prt_upload_scene.  Render launches the selected pipeline on the
+// context's stream; nothing in the render path allocates when the workspace from a previous call is large enough.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,6 +22,7 @@
 
 #include "../../include/prt.h"
 #include "bvh_build.h"
+#include "scene_pack.h"
 #include "prt_options.h"
 #include "dev_scene.h"
 #include "tex_upload.h"
@@ -98,11 +100,12 @@ struct DevBuf {
         if (e == hipSuccess) n = count;
         return e;
     }
-    hipError_t upload(const std::vector<T> & v) {
-        hipError_t e = ensure(v.size());
-        if (e != hipSuccess || v.empty()) return e;
-        return hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+    hipError_t upload(const T * v, size_t count) {
+        hipError_t e = ensure(count);
+        if (e != hipSuccess || !count) return e;
+        return hipMemcpy(p, v, count * sizeof(T), hipMemcpyHostToDevice);
     }
+    hipError_t upload(const std::vector<T> & v) { return upload(v.data(), v.size()); }
     void release() {
         if (p && !borrowed) (void)hipFree(p);
         borrowed = false;
@@ -110,6 +113,106 @@ struct DevBuf {
         n = 0;
     }
     size_t bytes() const { return n * sizeof(T); }
+};
+
+// The uploaded scene on the device: the arrays a clone borrows (clone_context).  What the host knows about them is the
+// context's SceneDesc (scene_pack.h); the kernels' view of them is its DevScene.
+struct SceneArrays {
+    DevBuf<float4> nodes, tris, shade, diffuse_dirs;
+    DevBuf<unsigned int> tri_rank;
+    DevBuf<DevMaterial> materials;
+    DevBuf<DevLight> lights;              // two copies of the table, desc.light_stride apart: shadow-tree roots in DevLight::pad, then every root at 0
+    DevBuf<DevTexture> textures;
+    DevBuf<unsigned int> texels;
+    DevBuf<float> srgb_lut;
+    DevBuf<float4> tri_uv, tri_tan;
+    DevBuf<float4> ref_spheres;           // the reference's sphere tree for near-tie resolution (dev_trace_common.h RefSphereWalk)
+
+    void borrow(const SceneArrays & o) {
+        nodes.borrow(o.nodes); tris.borrow(o.tris); shade.borrow(o.shade); diffuse_dirs.borrow(o.diffuse_dirs);
+        tri_rank.borrow(o.tri_rank); materials.borrow(o.materials); lights.borrow(o.lights);
+        textures.borrow(o.textures); texels.borrow(o.texels); srgb_lut.borrow(o.srgb_lut);
+        tri_uv.borrow(o.tri_uv); tri_tan.borrow(o.tri_tan); ref_spheres.borrow(o.ref_spheres);
+    }
+    void release() { borrow(SceneArrays()); }
+    // Through the null stream.  The arrays a scene does not have (textures, tangents, spheres) keep what they held.
+    hipError_t upload(const PackedScene & p) {
+        hipError_t e = nodes.upload(reinterpret_cast<const float4 *>(p.nodes.data()), p.nodes.size() / 4);
+        if (e == hipSuccess) e = tris.upload(p.tris);
+        if (e == hipSuccess) e = shade.upload(p.shade);
+        if (e == hipSuccess) e = tri_rank.upload(p.rank);
+        if (e == hipSuccess) e = materials.upload(p.materials);
+        if (e == hipSuccess) e = lights.upload(p.lights);
+        if (e == hipSuccess) e = diffuse_dirs.upload(p.diffuse_dirs);
+        if (e == hipSuccess && !p.ref_spheres.empty()) e = ref_spheres.upload(p.ref_spheres);
+        if (e == hipSuccess && p.desc.textured) e = textures.upload(p.textures);
+        if (e == hipSuccess && p.desc.textured) e = texels.upload(p.texels);
+        if (e == hipSuccess && p.desc.textured) e = srgb_lut.upload(p.srgb_lut);
+        if (e == hipSuccess && p.desc.textured) e = tri_uv.upload(p.tri_uv);
+        if (e == hipSuccess && p.keep.bumped) e = tri_tan.upload(p.tri_tan);
+        return e;
+    }
+    // The kernels' pointers; the optional arrays only where the scene has them.
+    void point(DevScene & sc, bool textured, bool bumped, bool spheres) const {
+        sc.nodes = nodes.p;
+        sc.tris = tris.p;
+        sc.shade = shade.p;
+        sc.tri_rank = tri_rank.p;
+        sc.materials = materials.p;
+        sc.lights = lights.p;
+        sc.diffuse_dirs = diffuse_dirs.p;
+        sc.textures = textured ? textures.p : nullptr;
+        sc.texels = textured ? texels.p : nullptr;
+        sc.srgb_lut = textured ? srgb_lut.p : nullptr;
+        sc.tri_uv = textured ? tri_uv.p : nullptr;
+        sc.tri_tan = bumped ? tri_tan.p : nullptr;
+        sc.ref_spheres = spheres ? ref_spheres.p : nullptr;
+    }
+};
+
+// The device tables that calls build on first use from what the upload kept (SceneKeep; their host halves are in
+// scene_pack.cpp), with the generation of the geometry each was filled from.  None is in prt_scene_info.device_bytes - a
+// render-only user pays no device memory for them -, later calls reuse them, and the next upload frees them.
+struct SceneTables {
+    // ray queries (prt_trace_rays, kernels_query.h): the first query after an upload builds the leaf -> (group, vertex0) table
+    // from the leaf order and the groups.
+    DevBuf<uint2> q_leaf_map;             // leaf slot -> (group, vertex0)
+    DevBuf<unsigned int> q_slot_of_rank;  // prt_trace_rays: the inverse of tri_rank (scan_closest); built with q_leaf_map's lifetime,
+                                          // and again after a prt_update_geometry that ranks the triangles anew
+    // geometry updates (prt_update_geometry, kernels_refit.h): the first update builds the leaf slot -> vertex indices table from
+    // the index buffers (24 B per triangle).
+    DevBuf<unsigned int> rf_table;        // leaf slot -> three position indices, three normal indices
+    // query gradients (prt_trace_rays_backward, kernels_query_grad.h; prt_closest_points_backward, kernels_closest_grad.h).  Built
+    // by the first call of either kind after an upload from the position index buffer and the groups.
+    DevBuf<unsigned int> qg_idx;          // the position index buffer
+    DevBuf<unsigned int> qg_runs;         // (first_index, index_count) per group
+    DevBuf<long long> qg_acc;             // position_count x 3 fixed-point accumulators
+    // signed distances (prt_signed_distance, dev_signed.h).  The adjacency table is topology: built by the first signed query
+    // after an upload from the position index buffer and the leaf order.  The accumulators are geometry: k_signed_normals refills
+    // them at the first signed query after an upload or a prt_update_geometry, which both bump geom_generation.
+    uint64_t sg_generation = 0;           // of the records sg_acc was filled from; 0 = never
+    DevBuf<unsigned int> sg_adj;          // leaf slot -> three position indices, three edge ids (24 B per triangle)
+    DevBuf<long long> sg_acc;             // (position_count + sg_edge_count) x 3 fixed-point accumulators (24 B each)
+    uint32_t sg_edge_count = 0;
+    // surface samples (prt_sample_surface, dev_sample.h).  The input triangle -> leaf slot table is topology: the inverse of
+    // the leaf order, built by the first sampling call after an upload (4 B per triangle).  The weights and their prefix sums are
+    // geometry: rebuilt on the device (kernels_sample.h) by the first sampling call after an upload or a prt_update_geometry
+    // (8 B per triangle of sums, 8 B per triangle of weights and 8 B per tile of scratch).
+    uint64_t sm_generation = 0;           // of the records sm_prefix was built from; 0 = never
+    DevBuf<unsigned int> sm_slot_of_input;
+    DevBuf<double> sm_weight;
+    DevBuf<unsigned long long> sm_prefix, sm_tile_sum;
+
+    void release() {
+        q_leaf_map.release(); q_slot_of_rank.release();
+        rf_table.release();
+        qg_idx.release(); qg_runs.release(); qg_acc.release();
+        sg_adj.release(); sg_acc.release();
+        sg_edge_count = 0;
+        sg_generation = 0;
+        sm_slot_of_input.release(); sm_weight.release(); sm_prefix.release(); sm_tile_sum.release();
+        sm_generation = 0;
+    }
 };
 
 }  // namespace
@@ -124,40 +227,21 @@ struct prt_ctx {
     std::string error;
     bool has_scene = false;
 
-    DevBuf<float4> nodes, tris, shade, diffuse_dirs, spec_dirs;
-    DevBuf<unsigned int> tri_rank;
-    DevBuf<DevMaterial> materials;
-    DevBuf<DevLight> lights;              // two copies of the table, light_stride apart: shadow-tree roots in DevLight::pad, then every root at 0
-    unsigned int light_stride = 1;
-    // shadow trees (include/prt.h): one entry per light; fresh = of the geometry on the device (an update makes them stale);
-    // origin_max = the |coordinate| of a shadow ray's origin that the exclusion bound covers (bvh_build.h), and what a
-    // render call's |ray_bias| and camera position may be for its shadow rays to stay inside it
-    std::vector<prt_shadow_tree_info> shadow_info;
-    bool shadow_trees_fresh = false;
-    float shadow_bias_max = 0.0f, shadow_cam_max = 0.0f;
-    // open triangles (include/prt.h): one entry per light; the flags lie in the shading records and go stale with the trees
-    // (shadow_trees_fresh).  A call takes them while its |ray_bias| is at most open_bias_max and its hits lie below open_reach,
-    // the bounds the upload computed them for; open_reach = 0: no light has flags.
-    std::vector<prt_shadow_open_info> shadow_open_info;
-    float shadow_open_bias_max = 0.0f, shadow_open_reach = 0.0f;
-    DevScene scene;
-    prt_scene_info info;
-    float scene_abs_max = 0.0f;
-    bool any_translucent = false;
-    bool point_lights = false;            // any point light: its shadow rays use the hit distance (raytracer.cpp:396), so they can be near-tied too
-    bool textured = false;                // any material has a texture map: the TEX kernel variants run
+    // The uploaded scene.  prt_upload_scene empties `keep` and `tables` at its top, fills `arrays`, and commits `desc` and `keep`
+    // in one step at its end, once every array lies on the device (has_scene says which side of that step the context is on).
+    // A clone borrows `arrays`, copies `desc` and `scene`, and has no `keep` and no `tables` (clone_context).
+    SceneArrays arrays;
+    SceneDesc desc;                       // scene_pack.h: what the host knows about the arrays
+    SceneKeep keep;                       // scene_pack.h: host memory for prt_update_geometry, the gradients, signed distances, sampling
+    SceneTables tables;
+    DevScene scene;                       // the kernels' view: SceneArrays::point, the counts, spec_dirs
+    uint64_t geom_generation = 0;         // of the records on the device: an upload and a prt_update_geometry bump it (SceneTables)
+    DevBuf<float4> spec_dirs;             // [material][spec_samples], rebuilt when a render asks for another spec_samples (build_spec_table)
+    unsigned int spec_table_samples = 0;
     // PRT_PIPELINE_DEFAULT: which pipeline won the try-out for a (scene, pixel set, sampling) configuration
     struct TuneEntry { uint64_t key[6]; unsigned int pipeline; };
     std::vector<TuneEntry> tuned;
     uint64_t scene_epoch = 0;
-    DevBuf<DevTexture> textures;
-    std::vector<DevTexture> kat_textures; // host copy of the texture table: prt_debug_device_kat checks KAT_TEXTURE's indices against it
-    DevBuf<unsigned int> texels;
-    DevBuf<float> srgb_lut;
-    DevBuf<float4> tri_uv, tri_tan;
-    DevBuf<float4> ref_spheres;           // the reference's sphere tree for near-tie resolution (dev_trace_common.h RefSphereWalk)
-    std::vector<float> material_ns;      // for rebuilding spec_dirs when spec_samples changes
-    unsigned int spec_table_samples = 0;
 
     // render workspace
     DevBuf<float4> sample_rgb;
@@ -192,16 +276,8 @@ struct prt_ctx {
     DevBuf<float4> adapt_f4;              // adaptive mode: scratch [max_spp][n] + running sums [n] + final colours [n]
     int cu_count = 0;                     // compute units this context may fill (all of the device's minus PRT_RESERVE_CUS)
     int reserved_cus = 0;
-    unsigned int stack_bound = 0;
     DevBuf<int> stack_spill;
-    // ray queries (prt_trace_rays, kernels_query.h).  The upload keeps the builder's leaf order and the groups; the first query
-    // after it builds the leaf -> (group, vertex0) table from them (not in prt_scene_info.device_bytes: a render-only user pays
-    // no device memory for it), and the next upload frees it.
-    std::vector<uint32_t> q_tri_order;    // leaf slot -> input triangle
-    std::vector<prt_group> q_groups;
-    DevBuf<uint2> q_leaf_map;             // leaf slot -> (group, vertex0)
-    DevBuf<unsigned int> q_slot_of_rank;  // prt_trace_rays: the inverse of tri_rank (scan_closest); built with q_leaf_map's lifetime,
-                                          // and again after a prt_update_geometry that ranks the triangles anew
+    // ray queries (prt_trace_rays, kernels_query.h)
     DevBuf<unsigned int> q_work;          // the batch's control words (BatchShared::work, dev_wave_loop.h)
     DevBuf<unsigned int> q_slow;          // rays handed to k_query_exact
     DevBuf<int> q_exact_stack;
@@ -209,44 +285,15 @@ struct prt_ctx {
     DevBuf<unsigned char> q_occ;
     DevBuf<unsigned char> q_hemi_flags;   // prt_hemisphere_visibility: one byte per item of a pass
     DevBuf<unsigned long long> rays_words;  // prt_render_rays: k_rays_check's three words
-    // geometry updates (prt_update_geometry, kernels_refit.h).  The upload keeps, on the host, the index buffers and the first
-    // node of every tree level; the first update builds the leaf slot -> vertex indices table from them (24 B per triangle; like
-    // q_leaf_map not in prt_scene_info.device_bytes, freed by the next upload).  The table and the scratch boxes are reused by
-    // later updates.
-    std::vector<uint32_t> rf_idx_positions, rf_idx_normals;
-    std::vector<unsigned int> rf_level_first;   // levels + 1 entries; empty: the tree is not level-ordered (never, for finish_wide's)
-    uint32_t rf_position_count = 0, rf_normal_count = 0;
-    bool rf_bumped = false;
-    DevBuf<unsigned int> rf_table;        // leaf slot -> three position indices, three normal indices
+    // geometry updates (prt_update_geometry, kernels_refit.h): the scratch boxes and the inputs, reused by later updates
     DevBuf<RefitBox> rf_boxes;            // every node's exact float box
     DevBuf<unsigned int> rf_bounds;       // k_refit_bounds' two words
     DevBuf<float> rf_in;                  // host entry point: positions, normals, tangents on the device
-    // query gradients (prt_trace_rays_backward, kernels_query_grad.h; prt_closest_points_backward, kernels_closest_grad.h).  Built by the first call after an upload from what the
-    // upload kept on the host (rf_idx_positions, q_groups); like q_leaf_map not in prt_scene_info.device_bytes, reused by later
-    // calls, freed by the next upload.
-    DevBuf<unsigned int> qg_idx;          // the position index buffer
-    DevBuf<unsigned int> qg_runs;         // (first_index, index_count) per group
-    DevBuf<long long> qg_acc;             // position_count x 3 fixed-point accumulators
+    // query gradients (prt_trace_rays_backward, kernels_query_grad.h; prt_closest_points_backward, kernels_closest_grad.h)
     DevBuf<unsigned int> qg_words;        // k_qgrad_scan's control words
     DevBuf<float> qg_io;                  // host entry point: the inputs and the requested gradients on the device
-    // signed distances (prt_signed_distance, dev_signed.h).  The adjacency table is topology: built by the first signed query
-    // after an upload from rf_idx_positions and q_tri_order.  The accumulators are geometry: k_signed_normals refills them at the
-    // first signed query after an upload or a prt_update_geometry, which both bump geom_generation.  Like q_leaf_map not in
-    // prt_scene_info.device_bytes, freed by the next upload.
-    uint64_t geom_generation = 0;         // of the records on the device
-    uint64_t sg_generation = 0;           // of the records sg_acc was filled from; 0 = never
-    DevBuf<unsigned int> sg_adj;          // leaf slot -> three position indices, three edge ids (24 B per triangle)
-    DevBuf<long long> sg_acc;             // (position_count + sg_edge_count) x 3 fixed-point accumulators (24 B each)
-    uint32_t sg_edge_count = 0;
-    // surface samples (prt_sample_surface, dev_sample.h).  The input triangle -> leaf slot table is topology: the inverse of
-    // q_tri_order, built by the first sampling call after an upload (4 B per triangle).  The weights and their prefix sums are
-    // geometry: rebuilt on the device (kernels_sample.h) by the first sampling call after an upload or a prt_update_geometry
-    // (8 B per triangle of sums, 8 B per triangle of weights and 8 B per tile of scratch).  Like q_leaf_map not in
-    // prt_scene_info.device_bytes, freed by the next upload.
-    uint64_t sm_generation = 0;           // of the records sm_prefix was built from; 0 = never
-    DevBuf<unsigned int> sm_slot_of_input;
-    DevBuf<double> sm_weight;
-    DevBuf<unsigned long long> sm_prefix, sm_tile_sum, sm_words;
+    // surface samples (prt_sample_surface, dev_sample.h)
+    DevBuf<unsigned long long> sm_words;
     unsigned long long sm_host_words[SAMPLE_WORDS] = {};   // the table's control words as last read back
     unsigned long long sm_read_words[SAMPLE_WORDS] = {};   // ... and where a rebuild's copy of them lands (it outlives a failed call)
 };
@@ -285,11 +332,12 @@ uint64_t max_rng_draws(uint32_t depth, uint32_t refl, uint32_t spec) {
     return 2 + node;
 }
 
-int build_spec_table(prt_ctx * ctx, unsigned int spec_samples) {
+// material_ns: the scene's specular exponents (SceneDesc::material_ns; the upload builds the table before it commits them).
+int build_spec_table(prt_ctx * ctx, const std::vector<float> & material_ns, unsigned int spec_samples) {
     unsigned int n = std::max(1u, spec_samples);
-    std::vector<float4> table(ctx->material_ns.size() * (size_t)n);
-    for (size_t m = 0; m < ctx->material_ns.size(); ++m)
-        for (unsigned int s = 0; s < n; ++s) table[m * n + s] = phong_tangent_dir(s, n, ctx->material_ns[m]);
+    std::vector<float4> table(material_ns.size() * (size_t)n);
+    for (size_t m = 0; m < material_ns.size(); ++m)
+        for (unsigned int s = 0; s < n; ++s) table[m * n + s] = phong_tangent_dir(s, n, material_ns[m]);
     HIP_TRY(ctx, ctx->spec_dirs.upload(table));
     ctx->spec_table_samples = n;
     ctx->scene.spec_dirs = ctx->spec_dirs.p;
@@ -347,7 +395,7 @@ TraceGrid trace_grid(const prt_ctx * ctx, int per_cu, unsigned int chunk_min, un
 unsigned int lds_stack_entries(const prt_ctx * ctx) {
     unsigned int stack_cap = STACK_LDS_CAP_DEFAULT;
     if (ctx->opt.stack_cap >= 0) stack_cap = (unsigned int)std::max(2ll, std::min(40ll, ctx->opt.stack_cap));
-    return std::min(ctx->stack_bound, stack_cap);
+    return std::min(ctx->desc.stack_bound, stack_cap);
 }
 
 struct PixelSet {
@@ -389,7 +437,7 @@ int chain_setup(prt_ctx * ctx, Chain & c, int index, const DevParams & P, bool r
     c.P = P;
     const size_t N = n_samples;
     const unsigned int levels = std::max(1u, P.bounce_depth);
-    const unsigned int fr4 = ctx->textured ? 7u : ring ? 5u : 4u;
+    const unsigned int fr4 = ctx->desc.textured ? 7u : ring ? 5u : 4u;
     const unsigned int n_lights = std::max(1u, ctx->scene.light_count);
     // float4 slab: frames + 2x3 closest queues + hits + 3 shadow arrays (accum aliases the shared sample_rgb)
     const size_t f4_total = (size_t)levels * fr4 * N + 6 * N + N + 3 * N * n_lights;
@@ -400,7 +448,7 @@ int chain_setup(prt_ctx * ctx, Chain & c, int index, const DevParams & P, bool r
     {
         // k_trace_exact's fixed grid: full-height stack columns for the rays k_trace hands over (near ties, overflowed columns)
         const size_t exact_lanes = 64 * 256;
-        HIP_TRY(ctx, w.slow_stack.ensure(stack_dwords(std::max(ctx->stack_bound, 4u), exact_lanes)));
+        HIP_TRY(ctx, w.slow_stack.ensure(stack_dwords(std::max(ctx->desc.stack_bound, 4u), exact_lanes)));
         c.P.exact_stack = w.slow_stack.p;
         c.P.exact_stack_stride = (unsigned int)exact_lanes;
     }
@@ -468,12 +516,12 @@ int chain_issue_round(prt_ctx * ctx, Chain & c, const WaveTuning & t) {
     if (c.n_closest) {
         if (t.shade_block == 1024) {
             const unsigned int sgrid = (c.n_closest + 1023) / 1024;
-            if (ctx->textured) hipLaunchKernelGGL((k_shade<true, 1024, true>), dim3(sgrid), dim3(1024), 0, stream, ctx->scene, c.P, B, c.cur, c.n_closest, ctx->counters.p);
+            if (ctx->desc.textured) hipLaunchKernelGGL((k_shade<true, 1024, true>), dim3(sgrid), dim3(1024), 0, stream, ctx->scene, c.P, B, c.cur, c.n_closest, ctx->counters.p);
             else if (t.ring) hipLaunchKernelGGL((k_shade<true, 1024, false>), dim3(sgrid), dim3(1024), 0, stream, ctx->scene, c.P, B, c.cur, c.n_closest, ctx->counters.p);
             else hipLaunchKernelGGL((k_shade<false, 1024, false>), dim3(sgrid), dim3(1024), 0, stream, ctx->scene, c.P, B, c.cur, c.n_closest, ctx->counters.p);
         } else {
             const unsigned int sgrid = (c.n_closest + 255) / 256;
-            if (ctx->textured) hipLaunchKernelGGL((k_shade<true, 256, true>), dim3(sgrid), dim3(256), 0, stream, ctx->scene, c.P, B, c.cur, c.n_closest, ctx->counters.p);
+            if (ctx->desc.textured) hipLaunchKernelGGL((k_shade<true, 256, true>), dim3(sgrid), dim3(256), 0, stream, ctx->scene, c.P, B, c.cur, c.n_closest, ctx->counters.p);
             else if (t.ring) hipLaunchKernelGGL((k_shade<true, 256, false>), dim3(sgrid), dim3(256), 0, stream, ctx->scene, c.P, B, c.cur, c.n_closest, ctx->counters.p);
             else hipLaunchKernelGGL((k_shade<false, 256, false>), dim3(sgrid), dim3(256), 0, stream, ctx->scene, c.P, B, c.cur, c.n_closest, ctx->counters.p);
         }
@@ -690,8 +738,8 @@ int launch_pool(prt_ctx * ctx, bool count, const DevCamera & cam, DevParams P, u
     // the EXACT launch's lanes continue their LDS stack columns in memory; k_pool_parked_shadows has full-height columns
     const unsigned int grid2 = exact_only ? grid : std::max(1u, std::min(grid, (unsigned int)ctx->cu_count));
     const size_t exact_lanes = (size_t)POOL_PARKED_SHADOW_BLOCKS * 256, spill_lanes = (size_t)grid2 * BLOCK;
-    const size_t spill_entries = ctx->stack_bound > stack_entries ? ctx->stack_bound - stack_entries : 0;
-    const size_t exact_ints = stack_dwords(std::max(ctx->stack_bound, 4u), exact_lanes);
+    const size_t spill_entries = ctx->desc.stack_bound > stack_entries ? ctx->desc.stack_bound - stack_entries : 0;
+    const size_t exact_ints = stack_dwords(std::max(ctx->desc.stack_bound, 4u), exact_lanes);
     HIP_TRY(ctx, ctx->stack_spill.ensure(exact_ints + stack_dwords(spill_entries, spill_lanes)));
     P.exact_stack = ctx->stack_spill.p;
     P.exact_stack_stride = (unsigned int)exact_lanes;
@@ -838,7 +886,7 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
 
     if (std::max(1u, params->spec_samples) != ctx->spec_table_samples) {
         HIP_TRY(ctx, hipStreamSynchronize(stream));
-        int rc = build_spec_table(ctx, params->spec_samples);
+        int rc = build_spec_table(ctx, ctx->desc.material_ns, params->spec_samples);
         if (rc) return rc;
         HIP_TRY(ctx, hipDeviceSynchronize());      // the table went through the null stream
     }
@@ -868,7 +916,7 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
     P.width = width;
     P.height = height;
     // (where the primary rays start: the camera position, or the largest |origin component| of the caller's rays)
-    float extent = ctx->scene_abs_max;
+    float extent = ctx->desc.scene_abs_max;
     if (rays) extent = std::max(extent, rays->origin_abs_max);
     else for (int a = 0; a < 3; ++a) extent = std::max(extent, fabsf(cam_in->position[a]));
     P.box_pad = extent * (1.0f / 65536.0f);
@@ -882,20 +930,20 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
     {
         // which copy of the light table: the shadow-tree roots, or every root at 0 - the option, trees of an older geometry, or a
         // call whose shadow-ray origins the upload's exclusion bound does not cover (include/prt.h "Shadow trees")
-        bool trees = opt.shadow_trees != 0 && ctx->shadow_trees_fresh && fabsf(params->ray_bias) <= ctx->shadow_bias_max;
-        if (rays) trees = trees && rays->origin_abs_max <= ctx->shadow_cam_max;
-        else for (int a = 0; a < 3; ++a) trees = trees && fabsf(cam_in->position[a]) <= ctx->shadow_cam_max;
-        ctx->scene.lights = ctx->lights.p + (trees ? 0u : ctx->light_stride);
+        bool trees = opt.shadow_trees != 0 && ctx->desc.shadow_trees_fresh && fabsf(params->ray_bias) <= ctx->desc.shadow_bias_max;
+        if (rays) trees = trees && rays->origin_abs_max <= ctx->desc.shadow_cam_max;
+        else for (int a = 0; a < 3; ++a) trees = trees && fabsf(cam_in->position[a]) <= ctx->desc.shadow_cam_max;
+        ctx->scene.lights = ctx->arrays.lights.p + (trees ? 0u : ctx->desc.light_stride);
     }
     P.elide_dead_shadow_rays = opt.trace_dead_shadow_rays ? 0u : 1u;
     {
         // the open-triangle flags (include/prt.h "Open triangles"): their own option, never while every ray is to be traced, and
         // only for a call inside the bounds they were computed for - the bias, and the camera guard the trees use
-        bool open = opt.shadow_open != 0 && !opt.trace_dead_shadow_rays && ctx->shadow_trees_fresh && ctx->shadow_open_reach > 0.0f &&
-                    fabsf(params->ray_bias) <= ctx->shadow_open_bias_max;
-        if (rays) open = open && rays->origin_abs_max <= ctx->shadow_cam_max;
-        else for (int a = 0; a < 3; ++a) open = open && fabsf(cam_in->position[a]) <= ctx->shadow_cam_max;
-        P.open_reach = open ? ctx->shadow_open_reach : 0.0f;
+        bool open = opt.shadow_open != 0 && !opt.trace_dead_shadow_rays && ctx->desc.shadow_trees_fresh && ctx->desc.shadow_open_reach > 0.0f &&
+                    fabsf(params->ray_bias) <= ctx->desc.shadow_open_bias_max;
+        if (rays) open = open && rays->origin_abs_max <= ctx->desc.shadow_cam_max;
+        else for (int a = 0; a < 3; ++a) open = open && fabsf(cam_in->position[a]) <= ctx->desc.shadow_cam_max;
+        P.open_reach = open ? ctx->desc.shadow_open_reach : 0.0f;
     }
     // tiled work order: sets made of full-width rows only (a whole frame or a range that starts at a row, row-block shards)
     P.tile_pixels = 0;
@@ -919,7 +967,7 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
     const bool count_visits = (params->pipeline & PRT_FLAG_COUNT_VISITS) != 0;
     // the compact 2-register RNG only covers opaque scenes with <= 15 draws per sample; textured scenes always take the
     // general variant (an alpha map can make any hit translucent)
-    const bool ring = adaptive || ctx->any_translucent || ctx->textured || max_rng_draws(P.bounce_depth, P.reflection_samples, P.spec_samples) > 15;
+    const bool ring = adaptive || ctx->desc.any_translucent || ctx->desc.textured || max_rng_draws(P.bounce_depth, P.reflection_samples, P.spec_samples) > 15;
 
     unsigned int pipeline = params->pipeline & PRT_PIPELINE_MASK;
     if (adaptive) {
@@ -1002,7 +1050,7 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
     const unsigned long long total_samples = (unsigned long long)px.n_pixels * unit_spp;
     unsigned int pass_pixels = px.n_pixels;
     {
-        const unsigned long long lv = std::max(1u, P.bounce_depth), fr4 = ctx->textured ? 7 : ring_eff ? 5 : 4, nl = std::max(1u, ctx->scene.light_count);
+        const unsigned long long lv = std::max(1u, P.bounce_depth), fr4 = ctx->desc.textured ? 7 : ring_eff ? 5 : 4, nl = std::max(1u, ctx->scene.light_count);
         unsigned long long per_sample = 32 + (ring ? 128 : 0);
         if (pipeline == PRT_PIPELINE_WAVEFRONT) per_sample += (lv * fr4 + 7 + 3 * nl) * 16 + (ring ? 32 : 16) + 4 * (1 + nl);
         if (pipeline == PRT_PIPELINE_POOL) per_sample += lv * fr4 * 16 + 32;
@@ -1073,13 +1121,13 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
             // frames' hit position fold away as they do for 0.  2 is used for the adaptive mode (-3.6 % on C4 10..50 spp); the
             // fixed-spp kernel for deep bounce trees allocates worse with it at 96 VGPRs (47 dwords spilled instead of 31: +1 %)
             // and stays on 1 (profiles/r03_adaptive.txt item 7)
-            const bool opaque = !ctx->any_translucent && !ctx->textured;
+            const bool opaque = !ctx->desc.any_translucent && !ctx->desc.textured;
             if (adaptive)
-                rc = ctx->textured ? launch_pool<256, 4, false, true, true, true>(ctx, count_visits, cam, P, n_samples, stack_entries)
+                rc = ctx->desc.textured ? launch_pool<256, 4, false, true, true, true>(ctx, count_visits, cam, P, n_samples, stack_entries)
                    : opaque ? launch_pool<256, PRT_ADAPT_WAVES, false, true, false, true, 2>(ctx, count_visits, cam, P, n_samples, stack_entries)
                             : launch_pool<256, PRT_ADAPT_WAVES, false, true, false, true, 1>(ctx, count_visits, cam, P, n_samples, stack_entries);
             else
-                rc = ctx->textured ? launch_pool<256, 4, false, true, true, false>(ctx, count_visits, cam, P, n_samples, stack_entries)
+                rc = ctx->desc.textured ? launch_pool<256, 4, false, true, true, false>(ctx, count_visits, cam, P, n_samples, stack_entries)
                    : !ring ? launch_pool<PRT_POOL_BLOCK, PRT_POOL_WAVES, false, true, false, false, 0>(ctx, count_visits, cam, P, n_samples, stack_entries)
                            : launch_pool<PRT_POOL_BLOCK, PRT_DEEP_WAVES, false, true, false, false, 1>(ctx, count_visits, cam, P, n_samples, stack_entries);
             launches += 1;
@@ -1153,7 +1201,7 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
             rs.elided_shadow_rays = h.elided_shadow_rays;
             rs.open_shadow_rays = h.open_shadow_rays;
             rs.variance_close_calls = h.variance_close_calls;
-            rs.stack_lds_entries = stack_entries; rs.stack_bound = ctx->stack_bound;
+            rs.stack_lds_entries = stack_entries; rs.stack_bound = ctx->desc.stack_bound;
             // k_pool's COUNT variants fill the table; the steps that have counters of their own are copied into their rows
             uint64_t * const rg = ctx->last_regions;
             for (int k = 0; k < 2 * PRT_REGION_COUNT; ++k) rg[k] = pipeline == PRT_PIPELINE_POOL ? h.region[k] : 0;
@@ -1215,7 +1263,7 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
                     100.0 * (double)h.phase_cycles[4] / (double)h.phase_cycles[3]);
         if (opt.debug_util && h.wave_node_steps)
             fprintf(stderr, "[prt] deepest stack %llu entries (LDS column %u, bound %u); %llu of %llu node visits (%.1f%%) hit no child after a hit was known\n",
-                    (unsigned long long)h.max_sp, stack_entries, ctx->stack_bound, (unsigned long long)h.culled,
+                    (unsigned long long)h.max_sp, stack_entries, ctx->desc.stack_bound, (unsigned long long)h.culled,
                     (unsigned long long)h.node_visits, 100.0 * (double)h.culled / (double)h.node_visits);
         memset(counters, 0, sizeof(*counters));
         counters->ray_count = h.ray_count;
@@ -1294,16 +1342,10 @@ struct StageList {
 
 // The leaf -> (group, vertex0) table of the queries (prt_trace_rays, prt_closest_points), built by the first of them after an upload.
 int ensure_leaf_map(prt_ctx * ctx, const char * who) {
-    if (ctx->q_leaf_map.p) return 0;
+    if (ctx->tables.q_leaf_map.p) return 0;
     const uint32_t n_tris = ctx->scene.tri_count;
-    if (ctx->q_tri_order.size() != n_tris) { ctx->error = std::string(who) + ": the scene's leaf order is not available"; return -2; }
-    std::vector<uint2> of_input(n_tris), map((size_t)n_tris + 1, make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu));
-    for (uint32_t g = 0; g < (uint32_t)ctx->q_groups.size(); ++g) {
-        const prt_group & pg = ctx->q_groups[g];
-        for (uint32_t k = 0; k < pg.index_count / 3; ++k) of_input[pg.first_index / 3 + k] = make_uint2(g, 3u * k);   // IntersectRayMesh's vertex0 = i
-    }
-    for (uint32_t slot = 0; slot < n_tris; ++slot) map[slot] = of_input[ctx->q_tri_order[slot]];
-    HIP_TRY(ctx, ctx->q_leaf_map.upload(map));
+    if (ctx->keep.tri_order.size() != n_tris) { ctx->error = std::string(who) + ": the scene's leaf order is not available"; return -2; }
+    HIP_TRY(ctx, ctx->tables.q_leaf_map.upload(keep_leaf_map(ctx->keep)));
     HIP_TRY(ctx, hipDeviceSynchronize());              // the upload went through the null stream
     return 0;
 }
@@ -1318,11 +1360,11 @@ int launch_walk(prt_ctx * ctx, Fast fast, Exact exact, const Args & A, unsigned 
     const size_t lds = stack_dwords(A.stack_lds_entries, BLOCK) * sizeof(int);
     const TraceRule rule = trace_rule(ctx, fast, lds);
     const TraceGrid g = trace_grid(ctx, rule.per_cu, rule.chunk_min, A.count);
-    hipLaunchKernelGGL(fast, dim3(g.grid), dim3(BLOCK), lds, ctx->stream, ctx->scene, A, ctx->q_leaf_map.p, fields, rule.keep_min, rule.node_min,
+    hipLaunchKernelGGL(fast, dim3(g.grid), dim3(BLOCK), lds, ctx->stream, ctx->scene, A, ctx->tables.q_leaf_map.p, fields, rule.keep_min, rule.node_min,
                        g.chunk, ctx->counters.p);
     HIP_TRY(ctx, hipGetLastError());
     constexpr unsigned int SLOW_BLOCKS = 64;               // A.exact_stack holds SLOW_BLOCKS * 256 columns
-    hipLaunchKernelGGL(exact, dim3(SLOW_BLOCKS), dim3(256), 0, ctx->stream, ctx->scene, A, ctx->q_leaf_map.p, fields, ctx->counters.p);
+    hipLaunchKernelGGL(exact, dim3(SLOW_BLOCKS), dim3(256), 0, ctx->stream, ctx->scene, A, ctx->tables.q_leaf_map.p, fields, ctx->counters.p);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
@@ -1334,21 +1376,21 @@ struct RayWalk {
     static const char * name() { return "prt_trace_rays"; }
     int prepare(prt_ctx * ctx, QueryArgs & A) const {
         ctx->scene.tie_widen_max = (unsigned int)std::max(0ll, std::min(64ll, ctx->opt.tie_widen_max));
-        A.replay_beyond = 64.0f * ctx->scene_abs_max;
-        A.scene_max = ctx->scene_abs_max;
+        A.replay_beyond = 64.0f * ctx->desc.scene_abs_max;
+        A.scene_max = ctx->desc.scene_abs_max;
         const uint32_t n_tris = ctx->scene.tri_count;
-        if (!ctx->q_slot_of_rank.p && n_tris) {
+        if (!ctx->tables.q_slot_of_rank.p && n_tris) {
             std::vector<unsigned int> rank(n_tris), slot_of_rank(n_tris, 0u);
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));          // an update's copy of the ranks runs on it
-            HIP_TRY(ctx, hipMemcpy(rank.data(), ctx->tri_rank.p, (size_t)n_tris * sizeof(unsigned int), hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(rank.data(), ctx->arrays.tri_rank.p, (size_t)n_tris * sizeof(unsigned int), hipMemcpyDeviceToHost));
             for (uint32_t slot = 0; slot < n_tris; ++slot) {
                 if (rank[slot] >= n_tris) { ctx->error = "prt_trace_rays: the scene's visit ranks are not a permutation"; return -2; }
                 slot_of_rank[rank[slot]] = slot;
             }
-            HIP_TRY(ctx, ctx->q_slot_of_rank.upload(slot_of_rank));
+            HIP_TRY(ctx, ctx->tables.q_slot_of_rank.upload(slot_of_rank));
             HIP_TRY(ctx, hipDeviceSynchronize());          // the upload went through the null stream
         }
-        A.slot_of_rank = ctx->q_slot_of_rank.p;
+        A.slot_of_rank = ctx->tables.q_slot_of_rank.p;
         return 0;
     }
     int tables(prt_ctx *, QueryArgs &, unsigned int) const { return 0; }
@@ -1409,7 +1451,7 @@ int run_batch(prt_ctx * ctx, const Walk & q, typename Walk::Args A, unsigned int
     // LDS stack column as the render pipelines size it; the exact kernel's fixed grid gets full-height global columns
     A.stack_lds_entries = lds_stack_entries(ctx);
     const size_t exact_lanes = 64 * 256;
-    HIP_TRY(ctx, ctx->q_exact_stack.ensure(stack_dwords(std::max(ctx->stack_bound, 4u), exact_lanes)));
+    HIP_TRY(ctx, ctx->q_exact_stack.ensure(stack_dwords(std::max(ctx->desc.stack_bound, 4u), exact_lanes)));
     A.exact_stack = ctx->q_exact_stack.p;
     A.exact_stack_stride = (unsigned int)exact_lanes;
     HIP_TRY(ctx, ctx->q_work.ensure(BATCH_WORDS));
@@ -1418,7 +1460,7 @@ int run_batch(prt_ctx * ctx, const Walk & q, typename Walk::Args A, unsigned int
     A.work = ctx->q_work.p;
     A.slow = ctx->q_slow.p;
     const bool device_pad = A.pad_max < 0.0f;
-    if (device_pad) A.pad_max = ctx->scene_abs_max;
+    if (device_pad) A.pad_max = ctx->desc.scene_abs_max;
 
     HIP_TRY(ctx, hipMemsetAsync(ctx->counters.p, 0, sizeof(DevCounters), stream));
     HIP_TRY(ctx, hipMemsetAsync(A.work, 0, BATCH_WORDS * sizeof(unsigned int), stream));
@@ -1486,58 +1528,41 @@ unsigned int signed_fields(const prt_signed_buffers * o) {
 // The tables of prt_signed_distance (dev_signed.h) into A.sign: the adjacency once per upload, the accumulators once per
 // geometry generation (k_signed_normals on the context's stream, ahead of the walk that reads them).
 int ensure_signed_tables(prt_ctx * ctx, ClosestArgs & A) {
-    const uint32_t n_tris = ctx->scene.tri_count, n_pos = ctx->rf_position_count;
-    if (ctx->q_tri_order.size() != n_tris || ctx->rf_idx_positions.size() != 3 * (size_t)n_tris) {
+    const uint32_t n_tris = ctx->scene.tri_count, n_pos = ctx->keep.position_count;
+    if (ctx->keep.tri_order.size() != n_tris || ctx->keep.idx_positions.size() != 3 * (size_t)n_tris) {
         ctx->error = "prt_signed_distance: the scene's index buffer is not available";
         return -2;
     }
-    if (!ctx->sg_adj.p) {
-        // edge ids: the distinct unordered pairs of position indices, numbered in sorted order
-        std::vector<uint64_t> keys(3 * (size_t)n_tris);
-        for (uint32_t t = 0; t < n_tris; ++t) {
-            const uint32_t * v = &ctx->rf_idx_positions[3 * (size_t)t];
-            const uint32_t pair[3][2] = { { v[0], v[1] }, { v[0], v[2] }, { v[1], v[2] } };      // ab, ac, bc
-            for (int k = 0; k < 3; ++k)
-                keys[3 * (size_t)t + k] = (uint64_t)std::min(pair[k][0], pair[k][1]) << 32 | std::max(pair[k][0], pair[k][1]);
-        }
-        std::vector<uint64_t> edges(keys);
-        std::sort(edges.begin(), edges.end());
-        edges.erase(std::unique(edges.begin(), edges.end()), edges.end());
-        std::vector<unsigned int> adj(6 * (size_t)n_tris);
-        for (uint32_t slot = 0; slot < n_tris; ++slot) {
-            const uint32_t t = ctx->q_tri_order[slot];
-            for (int k = 0; k < 3; ++k) {
-                adj[6 * (size_t)slot + k] = ctx->rf_idx_positions[3 * (size_t)t + k];
-                adj[6 * (size_t)slot + 3 + k] = (unsigned int)(std::lower_bound(edges.begin(), edges.end(), keys[3 * (size_t)t + k]) - edges.begin());
-            }
-        }
-        hipError_t e = ctx->sg_adj.upload(adj);
-        if (e == hipSuccess) e = ctx->sg_acc.ensure(3 * ((size_t)n_pos + edges.size()));
+    if (!ctx->tables.sg_adj.p) {
+        uint32_t edge_count = 0;
+        const std::vector<unsigned int> adj = keep_signed_adjacency(ctx->keep, &edge_count);
+        hipError_t e = ctx->tables.sg_adj.upload(adj);
+        if (e == hipSuccess) e = ctx->tables.sg_acc.ensure(3 * ((size_t)n_pos + edge_count));
         if (e == hipSuccess) e = hipDeviceSynchronize();          // the upload went through the null stream
         if (e != hipSuccess) {
-            ctx->sg_adj.release(); ctx->sg_acc.release();
+            ctx->tables.sg_adj.release(); ctx->tables.sg_acc.release();
             ctx->error = std::string("prt_signed_distance: table upload: ") + hipGetErrorString(e);
             return -10;
         }
-        ctx->sg_edge_count = (uint32_t)edges.size();
-        ctx->sg_generation = 0;
+        ctx->tables.sg_edge_count = edge_count;
+        ctx->tables.sg_generation = 0;
     }
-    A.sign.adj = ctx->sg_adj.p;
-    A.sign.acc = ctx->sg_acc.p;
+    A.sign.adj = ctx->tables.sg_adj.p;
+    A.sign.acc = ctx->tables.sg_acc.p;
     A.sign.position_count = n_pos;
-    A.sign.edge_count = ctx->sg_edge_count;
-    if (ctx->sg_generation != ctx->geom_generation) {
-        const size_t words = 3 * ((size_t)n_pos + ctx->sg_edge_count);
+    A.sign.edge_count = ctx->tables.sg_edge_count;
+    if (ctx->tables.sg_generation != ctx->geom_generation) {
+        const size_t words = 3 * ((size_t)n_pos + ctx->tables.sg_edge_count);
         const unsigned int cap = (unsigned int)std::max(1, ctx->cu_count) * 8u;
         const unsigned int grid0 = (unsigned int)std::max<size_t>(1, std::min<size_t>((words + 255) / 256, cap));
-        hipLaunchKernelGGL(k_signed_normals, dim3(grid0), dim3(256), 0, ctx->stream, ctx->tris.p, n_tris, A.sign, 0);
+        hipLaunchKernelGGL(k_signed_normals, dim3(grid0), dim3(256), 0, ctx->stream, ctx->arrays.tris.p, n_tris, A.sign, 0);
         HIP_TRY(ctx, hipGetLastError());
         if (n_tris) {
             const unsigned int grid1 = std::max(1u, std::min((n_tris + 255u) / 256u, cap));
-            hipLaunchKernelGGL(k_signed_normals, dim3(grid1), dim3(256), 0, ctx->stream, ctx->tris.p, n_tris, A.sign, 1);
+            hipLaunchKernelGGL(k_signed_normals, dim3(grid1), dim3(256), 0, ctx->stream, ctx->arrays.tris.p, n_tris, A.sign, 1);
             HIP_TRY(ctx, hipGetLastError());
         }
-        ctx->sg_generation = ctx->geom_generation;
+        ctx->tables.sg_generation = ctx->geom_generation;
     }
     return 0;
 }
@@ -1580,67 +1605,7 @@ int api_exception(std::string * err, const char * where) noexcept {
 #define PRT_API_CATCH_VOID } catch (...) {}
 
 // =============================================================================================================
-// Shared by prt_upload_scene and prt_update_geometry.
 namespace {
-
-// The reference's visit rank of every input triangle - the leaves of its sphere tree in the order TraceRay pops them (c1
-// first), ascending index inside a group - and the tree as the device's near-tie resolution reads it (RefSphereWalk).  Without
-// a usable tree (none given, a cycle, a group named twice, triangles left over): input order, and no spheres.
-void reference_ranks(const prt_group * groups, uint32_t group_count, const prt_bsphere * spheres, const int32_t * sphere_group,
-                     uint32_t sphere_count, uint32_t n_tris, std::vector<uint32_t> & rank_of_input, std::vector<float4> & ref_spheres) {
-    rank_of_input.assign(n_tris, 0u);
-    ref_spheres.clear();
-    std::vector<uint32_t> group_base(group_count, 0);
-    bool ranked = false;
-    if (spheres && sphere_group && sphere_count) {
-        std::vector<uint32_t> stack(1, 0u);
-        std::vector<uint8_t> seen(group_count, 0);
-        std::vector<uint32_t> first_rank(sphere_count, 0), pop_order(sphere_count, 0);
-        std::vector<uint8_t> popped(sphere_count, 0);
-        uint32_t next = 0, visited = 0;
-        bool ok = true;
-        while (!stack.empty() && ok) {
-            uint32_t i = stack.back();
-            stack.pop_back();
-            if (i >= sphere_count || ++visited > 2 * sphere_count || popped[i]) { ok = false; break; }
-            popped[i] = 1;
-            pop_order[i] = visited - 1;
-            first_rank[i] = next;                         // the first triangle the reference meets below this sphere
-            const prt_bsphere & bs = spheres[i];
-            if (bs.c0 && bs.c1) {
-                stack.push_back(bs.c0);
-                stack.push_back(bs.c1);
-            } else {
-                int32_t g = sphere_group[i];
-                if (g < 0 || (uint32_t)g >= group_count || seen[g]) { ok = false; break; }
-                seen[g] = 1;
-                group_base[g] = next;
-                next += groups[g].index_count / 3;
-            }
-        }
-        ranked = ok && next == n_tris;
-        if (ranked) {
-            ref_spheres.resize(2 * (size_t)sphere_count, make_float4(0, 0, 0, 0));
-            for (uint32_t i = 0; i < sphere_count; ++i) {
-                const prt_bsphere & bs = spheres[i];
-                ref_spheres[2 * (size_t)i] = make_float4(bs.center[0], bs.center[1], bs.center[2], bs.radius);
-                const bool inner = bs.c0 && bs.c1 && popped[i];
-                const uint32_t w[4] = { inner ? bs.c0 : 0u, inner ? bs.c1 : 0u, inner ? first_rank[bs.c0] : 0u, pop_order[i] };
-                float4 f;
-                memcpy(&f, w, 16);
-                ref_spheres[2 * (size_t)i + 1] = f;
-            }
-        }
-    }
-    if (ranked) {
-        for (uint32_t g = 0; g < group_count; ++g) {
-            uint32_t first = groups[g].first_index / 3, cnt = groups[g].index_count / 3;
-            for (uint32_t k = 0; k < cnt; ++k) rank_of_input[first + k] = group_base[g] + k;
-        }
-    } else {
-        for (uint32_t t = 0; t < n_tris; ++t) rank_of_input[t] = t;
-    }
-}
 
 // prt_update_geometry / prt_update_geometry_device: `device` says where positions / normals / tangents live.  Everything that
 // can refuse the update - the arguments, the coordinates (k_refit_bounds) - comes before the first write to the scene's
@@ -1650,13 +1615,13 @@ int update_geometry(prt_ctx * ctx, const prt_geometry_update * u, prt_update_inf
     if (info) memset(info, 0, sizeof(*info));
     if (!u || !u->positions) { ctx->error = "prt_update_geometry: null update or null positions"; return -1; }
     if (!ctx->has_scene) { ctx->error = "prt_update_geometry: upload a scene first"; return -2; }
-    if (u->position_count != ctx->rf_position_count) { ctx->error = "prt_update_geometry: position_count differs from the uploaded scene's"; return -1; }
-    if (u->normals && u->normal_count != ctx->rf_normal_count) { ctx->error = "prt_update_geometry: normal_count differs from the uploaded scene's"; return -1; }
+    if (u->position_count != ctx->keep.position_count) { ctx->error = "prt_update_geometry: position_count differs from the uploaded scene's"; return -1; }
+    if (u->normals && u->normal_count != ctx->keep.normal_count) { ctx->error = "prt_update_geometry: normal_count differs from the uploaded scene's"; return -1; }
     const uint32_t n_tris = ctx->scene.tri_count, n_nodes = ctx->scene.node_count;
-    const uint32_t levels = ctx->rf_level_first.empty() ? 0u : (uint32_t)ctx->rf_level_first.size() - 1u;
-    if (info) { info->levels = levels; info->node_count = n_nodes; info->abs_max = ctx->scene_abs_max; }
+    const uint32_t levels = ctx->keep.level_first.empty() ? 0u : (uint32_t)ctx->keep.level_first.size() - 1u;
+    if (info) { info->levels = levels; info->node_count = n_nodes; info->abs_max = ctx->desc.scene_abs_max; }
     if (n_tris == 0) return 0;                                    // nothing references a position: nothing moves
-    if (!levels || ctx->q_tri_order.size() != n_tris || ctx->rf_idx_positions.size() != 3 * (size_t)n_tris) {
+    if (!levels || ctx->keep.tri_order.size() != n_tris || ctx->keep.idx_positions.size() != 3 * (size_t)n_tris) {
         ctx->error = "prt_update_geometry: the uploaded tree is not level-ordered and cannot be refitted (upload the moved scene instead)";
         return -9;
     }
@@ -1667,26 +1632,18 @@ int update_geometry(prt_ctx * ctx, const prt_geometry_update * u, prt_update_inf
     // ---- host work that can fail, first: the reference's ranks for the moved scene's sphere tree
     std::vector<uint32_t> rank_of_input;
     std::vector<float4> ref_spheres;
-    reference_ranks(ctx->q_groups.data(), (uint32_t)ctx->q_groups.size(), u->spheres, u->sphere_group, u->sphere_count, n_tris, rank_of_input, ref_spheres);
+    reference_ranks(ctx->keep.groups.data(), (uint32_t)ctx->keep.groups.size(), u->spheres, u->sphere_group, u->sphere_count, n_tris, rank_of_input, ref_spheres);
     std::vector<unsigned int> rank((size_t)n_tris + 1, 0u);
-    for (uint32_t slot = 0; slot < n_tris; ++slot) rank[slot] = rank_of_input[ctx->q_tri_order[slot]];
+    for (uint32_t slot = 0; slot < n_tris; ++slot) rank[slot] = rank_of_input[ctx->keep.tri_order[slot]];
 
     // ---- the update's own device arrays (not the scene's): table, scratch boxes, the two words of k_refit_bounds, inputs
-    if (!ctx->rf_table.p) {
-        std::vector<unsigned int> table((size_t)n_tris * REFIT_TABLE_WORDS);
-        for (uint32_t slot = 0; slot < n_tris; ++slot) {
-            const uint32_t t = ctx->q_tri_order[slot];
-            for (uint32_t c = 0; c < 3; ++c) {
-                table[(size_t)slot * REFIT_TABLE_WORDS + c] = ctx->rf_idx_positions[3 * (size_t)t + c];
-                table[(size_t)slot * REFIT_TABLE_WORDS + 3 + c] = ctx->rf_idx_normals[3 * (size_t)t + c];
-            }
-        }
-        hipError_t e = ctx->rf_table.upload(table);
-        if (e != hipSuccess) { ctx->rf_table.release(); ctx->error = std::string("prt_update_geometry: table upload: ") + hipGetErrorString(e); return -10; }
+    if (!ctx->tables.rf_table.p) {
+        hipError_t e = ctx->tables.rf_table.upload(keep_refit_table(ctx->keep));
+        if (e != hipSuccess) { ctx->tables.rf_table.release(); ctx->error = std::string("prt_update_geometry: table upload: ") + hipGetErrorString(e); return -10; }
     }
     HIP_TRY(ctx, ctx->rf_boxes.ensure(n_nodes));
     HIP_TRY(ctx, ctx->rf_bounds.ensure(2));
-    const bool with_tangents = u->tangents && ctx->rf_bumped && ctx->tri_tan.p;      // one per normal of the upload
+    const bool with_tangents = u->tangents && ctx->keep.bumped && ctx->arrays.tri_tan.p;      // one per normal of the upload
     RefitArgs A;
     memset(&A, 0, sizeof(A));
     A.positions = u->positions;
@@ -1694,7 +1651,7 @@ int update_geometry(prt_ctx * ctx, const prt_geometry_update * u, prt_update_inf
     A.tangents = with_tangents ? u->tangents : nullptr;
     if (!device) {
         const size_t np = 3 * (size_t)u->position_count, nn = u->normals ? 3 * (size_t)u->normal_count : 0;
-        const size_t nt = with_tangents ? 3 * (size_t)ctx->rf_normal_count : 0;
+        const size_t nt = with_tangents ? 3 * (size_t)ctx->keep.normal_count : 0;
         HIP_TRY(ctx, ctx->rf_in.ensure(np + nn + nt));
         float * p = ctx->rf_in.p;
         HIP_TRY(ctx, hipMemcpyAsync(p, u->positions, np * sizeof(float), hipMemcpyHostToDevice, stream));
@@ -1702,11 +1659,11 @@ int update_geometry(prt_ctx * ctx, const prt_geometry_update * u, prt_update_inf
         if (nn) { HIP_TRY(ctx, hipMemcpyAsync(p, u->normals, nn * sizeof(float), hipMemcpyHostToDevice, stream)); A.normals = p; p += nn; }
         if (nt) { HIP_TRY(ctx, hipMemcpyAsync(p, u->tangents, nt * sizeof(float), hipMemcpyHostToDevice, stream)); A.tangents = p; }
     }
-    A.table = ctx->rf_table.p;
+    A.table = ctx->tables.rf_table.p;
     A.n_tris = n_tris;
     A.node_count = n_nodes;
-    A.nodes = ctx->nodes.p; A.tris = ctx->tris.p; A.shade = ctx->shade.p;
-    A.tri_tan = with_tangents ? ctx->tri_tan.p : nullptr;
+    A.nodes = ctx->arrays.nodes.p; A.tris = ctx->arrays.tris.p; A.shade = ctx->arrays.shade.p;
+    A.tri_tan = with_tangents ? ctx->arrays.tri_tan.p : nullptr;
     A.boxes = ctx->rf_boxes.p;
     A.bounds = ctx->rf_bounds.p;
 
@@ -1736,35 +1693,34 @@ int update_geometry(prt_ctx * ctx, const prt_geometry_update * u, prt_update_inf
             return -10;                                                                                      \
         }                                                                                                    \
     } while (0)
-    const bool had_spheres = ctx->scene.ref_spheres != nullptr;
-    const size_t old_sphere_bytes = had_spheres ? ctx->ref_spheres.bytes() : 0;
     hipLaunchKernelGGL(k_refit_records, dim3((n_tris + 255u) / 256u), dim3(256), 0, stream, A);
     REFIT_TRY(hipGetLastError());
     for (uint32_t l = levels; l-- > 0;) {                         // deepest level first; the stream is the only ordering
-        const unsigned int first = ctx->rf_level_first[l], count = ctx->rf_level_first[l + 1] - first;
+        const unsigned int first = ctx->keep.level_first[l], count = ctx->keep.level_first[l + 1] - first;
         hipLaunchKernelGGL(k_refit_level<BVH_WIDTH>, dim3((count + 63u) / 64u), dim3(64), 0, stream, A, first, count);
         REFIT_TRY(hipGetLastError());
     }
-    REFIT_TRY(hipMemcpyAsync(ctx->tri_rank.p, rank.data(), rank.size() * sizeof(unsigned int), hipMemcpyHostToDevice, stream));
-    ctx->q_slot_of_rank.release();                                // the next prt_trace_rays inverts the new ranks (the stream has drained by then)
+    REFIT_TRY(hipMemcpyAsync(ctx->arrays.tri_rank.p, rank.data(), rank.size() * sizeof(unsigned int), hipMemcpyHostToDevice, stream));
+    ctx->tables.q_slot_of_rank.release();                                // the next prt_trace_rays inverts the new ranks (the stream has drained by then)
     if (!ref_spheres.empty()) {
-        REFIT_TRY(ctx->ref_spheres.ensure(ref_spheres.size()));
-        REFIT_TRY(hipMemcpyAsync(ctx->ref_spheres.p, ref_spheres.data(), ref_spheres.size() * sizeof(float4), hipMemcpyHostToDevice, stream));
+        REFIT_TRY(ctx->arrays.ref_spheres.ensure(ref_spheres.size()));
+        REFIT_TRY(hipMemcpyAsync(ctx->arrays.ref_spheres.p, ref_spheres.data(), ref_spheres.size() * sizeof(float4), hipMemcpyHostToDevice, stream));
     }
     REFIT_TRY(hipEventRecord(ctx->ev[1], stream));
     REFIT_TRY(hipStreamSynchronize(stream));
     float ms = 0.0f;
     REFIT_TRY(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
 #undef REFIT_TRY
-    ctx->scene.ref_spheres = ref_spheres.empty() ? nullptr : ctx->ref_spheres.p;      // spheres of the old geometry are never kept
-    ctx->info.device_bytes = ctx->info.device_bytes - old_sphere_bytes + (ref_spheres.empty() ? 0 : ctx->ref_spheres.bytes());
-    ctx->scene_abs_max = abs_max;
+    ctx->scene.ref_spheres = ref_spheres.empty() ? nullptr : ctx->arrays.ref_spheres.p;      // spheres of the old geometry are never kept
+    ctx->desc.info.device_bytes += ref_spheres.size() * sizeof(float4) - ctx->desc.ref_sphere_bytes;
+    ctx->desc.ref_sphere_bytes = ref_spheres.size() * sizeof(float4);
+    ctx->desc.scene_abs_max = abs_max;
     // the shadow trees are of the uploaded geometry, in membership and in boxes: every shadow ray starts at the scene's root
     // until the next upload (render_pixels_once)
-    ctx->shadow_trees_fresh = false;
-    for (prt_shadow_tree_info & si : ctx->shadow_info) si.active = 0;
+    ctx->desc.shadow_trees_fresh = false;
+    for (prt_shadow_tree_info & si : ctx->desc.shadow_info) si.active = 0;
     // ... and so are the open-triangle flags: k_refit_records leaves the word where it is, no render reads it until the next upload
-    for (prt_shadow_open_info & oi : ctx->shadow_open_info) oi.active = 0;
+    for (prt_shadow_open_info & oi : ctx->desc.shadow_open_info) oi.active = 0;
     ctx->tuned.clear();                                           // a refitted tree may change which pipeline wins a try-out
     ctx->geom_generation++;                                       // the pseudonormals of prt_signed_distance are of the old records
     if (info) { info->device_ms = ms; info->abs_max = abs_max; }
@@ -1782,16 +1738,14 @@ unsigned int grad_grid(const prt_ctx * ctx, uint32_t count) {
 // The calls' own device data, built on the first gradient call of either kind after an upload: the position index buffer and
 // the groups' runs; the control words; np accumulators when the vertex gradient is wanted.
 int grad_prepare(prt_ctx * ctx, const char * what, size_t np, bool want_positions) {
-    if (ctx->rf_idx_positions.size() != 3 * (size_t)ctx->scene.tri_count) { ctx->error = std::string(what) + ": the scene's index buffer is not available"; return -2; }
-    if (!ctx->qg_idx.p || !ctx->qg_runs.p) {
-        std::vector<unsigned int> runs(2 * ctx->q_groups.size());
-        for (size_t g = 0; g < ctx->q_groups.size(); ++g) { runs[2 * g] = ctx->q_groups[g].first_index; runs[2 * g + 1] = ctx->q_groups[g].index_count; }
-        HIP_TRY(ctx, ctx->qg_idx.upload(ctx->rf_idx_positions));
-        HIP_TRY(ctx, ctx->qg_runs.upload(runs));
+    if (ctx->keep.idx_positions.size() != 3 * (size_t)ctx->scene.tri_count) { ctx->error = std::string(what) + ": the scene's index buffer is not available"; return -2; }
+    if (!ctx->tables.qg_idx.p || !ctx->tables.qg_runs.p) {
+        HIP_TRY(ctx, ctx->tables.qg_idx.upload(ctx->keep.idx_positions));
+        HIP_TRY(ctx, ctx->tables.qg_runs.upload(keep_group_runs(ctx->keep)));
         HIP_TRY(ctx, hipDeviceSynchronize());                     // the uploads went through the null stream
     }
     HIP_TRY(ctx, ctx->qg_words.ensure(QGRAD_WORDS));
-    if (want_positions) HIP_TRY(ctx, ctx->qg_acc.ensure(np));
+    if (want_positions) HIP_TRY(ctx, ctx->tables.qg_acc.ensure(np));
     return 0;
 }
 
@@ -1822,7 +1776,7 @@ int grad_resolve(prt_ctx * ctx, bool adds, float * g_positions, uint32_t positio
     if (adds) {
         QGradArgs R;                                              // k_qgrad_resolve reads these four fields
         memset(&R, 0, sizeof(R));
-        R.g_positions = g_positions; R.acc = ctx->qg_acc.p; R.position_count = position_count; R.unit_exponent = unit_exponent;
+        R.g_positions = g_positions; R.acc = ctx->tables.qg_acc.p; R.position_count = position_count; R.unit_exponent = unit_exponent;
         hipLaunchKernelGGL(k_qgrad_resolve, dim3((unsigned int)((np + 255) / 256)), dim3(256), 0, stream, R);
         HIP_TRY(ctx, hipGetLastError());
     } else if (g_positions && np) {
@@ -1915,7 +1869,7 @@ int grad_backward(prt_ctx * ctx, const char * what, const Grad & q, uint32_t pos
     if (!q.b) { ctx->error = std::string(what) + ": null batch"; return -1; }
     if (q.b->count && !q.complete()) { ctx->error = std::string(what) + ": " + Grad::required(); return -1; }
     if (!ctx->has_scene) { ctx->error = std::string(what) + ": no scene uploaded"; return -2; }
-    if (position_count != ctx->rf_position_count) { ctx->error = std::string(what) + ": position_count differs from the uploaded scene's"; return -1; }
+    if (position_count != ctx->keep.position_count) { ctx->error = std::string(what) + ": position_count differs from the uploaded scene's"; return -1; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = ctx->stream;
     const uint32_t count = q.b->count;
@@ -1940,10 +1894,10 @@ int grad_backward(prt_ctx * ctx, const char * what, const Grad & q, uint32_t pos
         HIP_TRY(ctx, io.carve(ctx->qg_io));
         if (io.upload(stream) != hipSuccess) { ctx->error = std::string(what) + ": copying the inputs to the device failed"; return -10; }
     }
-    A.idx_positions = ctx->qg_idx.p;
-    A.group_runs = ctx->qg_runs.p;
+    A.idx_positions = ctx->tables.qg_idx.p;
+    A.group_runs = ctx->tables.qg_runs.p;
     A.words = ctx->qg_words.p;
-    A.count = count; A.group_count = (unsigned int)ctx->q_groups.size(); A.position_count = position_count;
+    A.count = count; A.group_count = (unsigned int)ctx->keep.groups.size(); A.position_count = position_count;
 
     // ---- the references and the batch's largest contribution, before any output is written
     const unsigned int grid = grad_grid(ctx, count);
@@ -1954,7 +1908,7 @@ int grad_backward(prt_ctx * ctx, const char * what, const Grad & q, uint32_t pos
     if (const int rc = grad_scan_verdict(ctx, what, Grad::items(), count, stream, &scan)) return rc;
     const bool adds = want_p && scan.words[QGRAD_W_HIT] && scan.m > 0.0f;   // else the vertex gradient is zero
     A.unit_exponent = scan.unit_exponent;
-    A.acc = adds ? ctx->qg_acc.p : nullptr;
+    A.acc = adds ? ctx->tables.qg_acc.p : nullptr;
     if (adds) HIP_TRY(ctx, hipMemsetAsync(A.acc, 0, np * sizeof(long long), stream));
     if (adds || Grad::scatter_writes(A)) {
         const bool merge = ctx->opt.qgrad_merge < 0 ? PRT_QGRAD_MERGE_DEFAULT != 0 : ctx->opt.qgrad_merge != 0;
@@ -1993,7 +1947,7 @@ int trace_rays(prt_ctx * ctx, int mode, const prt_ray_batch * batch, const prt_h
     HIP_TRY(ctx, io.carve(ctx->q_io));
     if (fields & QF_OCCLUDED) { HIP_TRY(ctx, ctx->q_occ.ensure(n)); A.occluded = ctx->q_occ.p; }
     // batch_pad's extent from the valid rays' biased origins, on the host (k_query_pad's rule; work[BATCH_W_EXTENT] stays 0)
-    float extent = ctx->scene_abs_max;
+    float extent = ctx->desc.scene_abs_max;
     for (size_t i = 0; i < n; ++i) {
         const f3 o = ld3(batch->origins + 3 * i), d = ld3(batch->directions + 3 * i), ob = o + d * batch->ray_bias;
         const bool ok = std::isfinite(o.x) && std::isfinite(o.y) && std::isfinite(o.z) && std::isfinite(d.x) && std::isfinite(d.y) &&
@@ -2030,7 +1984,7 @@ int closest_points(prt_ctx * ctx, const prt_point_batch * batch, const prt_signe
     io.out(&A.feature, n, fields & CF_FEATURE);
     HIP_TRY(ctx, io.carve(ctx->q_io));
     // batch_pad's extent from the finite points, on the host (k_closest_pad's rule; work[BATCH_W_EXTENT] stays 0)
-    float extent = ctx->scene_abs_max;
+    float extent = ctx->desc.scene_abs_max;
     for (size_t i = 0; i < n; ++i) {
         const f3 q = ld3(batch->points + 3 * i);
         if (std::isfinite(q.x) && std::isfinite(q.y) && std::isfinite(q.z)) extent = std::max(extent, std::max(std::max(fabsf(q.x), fabsf(q.y)), fabsf(q.z)));
@@ -2055,8 +2009,8 @@ struct HemiWalk {
     typedef HemiArgs Args;
     static const char * name() { return "prt_hemisphere_visibility"; }
     int prepare(prt_ctx * ctx, HemiArgs & A) const {
-        A.replay_beyond = 64.0f * ctx->scene_abs_max;
-        A.scene_max = ctx->scene_abs_max;
+        A.replay_beyond = 64.0f * ctx->desc.scene_abs_max;
+        A.scene_max = ctx->desc.scene_abs_max;
         HIP_TRY(ctx, ctx->q_hemi_flags.ensure(batch_items(A)));
         A.flags = ctx->q_hemi_flags.p;
         return 0;
@@ -2136,8 +2090,8 @@ int hemisphere_visibility(prt_ctx * ctx, const prt_hemi_batch * b, const prt_hem
             const f3 p = ld3(b->points + 3 * i), nr = ld3(b->normals + 3 * i);
             if (hemi_point_valid(p, nr)) extent = std::max(extent, std::max(std::max(fabsf(p.x), fabsf(p.y)), fabsf(p.z)));
         }
-        A.pad_max = std::max(ctx->scene_abs_max, extent + fabsf(b->ray_bias));
-        if (!(A.pad_max >= 0.0f)) A.pad_max = ctx->scene_abs_max;          // a NaN bias: every ray is a miss by definition
+        A.pad_max = std::max(ctx->desc.scene_abs_max, extent + fabsf(b->ray_bias));
+        if (!(A.pad_max >= 0.0f)) A.pad_max = ctx->desc.scene_abs_max;          // a NaN bias: every ray is a miss by definition
         HIP_TRY(ctx, io.upload(stream));
     }
     const long long want_items = ctx->opt.hemi_pass_items >= 0 ? ctx->opt.hemi_pass_items : (1ll << 24);
@@ -2211,7 +2165,7 @@ int render_rays(prt_ctx * ctx, const prt_radiance_batch * b, const prt_params * 
     A.origins = b->origins; A.directions = b->directions;
     A.n_rays = n_rays;
     A.ray_bias = params->ray_bias;
-    A.origin_max = 64.0f * ctx->scene_abs_max;
+    A.origin_max = 64.0f * ctx->desc.scene_abs_max;
     A.first = (unsigned int)b->first;
     A.camera_stream = (b->flags & PRT_RAYS_CAMERA_STREAM) ? 1u : 0u;
     StageList io;
@@ -2275,36 +2229,33 @@ unsigned int sample_fields(const prt_sample_buffers * o) {
 int ensure_sample_table(prt_ctx * ctx, SampleTable & T, bool * rebuilt) {
     const uint32_t n_tris = ctx->scene.tri_count;
     *rebuilt = false;
-    if (ctx->q_tri_order.size() != n_tris) { ctx->error = "prt_sample_surface: the scene's leaf order is not available"; return -2; }
-    if (!ctx->sm_slot_of_input.p) {
-        std::vector<unsigned int> slot_of_input(n_tris);
-        for (uint32_t slot = 0; slot < n_tris; ++slot) {
-            if (ctx->q_tri_order[slot] >= n_tris) { ctx->error = "prt_sample_surface: the scene's leaf order is not a permutation"; return -2; }
-            slot_of_input[ctx->q_tri_order[slot]] = slot;
-        }
-        hipError_t e = ctx->sm_slot_of_input.upload(slot_of_input);
+    if (ctx->keep.tri_order.size() != n_tris) { ctx->error = "prt_sample_surface: the scene's leaf order is not available"; return -2; }
+    if (!ctx->tables.sm_slot_of_input.p) {
+        std::vector<unsigned int> slot_of_input;
+        if (!keep_slot_of_input(ctx->keep, &slot_of_input)) { ctx->error = "prt_sample_surface: the scene's leaf order is not a permutation"; return -2; }
+        hipError_t e = ctx->tables.sm_slot_of_input.upload(slot_of_input);
         if (e == hipSuccess) e = hipDeviceSynchronize();          // the upload went through the null stream
         if (e != hipSuccess) {
-            ctx->sm_slot_of_input.release();
+            ctx->tables.sm_slot_of_input.release();
             ctx->error = std::string("prt_sample_surface: table upload: ") + hipGetErrorString(e);
             return -10;
         }
-        ctx->sm_generation = 0;
+        ctx->tables.sm_generation = 0;
     }
     const unsigned int n_tiles = (n_tris + (unsigned int)SAMPLE_TILE - 1u) / (unsigned int)SAMPLE_TILE;
-    HIP_TRY(ctx, ctx->sm_weight.ensure(n_tris));
-    HIP_TRY(ctx, ctx->sm_prefix.ensure(n_tris));
-    HIP_TRY(ctx, ctx->sm_tile_sum.ensure(n_tiles));
+    HIP_TRY(ctx, ctx->tables.sm_weight.ensure(n_tris));
+    HIP_TRY(ctx, ctx->tables.sm_prefix.ensure(n_tris));
+    HIP_TRY(ctx, ctx->tables.sm_tile_sum.ensure(n_tiles));
     HIP_TRY(ctx, ctx->sm_words.ensure(SAMPLE_WORDS));
-    T.tris = ctx->tris.p;
-    T.slot_of_input = ctx->sm_slot_of_input.p;
-    T.weight = ctx->sm_weight.p;
-    T.C = ctx->sm_prefix.p;
-    T.tile_sum = ctx->sm_tile_sum.p;
+    T.tris = ctx->arrays.tris.p;
+    T.slot_of_input = ctx->tables.sm_slot_of_input.p;
+    T.weight = ctx->tables.sm_weight.p;
+    T.C = ctx->tables.sm_prefix.p;
+    T.tile_sum = ctx->tables.sm_tile_sum.p;
     T.words = ctx->sm_words.p;
     T.n_tris = n_tris;
     T.n_tiles = n_tiles;
-    if (ctx->sm_generation == ctx->geom_generation) return 0;
+    if (ctx->tables.sm_generation == ctx->geom_generation) return 0;
     hipStream_t stream = ctx->stream;
     HIP_TRY(ctx, hipEventRecord(ctx->ev[2], stream));
     HIP_TRY(ctx, hipMemsetAsync(T.words, 0, SAMPLE_WORDS * sizeof(unsigned long long), stream));
@@ -2357,14 +2308,14 @@ int sample_surface(prt_ctx * ctx, const prt_sample_request * rq, const prt_sampl
     memset(&T, 0, sizeof(T));
     bool rebuilt = false;
     if (const int rc = ensure_sample_table(ctx, T, &rebuilt)) return rc;
-    hipLaunchKernelGGL(k_sample, dim3(grad_grid(ctx, rq->count)), dim3(256), 0, stream, T, A, ctx->q_leaf_map.p, fields);
+    hipLaunchKernelGGL(k_sample, dim3(grad_grid(ctx, rq->count)), dim3(256), 0, stream, T, A, ctx->tables.q_leaf_map.p, fields);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ctx->ev[1], stream));
     if (!device) HIP_TRY(ctx, io.download(stream));
     HIP_TRY(ctx, hipStreamSynchronize(stream));
     if (rebuilt) {
         memcpy(ctx->sm_host_words, ctx->sm_read_words, sizeof(ctx->sm_host_words));
-        ctx->sm_generation = ctx->geom_generation;
+        ctx->tables.sm_generation = ctx->geom_generation;
     }
     if (info) {
         float ms = 0.0f, tms = 0.0f;
@@ -2458,7 +2409,7 @@ prt_ctx * prt_create(int device_id) {
         if (ctx->cu_count <= 0) ctx->cu_count = 256;
     }
     memset(&ctx->scene, 0, sizeof(ctx->scene));
-    memset(&ctx->info, 0, sizeof(ctx->info));
+    memset(&ctx->desc.info, 0, sizeof(ctx->desc.info));
     memset(&ctx->last_stats, 0, sizeof(ctx->last_stats));
     prt_options_from_env(ctx->opt);       // the environment is read here and nowhere else
     // PRT_RESERVE_CUS=k (multi-GPU callers): the context's streams are created with a CU mask that leaves k compute units to
@@ -2520,15 +2471,12 @@ void prt_destroy(prt_ctx * ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    ctx->nodes.release(); ctx->tris.release(); ctx->shade.release(); ctx->diffuse_dirs.release(); ctx->spec_dirs.release();
-    ctx->tri_rank.release(); ctx->materials.release(); ctx->lights.release();
+    ctx->arrays.release(); ctx->tables.release(); ctx->spec_dirs.release();
     ctx->sample_rgb.release(); ctx->frame_out.release(); ctx->counters.release(); ctx->ring_ws.release(); ctx->pixel_list.release(); ctx->wf_counts.release(); ctx->stack_spill.release(); ctx->pool_f4.release(); ctx->pool_park.release(); ctx->pool_fin.release(); ctx->pool_args.release(); ctx->adapt_f4.release(); ctx->wave_times.release();
-    ctx->textures.release(); ctx->texels.release(); ctx->srgb_lut.release(); ctx->tri_uv.release(); ctx->tri_tan.release();
-    ctx->ref_spheres.release();
-    ctx->q_leaf_map.release(); ctx->q_slot_of_rank.release(); ctx->q_work.release(); ctx->q_slow.release(); ctx->q_exact_stack.release(); ctx->q_io.release(); ctx->q_occ.release(); ctx->q_hemi_flags.release();
-    ctx->rf_table.release(); ctx->rf_boxes.release(); ctx->rf_bounds.release(); ctx->rf_in.release();
-    ctx->qg_idx.release(); ctx->qg_runs.release(); ctx->qg_acc.release(); ctx->qg_words.release(); ctx->qg_io.release();
-    ctx->sm_slot_of_input.release(); ctx->sm_weight.release(); ctx->sm_prefix.release(); ctx->sm_tile_sum.release(); ctx->sm_words.release();
+    ctx->q_work.release(); ctx->q_slow.release(); ctx->q_exact_stack.release(); ctx->q_io.release(); ctx->q_occ.release(); ctx->q_hemi_flags.release(); ctx->rays_words.release();
+    ctx->rf_boxes.release(); ctx->rf_bounds.release(); ctx->rf_in.release();
+    ctx->qg_words.release(); ctx->qg_io.release();
+    ctx->sm_words.release();
     for (int c = 0; c < PRT_MAX_CHAINS; ++c) {
         prt_ctx::ChainWs & w = ctx->chain[c];
         w.f4.release(); w.rng.release(); w.counts.release(); w.overflow.release(); w.slow_stack.release();
@@ -2580,326 +2528,60 @@ int prt_get_region_stats(const prt_ctx * ctx, uint64_t * out, uint32_t n) {
 int prt_upload_scene(prt_ctx * ctx, const prt_scene_desc * s) {
     PRT_API_TRY
     if (!ctx) return -1;
-    if (!s || (s->index_count % 3) != 0) { ctx->error = "prt_upload_scene: null scene or index_count not a multiple of 3"; return -1; }
-    if (s->material_count == 0) { ctx->error = "prt_upload_scene: at least one material is required"; return -1; }
+    int rc = check_scene_desc(s, &ctx->error);                 // scene_pack.cpp, like everything below that needs no device
+    if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    // The old scene goes here; the new one arrives in ONE step at the end, when all of it lies on the device.  Until then the
+    // context holds nothing of it: a failed upload leaves it describing no scene, never half of one.
+    ctx->tables.release();
+    ctx->keep = SceneKeep();
     ctx->has_scene = false;
-    ctx->q_leaf_map.release(); ctx->q_slot_of_rank.release();
-    ctx->q_tri_order.clear();
-    ctx->q_groups.clear();
-    ctx->rf_table.release();
-    ctx->qg_idx.release(); ctx->qg_runs.release(); ctx->qg_acc.release();
-    ctx->sg_adj.release(); ctx->sg_acc.release();
-    ctx->sg_edge_count = 0;
-    ctx->sm_slot_of_input.release(); ctx->sm_weight.release(); ctx->sm_prefix.release(); ctx->sm_tile_sum.release();
-    ctx->sm_generation = 0;
-    ctx->rf_idx_positions.clear();
-    ctx->rf_idx_normals.clear();
-    ctx->rf_level_first.clear();
-    const uint32_t n_tris = s->index_count / 3;
-    if (n_tris >= (1u << 26)) { ctx->error = "prt_upload_scene: 2^26 triangles or more (the traversal addresses nodes and triangles by 32-bit byte offsets)"; return -1; }
-
-    // per-triangle group / material lookup + validation of every index the kernels will follow
-    std::vector<int32_t> tri_material(n_tris, 0);
-    std::vector<uint8_t> covered(n_tris, 0);
-    for (uint32_t g = 0; g < s->group_count; ++g) {
-        const prt_group & pg = s->groups[g];
-        if (pg.first_index % 3 || pg.index_count % 3 || (uint64_t)pg.first_index + pg.index_count > s->index_count) {
-            ctx->error = "prt_upload_scene: group index range is not a whole run of triangles inside the index buffers";
-            return -1;
-        }
-        if (pg.material < 0 || (uint32_t)pg.material >= s->material_count) { ctx->error = "prt_upload_scene: group material out of range"; return -1; }
-        for (uint32_t t = pg.first_index / 3; t < (pg.first_index + pg.index_count) / 3; ++t) { tri_material[t] = pg.material; covered[t] = 1; }
-    }
-    for (uint32_t t = 0; t < n_tris; ++t)
-        if (!covered[t]) { ctx->error = "prt_upload_scene: triangle not covered by any group"; return -1; }
-    for (uint32_t i = 0; i < s->index_count; ++i) {
-        if (s->idx_positions[i] >= s->position_count || s->idx_normals[i] >= s->normal_count ||
-            s->idx_texcoords[i] >= s->texcoord_count) {
-            ctx->error = "prt_upload_scene: vertex index out of range (the reference would read out of bounds here)";
-            return -1;
-        }
-    }
-    bool textured = false, bumped = false;
-    for (uint32_t m = 0; m < s->material_count; ++m) {
-        const prt_material & pm = s->materials[m];
-        const int32_t slots[5] = { pm.ambient_texture, pm.diffuse_texture, pm.specular_texture, pm.alpha_texture, pm.bump_texture };
-        for (int k = 0; k < 5; ++k) {
-            if (slots[k] < 0) continue;
-            textured = true;
-            if (k == 4) bumped = true;
-            if (!s->textures || (uint32_t)slots[k] >= s->texture_count) { ctx->error = "prt_upload_scene: material texture slot out of range"; return -1; }
-            const prt_texture & t = s->textures[slots[k]];
-            // size - 2 is the sampling scale (texture.cpp:63-64): below 2 it wraps around as u32 in the reference
-            if (!t.texels || t.size_x < 2 || t.size_y < 2 || t.channels < 1 || t.channels > 4) {
-                ctx->error = "prt_upload_scene: texture needs texels, 1..4 channels and at least 2 x 2 texels";
-                return -1;
-            }
-        }
-    }
-    if (textured && s->texture_count >= DEV_TEX_NONE) { ctx->error = "prt_upload_scene: more than 65534 textures"; return -1; }
-    if (bumped && !s->tangents) { ctx->error = "prt_upload_scene: a material has a bump map but the scene has no tangents"; return -1; }
 
     // ---- BVH over un-indexed triangles
     auto t0 = std::chrono::steady_clock::now();
-    std::vector<float> verts((size_t)n_tris * 9);
-    for (uint32_t t = 0; t < n_tris; ++t)
-        for (int c = 0; c < 3; ++c) memcpy(&verts[(size_t)t * 9 + 3 * c], s->positions + 3 * (size_t)s->idx_positions[3 * t + c], 12);
-    for (size_t i = 0; i < verts.size(); ++i)
-        if (!(fabsf(verts[i]) < 1e18f)) { ctx->error = "prt_upload_scene: vertex coordinate is not finite or exceeds 1e18"; return -1; }
+    const uint32_t n_tris = s->index_count / 3;
+    std::vector<float> verts;
+    if ((rc = unindex_scene(s, &verts, &ctx->error))) return rc;
     BvhWide bvh;
-    unsigned int hw = std::max(1u, std::thread::hardware_concurrency());
-    unsigned int leaf_max = BVH_LEAF_MAX;
-    if (ctx->opt.leaf_max >= 0) leaf_max = (unsigned int)std::max(1ll, std::min(4ll, ctx->opt.leaf_max));   // experiment knob
-    const float trav_cost = (float)ctx->opt.sah_trav_cost;                                                  // experiment knob
+    ScenePackOptions how;
+    how.threads = std::min(std::max(1u, std::thread::hardware_concurrency()), 16u);
+    how.leaf_max = BVH_LEAF_MAX;
+    if (ctx->opt.leaf_max >= 0) how.leaf_max = (unsigned int)std::max(1ll, std::min(4ll, ctx->opt.leaf_max));   // experiment knob
+    how.sah_trav_cost = (float)ctx->opt.sah_trav_cost;                                                          // experiment knob
+    how.shadow_tree_ratio = (uint32_t)std::max(0ll, std::min(100ll, ctx->opt.shadow_tree_ratio));
+    how.bvh = &ctx->opt.bvh;
     if (ctx->opt.bvh_builder_lbvh) {
         // fast build for scenes that change every frame: radix tree on the GPU (bvh_lbvh.h), same quantised wide back end
-        int rc = build_bvh_lbvh(ctx, verts.data(), n_tris, leaf_max, &bvh);
-        if (rc) return rc;
+        if ((rc = build_bvh_lbvh(ctx, verts.data(), n_tris, how.leaf_max, &bvh))) return rc;
     } else {
-        build_bvh_wide(BVH_WIDTH, verts.data(), n_tris, leaf_max, std::min(hw, 16u), &bvh, trav_cost, &ctx->opt.bvh);
+        build_bvh_wide(BVH_WIDTH, verts.data(), n_tris, how.leaf_max, how.threads, &bvh, how.sah_trav_cost, how.bvh);
     }
-    double build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    const double build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     // every address the traversal kernels will form from the tree is checked on the host before the tree is uploaded (bvh_check.cpp)
     if (const char * bad = validate_bvh_links(bvh, n_tris)) { ctx->error = std::string("prt_upload_scene: the builder produced a broken tree - ") + bad; return -9; }
 
-    // ---- reference visit rank: leaves of the sphere tree in the order TraceRay pops them (c1 first)
-    std::vector<uint32_t> rank_of_input;
-    std::vector<float4> ref_spheres;                          // (centre, radius) (c0, c1, first rank of c0's triangles, pop order)
-    reference_ranks(s->groups, s->group_count, s->spheres, s->sphere_group, s->sphere_count, n_tris, rank_of_input, ref_spheres);
+    // ---- every array and what describes it, on the host (the shadow trees are built and checked in there)
+    PackedScene packed;
+    if ((rc = pack_scene(s, verts, std::move(bvh), how, &packed, &ctx->error))) return rc;
+    packed.desc.info.bvh_build_ms = build_ms;
 
-    // ---- device records in BVH leaf order
-    const uint32_t n_rec = n_tris + 1;                              // + the all-zero dummy triangle empty BVH slots point at
-    std::vector<float4> tris((size_t)n_rec * 3, make_float4(0, 0, 0, 0)), shade((size_t)n_rec * 4, make_float4(0, 0, 0, 0));
-    std::vector<unsigned int> rank(n_rec, 0);
-    std::vector<float4> tri_uv(textured ? (size_t)n_rec * 2 : 0, make_float4(0, 0, 0, 0));
-    std::vector<float4> tri_tan(bumped ? (size_t)n_rec * 3 : 0, make_float4(0, 0, 0, 0));
-    float abs_max = 0.0f;
-    // input triangle t's 48-byte record at `slot` of the record array; returns n
-    auto put_tri_record = [&](uint32_t t, size_t slot) {
-        return tri_record(ld3(&verts[(size_t)t * 9]), ld3(&verts[(size_t)t * 9 + 3]), ld3(&verts[(size_t)t * 9 + 6]), &tris[slot * 3]);
-    };
-    std::vector<float> rec_normals((size_t)n_tris * 3);          // per INPUT triangle: n as its record holds it (the shadow trees classify by it)
-    for (uint32_t slot = 0; slot < n_tris; ++slot) {
-        const uint32_t t = bvh.tri_order[slot];
-        const f3 n = put_tri_record(t, slot);
-        { const float4 stored = tris[(size_t)slot * 3 + 2]; rec_normals[(size_t)t * 3] = stored.y; rec_normals[(size_t)t * 3 + 1] = stored.z; rec_normals[(size_t)t * 3 + 2] = stored.w; }
-        const float * n0 = s->normals + 3 * (size_t)s->idx_normals[3 * t + 0];
-        const float * n1 = s->normals + 3 * (size_t)s->idx_normals[3 * t + 1];
-        const float * n2 = s->normals + 3 * (size_t)s->idx_normals[3 * t + 2];
-        const float * u0 = s->texcoords + 2 * (size_t)s->idx_texcoords[3 * t + 0];
-        const float * u1 = s->texcoords + 2 * (size_t)s->idx_texcoords[3 * t + 1];
-        const float * u2 = s->texcoords + 2 * (size_t)s->idx_texcoords[3 * t + 2];
-        float mbits;
-        int32_t mi = tri_material[t];
-        memcpy(&mbits, &mi, 4);
-        shade[(size_t)slot * 4 + 0] = make_float4(n0[0], n0[1], n0[2], n1[0]);
-        shade[(size_t)slot * 4 + 1] = make_float4(n1[1], n1[2], n2[0], n2[1]);
-        // the geometric normal n = Cross(ab, ac) rides in the shading record too, so a shaded hit costs ONE 64 B
-        // gather instead of two; texture coordinates and tangents have their own arrays, only for textured scenes
-        shade[(size_t)slot * 4 + 2] = make_float4(n2[2], n.x, n.y, n.z);
-        shade[(size_t)slot * 4 + 3] = make_float4(0.0f, 0.0f, 0.0f, mbits);
-        if (textured) tex_pack_uv(u0, u1, u2, &tri_uv[(size_t)slot * 2]);              // tex_upload.h
-        if (bumped) {                                             // mesh->tangents[idx_normals[...]], raytracer.cpp:470-473
-            const float * g0 = s->tangents + 3 * (size_t)s->idx_normals[3 * t + 0];
-            const float * g1 = s->tangents + 3 * (size_t)s->idx_normals[3 * t + 1];
-            const float * g2 = s->tangents + 3 * (size_t)s->idx_normals[3 * t + 2];
-            tex_pack_tangents(g0, g1, g2, &tri_tan[(size_t)slot * 3]);
-        }
-        rank[slot] = rank_of_input[t];
-        for (int k = 0; k < 9; ++k) abs_max = std::max(abs_max, fabsf(verts[(size_t)t * 9 + k]));
-    }
-
-    std::vector<DevMaterial> mats(s->material_count);
-    ctx->material_ns.resize(s->material_count);
-    ctx->any_translucent = false;
-    for (uint32_t m = 0; m < s->material_count; ++m) {
-        const prt_material & pm = s->materials[m];
-        DevMaterial & d = mats[m];
-        memset(&d, 0, sizeof(d));
-        for (int k = 0; k < 3; ++k) { d.ambient[k] = pm.ambient_color[k]; d.diffuse[k] = pm.diffuse_color[k]; d.specular[k] = pm.specular_color[k]; }
-        d.specular_intensity = pm.specular_intensity;
-        d.index_of_refraction = pm.index_of_refraction;
-        d.alpha = pm.alpha;
-        tex_pack_material_slots(pm, d);
-        ctx->material_ns[m] = pm.specular_intensity;
-        if (!(pm.alpha >= 1.0f)) ctx->any_translucent = true;      // alpha < 1 (or NaN): continuation rays, unbounded draws
-    }
-    // textures: RGBA8 by GetTexel's channel rules (texture.cpp:27-41) + the 256 values Color_SRGBToLinear can take
-    std::vector<DevTexture> dev_tex;
-    std::vector<unsigned int> texel_pool;
-    std::vector<float> lut;
-    if (textured) {                                                // tex_upload.h
-        if (!tex_expand_rgba8(s->textures, s->texture_count, dev_tex, texel_pool)) { ctx->error = "prt_upload_scene: more than 2^32 texels"; return -1; }
-        tex_fill_srgb_lut(lut);
-    }
-    ctx->kat_textures = dev_tex;
-    const uint32_t light_stride = std::max(1u, s->light_count);
-    std::vector<DevLight> lights(2 * (size_t)light_stride);       // [0, stride): shadow-tree roots in pad; [stride, 2 stride): every root 0
-    memset(lights.data(), 0, lights.size() * sizeof(DevLight));
-    for (uint32_t l = 0; l < s->light_count; ++l) {
-        const prt_light & pl = s->lights[l];
-        DevLight & d = lights[l];
-        d.type = pl.type;
-        for (int k = 0; k < 3; ++k) { d.color[k] = pl.color[k]; d.position[k] = pl.position[k]; d.facing[k] = pl.facing[k]; }
-        d.falloff = pl.falloff;
-    }
-    ctx->point_lights = false;
-    for (uint32_t l = 0; l < s->light_count; ++l) ctx->point_lights = ctx->point_lights || s->lights[l].type == PRT_LIGHT_POINT;
-    std::vector<float4> ddirs(1024);
-    for (uint32_t i = 0; i < 1024; ++i) ddirs[i] = diffuse_tangent_dir(i);
-
-    // ---- shadow trees (include/prt.h, bvh_build.h): behind the scene's nodes and records, links rebased
-    std::vector<uint32_t> node_words(bvh.nodes);
-    uint32_t all_nodes = bvh.node_count, all_recs = n_rec;
-    // (the context learns of all this only once every tree is built and checked: a failed upload leaves it describing nothing new)
-    unsigned int stack_bound = bvh.stack_bound;
-    std::vector<prt_shadow_tree_info> shadow_info(s->light_count, prt_shadow_tree_info());
-    // origins the bound covers: a shadow ray starts at (hit + n * bias) + d * bias; the hit is taken to lie within 16 extents of
-    // the origin for a camera within 4 and a bias of at most one extent; render_pixels_once holds a call to that
-    const double shadow_origin_max = 32.0 * (double)abs_max;
-    uint32_t shadow_trees = 0;
-    // open triangles (bvh_build.h): for the same lights, whatever the size rule says about a tree; bit l of the first spare
-    // word of a triangle's shading record, the integer's bits in the float
-    std::vector<prt_shadow_open_info> open_info(s->light_count, prt_shadow_open_info());
-    const ShadowOpenBounds open_bounds = shadow_open_bounds((double)abs_max);
-    std::vector<uint32_t> open_mask;                             // per INPUT triangle
-    bool any_open = false;
-    std::vector<std::vector<uint32_t>> occluder_ids(std::min<uint32_t>(s->light_count, (uint32_t)PRT_MAX_SHADOW_TREES));   // one pass over the normals per light: the tree loop below takes the list
-    for (uint32_t l = 0; l < s->light_count && l < (uint32_t)PRT_MAX_SHADOW_TREES && abs_max > 0.0f; ++l) {
-        if (s->lights[l].type != 0) continue;
-        const auto to = std::chrono::steady_clock::now();
-        const float dir[3] = { lights[l].facing[0] * -1.0f, lights[l].facing[1] * -1.0f, lights[l].facing[2] * -1.0f };   // as the kernels form it
-        std::vector<uint32_t> & ids = occluder_ids[l];
-        shadow_occluders(rec_normals.data(), n_tris, dir, shadow_origin_max, &ids);
-        std::vector<uint8_t> open;
-        prt_shadow_open_info & oi = open_info[l];
-        oi.bias_max = (float)open_bounds.bias_max; oi.reach = (float)open_bounds.reach;
-        oi.open_count = shadow_open_flags(verts.data(), rec_normals.data(), n_tris, dir, ids, open_bounds, std::min(hw, 16u), &open);
-        if (oi.open_count) {
-            if (open_mask.empty()) open_mask.assign(n_tris, 0u);
-            for (uint32_t t = 0; t < n_tris; ++t) open_mask[t] |= (uint32_t)open[t] << l;
-            any_open = true;
-        }
-        oi.classified = 1;
-        oi.active = oi.open_count ? 1u : 0u;
-        oi.classify_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - to).count();
-    }
-    if (any_open)
-        for (uint32_t slot = 0; slot < n_tris; ++slot) memcpy(&shade[(size_t)slot * 4 + 3].x, &open_mask[bvh.tri_order[slot]], 4);
-    for (uint32_t l = 0; l < s->light_count && abs_max > 0.0f; ++l) {
-        if (s->lights[l].type != 0 || shadow_trees >= (uint32_t)PRT_MAX_SHADOW_TREES) continue;
-        prt_shadow_tree_info & si = shadow_info[l];
-        const auto ts = std::chrono::steady_clock::now();
-        const float dir[3] = { lights[l].facing[0] * -1.0f, lights[l].facing[1] * -1.0f, lights[l].facing[2] * -1.0f };   // as the kernels form it
-        ShadowTreeBuild sb;
-        sb.width = BVH_WIDTH; sb.leaf_max = leaf_max; sb.threads = std::min(hw, 16u); sb.trav_cost = trav_cost; sb.opt = &ctx->opt.bvh;
-        sb.ratio_percent = (uint32_t)std::max(0ll, std::min(100ll, ctx->opt.shadow_tree_ratio));
-        ShadowTreeResult sr;
-        std::vector<uint32_t> rec_tri;
-        BvhWide sub;
-        const char * bad = append_shadow_tree(sb, verts.data(), rec_normals.data(), n_tris, dir, shadow_origin_max, &node_words, all_nodes, all_recs, &rec_tri, &sr, &sub,
-                                              l < occluder_ids.size() ? &occluder_ids[l] : nullptr);
-        if (!bad && sr.built) bad = validate_bvh_links(sub, sr.triangle_count);
-        if (bad) { ctx->error = std::string("prt_upload_scene: the builder produced a broken shadow tree - ") + bad; return -9; }
-        si.triangle_count = sr.triangle_count;
-        si.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ts).count();
-        if (!sr.built) continue;
-        tris.resize(((size_t)all_recs + rec_tri.size()) * 3, make_float4(0, 0, 0, 0));
-        for (size_t i = 0; i < rec_tri.size(); ++i)
-            if (rec_tri[i] != 0xFFFFFFFFu) put_tri_record(rec_tri[i], (size_t)all_recs + i);         // (the tree's own dummy record stays all-zero)
-        si.built = si.active = 1;
-        si.node_count = sr.node_count;
-        si.root = sr.root;
-        si.stack_bound = sr.stack_bound;
-        si.device_bytes = (uint64_t)sr.node_count * BVH_NODE_BYTES + (uint64_t)rec_tri.size() * 48u;
-        const int root = (int)sr.root;
-        memcpy(&lights[l].pad, &root, 4);
-        all_nodes += sr.node_count;
-        all_recs += (uint32_t)rec_tri.size();
-        stack_bound = std::max(stack_bound, sr.stack_bound);
-        shadow_trees++;
-    }
-    for (uint32_t l = 0; l < light_stride; ++l) { lights[light_stride + l] = lights[l]; lights[light_stride + l].pad = 0.0f; }
-
-    std::vector<float4> nodes4(node_words.size() / 4);
-    memcpy(nodes4.data(), node_words.data(), node_words.size() * sizeof(uint32_t));
-
-    HIP_TRY(ctx, ctx->nodes.upload(nodes4));
-    HIP_TRY(ctx, ctx->tris.upload(tris));
-    HIP_TRY(ctx, ctx->shade.upload(shade));
-    HIP_TRY(ctx, ctx->tri_rank.upload(rank));
-    HIP_TRY(ctx, ctx->materials.upload(mats));
-    HIP_TRY(ctx, ctx->lights.upload(lights));
-    HIP_TRY(ctx, ctx->diffuse_dirs.upload(ddirs));
-    if (!ref_spheres.empty()) HIP_TRY(ctx, ctx->ref_spheres.upload(ref_spheres));
-    ctx->textured = textured;
-    if (textured) {
-        HIP_TRY(ctx, ctx->textures.upload(dev_tex));
-        HIP_TRY(ctx, ctx->texels.upload(texel_pool));
-        HIP_TRY(ctx, ctx->srgb_lut.upload(lut));
-        HIP_TRY(ctx, ctx->tri_uv.upload(tri_uv));
-        if (bumped) HIP_TRY(ctx, ctx->tri_tan.upload(tri_tan));
-    }
-
+    // ---- onto the device
+    HIP_TRY(ctx, ctx->arrays.upload(packed));
     DevScene & sc = ctx->scene;
-    sc.nodes = ctx->nodes.p;
-    sc.tris = ctx->tris.p;
-    sc.shade = ctx->shade.p;
-    sc.tri_rank = ctx->tri_rank.p;
-    sc.materials = ctx->materials.p;
-    sc.lights = ctx->lights.p;
-    sc.diffuse_dirs = ctx->diffuse_dirs.p;
-    sc.light_count = s->light_count;
-    sc.material_count = s->material_count;
+    ctx->arrays.point(sc, packed.desc.textured, packed.keep.bumped, !packed.ref_spheres.empty());
+    sc.light_count = packed.light_count;
+    sc.material_count = packed.material_count;
     sc.tri_count = n_tris;
-    sc.node_count = bvh.node_count;
-    sc.textures = textured ? ctx->textures.p : nullptr;
-    sc.texels = textured ? ctx->texels.p : nullptr;
-    sc.srgb_lut = textured ? ctx->srgb_lut.p : nullptr;
-    sc.tri_uv = textured ? ctx->tri_uv.p : nullptr;
-    sc.tri_tan = bumped ? ctx->tri_tan.p : nullptr;
-    sc.ref_spheres = ref_spheres.empty() ? nullptr : ctx->ref_spheres.p;
+    sc.node_count = packed.desc.info.bvh_node_count;
     sc.tie_widen_max = 8;                                     // render_pixels_once sets the option's value per call
     sc.near_tie_unresolved = &ctx->counters.p->near_tie_unresolved;
-    ctx->spec_table_samples = 0;
-    int rc = build_spec_table(ctx, 1);
-    if (rc) return rc;
-
-    ctx->scene_abs_max = abs_max;
-    // the trees, the two light tables and the bound's limits: only now that all of it lies on the device
-    ctx->stack_bound = stack_bound;
-    ctx->shadow_info.swap(shadow_info);
-    ctx->shadow_bias_max = abs_max;
-    ctx->shadow_cam_max = 4.0f * abs_max;
-    ctx->shadow_open_info.swap(open_info);
-    ctx->shadow_open_bias_max = any_open ? (float)open_bounds.bias_max : 0.0f;       // (both exact in float: powers of two times abs_max)
-    ctx->shadow_open_reach = any_open ? (float)open_bounds.reach : 0.0f;
-    ctx->light_stride = light_stride;
-    ctx->shadow_trees_fresh = true;
-    prt_scene_info & info = ctx->info;
-    info.triangle_count = n_tris;
-    info.bvh_node_count = bvh.node_count;
-    info.bvh_max_depth = bvh.max_depth;
-    info.bvh_node_bytes = BVH_NODE_BYTES;
-    info.tri_record_bytes = 48;
-    info.shade_record_bytes = 64;
-    info.device_bytes = ctx->nodes.bytes() + ctx->tris.bytes() + ctx->shade.bytes() + ctx->tri_rank.bytes() +
-                        ctx->materials.bytes() + ctx->lights.bytes() + ctx->diffuse_dirs.bytes() + ctx->spec_dirs.bytes() +
-                        (textured ? ctx->textures.bytes() + ctx->texels.bytes() + ctx->srgb_lut.bytes() + ctx->tri_uv.bytes() : 0) +
-                        (bumped ? ctx->tri_tan.bytes() : 0) + (ref_spheres.empty() ? 0 : ctx->ref_spheres.bytes());
-    info.bvh_build_ms = build_ms;
-    ctx->q_tri_order.swap(bvh.tri_order);
-    ctx->q_groups.assign(s->groups, s->groups + s->group_count);
-    // what a later prt_update_geometry needs (host memory only)
-    ctx->rf_idx_positions.assign(s->idx_positions, s->idx_positions + s->index_count);
-    ctx->rf_idx_normals.assign(s->idx_normals, s->idx_normals + s->index_count);
-    ctx->rf_position_count = s->position_count;
-    ctx->rf_normal_count = s->normal_count;
-    ctx->rf_bumped = bumped;
-    if (!refit_level_table<BVH_WIDTH>(bvh.nodes.data(), bvh.node_count, &ctx->rf_level_first)) ctx->rf_level_first.clear();
+    if ((rc = build_spec_table(ctx, packed.desc.material_ns, 1))) return rc;
     HIP_TRY(ctx, hipDeviceSynchronize());      // uploads went through the null stream; renders use the context's non-blocking streams
+
+    // ---- the commit: only now does the context describe the new scene
+    ctx->desc = std::move(packed.desc);
+    ctx->keep = std::move(packed.keep);
     ctx->has_scene = true;
     ctx->scene_epoch++;
     ctx->geom_generation++;
@@ -2912,7 +2594,7 @@ int prt_get_scene_info(const prt_ctx * ctx, prt_scene_info * info) {
     PRT_API_TRY
     if (!ctx || !info) return -1;
     if (!ctx->has_scene) return -2;
-    *info = ctx->info;
+    *info = ctx->desc.info;
     return 0;
     PRT_API_CATCH_RC(nullptr, "prt_get_scene_info")
 }
@@ -2921,8 +2603,8 @@ int prt_get_shadow_trees(const prt_ctx * ctx, prt_shadow_tree_info * out, uint32
     PRT_API_TRY
     if (!ctx || (!out && cap)) return -1;
     if (!ctx->has_scene) return -2;
-    for (size_t l = 0; l < ctx->shadow_info.size() && l < cap; ++l) out[l] = ctx->shadow_info[l];
-    return (int)ctx->shadow_info.size();
+    for (size_t l = 0; l < ctx->desc.shadow_info.size() && l < cap; ++l) out[l] = ctx->desc.shadow_info[l];
+    return (int)ctx->desc.shadow_info.size();
     PRT_API_CATCH_RC(nullptr, "prt_get_shadow_trees")
 }
 
@@ -2931,8 +2613,8 @@ int prt_get_shadow_open(const prt_ctx * ctx, prt_shadow_open_info * out, uint32_
     PRT_API_TRY
     if (!ctx) return -1;
     if (!ctx->has_scene) return -2;
-    for (uint32_t l = 0; l < cap && l < ctx->shadow_open_info.size() && out; ++l) out[l] = ctx->shadow_open_info[l];
-    return (int)ctx->shadow_open_info.size();
+    for (uint32_t l = 0; l < cap && l < ctx->desc.shadow_open_info.size() && out; ++l) out[l] = ctx->desc.shadow_open_info[l];
+    return (int)ctx->desc.shadow_open_info.size();
     PRT_API_CATCH_RC(nullptr, "prt_get_shadow_open")
 }
 
@@ -3187,7 +2869,7 @@ int prt_debug_check_refit(prt_ctx * ctx, const prt_scene_desc * s, uint64_t * ou
     if (!s || !out || s->index_count % 3) { ctx->error = "prt_debug_check_refit: null scene or output"; return -1; }
     if (!ctx->has_scene) { ctx->error = "prt_debug_check_refit: upload a scene first"; return -2; }
     const uint32_t n_tris = s->index_count / 3;
-    if (n_tris != ctx->scene.tri_count || ctx->q_tri_order.size() != n_tris) { ctx->error = "prt_debug_check_refit: the scene's triangle count differs from the uploaded scene's"; return -1; }
+    if (n_tris != ctx->scene.tri_count || ctx->keep.tri_order.size() != n_tris) { ctx->error = "prt_debug_check_refit: the scene's triangle count differs from the uploaded scene's"; return -1; }
     for (uint32_t i = 0; i < s->index_count; ++i)
         if (s->idx_positions[i] >= s->position_count) { ctx->error = "prt_debug_check_refit: vertex index out of range"; return -1; }
     std::vector<float> verts((size_t)n_tris * 9);
@@ -3198,11 +2880,11 @@ int prt_debug_check_refit(prt_ctx * ctx, const prt_scene_desc * s, uint64_t * ou
     BvhWide bvh;
     bvh.node_dwords = BVH_WIDTH == 8 ? BVH8_NODE_DWORDS : BVH4_NODE_DWORDS;
     bvh.node_count = ctx->scene.node_count;
-    bvh.max_depth = ctx->info.bvh_max_depth;
-    bvh.stack_bound = ctx->stack_bound;
+    bvh.max_depth = ctx->desc.info.bvh_max_depth;
+    bvh.stack_bound = ctx->desc.stack_bound;
     bvh.nodes.resize((size_t)bvh.node_count * bvh.node_dwords);
-    bvh.tri_order = ctx->q_tri_order;
-    HIP_TRY(ctx, hipMemcpy(bvh.nodes.data(), ctx->nodes.p, bvh.nodes.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    bvh.tri_order = ctx->keep.tri_order;
+    HIP_TRY(ctx, hipMemcpy(bvh.nodes.data(), ctx->arrays.nodes.p, bvh.nodes.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (const char * bad = validate_bvh_links(bvh, n_tris)) { ctx->error = std::string("prt_debug_check_refit: ") + bad; return -9; }
     check_bvh_wide(verts.data(), n_tris, bvh, out);
     return 0;
@@ -3217,10 +2899,10 @@ int prt_debug_device_kat(prt_ctx * ctx, int kind, const void * in, size_t in_byt
     if (!in || !out || !n) { ctx->error = "prt_debug_device_kat: null buffers"; return -1; }
     if (kind == KAT_TEXTURE) {                                  // the kinds that follow indices into the scene: checked here, not on the device
         if (in_bytes != (size_t)n * 12 || out_bytes != (size_t)n * 16) { ctx->error = "prt_debug_device_kat: KAT_TEXTURE takes 3 floats and gives 4 per record"; return -1; }
-        if (!ctx->textured) { ctx->error = "prt_debug_device_kat: KAT_TEXTURE needs a scene with texture maps"; return -2; }
+        if (!ctx->desc.textured) { ctx->error = "prt_debug_device_kat: KAT_TEXTURE needs a scene with texture maps"; return -2; }
         for (uint32_t i = 0; i < n; ++i) {
             const float ti = ((const float *)in)[3 * (size_t)i];
-            if (!(ti >= 0.0f && ti < (float)ctx->kat_textures.size()) || ctx->kat_textures[(size_t)ti].size_x < 2) {
+            if (!(ti >= 0.0f && ti < (float)ctx->desc.kat_textures.size()) || ctx->desc.kat_textures[(size_t)ti].size_x < 2) {
                 ctx->error = "prt_debug_device_kat: KAT_TEXTURE record names no usable texture";
                 return -1;
             }
@@ -3398,23 +3080,12 @@ prt_ctx * clone_context(prt_ctx * src) {
     prt_ctx * c = prt_create(src->device);
     if (!c) return nullptr;
     c->opt = src->opt;
-    c->nodes.borrow(src->nodes); c->tris.borrow(src->tris); c->shade.borrow(src->shade); c->diffuse_dirs.borrow(src->diffuse_dirs);
-    c->tri_rank.borrow(src->tri_rank); c->materials.borrow(src->materials); c->lights.borrow(src->lights);
-    c->textures.borrow(src->textures); c->texels.borrow(src->texels); c->srgb_lut.borrow(src->srgb_lut);
-    c->tri_uv.borrow(src->tri_uv); c->tri_tan.borrow(src->tri_tan); c->ref_spheres.borrow(src->ref_spheres);
+    c->arrays.borrow(src->arrays);
+    c->desc = src->desc;
     c->scene = src->scene;
     c->scene.near_tie_unresolved = &c->counters.p->near_tie_unresolved;      // its own counters
     c->scene.spec_dirs = nullptr;
     c->spec_table_samples = 0;              // its own specular direction table, built at its first render
-    c->material_ns = src->material_ns;
-    c->info = src->info;
-    c->scene_abs_max = src->scene_abs_max;
-    c->any_translucent = src->any_translucent; c->point_lights = src->point_lights; c->textured = src->textured;
-    c->kat_textures = src->kat_textures;
-    c->stack_bound = src->stack_bound;
-    c->light_stride = src->light_stride; c->shadow_info = src->shadow_info; c->shadow_trees_fresh = src->shadow_trees_fresh;
-    c->shadow_bias_max = src->shadow_bias_max; c->shadow_cam_max = src->shadow_cam_max;
-    c->shadow_open_info = src->shadow_open_info; c->shadow_open_bias_max = src->shadow_open_bias_max; c->shadow_open_reach = src->shadow_open_reach;
     c->pool_park_cap = src->pool_park_cap; c->pool_spark_cap = src->pool_spark_cap;
     c->has_scene = src->has_scene;
     c->scene_epoch = 1;
@@ -3440,9 +3111,11 @@ void multi_worker(prt_multi * m, unsigned int f, unsigned int g) {
             prt_ctx * c = L.ctx[g], * c0 = L.ctx[0];
             const size_t rows = prt_shard_rows(L.height, PRT_MULTI_BLOCK_ROWS, g, n);
             const uint32_t max_rows = prt_shard_rows(L.height, PRT_MULTI_BLOCK_ROWS, 0, n);      // rank 0 owns the most rows
-            hipError_t e = hipSetDevice(c->device);
-            if (e == hipSuccess) e = L.shard[g].ensure(std::max<size_t>(1, rows * L.width));
-            if (e != hipSuccess) { rc = PRT_ERR_HIP; err = std::string("shard buffer: ") + hipGetErrorString(e); }
+            hipError_t e = hipSuccess;
+            if (!c || !c0) { rc = PRT_ERR_NO_SCENE; err = "prt_multi worker: the lane has lost a context"; }
+            if (!rc) e = hipSetDevice(c->device);
+            if (!rc && e == hipSuccess) e = L.shard[g].ensure(std::max<size_t>(1, rows * L.width));
+            if (!rc && e != hipSuccess) { rc = PRT_ERR_HIP; err = std::string("shard buffer: ") + hipGetErrorString(e); }
             if (!rc) {
                 rc = prt_render_shard_device(c, &L.cam, &L.params, L.width, L.height, PRT_MULTI_BLOCK_ROWS, g, n, L.shard[g].p, &ctr);
                 if (rc) err = prt_last_error(c);
@@ -3583,7 +3256,11 @@ int prt_multi_upload_scene(prt_multi * m, const prt_scene_desc * scene) {
     for (size_t f = 1; f < m->lane.size(); ++f)
         for (size_t g = 0; g < m->devices.size(); ++g) {
             m->lane[f].ctx[g] = clone_context(m->lane[0].ctx[g]);
-            if (!m->lane[f].ctx[g]) { m->error = std::string("prt_multi_upload_scene: ") + g_create_error; return PRT_ERR_HIP; }
+            if (m->lane[f].ctx[g]) continue;
+            // a lane is whole or absent: prt_multi_submit takes none with a context missing
+            for (size_t k = 0; k < g; ++k) { prt_destroy(m->lane[f].ctx[k]); m->lane[f].ctx[k] = nullptr; }
+            m->error = std::string("prt_multi_upload_scene: ") + g_create_error;
+            return PRT_ERR_HIP;
         }
     return 0;
     PRT_API_CATCH_RC_MULTI(m, "prt_multi_upload_scene")
@@ -3603,18 +3280,15 @@ int prt_multi_update_geometry(prt_multi * m, const prt_geometry_update * update)
         rc = prt_update_geometry(m->lane[0].ctx[g], update, nullptr);
         if (rc) m->error = prt_last_error(m->lane[0].ctx[g]);
     }
-    // ... and the other lanes' contexts share them, with copies of what describes them: those follow (also after a failure:
+    // ... and the other lanes' contexts share them, with a copy of what describes them: it follows (also after a failure:
     // a context that lost its scene takes its clones' with it)
     for (size_t f = 1; f < m->lane.size(); ++f)
         for (size_t g = 0; g < m->devices.size(); ++g) {
             prt_ctx * src = m->lane[0].ctx[g], * c = m->lane[f].ctx[g];
             if (!src || !c) continue;
-            c->ref_spheres.borrow(src->ref_spheres);              // the update may have allocated or enlarged it
+            c->arrays.ref_spheres.borrow(src->arrays.ref_spheres);              // the update may have allocated or enlarged it
             c->scene.ref_spheres = src->scene.ref_spheres;
-            c->scene_abs_max = src->scene_abs_max;
-            c->shadow_trees_fresh = src->shadow_trees_fresh; c->shadow_info = src->shadow_info;
-            c->shadow_open_info = src->shadow_open_info;          // (the bounds are the upload's and came with the clone)
-            c->info = src->info;
+            c->desc = src->desc;
             c->has_scene = src->has_scene;
             c->tuned.clear();
         }
@@ -3639,7 +3313,7 @@ int prt_multi_submit(prt_multi * m, const prt_camera * cam, const prt_params * p
     {
         std::lock_guard<std::mutex> lk(m->mu);
         for (MultiLane & c : m->lane)
-            if (!c.busy && c.ctx[0]) { L = &c; break; }
+            if (!c.busy && std::find(c.ctx.begin(), c.ctx.end(), nullptr) == c.ctx.end()) { L = &c; break; }
         if (!L) { m->error = "prt_multi_submit: every lane has a frame in flight (prt_multi_wait the oldest ticket first)"; return PRT_ERR_IN_FLIGHT; }
         L->busy = true;                      // reserved; the workers start below, when the buffers are there
     }

@@ -1,6 +1,6 @@
 // shadow_open_host_harness.cpp - the open triangles of a directional light (par_raytracer_amd/csrc/bvh_build.h) on the host: the
-// classification prt_upload_scene runs (shadow_occluders, shadow_open_bounds, shadow_open_flags - the very functions it calls)
-// on the scenes of a case file, and a brute-force check of what the flags promise.  It prints one line per fact and
+// classification prt_upload_scene runs (pack_scene of scene_pack.cpp, the very function it calls, read back out of the packed
+// records) on the scenes of a case file, and a brute-force check of what the flags promise.  It prints one line per fact and
 // tests/test_shadow_open_host.py asserts on them:
 //   flags    triangles, occluders, triangles facing the light, open ones, a hash of the flags (equal for both tree widths: the
 //            classification never sees a tree), the bounds
@@ -14,6 +14,7 @@
 //
 // Case file: u32 scenes; per scene a 32-byte name, u32 n_tris, 3 floats d (towards the light, as the kernels form it: facing
 // * -1), 9 n_tris floats.
+#include <algorithm>
 #include <cfloat>
 #include <cstdio>
 #include <cstdlib>
@@ -22,6 +23,7 @@
 #include <vector>
 
 #include "harness_mesh.h"
+#include "harness_desc.h"
 #include "harness_io.h"
 
 using namespace prt;
@@ -31,8 +33,6 @@ enum { WIDTH = 8 };
 #else
 enum { WIDTH = 4 };
 #endif
-
-static float abs_max_of(const std::vector<float> & v) { float m = 0.0f; for (float x : v) m = fmaxf(m, fabsf(x)); return m; }
 
 static std::vector<float> stored_normals(const std::vector<float> & verts) {
     std::vector<float> n(verts.size() / 3);
@@ -58,16 +58,57 @@ static bool occluded(const std::vector<float4> & recs, uint32_t n_tris, f3 pos, 
     return false;
 }
 
+// What prt_upload_scene makes of the triangles under one directional light along d: its host half itself (scene_pack.cpp through
+// tests/harness_desc.h pack_as_upload), read back in input order - the flags out of the shading records' spare word, the normals
+// out of the triangle records, the occluders out of the light's tree (built whatever its size: ratio 100).
+struct Classified {
+    std::vector<uint8_t> open;
+    std::vector<float> normals;
+    std::vector<uint32_t> occ;                                   // ascending
+    uint32_t n_open = 0;
+    double bias_max = 0.0, reach = 0.0, abs_max = 0.0;
+};
+static Classified classify(const std::vector<float> & verts, const float d[3], uint32_t threads) {
+    OwnedScene owned = flat_scene(verts);
+    owned.lights.push_back(light_towards(d));
+    BvhBuildOptions bopt;
+    ScenePackOptions how;
+    how.threads = threads; how.shadow_tree_ratio = 100; how.bvh = &bopt;
+    PackedScene P;
+    std::vector<float> unindexed;
+    std::string error;
+    if (pack_as_upload(owned.desc(), WIDTH, how, &P, &unindexed, &error)) { fprintf(stderr, "shadow_open_host_harness: %s\n", error.c_str()); exit(2); }
+    const uint32_t n = (uint32_t)(verts.size() / 9);
+    Classified c;
+    c.open.assign(n, 0);
+    c.normals.assign((size_t)n * 3, 0.0f);
+    for (uint32_t slot = 0; slot < n; ++slot) {
+        const uint32_t t = P.keep.tri_order[slot];
+        uint32_t mask;
+        memcpy(&mask, &P.shade[(size_t)slot * 4 + 3].x, 4);
+        c.open[t] = (uint8_t)(mask & 1u);
+        const float4 r2 = P.tris[(size_t)slot * 3 + 2];
+        c.normals[(size_t)t * 3] = r2.y; c.normals[(size_t)t * 3 + 1] = r2.z; c.normals[(size_t)t * 3 + 2] = r2.w;
+    }
+    for (uint32_t t : P.shadow_rec_tri)
+        if (t != 0xFFFFFFFFu) c.occ.push_back(t);
+    std::sort(c.occ.begin(), c.occ.end());
+    const prt_shadow_open_info & oi = P.desc.shadow_open_info[0];
+    c.n_open = oi.open_count;
+    c.bias_max = oi.bias_max; c.reach = oi.reach; c.abs_max = P.desc.scene_abs_max;
+    return c;
+}
+
 static void scene(const char * name, const std::vector<float> & verts, const float d[3]) {
     const uint32_t n = (uint32_t)(verts.size() / 9);
-    const float A = abs_max_of(verts);
-    const std::vector<float> normals = stored_normals(verts);
-    std::vector<uint32_t> occ;
-    shadow_occluders(normals.data(), n, d, 32.0 * (double)A, &occ);
-    const ShadowOpenBounds b = shadow_open_bounds((double)A);
-    std::vector<uint8_t> open, open1;
-    const uint32_t n_open = shadow_open_flags(verts.data(), normals.data(), n, d, occ, b, 4, &open);
-    shadow_open_flags(verts.data(), normals.data(), n, d, occ, b, 1, &open1);            // the threads change nothing
+    const Classified c4 = classify(verts, d, 4);
+    const std::vector<uint8_t> open1 = classify(verts, d, 1).open;                       // the threads change nothing
+    const std::vector<uint8_t> & open = c4.open;
+    const std::vector<float> & normals = c4.normals;
+    const std::vector<uint32_t> & occ = c4.occ;
+    const uint32_t n_open = c4.n_open;
+    const float A = (float)c4.abs_max;
+    struct { double bias_max, reach; } b = { c4.bias_max, c4.reach };
     uint64_t hash = 1469598103934665603ull, facing = 0, facing_open = 0;
     for (uint32_t t = 0; t < n; ++t) {
         hash = (hash ^ open[t]) * 1099511628211ull;
@@ -233,13 +274,8 @@ int main(int argc, char ** argv) {
             const uint32_t n = rd<uint32_t>(fin, 1)[0];
             const std::vector<float> d = rd<float>(fin, 3);
             const std::vector<float> verts = rd<float>(fin, (size_t)n * 9);
-            const std::vector<float> normals = stored_normals(verts);
-            std::vector<uint32_t> occ;
-            shadow_occluders(normals.data(), n, d.data(), 32.0 * (double)abs_max_of(verts), &occ);
-            std::vector<uint8_t> open;
-            shadow_open_flags(verts.data(), normals.data(), n, d.data(), occ, shadow_open_bounds((double)abs_max_of(verts)), 2, &open);
             wr(fout, &n, 1);
-            wr(fout, open);
+            wr(fout, classify(verts, d.data(), 2).open);
         }
         fclose(fin);
         fclose(fout);

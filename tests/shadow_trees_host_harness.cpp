@@ -1,6 +1,6 @@
 // shadow_trees_host_harness.cpp - the shadow trees of a directional light (par_raytracer_amd/csrc/bvh_build.h) on the host: the
-// classification, the trees as prt_upload_scene appends them behind the scene's (append_shadow_tree, the very function it
-// calls) and the device traversal (dev_trace*.h through tests/hip_shim, one lane at a time) started at their roots.  It prints
+// classification, the trees as prt_upload_scene appends them behind the scene's (pack_scene of scene_pack.cpp, the very function
+// it calls) and the device traversal (dev_trace*.h through tests/hip_shim, one lane at a time) started at their roots.  It prints
 // one line per fact and tests/test_shadow_trees_host.py asserts on them:
 //   exclusion  no excluded triangle ever has the device's dd = Dot(o - (o + d), n) > 0: random origins, origins on the
 //              surface, origins 4 x outside the bounds, origins at the bound and next to powers of two, for the scene scaled by
@@ -14,13 +14,14 @@
 //              scene with 0, 1 and 2 directional lights and for an empty set (a plane that faces its light)
 //
 //   g++ -O1 -std=c++17 -ffp-contract=off -Itests/hip_shim -Ipar_raytracer_amd/csrc [-DPRT_BVH8] tests/shadow_trees_host_harness.cpp
-//       par_raytracer_amd/csrc/bvh_build.cpp par_raytracer_amd/csrc/bvh_check.cpp -pthread -o /tmp/st && /tmp/st
+//       par_raytracer_amd/csrc/scene_pack.cpp par_raytracer_amd/csrc/bvh_build.cpp par_raytracer_amd/csrc/bvh_check.cpp -pthread -o /tmp/st && /tmp/st
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #include "harness_mesh.h"
+#include "harness_desc.h"
 #include "harness_scene.h"
 
 using namespace prt;
@@ -79,59 +80,44 @@ static f3 origin_for(int k, const float * t, float A, float M, f3 d) {
 
 struct Scene {
     std::vector<float> verts;
-    BvhWide bvh;
-    std::vector<uint32_t> node_words;
-    std::vector<float4> tris;
-    uint32_t n_tris = 0, all_nodes = 0, all_recs = 0, stack_bound = 0;
-    struct Tree { ShadowTreeResult r; uint32_t rec_base; std::vector<uint32_t> rec_tri; f3 d; };
+    PackedScene P;                                               // as prt_upload_scene lays it out (scene_pack.h)
+    uint32_t n_tris = 0, node_count = 0, stack_bound = 0;
+    struct Tree { prt_shadow_tree_info r; uint32_t rec_base; f3 d; };
     std::vector<Tree> trees;
 };
 
-// What prt_upload_scene does: the scene's tree and records, then one tree per light behind them.  Prints the links lines.
+// prt_upload_scene's host half (tests/harness_desc.h pack_as_upload: check, un-index, tree, pack) on the triangles of S under
+// one directional light per direction: the scene's tree and records, then one tree per light behind them.  Prints the links lines.
 static void upload(Scene & S, const char * name, const std::vector<f3> & dirs, uint32_t ratio) {
-    S.n_tris = (uint32_t)(S.verts.size() / 9);
+    OwnedScene owned = flat_scene(S.verts);
+    for (const f3 & dv : dirs) { const float d[3] = { dv.x, dv.y, dv.z }; owned.lights.push_back(light_towards(d)); }
     BvhBuildOptions bopt;
-    build_bvh_wide(WIDTH, S.verts.data(), S.n_tris, 4, 2, &S.bvh, 1.0f, &bopt);
-    S.tris = mesh::records(S.verts, S.n_tris, S.bvh.tri_order.data());
-    S.node_words = S.bvh.nodes;
-    S.all_nodes = S.bvh.node_count;
-    S.all_recs = S.n_tris + 1;
-    S.stack_bound = S.bvh.stack_bound;
-    const float A = abs_max_of(S.verts);
-    printf("links %s width %d lights %zu | scene validate %s\n", name, (int)WIDTH, dirs.size(), validate_bvh_links(S.bvh, S.n_tris) ? "bad" : "null");
-    for (size_t l = 0; l < dirs.size(); ++l) {
+    ScenePackOptions how;
+    how.leaf_max = 4; how.threads = 2; how.sah_trav_cost = 1.0f; how.shadow_tree_ratio = ratio; how.bvh = &bopt;
+    std::string error;
+    std::vector<float> verts;
+    const int rc = pack_as_upload(owned.desc(), WIDTH, how, &S.P, &verts, &error);
+    const char * append = rc ? error.c_str() : "null";           // a broken shadow tree refuses the whole upload
+    S.n_tris = (uint32_t)(S.verts.size() / 9);
+    S.node_count = S.P.desc.info.bvh_node_count;
+    S.stack_bound = S.P.desc.stack_bound;
+    printf("links %s width %d lights %zu | scene validate %s\n", name, (int)WIDTH, dirs.size(), rc || validate_bvh_links(packed_scene_tree(S.P), S.n_tris) ? "bad" : "null");
+    for (size_t l = 0; l < dirs.size() && !rc; ++l) {
         Scene::Tree T;
         T.d = dirs[l];
-        T.rec_base = S.all_recs;
-        ShadowTreeBuild how;
-        how.width = WIDTH; how.threads = 2; how.ratio_percent = ratio; how.opt = &bopt;
-        const float d[3] = { T.d.x, T.d.y, T.d.z };
-        BvhWide sub;
-        const char * bad = append_shadow_tree(how, S.verts.data(), stored_normals(S.verts).data(), S.n_tris, d, 32.0 * A, &S.node_words, S.all_nodes, S.all_recs, &T.rec_tri, &T.r, &sub);
-        if (!bad && T.r.built) bad = validate_bvh_links(sub, T.r.triangle_count);          // as prt_upload_scene does
+        T.r = S.P.desc.shadow_info[l];
+        T.rec_base = 0;
         uint64_t out[6] = { 0, 0, 0, 0, 0, 0 };
         const char * reread = "skipped";
-        if (!bad && T.r.built) {
-            S.tris.resize(((size_t)S.all_recs + T.rec_tri.size()) * 3, make_float4(0, 0, 0, 0));
-            for (size_t i = 0; i < T.rec_tri.size(); ++i)
-                if (T.rec_tri[i] != 0xFFFFFFFFu) put_record(S.tris, (size_t)S.all_recs + i, &S.verts[(size_t)T.rec_tri[i] * 9]);
+        if (T.r.built) {
             // the tree read back out of the shared arrays: moved home again it must pass the checks of a tree of its own
-            const uint32_t m = (uint32_t)T.rec_tri.size() - 1u;
-            BvhWide t;
-            t.node_dwords = S.bvh.node_dwords; t.node_count = T.r.node_count; t.stack_bound = T.r.stack_bound;
-            t.nodes.assign(S.node_words.begin() + (size_t)S.all_nodes * t.node_dwords, S.node_words.end());
-            BvhWide home = t;
-            rebase_bvh_nodes(t, 0u - S.all_nodes, 0u - S.all_recs, home.nodes.data());
-            std::vector<float> own((size_t)m * 9);
-            for (uint32_t i = 0; i < m; ++i) { memcpy(&own[(size_t)i * 9], &S.verts[(size_t)T.rec_tri[i] * 9], 36); home.tri_order.push_back(i); }
-            reread = validate_bvh_links(home, m) ? "bad" : "null";
-            if (m) check_bvh_wide(own.data(), m, home, out);
-            S.all_nodes += T.r.node_count;
-            S.all_recs += (uint32_t)T.rec_tri.size();
-            if (T.r.stack_bound > S.stack_bound) S.stack_bound = T.r.stack_bound;
+            std::vector<float> own;
+            const BvhWide home = packed_shadow_tree_home(S.P, verts, (uint32_t)l, &own, &T.rec_base);
+            reread = validate_bvh_links(home, T.r.triangle_count) ? "bad" : "null";
+            if (T.r.triangle_count) check_bvh_wide(own.data(), T.r.triangle_count, home, out);
         }
         printf("links %s width %d light %zu | built %u occluders %u of %u nodes %u root %u append %s reread %s violations %llu refs %llu\n", name, (int)WIDTH, l,
-               T.r.built, T.r.triangle_count, S.n_tris, T.r.node_count, T.r.root, bad ? bad : "null", reread,
+               T.r.built, T.r.triangle_count, S.n_tris, T.r.node_count, T.r.root, append, reread,
                (unsigned long long)out[0], (unsigned long long)out[5]);
         S.trees.push_back(T);
     }
@@ -140,7 +126,7 @@ static void upload(Scene & S, const char * name, const std::vector<f3> & dirs, u
 // Shadow rays as a render starts them (kernels_wave.h shade_entry_on): from a point of the surface, off along the normal and the
 // light by the bias.  Hit / miss of the light's tree, of the scene's tree and of a loop over every triangle.
 static void brute(const Scene & S, const char * name, int n_rays) {
-    mesh::Walk lane(S.node_words.data(), S.bvh.node_count, S.tris, S.n_tris, S.stack_bound);
+    mesh::Walk lane(S.P.nodes.data(), S.node_count, S.P.tris, S.n_tris, S.stack_bound);
     const DevScene & sc = lane.sc;
     GlobalStack & stk = lane.stk;
     const float A = abs_max_of(S.verts), pad = A * (1.0f / 65536.0f), bias = 1e-3f;
@@ -158,7 +144,7 @@ static void brute(const Scene & S, const char * name, int n_rays) {
             const f3 qp = ob - (ob + T.d);
             bool any = false;
             for (uint32_t s = 0; s < S.n_tris && !any; ++s) {
-                const float4 r0 = S.tris[3 * (size_t)s], r1 = S.tris[3 * (size_t)s + 1], r2 = S.tris[3 * (size_t)s + 2];
+                const float4 r0 = S.P.tris[3 * (size_t)s], r1 = S.P.tris[3 * (size_t)s + 1], r2 = S.P.tris[3 * (size_t)s + 2];
                 float ht, hv, hw;
                 bool near;
                 any = tri_test(ob, T.d, qp, mk3(r0.x, r0.y, r0.z), mk3(r0.w, r1.x, r1.y), mk3(r1.z, r1.w, r2.x), mk3(r2.y, r2.z, r2.w),

@@ -265,7 +265,7 @@ def test_the_flags_against_the_devices_own_occlusion_query(renderer_of, key, tmp
         harness.put(f, ([1], np.uint32))
         f.write(key.encode().ljust(32, b"\0"))
         harness.put(f, ([len(verts)], np.uint32), (direction, np.float32), (verts, np.float32))
-    exe = harness.build("shadow_open_host_harness.cpp", tmp_path, "so_flags", sources=("bvh_build.cpp",), flags=("-O2",))
+    exe = harness.build("shadow_open_host_harness.cpp", tmp_path, "so_flags", sources=("scene_pack.cpp", "bvh_build.cpp", "bvh_check.cpp"), flags=("-O2",))
     harness.run(exe, "flags", cases, results)
     rd = harness.Reader.of_file(results)
     (n,) = rd.unpack("<I")

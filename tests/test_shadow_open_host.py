@@ -47,7 +47,7 @@ def lines(tmp_path_factory):
             harness.put(f, ([len(verts)], np.uint32), (direction, np.float32), (verts, np.float32))
     out = {}
     for width in WIDTHS:
-        exe = harness.build("shadow_open_host_harness.cpp", d, "so%d" % width, bvh8=width == 8, sources=("bvh_build.cpp",), flags=("-O2",))
+        exe = harness.build("shadow_open_host_harness.cpp", d, "so%d" % width, bvh8=width == 8, sources=("scene_pack.cpp", "bvh_build.cpp", "bvh_check.cpp"), flags=("-O2",))
         out[width] = harness.run(exe, cases, timeout=300).splitlines()
     print("\n".join(ln for ln in out[4] if ln.startswith(("flags", "brute"))))          # the recorded shares (pytest -s shows them)
     return out

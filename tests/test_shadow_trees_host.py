@@ -1,7 +1,7 @@
 """Shadow trees on the host (par_raytracer_amd/csrc/bvh_build.h, include/prt.h "Shadow trees"): the classification of the
 triangles a directional light's shadow rays can hit, and the trees prt_upload_scene appends behind the scene's for them.
-tests/shadow_trees_host_harness.cpp - g++, bvh_build.cpp + bvh_check.cpp + the device traversal through tests/hip_shim, both
-tree widths - calls the function the upload calls (append_shadow_tree) and prints one line per fact; the assertions are here.
+tests/shadow_trees_host_harness.cpp - g++, scene_pack.cpp + bvh_build.cpp + bvh_check.cpp + the device traversal through
+tests/hip_shim, both tree widths - calls the function the upload calls (pack_scene) and prints one line per fact; the assertions are here.
 
 The exclusion property is the one the images rest on: a triangle may be left out only if the device's own expression
 dd = Dot(o - (o + d), n) is <= 0 for every origin a render can produce.  The bound is derived in DESIGN.md section 2; nothing
@@ -25,7 +25,7 @@ def lines(tmp_path_factory):
     out = {}
     for width in WIDTHS:
         exe = harness.build("shadow_trees_host_harness.cpp", tmp_path_factory.mktemp("shadow_trees"), "st%d" % width, bvh8=width == 8,
-                            sources=("bvh_build.cpp", "bvh_check.cpp"))
+                            sources=("scene_pack.cpp", "bvh_build.cpp", "bvh_check.cpp"))
         out[width] = harness.run(exe, timeout=120).splitlines()
     return out
 
