@@ -848,6 +848,24 @@ typedef struct prt_shadow_open_info {
 } prt_shadow_open_info;
 int prt_get_shadow_open(const prt_ctx * ctx, prt_shadow_open_info * out, uint32_t cap);
 
+/* Normal cones.  The triangle test is single-sided, so a closest-hit ray can only hit triangles whose normal faces it.
+ * prt_upload_scene gives every node of the scene's 4-wide tree (not the lights' occluder trees, not the 8-wide build) a cone
+ * that bounds the record normals of all triangles below it, in the 3 x 23 mantissa bits of the node's three power-of-two grid
+ * steps; a camera, bounce or point-light shadow ray whose direction faces away from the whole cone does not descend.  Images,
+ * ray_count and shaded_hits are the same bits either way; tri_tests and the work behind node_visits fall (a culled step still
+ * counts as a node visit; prt_render_stats.cone_culled_nodes counts them).  Option NORMAL_CONES (default 1) is read AT UPLOAD:
+ * with 0 no bits are written.  A render call leaves the cones alone when its |ray_bias| or camera lies outside the shadow
+ * trees' guard, and prt_render_rays always does (its rays travel along the caller's directions, which need not be unit
+ * length).  The batched queries never take them.
+ * AFTER prt_update_geometry a 4-wide scene has no cones: the refit writes every node's grid steps afresh, mantissas zero, so
+ * nothing is ever stale; recomputing cones on the device is left to a later change.  The next prt_upload_scene attaches them again. */
+typedef struct prt_normal_cone_info {
+    uint32_t coned_nodes;          /* nodes of the scene's tree that carried a cone when it was uploaded */
+    uint32_t reserved;
+    double attach_ms;              /* host time of attaching them, beside prt_scene_info.bvh_build_ms */
+} prt_normal_cone_info;
+int prt_get_normal_cones(const prt_ctx * ctx, prt_normal_cone_info * out);
+
 /* Diagnostics of the context's last render call made with PRT_FLAG_COUNT_VISITS (bench.py's roofline block):
  * wave-level step counts - lane utilisation of a loop = lane-level count / (64 x wave-level count) -, where the waves of the
  * pool pipeline spent their time, and how many rays took the slow path (near-tied hits, include/prt.h "Determinism"). */
@@ -869,6 +887,9 @@ typedef struct prt_render_stats {
                                                 * a caller compiled against a header without it must be recompiled, or
                                                 * prt_get_render_stats writes 8 bytes past its struct; prt_get_shadow_open is
                                                 * the symbol whose presence tells the two libraries apart */
+    uint64_t cone_culled_nodes;                /* lane-level node steps that a normal cone culled ("Normal cones" above; they are in
+                                                * node_visits); 0 with NORMAL_CONES=0.  Appended like open_shadow_rays, without a new
+                                                * PRT_ABI_VERSION: prt_get_normal_cones is the symbol that tells the libraries apart */
 } prt_render_stats;
 int prt_get_render_stats(const prt_ctx * ctx, prt_render_stats * stats);
 
@@ -920,6 +941,9 @@ int prt_debug_check_bvh(const prt_scene_desc * scene, uint64_t * out);
 /* The same check on the tree of the GPU LBVH builder (option BVH_BUILDER=lbvh at upload: radix tree built on the
  * device, bvh_lbvh.h; an alternative for scenes that change every frame - ~10x faster to build, slower to traverse). */
 int prt_debug_check_bvh_lbvh(prt_ctx * ctx, const prt_scene_desc * scene, uint64_t * out);
+/* Host only: the same tree with its normal cones attached as an upload attaches them; out[0] = (coned node, triangle below it)
+ * pairs whose record normal the stored bits do not cover (0 for a sound tree), out[1] = nodes with a cone. */
+int prt_debug_check_cones(const prt_scene_desc * scene, uint64_t * out);
 /* The radix tree of that builder as the device made it, before the host back end (GPU test-suite: compared element by
  * element, with ==, against a host construction).  verts9: n_tris x 9 floats, the un-indexed corners; the scene bounds are
  * taken from them exactly as an upload takes them.  Every output is caller-allocated and may be NULL (then it is not

@@ -255,6 +255,12 @@ class Renderer:
         self._check(min(0, self._lib.prt_get_shadow_open(self._ctx, out, n)), "prt_get_shadow_open")
         return [out[i] for i in range(n)]
 
+    def normal_cones(self) -> dict:
+        """The scene's normal cones (include/prt.h "Normal cones"): nodes that carried one at upload, and the host time of attaching them."""
+        out = capi.PrtNormalConeInfo()
+        self._check(self._lib.prt_get_normal_cones(self._ctx, C.byref(out)), "prt_get_normal_cones")
+        return out.as_dict()
+
     def render_stats(self) -> "capi.PrtRenderStats":
         """Diagnostics of the last render made with FLAG_COUNT_VISITS (lane utilisation, phase times, parked rays)."""
         st = capi.PrtRenderStats()

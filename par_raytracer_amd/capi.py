@@ -112,7 +112,14 @@ class PrtRenderStats(C.Structure):
                 ("wave_tri_steps", C.c_uint64), ("wave_leaf_visits", C.c_uint64), ("wave_refills", C.c_uint64),
                 ("deepest_stack", C.c_uint64), ("phase_cycles", C.c_uint64 * 5), ("parked_rays", C.c_uint64),
                 ("parked_shadow_rays", C.c_uint64), ("elided_shadow_rays", C.c_uint64), ("variance_close_calls", C.c_uint64), ("stack_lds_entries", C.c_uint32), ("stack_bound", C.c_uint32),
-                ("open_shadow_rays", C.c_uint64)]
+                ("open_shadow_rays", C.c_uint64), ("cone_culled_nodes", C.c_uint64)]
+
+
+class PrtNormalConeInfo(C.Structure):
+    _fields_ = [("coned_nodes", C.c_uint32), ("reserved", C.c_uint32), ("attach_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class PrtRayBatch(C.Structure):
@@ -216,7 +223,7 @@ BUILD_EXPERIMENTAL, BUILD_BVH4 = 1, 2
 
 # Every symbol include/prt.h declares; tests/test_capi_symbols.py checks the library exports them all.
 PRT_SYMBOLS = ["prt_create", "prt_destroy", "prt_last_error", "prt_abi_version", "prt_set_option", "prt_build_flags", "prt_upload_scene", "prt_render",
-               "prt_render_device", "prt_shard_rows", "prt_render_shard_device", "prt_render_shard", "prt_render_pixel_list", "prt_get_scene_info", "prt_get_shadow_trees", "prt_get_shadow_open", "prt_get_render_stats", "prt_debug_check_bvh", "prt_debug_check_bvh_lbvh", "prt_debug_lbvh_tree", "prt_debug_device_kat",
+               "prt_render_device", "prt_shard_rows", "prt_render_shard_device", "prt_render_shard", "prt_render_pixel_list", "prt_get_scene_info", "prt_get_shadow_trees", "prt_get_shadow_open", "prt_get_normal_cones", "prt_get_render_stats", "prt_debug_check_bvh", "prt_debug_check_cones", "prt_debug_check_bvh_lbvh", "prt_debug_lbvh_tree", "prt_debug_device_kat",
                "prt_multi_create", "prt_multi_destroy", "prt_multi_last_error", "prt_multi_device_count", "prt_multi_context",
                "prt_multi_upload_scene", "prt_multi_render", "prt_multi_depth", "prt_multi_submit", "prt_multi_wait", "prt_debug_throw",
                "prt_trace_rays", "prt_trace_rays_device", "prt_get_region_stats",
@@ -291,6 +298,9 @@ def hip_lib() -> C.CDLL:
             lib.prt_get_shadow_open.argtypes = [C.c_void_p, C.POINTER(PrtShadowOpenInfo), C.c_uint32]
         if hasattr(lib, "prt_get_region_stats"):       # (absent from a PRT_HIP_LIB build of an earlier commit, in an A/B run against it)
             lib.prt_get_region_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32]
+        if hasattr(lib, "prt_get_normal_cones"):       # (absent from a PRT_HIP_LIB build of an earlier commit)
+            lib.prt_get_normal_cones.argtypes = [C.c_void_p, C.POINTER(PrtNormalConeInfo)]
+            lib.prt_debug_check_cones.argtypes = [C.POINTER(PrtSceneDesc), C.POINTER(C.c_uint64)]
         lib.prt_debug_check_bvh.argtypes = [C.POINTER(PrtSceneDesc), C.POINTER(C.c_uint64)]
         lib.prt_debug_check_bvh_lbvh.argtypes = [C.c_void_p, C.POINTER(PrtSceneDesc), C.POINTER(C.c_uint64)]
         if hasattr(lib, "prt_debug_lbvh_tree"):        # (absent from a PRT_HIP_LIB build of an earlier commit)

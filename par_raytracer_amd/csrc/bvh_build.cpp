@@ -2,6 +2,7 @@
 // tree built elsewhere, collapsed to 4 or 8 children per node and quantised (one back end, finish_wide).
 #include "bvh_build.h"
 #include "prt_options.h"
+#include "dev_scene.h"
 
 #include <algorithm>
 #include <atomic>
@@ -575,15 +576,23 @@ void build_bvh_wide(int width, const float * verts, uint32_t n_tris, uint32_t le
 // cost 2^-52 D N1) and the margin is raised by 2^-20 of itself for its own rounding.  N1 and D are kept inside ranges where
 // no product of the float expression can overflow, and where an underflow (or a flushed subnormal, 2^-126 a term) is far
 // below the margin: N1 in [2^-60, 2^60], D in [2^-20, 2^20], M <= 2^60.
+// The part of that margin that does not depend on the normal, for directions with max |d_k| = D and origins within M:
+// E + 4 u (D + E) + 2^-52 D x 4; *E_out gets E.  shadow_tri_excluded and the normal cones (below) both multiply it by N1.
+static double dd_margin(double D, double origin_max, double * E_out = nullptr) {
+    const double u = 5.9604644775390625e-8;
+    const double E = u * (origin_max + 2.0 * D) * (1.0 + u);
+    if (E_out) *E_out = E;
+    return E + 4.0 * u * (D + E) + D * 8.881784197001252e-16;
+}
+
 bool shadow_tri_excluded(const float n[3], const float d[3], double origin_max) {
-    const double u = 5.9604644775390625e-8, lo60 = 8.673617379884035e-19, hi60 = 1152921504606846976.0;
+    const double lo60 = 8.673617379884035e-19, hi60 = 1152921504606846976.0;
     const double D = std::max(std::max(fabs((double)d[0]), fabs((double)d[1])), fabs((double)d[2]));
     const double N1 = fabs((double)n[0]) + fabs((double)n[1]) + fabs((double)n[2]);
     if (!(N1 >= lo60 && N1 <= hi60)) return false;                         // zero area, tiny, huge or not finite: kept
     if (!(D >= 9.5367431640625e-7 && D <= 1048576.0)) return false;
     if (!(origin_max >= 0.0 && origin_max <= hi60)) return false;
-    const double E = u * (origin_max + 2.0 * D) * (1.0 + u);
-    const double margin = N1 * (E + 4.0 * u * (D + E) + D * 8.881784197001252e-16) * (1.0 + 9.5367431640625e-7);
+    const double margin = N1 * dd_margin(D, origin_max) * (1.0 + 9.5367431640625e-7);
     const double dn = (double)d[0] * (double)n[0] + (double)d[1] * (double)n[1] + (double)d[2] * (double)n[2];
     return dn >= margin;
 }
@@ -592,6 +601,151 @@ void shadow_occluders(const float * normals, uint32_t n_tris, const float d[3], 
     ids->clear();
     for (uint32_t t = 0; t < n_tris; ++t)
         if (!shadow_tri_excluded(normals + 3 * (size_t)t, d, origin_max)) ids->push_back(t);
+}
+
+// ---- normal cones (bvh_build.h).  The stored integers q = (q_x, q_y, q_z), alpha = |q|, a = q / alpha,
+// ONE = CONE_ONE, L = 1 + 2^-20 (the longest direction the library normalises), u = 2^-24.
+//   the predicate   fl(q.d) = fma(q_z, d_z, fma(q_y, d_y, fl(q_x d_x))) >= ONE.  The converts are exact (|q_k| < 2^22); the three
+//       roundings cost at most 4 u alpha |d| together (Cauchy-Schwarz on Sum |q_k d_k|), an underflow 2^-149 a term.  So an
+//       accepted d has q.d >= c := ONE - 4 u alpha L - 1e-30 exactly, i.e. a.d >= c / alpha, and |d| >= c / alpha > 2^-11.
+//   the region      {d : a.d >= c / alpha, |d| <= L} is convex; d.n is linear and takes its minimum at an extreme point: on the
+//       sphere |d| = L, at polar angle 90 deg - beta' from a with sin beta' >= s := c / (alpha L).  For a normal at angle phi from a
+//       the smallest d.n / |n| there is L sin(beta' - phi), increasing in beta' up to 90 deg: the minimum is on the rim,
+//           min d.n = |n| L (s cos phi - sqrt(1 - s^2) sin phi).
+//   the test        dd <= 0 is certain where d.n >= N1 C, C = (E + 4 u (D + E) + 2^-50 D)(1 + 2^-20) with D = L and
+//       E = u (M + 2 L)(1 + u): shadow_tri_excluded's margin for the longest direction (its D >= 2^-20 holds: |d| > 2^-11).
+// A normal is covered when the minimum is at least that, with 1e-9 of it and 1e-13 to spare for the doubles here.
+bool cone_covers_normal(uint32_t d3, uint32_t d14, uint32_t d15, const float n[3], double origin_max) {
+    const double q[3] = { (double)cone_component(d3), (double)cone_component(d14), (double)cone_component(d15) };
+    if (q[0] == 0.0 && q[1] == 0.0 && q[2] == 0.0) return true;
+    const double u = 5.9604644775390625e-8, lo60 = 8.673617379884035e-19, hi60 = 1152921504606846976.0;
+    const double m[3] = { (double)n[0], (double)n[1], (double)n[2] };
+    const double N1 = fabs(m[0]) + fabs(m[1]) + fabs(m[2]);
+    if (N1 == 0.0) return true;                                            // dd = 0: rejected whatever the ray
+    if (!(N1 >= lo60 && N1 <= hi60)) return false;
+    if (!(origin_max >= 0.0 && origin_max <= hi60)) return false;
+    const double L = 1.0 + 9.5367431640625e-7;
+    const double C = dd_margin(L, origin_max) * (1.0 + 9.5367431640625e-7);
+    const double alpha = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]);
+    const double c = (double)CONE_ONE - (4.0 * u * alpha * L + 1e-30);
+    if (!(c > 0.0)) return false;
+    const double s = c / (alpha * L);
+    if (s >= 1.0) return true;                                             // no direction is accepted
+    const double nl = sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]);
+    const double x[3] = { q[1] * m[2] - q[2] * m[1], q[2] * m[0] - q[0] * m[2], q[0] * m[1] - q[1] * m[0] };
+    const double cos_phi = (q[0] * m[0] + q[1] * m[1] + q[2] * m[2]) / (alpha * nl);
+    const double sin_phi = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]) / (alpha * nl);
+    const double least = L * (s * cos_phi - sqrt(1.0 - s * s) * sin_phi);
+    return least >= (N1 / nl) * C * (1.0 + 1e-9) + 1e-13;
+}
+
+uint32_t count_normal_cones(const uint32_t * nodes, uint32_t node_count) {
+    uint32_t n = 0;
+    for (uint32_t i = 0; i < node_count; ++i) {
+        const uint32_t * d = nodes + (size_t)i * BVH4_NODE_DWORDS;
+        if ((d[3] | d[14] | d[15]) & 0x007FFFFFu) ++n;
+    }
+    return n;
+}
+
+uint32_t attach_normal_cones(BvhWide & bvh, const float * normals, uint32_t n_tris, double origin_max, uint32_t threads) {
+    const uint32_t nc = bvh.node_count;
+    if (bvh.node_dwords != BVH4_NODE_DWORDS || nc == 0 || bvh.nodes.size() != (size_t)nc * BVH4_NODE_DWORDS || bvh.tri_order.size() != n_tris || n_tris == 0) return 0;
+    // unit normals in leaf order.  state 0: a zero normal (ignored), 1: usable, 2: not finite, tiny or huge (no cone above it)
+    struct Unit { double v[3]; uint32_t state; };
+    std::vector<Unit> unit(n_tris);
+    for (uint32_t slot = 0; slot < n_tris; ++slot) {
+        Unit & un = unit[slot];
+        un.v[0] = un.v[1] = un.v[2] = 0.0;
+        un.state = 2;
+        const uint32_t t = bvh.tri_order[slot];
+        if (t >= n_tris) continue;
+        const float * n = normals + 3 * (size_t)t;
+        const double N1 = fabs((double)n[0]) + fabs((double)n[1]) + fabs((double)n[2]);
+        if (N1 == 0.0) { un.state = 0; continue; }
+        if (!(N1 >= 8.673617379884035e-19 && N1 <= 1152921504606846976.0)) continue;
+        const double l = sqrt((double)n[0] * n[0] + (double)n[1] * n[1] + (double)n[2] * n[2]);
+        for (int a = 0; a < 3; ++a) un.v[a] = (double)n[a] / l;
+        un.state = 1;
+    }
+    // every node's triangles, bottom up (children follow their parent in breadth-first order): a run of slots, or no cone
+    std::vector<uint32_t> lo(nc, 0xFFFFFFFFu), hi(nc, 0u), cnt(nc, 0u);
+    std::vector<uint8_t> bad(nc, 0);
+    for (uint32_t ni = nc; ni-- > 0;) {
+        const uint32_t * d = &bvh.nodes[(size_t)ni * BVH4_NODE_DWORDS];
+        for (int k = 0; k < 4; ++k) {
+            const int32_t link = (int32_t)d[10 + k];
+            uint32_t f, e, c;
+            if (link >= 0) {
+                const uint32_t ch = (uint32_t)link;
+                if (ch <= ni || ch >= nc || bad[ch]) { bad[ni] = 1; continue; }
+                if (!cnt[ch]) continue;
+                f = lo[ch]; e = hi[ch]; c = cnt[ch];
+            } else {
+                f = (uint32_t)~link >> 2;
+                c = ((uint32_t)~link & 3u) + 1u;
+                if (f >= n_tris) continue;                                  // the dummy record of an empty slot
+                if ((uint64_t)f + c > n_tris) { bad[ni] = 1; continue; }
+                e = f + c;
+            }
+            lo[ni] = std::min(lo[ni], f); hi[ni] = std::max(hi[ni], e); cnt[ni] += c;
+        }
+    }
+    const double first_margin = 1.8 * dd_margin(1.0 + 9.5367431640625e-7, origin_max) + 3.0e-4;     // sqrt(3) C, and the axis' own quantisation (0.87 / alpha rad)
+    std::vector<uint32_t> words((size_t)nc * 3, 0u);
+    auto cone_of = [&](uint32_t ni) -> bool {
+        if (bad[ni] || !cnt[ni] || hi[ni] - lo[ni] != cnt[ni]) return false;
+        double sum[3] = { 0.0, 0.0, 0.0 };
+        uint32_t usable = 0;
+        for (uint32_t s = lo[ni]; s < hi[ni]; ++s) {
+            if (unit[s].state == 2) return false;
+            if (unit[s].state == 1) { for (int a = 0; a < 3; ++a) sum[a] += unit[s].v[a]; ++usable; }
+        }
+        if (!usable) return false;
+        const double len = sqrt(sum[0] * sum[0] + sum[1] * sum[1] + sum[2] * sum[2]);
+        if (!(len > 1e-9 * (double)usable)) return false;
+        const double axis[3] = { sum[0] / len, sum[1] / len, sum[2] / len };
+        double min_cos = 1.0;
+        for (uint32_t s = lo[ni]; s < hi[ni]; ++s) {
+            if (unit[s].state != 1) continue;
+            min_cos = std::min(min_cos, axis[0] * unit[s].v[0] + axis[1] * unit[s].v[1] + axis[2] * unit[s].v[2]);
+            if (!(min_cos > 0.0)) return false;                            // half angle of 90 degrees or more
+        }
+        double denom = sqrt(std::max(0.0, 1.0 - min_cos * min_cos)) + first_margin;
+        for (int it = 0; it < 24; ++it) {
+            denom = std::max(denom, 1.0e-3);                                // |q_k| <= ONE / 1e-3 < 2^22
+            if (denom > 1.0) return false;
+            uint32_t w[3];
+            for (int a = 0; a < 3; ++a) w[a] = (uint32_t)(int32_t)llround(axis[a] * ((double)CONE_ONE / denom)) & 0x007FFFFFu;
+            bool ok = (w[0] | w[1] | w[2]) != 0u;
+            for (uint32_t s = lo[ni]; ok && s < hi[ni]; ++s)
+                if (unit[s].state == 1) ok = cone_covers_normal(w[0], w[1], w[2], normals + 3 * (size_t)bvh.tri_order[s], origin_max);
+            if (ok) { for (int a = 0; a < 3; ++a) words[(size_t)ni * 3 + a] = w[a]; return true; }
+            denom = denom * 1.03 + 1.0e-4;
+        }
+        return false;
+    };
+    // nodes are independent of each other: whichever thread takes a node writes the same words
+    std::atomic<uint32_t> next(0);
+    auto worker = [&]() {
+        for (;;) {
+            const uint32_t base = next.fetch_add(64u);
+            if (base >= nc) break;
+            for (uint32_t ni = base; ni < std::min(nc, base + 64u); ++ni) cone_of(ni);
+        }
+    };
+    const uint32_t nt = std::max(1u, std::min(threads, 64u));
+    std::vector<std::thread> pool;
+    for (uint32_t t = 1; t < nt; ++t) pool.emplace_back(worker);
+    worker();
+    for (std::thread & t : pool) t.join();
+    const int scale_dword[3] = { 3, 14, 15 };
+    for (uint32_t ni = 0; ni < nc; ++ni)
+        for (int a = 0; a < 3; ++a) {
+            uint32_t & d = bvh.nodes[(size_t)ni * BVH4_NODE_DWORDS + scale_dword[a]];
+            d = (d & 0xFF800000u) | words[(size_t)ni * 3 + a];
+        }
+    return count_normal_cones(bvh.nodes.data(), nc);
 }
 
 // ---- open triangles (bvh_build.h).  How far from R a shadow ray can start, for a hit the render takes the flag for.

@@ -137,6 +137,26 @@ bool shadow_open_margins(const float * tri9, const float n[3], const float d[3],
 uint32_t shadow_open_flags(const float * verts, const float * normals, uint32_t n_tris, const float d[3], const std::vector<uint32_t> & occluders,
                            const ShadowOpenBounds & b, uint32_t threads, std::vector<uint8_t> * open);
 
+// ---- normal cones: per node of a 4-wide tree, a cone that bounds the record normals of every triangle below it, in the
+// mantissas of the node's three grid steps (layout and predicate: dev_scene.h cone_faces_away).  A closest-hit ray whose
+// direction the predicate accepts fails dd = Dot(qp, n) <= 0 on all of those triangles and does not descend.
+//
+// cone_covers_normal: what the stored bits (the node's dwords 3, 14, 15) promise about ONE triangle below the node, whose record
+// holds the normal n - the three floats as stored.  True when every direction d, |d| <= 1 + 2^-20, that the predicate AS THE
+// DEVICE EVALUATES IT accepts gives the device's own dd <= 0 for every origin with |o_k| <= origin_max (DESIGN.md section 2
+// has the derivation; the dd part is shadow_tri_excluded's bound).  Also true for all-zero bits (no cone) and for a zero normal
+// (dd is 0: the test rejects it whatever the ray); false for a normal that is not finite, tiny or huge under a node with bits.
+bool cone_covers_normal(uint32_t d3, uint32_t d14, uint32_t d15, const float n[3], double origin_max);
+// Writes the cones of a 4-wide tree (an 8-wide tree is left alone), each from the triangles of its node's own range:
+// axis = the mean of the unit normals, A = axis / (sin(half angle) + margin) quantised, then shrunk until cone_covers_normal
+// holds for every triangle of the range.  No cone (the mantissas stay zero) for a node whose half angle reaches 90 degrees,
+// whose triangles are not one run of leaf-order slots, or with a normal that is not finite, tiny or huge below it.
+// normals: 3 floats per INPUT triangle, the record normals.  The bits do not depend on `threads`.  Returns the nodes with a cone.
+// Not part of build_bvh_wide: a refit reproduces that function's nodes bit for bit, and a refit clears the mantissas.
+uint32_t attach_normal_cones(BvhWide & bvh, const float * normals, uint32_t n_tris, double origin_max, uint32_t threads);
+// Nodes of a 4-wide node array whose mantissas hold a cone.
+uint32_t count_normal_cones(const uint32_t * nodes, uint32_t node_count);
+
 // bvh_check.cpp.  Every address the traversal kernels will form from the tree, checked on the host before the tree is
 // uploaded: a message naming the first node link or triangle range outside the arrays, or NULL.  O(nodes), links only.
 const char * validate_bvh_links(const BvhWide & bvh, uint32_t n_tris);
@@ -145,5 +165,9 @@ const char * validate_bvh_links(const BvhWide & bvh, uint32_t n_tris);
 // referenced by exactly one leaf, and the layout's own invariants hold.  out[0] = violations, out[1] = nodes,
 // out[2] = depth, out[3] = stack bound, out[4] = leaves, out[5] = triangles referenced.
 void check_bvh_wide(const float * verts, uint32_t n_tris, const BvhWide & bvh, uint64_t * out);
+// bvh_check.cpp.  The normal cones of a 4-wide tree: the number of (coned node, triangle below it) pairs that
+// cone_covers_normal refuses, with the record normal computed from the corners as the uploader does.  (Its own function and
+// not a seventh word of check_bvh_wide's output: that function's callers hand it arrays of six.)  *coned_nodes: nodes with a cone.
+uint64_t check_bvh_cones(const float * verts, uint32_t n_tris, const BvhWide & bvh, double origin_max, uint64_t * coned_nodes);
 
 }  // namespace prt

@@ -1,6 +1,7 @@
 // bvh_check.cpp - the host's reading of the two node layouts bvh_build.cpp writes, and the two checks built on it: the
 // O(nodes) link validation that guards every upload, and the full geometric check of the test-suite.  Host only.
 #include "bvh_build.h"
+#include "dev_math.h"
 
 #include <algorithm>
 #include <cmath>
@@ -36,8 +37,9 @@ void decode4(const uint32_t * d, uint32_t n_tris, Node * n) {
     n->n_slots = 4;
     for (int a = 0; a < 3; ++a) {
         memcpy(&n->org[a], &d[a], 4);
-        memcpy(&n->scale[a], &d[scale_dword[a]], 4);
-        if (!power_of_two(d[scale_dword[a]]) || (d[scale_dword[a]] & 0x007FFFFFu)) n->faults++;
+        const uint32_t step = d[scale_dword[a]] & 0xFF800000u;               // the mantissa may hold the node's normal cone (dev_scene.h)
+        memcpy(&n->scale[a], &step, 4);
+        if (!power_of_two(d[scale_dword[a]])) n->faults++;
     }
     uint32_t used = 0;
     while (used < 4 && !(((d[4] >> (8 * used)) & 0xFFu) == 255u && ((d[7] >> (8 * used)) & 0xFFu) == 0u)) ++used;
@@ -189,6 +191,43 @@ void check_bvh_wide(const float * verts, uint32_t n_tris, const BvhWide & bvh, u
     for (uint32_t t = 0; t < n_tris; ++t) if (!seen[t]) violations++;
     if (L && L->nodes_once) for (uint32_t i = 0; i < bvh.node_count; ++i) if (!node_seen[i]) violations++;
     out[0] = violations; out[1] = bvh.node_count; out[2] = bvh.max_depth; out[3] = bvh.stack_bound; out[4] = leaves; out[5] = refs;
+}
+
+// Normal cones (bvh_build.h): every (node with a cone, triangle below it) pair whose record normal - computed from the corners
+// as the uploader computes it, tri_record - the stored bits do not cover.  A walk from the root with the list of coned
+// ancestors: O(triangles x depth).  origin_max as attach_normal_cones got it.
+uint64_t check_bvh_cones(const float * verts, uint32_t n_tris, const BvhWide & bvh, double origin_max, uint64_t * coned_nodes) {
+    uint64_t violations = 0, coned = 0;
+    if (coned_nodes) *coned_nodes = 0;
+    if (bvh.node_dwords != BVH4_NODE_DWORDS || validate_bvh_links(bvh, n_tris)) return 0;
+    struct Item { uint32_t node, depth; };
+    std::vector<Item> stack(1, Item{ 0u, 0u });
+    std::vector<uint32_t> above;                       // the coned nodes on the path to the node being visited
+    std::vector<uint32_t> above_depth;
+    while (!stack.empty()) {
+        const Item it = stack.back();
+        stack.pop_back();
+        while (!above_depth.empty() && above_depth.back() >= it.depth) { above.pop_back(); above_depth.pop_back(); }
+        const uint32_t * d = &bvh.nodes[(size_t)it.node * BVH4_NODE_DWORDS];
+        if ((d[3] | d[14] | d[15]) & 0x007FFFFFu) { above.push_back(it.node); above_depth.push_back(it.depth); ++coned; }
+        for (int k = 0; k < 4; ++k) {
+            const int32_t link = (int32_t)d[10 + k];
+            if (link >= 0) { stack.push_back(Item{ (uint32_t)link, it.depth + 1u }); continue; }
+            const uint32_t first = (uint32_t)~link >> 2, count = ((uint32_t)~link & 3u) + 1u;
+            for (uint32_t i = 0; i < count && first + i < n_tris; ++i) {
+                const float * v = verts + 9 * (size_t)bvh.tri_order[first + i];
+                float4 rec[3];
+                tri_record(mk3(v[0], v[1], v[2]), mk3(v[3], v[4], v[5]), mk3(v[6], v[7], v[8]), rec);
+                const float n[3] = { rec[2].y, rec[2].z, rec[2].w };
+                for (uint32_t a : above) {
+                    const uint32_t * c = &bvh.nodes[(size_t)a * BVH4_NODE_DWORDS];
+                    if (!cone_covers_normal(c[3], c[14], c[15], n, origin_max)) ++violations;
+                }
+            }
+        }
+    }
+    if (coned_nodes) *coned_nodes = coned;
+    return violations;
 }
 
 }  // namespace prt

@@ -168,7 +168,7 @@ PRT_D void point_node_step(const DevScene & sc, TravRay & r, const STK & stk, Tr
     const uint4 * np = reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(sc.nodes) + ((unsigned int)r.node << 6));
     const uint4 w0 = np[0], w1 = np[1], w2 = np[2], w3 = np[3];
     if (COUNT) { st.nodes++; if (first_active_lane()) st.wnodes++; if ((unsigned int)r.sp > st.max_sp) st.max_sp = (unsigned int)r.sp; }
-    const float sx = __uint_as_float(w0.w), sy = __uint_as_float(w3.z), sz = __uint_as_float(w3.w);
+    const float sx = __uint_as_float(node_grid_step(w0.w)), sy = __uint_as_float(node_grid_step(w3.z)), sz = __uint_as_float(node_grid_step(w3.w));      // (the mantissas may hold a normal cone: dev_scene.h)
     const float ex = r.o.x - __uint_as_float(w0.x), ey = r.o.y - __uint_as_float(w0.y), ez = r.o.z - __uint_as_float(w0.z);
     const float lx = -(ex + pad), ly = -(ey + pad), lz = -(ez + pad);
     const float hx = ex - pad, hy = ey - pad, hz = ez - pad;

@@ -15,6 +15,13 @@
 //              One node visit = one 64 B fetch that decides about four subtrees: half the bytes per ray of
 //              an uncompressed binary node with the same fetch size, and half the dependent fetches.
 //              Nodes are numbered breadth-first, so the top of the tree is one contiguous block.
+//              NORMAL CONE.  The three grid steps are powers of two, so the 3 x 23 mantissa bits of d3, d14 and d15 are free:
+//              they hold a vector A = (A.x, A.y, A.z), one signed 23-bit integer per word (two's complement, x in d3, y in
+//              d14, z in d15), in units of 1 / CONE_ONE.  A = axis / (sin(half angle) + margin) for a cone that bounds the
+//              record normals of every triangle below the node; a ray of direction d with A . d >= 1 meets only back faces
+//              there and need not descend (cone_faces_away below; bvh_build.h attach_normal_cones writes the bits, DESIGN.md
+//              section 2 derives the margin).  All zero: no cone.  Every reader of a grid step masks the mantissa off
+//              (node_grid_step); a refit writes the three words afresh and so clears the cone (dev_refit.h).
 //   tris       48 B per triangle = 3 x float4, in BVH leaf order, un-indexed and pre-differenced:
 //                (a.xyz, ab.x) (ab.yz, ac.xy) (ac.z, n.xyz)   with ab = b-a, ac = c-a, n = Cross(ab, ac)
 //              computed on the host with the reference's float expressions (raytracer.cpp:85-91), so the
@@ -39,6 +46,21 @@
 #include "dev_math.h"
 
 namespace prt {
+
+// A 4-wide node's grid step from d3 / d14 / d15: the exponent alone (the mantissa may hold the node's normal cone).
+PRT_HD unsigned int node_grid_step(unsigned int w) { return w & 0x7F800000u; }
+enum { CONE_ONE = 4096, CONE_COMPONENT_MAX = (1 << 22) - 1 };
+// One component of A as the integer it is stored as.
+PRT_HD int cone_component(unsigned int w) { return (int)(w << 9) >> 9; }
+// The one statement of the cull predicate: true when the cone in the mantissas of d3, d14, d15 proves that a ray of direction
+// `dir` (|dir| <= 1 + 2^-20, normalised by the library) fails the single-sided triangle test on every triangle below the node.
+// A . dir >= 1 in the stored units: three exact converts, a product and two fused multiply-adds, whose rounding the builder's
+// margin covers.  False by construction for all-zero words (0 >= 4096), for a NaN anywhere and for a direction of length 0.
+PRT_HD bool cone_faces_away(unsigned int d3, unsigned int d14, unsigned int d15, f3 dir) {
+    const float ax = (float)cone_component(d3), ay = (float)cone_component(d14), az = (float)cone_component(d15);
+    const float s = __builtin_fmaf(az, dir.z, __builtin_fmaf(ay, dir.y, ax * dir.x));
+    return s >= (float)CONE_ONE;
+}
 
 struct DevMaterial {          // 64 B
     float ambient[3];
@@ -161,8 +183,13 @@ struct DevParams {
     // adaptive sampling (main.cpp:245-258): on when max_spp > spp; k_pool<ADAPT> only
     unsigned int max_spp;
     float variance_threshold;
+    // normal cones (the node layout above): 0, or TRACE_NO_CONE - or'ed into the kind of every closest-hit ray of the call: the
+    // option, a call outside the bounds the cones were computed for, or rays along the caller's own directions (prt_render_rays).
+    // It lies in the struct's four bytes of tail padding: no field moves and the size stays (the assertion below).
+    unsigned int no_cones;
 };
 
+static_assert(offsetof(DevParams, no_cones) == 140 && sizeof(DevParams) == 144, "no_cones fills the tail padding");
 static_assert(offsetof(DevParams, open_reach) == 68 && offsetof(DevParams, pixel_list) == 72, "open_reach fills the padding in front of pixel_list");
 
 // Work item (position in the order pixels are handed out, whole call) -> local pixel (position in the call's output).
@@ -219,6 +246,8 @@ struct DevCounters {          // device-side accumulators (atomics, one add per 
     // of elided_shadow_rays: elided by an open-triangle flag (k_pool: COUNT builds only; k_shade: always).  The last word, so
     // that every counter above keeps the offset that kernels which never add to this one have always used
     unsigned long long open_shadow_rays;
+    // lane-level node steps that a normal cone culled (COUNT builds only; they are in node_visits too).  The last word, likewise
+    unsigned long long cone_culled_nodes;
 };
 
 // Per-sample radiance accumulator of the wavefront and pool pipelines: 2^-32 fixed point in 64-bit integers.  A sample's

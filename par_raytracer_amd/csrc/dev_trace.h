@@ -7,8 +7,9 @@
 //   trav_idle(r), trav_init(r, o, d, kind, pad, stk, root = 0)                no ray / a ray at the root of a tree
 //   trav_start<ANY_LENGTH>(r, o, d, kind, pad, stk)                           the same, for directions of any length (below)
 //   trav_walking(r), trav_done(r)                                             wants a node step / ended; neither: holds a leaf
-//   trav_node_step<STK, COUNT>(sc, r, stk, st, pad), trav_leaf<STK, COUNT>(sc, r, stk, st)
+//   trav_node_step<STK, COUNT, CONES = false>(sc, r, stk, st, pad), trav_leaf<STK, COUNT>(sc, r, stk, st)
 //   trav_leaf_range(r, first, count), trav_leaf_next(r, stk)                  the held leaf's triangles, and the step past it
+//   trav_cone_kind(P)                                                         what a call ors into its closest-hit rays' kind
 //   trav_wants_resolve(r, stk), trav_needs_slow_path(r, stk)                  what the marker says after the end
 // Code outside the two traversal files never reads r.node itself.
 #pragma once
@@ -140,13 +141,14 @@ PRT_D HitRec resolve_near_ties(const DevScene & sc, f3 o, f3 d, float pad, float
 // of work), and only then does the wave run the triangle code.  With 64 lanes a fused node-or-leaf loop would execute the (4x
 // longer) leaf body in almost every iteration.  Near ties are decided on the spot: this is the form for the slow paths, on a
 // stack that cannot overflow.  ANY_LENGTH: the queries' form (trav_start).  root: where an any-hit ray starts (a closest-hit
-// ray's near ties are replayed over the scene's tree: it always starts at 0).
-template <class STK, bool COUNT, bool ANY_LENGTH = false>
+// ray's near ties are replayed over the scene's tree: it always starts at 0).  CONES: the walk takes the nodes' normal cones
+// (the render kernels' slow paths; the replay of near ties never does - it only meets triangles the cones leave alone).
+template <class STK, bool COUNT, bool ANY_LENGTH = false, bool CONES = false>
 PRT_D HitRec trace_ray(const DevScene & sc, f3 o, f3 d, int kind, float pad, const STK & stk, TraceStats & st, int root = 0) {
     TravRay r;
     trav_start<ANY_LENGTH>(r, o, d, kind, pad, stk, root);
     for (;;) {
-        while (trav_walking(r)) trav_node_step<STK, COUNT>(sc, r, stk, st, pad);
+        while (trav_walking(r)) trav_node_step<STK, COUNT, CONES>(sc, r, stk, st, pad);
         if (trav_done(r)) break;
         if (trav_leaf<STK, COUNT>(sc, r, stk, st)) return r.best;           // any-hit ray: found its occluder
     }

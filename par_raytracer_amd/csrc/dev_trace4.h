@@ -15,7 +15,7 @@ struct TravRay {
     float pnx, pny, pnz;              // (o +- pad) / direction for the plane the ray ENTERS through on each axis; the plane it
                                       // leaves through is 2 pad |1 / direction| further on (pad always widens the box)
     HitRec best;
-    int node, sp, kind;               // kind: TRACE_CLOSEST / TRACE_ANY
+    int node, sp, kind;               // kind: TRACE_CLOSEST / TRACE_ANY, | TRACE_NO_CONE
 };
 
 
@@ -85,6 +85,9 @@ struct GlobalStack {
     PRT_D void flag(int bit) const { col[0] |= bit; }
 };
 
+// What a render call ors into the kind of its closest-hit rays: TRACE_NO_CONE where the call leaves the cones alone (DevParams::no_cones)
+PRT_D int trav_cone_kind(const DevParams & P) { return (int)P.no_cones; }
+
 // The states of a lane's ray, as the kernels' loops ask for them
 PRT_D void trav_idle(TravRay & r) { r.node = TRAV_SENTINEL; r.sp = 0; r.kind = 0; }          // no ray
 PRT_D bool trav_walking(const TravRay & r) { return r.node >= 0; }                            // wants a node step (else: holds a leaf, or is done)
@@ -94,7 +97,7 @@ PRT_D bool trav_done(const TravRay & r) { return trav_done(r.node); }
 // and a found occluder is final whatever happened before).
 template <class STK> PRT_D int trav_end_flags(const TravRay & r, const STK &) { return trav_done(r.node) ? (r.node & 3) : 0; }
 // the hit of a closest-hit ray has company within a few ulp: the reference's visit order decides (resolve_near_ties)
-template <class STK> PRT_D bool trav_wants_resolve(const TravRay & r, const STK & stk) { return r.kind == TRACE_CLOSEST && (trav_end_flags(r, stk) & TRAV_FLAG_NEAR) != 0 && r.best.tri >= 0; }
+template <class STK> PRT_D bool trav_wants_resolve(const TravRay & r, const STK & stk) { return !(r.kind & TRACE_ANY) && (trav_end_flags(r, stk) & TRAV_FLAG_NEAR) != 0 && r.best.tri >= 0; }
 // fast kernels: the ray cannot be finished here (near tie, or a dropped push): it goes to the slow path
 template <class STK> PRT_D bool trav_needs_slow_path(const TravRay & r, const STK & stk) { return (trav_end_flags(r, stk) & TRAV_FLAG_OVERFLOW) != 0 || trav_wants_resolve(r, stk); }
 
@@ -151,16 +154,25 @@ PRT_D void cswap(float & ka, float & kb, int & la, int & lb) {
 // so after 3 scale products and 6 FMAs per node every plane costs one byte->float convert and one FMA.
 // The slab test may use FMA: it only has to be conservative, and the boxes are widened by `pad`.
 // (The top levels of the tree staged in LDS, round 4: no gain, profiles/r04_experiments.txt section 1.)
-template <class STK, bool COUNT>
+// CONES (the render kernels): a closest-hit ray that the node's normal cone proves to meet only back faces below this node
+// (dev_scene.h cone_faces_away) hits no child - every key is inf - and pops.  The step still counts as a node visit.
+template <class STK, bool COUNT, bool CONES = false>
 PRT_D void trav_node_step(const DevScene & sc, TravRay & r, const STK & stk, TraceStats & st, float pad) {
     // 32-bit byte offset from the (scalar) array base: the loads take the SGPR-base + VGPR-offset form and no 64-bit address is
     // built per lane (-0.7 % frame time; upload caps the scene at 2^26 triangles, so nodes * 64 and triangles * 48 fit)
     const uint4 * np = reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(sc.nodes) + ((unsigned int)r.node << 6));
     const uint4 w0 = np[0], w1 = np[1], w2 = np[2], w3 = np[3];
     if (COUNT) { st.nodes++; if (first_active_lane()) st.wnodes++; if ((unsigned int)r.sp > st.max_sp) st.max_sp = (unsigned int)r.sp; }
-    const float kx = __uint_as_float(w0.w) * r.ix;
-    const float ky = __uint_as_float(w3.z) * r.iy;
-    const float kz = __uint_as_float(w3.w) * r.iz;
+    const float kx = __uint_as_float(node_grid_step(w0.w)) * r.ix;
+    const float ky = __uint_as_float(node_grid_step(w3.z)) * r.iy;
+    const float kz = __uint_as_float(node_grid_step(w3.w)) * r.iz;
+    // a culled lane's boxes are tested against a far end below every entry distance (tmin >= 0): no child is hit
+    float t_far = r.best.t;
+    if (CONES) {
+        const bool cull = !(r.kind & (TRACE_ANY | TRACE_NO_CONE)) && cone_faces_away(w0.w, w3.z, w3.w, r.d);
+        if (COUNT && cull) st.cone_culls++;
+        t_far = cull ? -1.0f : t_far;
+    }
     const float ox = __uint_as_float(w0.x), oy = __uint_as_float(w0.y), oz = __uint_as_float(w0.z);
     // entry / exit parameter of the node origin on each axis; the ray's direction signs pick, per axis, which
     // quantised plane set (lo or hi bytes) is the entry side - no per-plane min/max, and an empty child slot
@@ -186,7 +198,7 @@ PRT_D void trav_node_step(const DevScene & sc, TravRay & r, const STK & stk, Tra
         const float nz = __builtin_fmaf((float)((qnz >> (8 * k)) & 0xFFu), kz, cnz);
         const float fz = __builtin_fmaf((float)((qfz >> (8 * k)) & 0xFFu), kz, cfz);
         const float tmin = fmaxf(fmaxf(fmaxf(nx, ny), nz), 0.0f);
-        const float tmax = fminf(fminf(fminf(fx, fy), fz), r.best.t);
+        const float tmax = fminf(fminf(fminf(fx, fy), fz), t_far);
         key[k] = tmin <= tmax ? tmin : inf;
     }
     // sorting network for 4 keys, ascending; misses (inf) sink to the end

@@ -161,7 +161,10 @@ PRT_D void trav_init(TravRay & r, f3 o, f3 d, int kind, float pad, const STK & s
 // child was hit, take the next child from the entry on top of the stack.
 //   plane = origin + q * 2^e  =>  t = (plane - o -+ pad) / d = q * (2^e / d) + (origin / d - (o +- pad) / d)
 // The slab test may use FMA: it only has to be conservative, and the boxes are widened by `pad`.
-template <class STK, bool COUNT>
+// An 8-wide tree carries no cones: nothing is or'ed into a ray's kind, and the kernels are the code they were
+PRT_D int trav_cone_kind(const DevParams &) { return 0; }
+
+template <class STK, bool COUNT, bool CONES = false>      // (CONES: the 4-wide layout's; an 8-wide tree carries no cones)
 PRT_D void trav_node_step(const DevScene & sc, TravRay & r, const STK & stk, TraceStats & st, float pad) {
     // 32-bit byte offset from the (scalar) array base (upload caps the scene at 2^26 triangles)
     const uint4 * np = reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(sc.nodes) + (unsigned int)r.node * (unsigned int)BVH_NODE_BYTES);

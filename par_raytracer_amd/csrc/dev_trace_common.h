@@ -39,13 +39,16 @@ PRT_D HitRec hit_miss() {
     return h;
 }
 
-enum { TRACE_CLOSEST = 0, TRACE_ANY = 1 };
+// TRACE_NO_CONE: a closest-hit ray that must not take the nodes' normal cones (dev_scene.h) - its direction is not one the
+// library normalised, or the call lies outside the cones' bounds.  Any-hit rays never take them.
+enum { TRACE_CLOSEST = 0, TRACE_ANY = 1, TRACE_NO_CONE = 2 };
 
 struct TraceStats {
     unsigned int nodes = 0, tris = 0;
     unsigned int wnodes = 0, wleaves = 0, wtris = 0, wrefills = 0;   // counted by the first active lane only (wave-level steps)
     unsigned int wrays = 0;                          // k_pool: lanes that held a ray, summed over the wave-level node steps
     unsigned int max_sp = 0, culled = 0;             // deepest stack use; popped nodes whose entry distance was already beyond the hit
+    unsigned int cone_culls = 0;                     // lane-level node steps that the node's normal cone culled
     unsigned int wdescend = 0, wpop = 0, wpush = 0;  // wave-level node steps in which a lane went down into a child / took its next node from the stack; wave-level pushes
 };
 

@@ -30,6 +30,7 @@ PRT_D void trace_stats_flush(DevCounters * ctr, const TraceStats & st) {
         atomicAdd(&ctr->wave_refills, (unsigned long long)st.wrefills);
         atomicMax(&ctr->max_sp, (unsigned long long)st.max_sp);
     }
+    if (st.cone_culls) atomicAdd(&ctr->cone_culled_nodes, (unsigned long long)st.cone_culls);
 }
 
 // Items 0 .. total, handed out through *head in chunks.  COUNT: the refills are counted (st.wrefills).
@@ -102,11 +103,11 @@ PRT_D void wave_loop(Job & job, const LdsStack<BLOCK> & stack, TraceStats & st, 
 }
 
 // A job's node and leaf steps for rays (k_trace, k_query): the traversal of dev_trace.h under box pad `pad`.
-template <int BLOCK, bool COUNT>
+template <int BLOCK, bool COUNT, bool CONES = false>
 struct RaySteps {
     const DevScene & sc;
     float pad;
-    PRT_D void node_step(TravRay & r, const LdsStack<BLOCK> & stack, TraceStats & st) const { trav_node_step<LdsStack<BLOCK>, COUNT>(sc, r, stack, st, pad); }
+    PRT_D void node_step(TravRay & r, const LdsStack<BLOCK> & stack, TraceStats & st) const { trav_node_step<LdsStack<BLOCK>, COUNT, CONES>(sc, r, stack, st, pad); }
     PRT_D bool leaf(TravRay & r, const LdsStack<BLOCK> & stack, TraceStats & st) const { return trav_leaf<LdsStack<BLOCK>, COUNT>(sc, r, stack, st); }
 };
 

@@ -549,7 +549,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
                         sample = as_i(ro.w);
                         const f3 d = mk3(rd.x, rd.y, rd.z);
                         const f3 ob = mk3(ro.x, ro.y, ro.z) + d * P.ray_bias;          // raytracer.cpp:163
-                        trav_init(r, ob, d, kind == WF_KIND_SHADOW_ANY ? TRACE_ANY : TRACE_CLOSEST, P.box_pad, stack, kind == WF_KIND_SHADOW_ANY ? as_i(rd.w) : 0);
+                        trav_init(r, ob, d, kind == WF_KIND_SHADOW_ANY ? TRACE_ANY : TRACE_CLOSEST | trav_cone_kind(P), P.box_pad, stack, kind == WF_KIND_SHADOW_ANY ? as_i(rd.w) : 0);
                         ray = (int)idx;
                     }
                     next += take;
@@ -565,7 +565,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_pool(const PoolArgs * args, De
                     const int nmin = node_min < wfrac ? node_min : wfrac;
                     const unsigned int with_ray = COUNT ? (unsigned int)__popcll(__ballot(true)) : 0u;
                     while (trav_walking(r)) {
-                        trav_node_step<Stack, COUNT>(sc, r, stack, st, P.box_pad);
+                        trav_node_step<Stack, COUNT, true>(sc, r, stack, st, P.box_pad);
                         if (COUNT && first_active_lane()) { st.wrays += with_ray; if (dry) { dry_steps += 1ull; dry_rays += with_ray; } }
                         if (__popcll(__ballot(trav_walking(r))) < nmin) break;
                     }
@@ -1020,7 +1020,7 @@ __global__ __launch_bounds__(256) void k_pool_parked_shadows(const PoolArgs * ar
         const f3 d = mk3(rd.x, rd.y, rd.z);
         const f3 ob = mk3(ro.x, ro.y, ro.z) + d * P.ray_bias;                   // raytracer.cpp:163
         const int root = pay.w < 0.0f ? light_shadow_root(sc.lights[(unsigned int)(-pay.w) - 1u]) : 0;
-        const HitRec h = trace_ray<GlobalStack, COUNT>(sc, ob, d, pay.w < 0.0f ? TRACE_ANY : TRACE_CLOSEST, P.box_pad, slow, st, root);
+        const HitRec h = trace_ray<GlobalStack, COUNT, false, true>(sc, ob, d, pay.w < 0.0f ? TRACE_ANY : TRACE_CLOSEST | trav_cone_kind(P), P.box_pad, slow, st, root);
         if (shadow_lit(h, pay.w)) accum_add(A.B.accum + sample, mk3(pay.x, pay.y, pay.z));
     }
     if (COUNT) trace_stats_flush<false>(ctr, st);

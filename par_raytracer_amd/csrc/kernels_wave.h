@@ -131,7 +131,7 @@ PRT_D TraceEntry trace_entry(const DevScene & sc, const DevParams & P, const Wav
     e.ob = mk3(ro.x, ro.y, ro.z) + e.d * P.ray_bias;
     return e;
 }
-PRT_D int trace_entry_mode(const TraceEntry & e) { return e.kind == WF_KIND_SHADOW_ANY ? TRACE_ANY : TRACE_CLOSEST; }
+PRT_D int trace_entry_mode(const TraceEntry & e, const DevParams & P) { return e.kind == WF_KIND_SHADOW_ANY ? TRACE_ANY : TRACE_CLOSEST | trav_cone_kind(P); }
 // The traced entry's result: a closest-hit ray's record for k_shade; a shadow ray adds its precomputed radiance when unoccluded.
 PRT_D void trace_entry_emit(const WaveBuffers & B, unsigned int n_closest, unsigned int idx, const HitRec & best, float4 payload, int sample) {
     if (idx < n_closest) B.hits[idx] = make_float4(best.t, best.v, best.w, as_f(best.tri));
@@ -140,7 +140,7 @@ PRT_D void trace_entry_emit(const WaveBuffers & B, unsigned int n_closest, unsig
 
 // k_trace's job for the wave loop: a lane's item is a queue entry; every entry walks.
 template <int BLOCK, bool COUNT>
-struct TraceJob : RaySteps<BLOCK, COUNT> {
+struct TraceJob : RaySteps<BLOCK, COUNT, true> {
     const DevParams & P;
     const WaveBuffers & B;
     int cur;
@@ -150,7 +150,7 @@ struct TraceJob : RaySteps<BLOCK, COUNT> {
     PRT_D bool start(unsigned int idx, TravRay & r, const LdsStack<BLOCK> & stack) {
         const TraceEntry e = trace_entry(this->sc, P, B, cur, n_closest, idx, payload);
         sample = e.sample;
-        trav_init(r, e.ob, e.d, trace_entry_mode(e), this->pad, stack, e.root);
+        trav_init(r, e.ob, e.d, trace_entry_mode(e, P), this->pad, stack, e.root);
         return true;
     }
     PRT_D void finish(unsigned int idx, const TravRay & r, const LdsStack<BLOCK> & stack) const {
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256) void k_trace_exact(DevScene sc, DevParams P, W
     exact_list_walk<COUNT>(B.overflow, B.counts[3], P.exact_stack, P.exact_stack_stride, ctr, [&](unsigned int idx, const GlobalStack & slow, TraceStats & st) {
         float4 payload = make_float4(0, 0, 0, 0);
         const TraceEntry e = trace_entry(sc, P, B, cur, n_closest, idx, payload);
-        const HitRec best = trace_ray<GlobalStack, COUNT>(sc, e.ob, e.d, trace_entry_mode(e), P.box_pad, slow, st, e.root);
+        const HitRec best = trace_ray<GlobalStack, COUNT, false, true>(sc, e.ob, e.d, trace_entry_mode(e, P), P.box_pad, slow, st, e.root);
         trace_entry_emit(B, n_closest, idx, best, payload, e.sample);
     });
 }

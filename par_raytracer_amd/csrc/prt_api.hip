@@ -937,6 +937,14 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
     }
     P.elide_dead_shadow_rays = opt.trace_dead_shadow_rays ? 0u : 1u;
     {
+        // the nodes' normal cones (dev_scene.h): for directions the library normalised itself - not the caller's, which
+        // prt_render_rays' first rays and their alpha continuations carry - and for origins inside the bound the upload
+        // computed them for, which is the trees' guard
+        bool cones = !rays && fabsf(params->ray_bias) <= ctx->desc.shadow_bias_max;
+        for (int a = 0; a < 3 && cones; ++a) cones = fabsf(cam_in->position[a]) <= ctx->desc.shadow_cam_max;
+        P.no_cones = cones ? 0u : (unsigned int)TRACE_NO_CONE;
+    }
+    {
         // the open-triangle flags (include/prt.h "Open triangles"): their own option, never while every ray is to be traced, and
         // only for a call inside the bounds they were computed for - the bias, and the camera guard the trees use
         bool open = opt.shadow_open != 0 && !opt.trace_dead_shadow_rays && ctx->desc.shadow_trees_fresh && ctx->desc.shadow_open_reach > 0.0f &&
@@ -1200,6 +1208,7 @@ int render_pixels_once(prt_ctx * ctx, const prt_camera * cam_in, const prt_param
             rs.parked_rays = h.park_peak[0]; rs.parked_shadow_rays = h.park_peak[1];
             rs.elided_shadow_rays = h.elided_shadow_rays;
             rs.open_shadow_rays = h.open_shadow_rays;
+            rs.cone_culled_nodes = h.cone_culled_nodes;
             rs.variance_close_calls = h.variance_close_calls;
             rs.stack_lds_entries = stack_entries; rs.stack_bound = ctx->desc.stack_bound;
             // k_pool's COUNT variants fill the table; the steps that have counters of their own are copied into their rows
@@ -1721,6 +1730,8 @@ int update_geometry(prt_ctx * ctx, const prt_geometry_update * u, prt_update_inf
     for (prt_shadow_tree_info & si : ctx->desc.shadow_info) si.active = 0;
     // ... and so are the open-triangle flags: k_refit_records leaves the word where it is, no render reads it until the next upload
     for (prt_shadow_open_info & oi : ctx->desc.shadow_open_info) oi.active = 0;
+    // the refit wrote every node's grid steps afresh, mantissas zero (dev_refit.h): the scene's tree carries no cone any more
+    ctx->desc.cone_info.coned_nodes = 0;
     ctx->tuned.clear();                                           // a refitted tree may change which pipeline wins a try-out
     ctx->geom_generation++;                                       // the pseudonormals of prt_signed_distance are of the old records
     if (info) { info->device_ms = ms; info->abs_max = abs_max; }
@@ -2550,6 +2561,7 @@ int prt_upload_scene(prt_ctx * ctx, const prt_scene_desc * s) {
     if (ctx->opt.leaf_max >= 0) how.leaf_max = (unsigned int)std::max(1ll, std::min(4ll, ctx->opt.leaf_max));   // experiment knob
     how.sah_trav_cost = (float)ctx->opt.sah_trav_cost;                                                          // experiment knob
     how.shadow_tree_ratio = (uint32_t)std::max(0ll, std::min(100ll, ctx->opt.shadow_tree_ratio));
+    how.normal_cones = ctx->opt.normal_cones != 0;
     how.bvh = &ctx->opt.bvh;
     if (ctx->opt.bvh_builder_lbvh) {
         // fast build for scenes that change every frame: radix tree on the GPU (bvh_lbvh.h), same quantised wide back end
@@ -2606,6 +2618,15 @@ int prt_get_shadow_trees(const prt_ctx * ctx, prt_shadow_tree_info * out, uint32
     for (size_t l = 0; l < ctx->desc.shadow_info.size() && l < cap; ++l) out[l] = ctx->desc.shadow_info[l];
     return (int)ctx->desc.shadow_info.size();
     PRT_API_CATCH_RC(nullptr, "prt_get_shadow_trees")
+}
+
+int prt_get_normal_cones(const prt_ctx * ctx, prt_normal_cone_info * out) {
+    PRT_API_TRY
+    if (!ctx || !out) return -1;
+    if (!ctx->has_scene) return -2;
+    *out = ctx->desc.cone_info;
+    return 0;
+    PRT_API_CATCH_RC(nullptr, "prt_get_normal_cones")
 }
 
 static_assert((float)ShadowOpenBounds::min_cos == PRT_SHADOW_OPEN_MIN_COS, "the margins assume the kernels' grazing threshold");
@@ -2966,6 +2987,32 @@ int prt_debug_check_bvh(const prt_scene_desc * s, uint64_t * out) {
     check_bvh_wide(verts.data(), n_tris, bvh, out);
     return 0;
     PRT_API_CATCH_RC(nullptr, "prt_debug_check_bvh")
+}
+
+// The normal cones of the same tree (bvh_build.h attach_normal_cones, over the record normals and the origin bound of an upload):
+// out[0] = (coned node, triangle below it) pairs the stored bits do not cover (check_bvh_cones), out[1] = nodes with a cone.
+int prt_debug_check_cones(const prt_scene_desc * s, uint64_t * out) {
+    PRT_API_TRY
+    if (!s || !out || s->index_count % 3) return -1;
+    const uint32_t n_tris = s->index_count / 3;
+    std::vector<float> verts((size_t)n_tris * 9), normals((size_t)n_tris * 3);
+    float abs_max = 0.0f;
+    for (uint32_t t = 0; t < n_tris; ++t) {
+        for (int c = 0; c < 3; ++c) memcpy(&verts[(size_t)t * 9 + 3 * c], s->positions + 3 * (size_t)s->idx_positions[3 * t + c], 12);
+        float4 rec[3];
+        tri_record(ld3(&verts[(size_t)t * 9]), ld3(&verts[(size_t)t * 9 + 3]), ld3(&verts[(size_t)t * 9 + 6]), rec);
+        normals[(size_t)t * 3] = rec[2].y; normals[(size_t)t * 3 + 1] = rec[2].z; normals[(size_t)t * 3 + 2] = rec[2].w;
+        for (int k = 0; k < 9; ++k) abs_max = std::max(abs_max, fabsf(verts[(size_t)t * 9 + k]));
+    }
+    PrtOptions opt;
+    prt_options_from_env(opt);
+    BvhWide bvh;
+    build_bvh_wide(BVH_WIDTH, verts.data(), n_tris, BVH_LEAF_MAX, 4, &bvh, 1.0f, &opt.bvh);
+    if (validate_bvh_links(bvh, n_tris)) return -9;
+    attach_normal_cones(bvh, normals.data(), n_tris, 32.0 * (double)abs_max, 4);
+    out[0] = check_bvh_cones(verts.data(), n_tris, bvh, 32.0 * (double)abs_max, &out[1]);
+    return 0;
+    PRT_API_CATCH_RC(nullptr, "prt_debug_check_cones")
 }
 
 // The same check on the tree of the GPU LBVH builder (needs a context: the radix tree is built on its device).

@@ -34,6 +34,7 @@ struct PrtOptions {
     long long shadow_trees = 1;             // read per render: 1 = a directional light's shadow rays start at its occluder tree where the upload built one, 0 = at the scene's root (same image; A/B and tests)
     long long shadow_tree_ratio = 75;       // read at upload: a light gets a tree when its occluders are at most this many hundredths of the scene's triangles
     long long shadow_open = 1;              // read per render: 1 = a directional light's shadow ray that starts on a triangle the upload found open for it is counted and credited at the hit, not traced; 0 = traced (same image; A/B and tests).  Independent of SHADOW_TREES
+    long long normal_cones = 1;             // read at upload: 1 = the scene's 4-wide nodes get normal cones (dev_scene.h; closest-hit rays skip subtrees that face away from them), 0 = no bits are written (same image; A/B and tests)
     // ---- diagnostics
     long long debug_util = 0, debug_rounds = 0;
     // ---- tuning; -1 = automatic
@@ -67,7 +68,7 @@ inline const OptEntry * option_table(size_t * n) {
         { "TRACE_DEAD_SHADOW_RAYS", &PrtOptions::trace_dead_shadow_rays, nullptr }, { "POOL_EXACT", &PrtOptions::pool_exact, nullptr },
         { "TIE_WIDEN_MAX", &PrtOptions::tie_widen_max, nullptr },
         { "SHADOW_TREES", &PrtOptions::shadow_trees, nullptr }, { "SHADOW_TREE_RATIO", &PrtOptions::shadow_tree_ratio, nullptr },
-        { "SHADOW_OPEN", &PrtOptions::shadow_open, nullptr },
+        { "SHADOW_OPEN", &PrtOptions::shadow_open, nullptr }, { "NORMAL_CONES", &PrtOptions::normal_cones, nullptr },
         { "DEBUG_UTIL", &PrtOptions::debug_util, nullptr }, { "DEBUG_ROUNDS", &PrtOptions::debug_rounds, nullptr },
         { "CHUNK_MIN", &PrtOptions::chunk_min, nullptr }, { "TRACE_BLOCKS_PER_CU", &PrtOptions::trace_blocks_per_cu, nullptr },
         { "KEEP_MIN", &PrtOptions::keep_min, nullptr }, { "NODE_MIN", &PrtOptions::node_min, nullptr }, { "NODE_FRAC", &PrtOptions::node_frac, nullptr },

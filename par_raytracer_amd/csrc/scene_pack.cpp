@@ -234,15 +234,21 @@ int pack_scene(const prt_scene_desc * s, const std::vector<float> & verts, BvhWi
     for (uint32_t i = 0; i < 1024; ++i) P.diffuse_dirs[i] = diffuse_tangent_dir(i);
 
     // ---- shadow trees (include/prt.h, bvh_build.h): behind the scene's nodes and records, links rebased
+    // origins the bounds below cover: a shadow ray starts at (hit + n * bias) + d * bias; the hit is taken to lie within 16 extents of
+    // the origin for a camera within 4 and a bias of at most one extent (DESIGN.md section 2); render_pixels_once holds a call to that
+    const double shadow_origin_max = 32.0 * (double)abs_max;
+    // ---- normal cones (bvh_build.h): on the scene's tree only - every triangle of a light's occluder tree faces its rays
+    if (opt.normal_cones && width == 4 && abs_max > 0.0f) {
+        const auto tc = std::chrono::steady_clock::now();
+        desc.cone_info.coned_nodes = attach_normal_cones(bvh, rec_normals.data(), n_tris, shadow_origin_max, opt.threads);
+        desc.cone_info.attach_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tc).count();
+    }
     std::vector<uint32_t> & node_words = P.nodes;
     node_words = std::move(bvh.nodes);
     uint32_t all_nodes = bvh.node_count, all_recs = n_rec;
     unsigned int stack_bound = bvh.stack_bound;
     std::vector<prt_shadow_tree_info> & shadow_info = desc.shadow_info;
     shadow_info.assign(s->light_count, prt_shadow_tree_info());
-    // origins the bound covers: a shadow ray starts at (hit + n * bias) + d * bias; the hit is taken to lie within 16 extents of
-    // the origin for a camera within 4 and a bias of at most one extent (DESIGN.md section 2); render_pixels_once holds a call to that
-    const double shadow_origin_max = 32.0 * (double)abs_max;
     uint32_t shadow_trees = 0;
     // open triangles (bvh_build.h): for the same lights, whatever the size rule says about a tree; bit l of the first spare
     // word of a triangle's shading record, the integer's bits in the float

@@ -43,6 +43,9 @@ struct SceneDesc {
     // the bounds the upload computed them for; open_reach = 0: no light has flags.
     std::vector<prt_shadow_open_info> shadow_open_info;
     float shadow_open_bias_max = 0.0f, shadow_open_reach = 0.0f;
+    // normal cones (dev_scene.h): nodes of the scene's tree that carry one, and what attaching them cost.  They hold for the calls
+    // the shadow trees hold for (shadow_bias_max, shadow_cam_max); a refit clears them node by node, so they are never stale.
+    prt_normal_cone_info cone_info = prt_normal_cone_info();
 };
 
 // What the upload keeps on the host for later calls: the queries' leaf map, prt_update_geometry's table and ranks, the gradients'
@@ -80,6 +83,7 @@ struct ScenePackOptions {
     uint32_t leaf_max = 4;
     float sah_trav_cost = 1.0f;
     uint32_t shadow_tree_ratio = 75;      // hundredths of the scene's triangles
+    bool normal_cones = true;             // attach_normal_cones on the scene's tree (4-wide only; never on the lights' occluder trees)
     const BvhBuildOptions * bvh = nullptr;
     uint32_t threads = 1;
 };

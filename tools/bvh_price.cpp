@@ -2,7 +2,7 @@
 // depth per ray for the 4-wide quantised BVH (sorted children, csrc/dev_trace4.h) and the 8-wide one with its children sorted
 // along one axis per node (csrc/dev_trace8.h), on the same rays.  Host only; links csrc/bvh_build.cpp.
 //
-//   g++ -O2 -std=c++17 -pthread -Ipar_raytracer_amd/csrc tools/bvh_price.cpp par_raytracer_amd/csrc/bvh_build.cpp -o /tmp/bvh_price
+//   g++ -O2 -std=c++17 -ffp-contract=off -pthread -Itests/hip_shim -Ipar_raytracer_amd/csrc tools/bvh_price.cpp par_raytracer_amd/csrc/bvh_build.cpp -o /tmp/bvh_price
 //   python3 tools/bvh_price_scene.py terrain_1m /tmp/terrain.bin && /tmp/bvh_price /tmp/terrain.bin
 //
 // Input file: u32 n_tris, 9 floats per triangle, then camera position (3 floats), facing (3), fov (1).
@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "bvh_build.h"
+#include "dev_scene.h"
 #include "prt_options.h"
 
 using namespace prt;
@@ -64,7 +65,8 @@ static float bits_f(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
 struct Hit { double t = 1e300; int tri = -1; };
 
 // ---- 4-wide: csrc/dev_trace.h trav_node_step / trav_leaf
-static Hit trace4(const Bvh4Result & bvh, const Ray & r, Stats & st) {
+// cones: closest-hit rays take the nodes' normal cones (bvh_build.h attach_normal_cones) through the kernels' own predicate
+static Hit trace4(const Bvh4Result & bvh, const Ray & r, Stats & st, bool cones = false) {
     Hit best;
     std::vector<int32_t> stack;
     int32_t node = 0;
@@ -76,11 +78,12 @@ static Hit trace4(const Bvh4Result & bvh, const Ray & r, Stats & st) {
             st.nodes++;
             const uint32_t * d = &bvh.nodes[(size_t)node * 16];
             const double org[3] = { bits_f(d[0]), bits_f(d[1]), bits_f(d[2]) };
-            const double sc[3] = { bits_f(d[3]), bits_f(d[14]), bits_f(d[15]) };
+            const double sc[3] = { bits_f(prt::node_grid_step(d[3])), bits_f(prt::node_grid_step(d[14])), bits_f(prt::node_grid_step(d[15])) };
+            const bool culled = cones && !r.any && prt::cone_faces_away(d[3], d[14], d[15], prt::mk3((float)r.d.x, (float)r.d.y, (float)r.d.z));
             double key[4];
             int32_t link[4];
             int n = 0;
-            for (int k = 0; k < 4; ++k) {
+            for (int k = 0; k < 4 && !culled; ++k) {
                 double tmin = 0.0, tmax = best.t;
                 for (int a = 0; a < 3; ++a) {
                     const double lo = org[a] + ((d[4 + a] >> (8 * k)) & 0xFF) * sc[a], hi = org[a] + ((d[7 + a] >> (8 * k)) & 0xFF) * sc[a];
@@ -269,12 +272,18 @@ int main(int argc, char ** argv) {
         if (a.tri >= 0) o.occluded++;
     };
 
-    Stats s4[3], s8d[3], s8a[3];            // primary, shadow, bounce
-    uint64_t mismatches = 0;
+    Stats s4[3], s8d[3], s8a[3], s4c[3];    // primary, shadow, bounce; s4c: the 4-wide tree with its normal cones attached
+    uint64_t mismatches = 0, cone_mismatches = 0;
+    Bvh4Result b4c = b4;
+    const auto t_cones = std::chrono::steady_clock::now();
+    const uint32_t coned = attach_normal_cones(b4c, rec_normals.data(), n_tris, 32.0 * abs_max, 8);
+    const double cones_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_cones).count();
     uint64_t rng = 0x9E3779B97F4A7C15ull;
     auto rnd = [&]() { rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17; return (double)(rng >> 11) / 9007199254740992.0; };
     auto trace_all = [&](const Ray & r, int cls) {
         const Hit h4 = trace4(b4, r, s4[cls]);
+        const Hit hc = trace4(b4c, r, s4c[cls], true);
+        if (hc.tri != h4.tri || hc.t != h4.t) cone_mismatches++;
         const Hit h8 = trace8u(b8, r, s8a[cls], 2);
         trace8u(b8, r, s8d[cls], 1);
         if (r.any ? (h4.tri < 0) != (h8.tri < 0) : (h4.tri < 0) != (h8.tri < 0) || (h4.tri >= 0 && std::fabs(h4.t - h8.t) > 1e-9 * std::max(1.0, h4.t))) mismatches++;
@@ -310,6 +319,7 @@ int main(int argc, char ** argv) {
     for (int k = 0; k < 3; ++k) {
         printf("-- %s rays: %llu\n", cls[k], (unsigned long long)s4[k].rays);
         report("4-wide, sorted children (64 B)", s4[k], b4.node_count, 64, b4.max_depth);
+        report("4-wide, a node tests its own cone", s4c[k], b4c.node_count, 64, b4c.max_depth);
         report("8-wide, one axis per node (80 B)", s8a[k], b8.node_count, 80, b8.max_depth);
         report("8-wide, sorted by entry distance", s8d[k], b8.node_count, 80, b8.max_depth);
     }
@@ -324,6 +334,8 @@ int main(int argc, char ** argv) {
     report("8-wide, one axis per node (80 B)", t8a, b8.node_count, 80, b8.max_depth);
     report("8-wide, sorted by entry distance", t8d, b8.node_count, 80, b8.max_depth);
     printf("hit / miss or distance mismatches between the two trees: %llu\n", (unsigned long long)mismatches);
+    printf("-- normal cones: %u of %u nodes carry one (attached in %.1f ms); hit or distance mismatches against the plain walk: %llu\n", coned, b4c.node_count, cones_ms,
+           (unsigned long long)cone_mismatches);
     printf("-- shadow trees: possible occluders %zu of %u; traced shadow rays: %llu\n", occ_ids.size(), n_tris, (unsigned long long)s_full.rays);
     report("4-wide, the scene's tree", s_full, b4.node_count, 64, b4.max_depth);
     report("4-wide, the light's occluders", s_occ, bocc.node_count, 64, bocc.max_depth);
@@ -339,5 +351,5 @@ int main(int argc, char ** argv) {
                o.taken ? (double)o.nodes / o.taken : 0.0, o.taken ? (double)o.tris / o.taken : 0.0, (unsigned long long)o.occluded);
         open_occluded += o.occluded;
     }
-    return mismatches || occ_mismatches || open_occluded ? 1 : 0;
+    return mismatches || occ_mismatches || open_occluded || cone_mismatches ? 1 : 0;
 }
