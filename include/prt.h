@@ -743,6 +743,61 @@ int prt_render_rays(prt_ctx * ctx, const prt_radiance_batch * batch, const prt_p
 int prt_render_rays_device(prt_ctx * ctx, const prt_radiance_batch * batch, const prt_params * params, void * d_rgba_out,
                            prt_counters * counters);
 
+/* ---- a ray's K nearest hits, both sides, resumable ----------------------------------------------------------------------------
+ * What a ray hits after its first hit: wall thickness (entry and exit), depth peeling, x-ray ordering, picking through a surface,
+ * crossing counts along a segment - without re-shooting the ray from behind its last hit.  At most k <= PRT_MAX_HITS hits per ray in
+ * fixed slots, under a total order that makes the answer a pure function of (scene, ray), with a cursor that pages through all
+ * of them exactly.  No containment is claimed: prt_signed_distance is the inside / outside query.
+ * THE DEFINITION.  For ray i let o be the biased origin origin + direction * ray_bias, d the direction as given and
+ * qp = o - (o + d), as prt_trace_rays forms them.  A triangle record (a, ab, ac, n) is a FRONT candidate when PRT_QUERY_OCCLUDED's
+ * rule accepts it: tri_geom(o, qp, a, ab, ac, n) is true (csrc/dev_trace_common.h: the geometric part of the reference's
+ * IntersectRayTriangle), !(t > FLT_MAX * dd), and th = t * (1.0f / dd) satisfies th < tmax[i].  tmax NULL, +inf and FLT_MAX all
+ * mean no limit; a tmax that is 0, negative or NaN gives no candidates.  With PRT_HITS_BACK_FACES the record is also a BACK
+ * candidate when the same rule accepts the record (a, ac, ab, -n); its barycentrics (v', w') are reported in the order of the real
+ * corners: v = w', w = v'.  A record cannot be both, because dd decides.
+ * The key of a candidate is (th as a float, group, vertex0), compared lexicographically; it is unique per candidate.  With a
+ * cursor only the candidates whose key is strictly greater than (after_t[i], after_group[i], after_vertex0[i]) remain;
+ * after_group[i] < 0 means no cursor for that ray, a NaN after_t leaves nothing.  The answer is the k smallest remaining
+ * candidates in key order: hit_count[i] = min(k, remaining); slot s < hit_count holds t = th, bw = (1 - v - w, v, w) with
+ * v, w = v * ood, w * ood as IntersectRayTriangle forms them, vertex0, group and back (0 / 1); slots s >= hit_count hold the
+ * queries' miss record: t = FLT_MAX, zeros, group = -1, vertex0 = 0xFFFFFFFF, back = 0.  To page, pass the last filled slot's
+ * (t, group, vertex0) as the next call's cursor until hit_count < k.
+ * A ray that is a miss by definition (a non-finite origin, direction or biased origin, a zero direction) has hit_count = 0 and
+ * does not affect the other rays.  The result is a pure function of (scene as it lies on the device, ray, ray_bias, tmax, k,
+ * flags, cursor): the same bits for every tree (SAH, LBVH, 8-wide, refitted), schedule option, STACK_CAP, entry point, batch order
+ * and run, and the same bits as a brute force over all triangles on the host.  There are no near-tie replays and no sphere walk.
+ * Two consequences: hit_count > 0 (front only, no cursor) exactly when PRT_QUERY_OCCLUDED with the same tmax answers 1; and
+ * t of slot 0 <= PRT_QUERY_CLOSEST's t for every ray, equal in bits wherever both name the same (group, vertex0).
+ * Front slots can be handed to prt_trace_rays_backward as they are; back hits are skipped by its facing test.
+ * Counters and stream contract: prt_trace_rays' (PRT_FLAG_COUNT_VISITS goes in the last `flags`).
+ * Errors: -1 NULL request or buffers, NULL origins / directions with count > 0, k outside 1..PRT_MAX_HITS, an unknown flag, a
+ * cursor given in part; -2 no scene; -10 a HIP call failed.  count == 0 writes nothing and returns 0. */
+enum { PRT_MAX_HITS = 16 };
+enum { PRT_HITS_BACK_FACES = 1 };
+typedef struct prt_hits_request {
+    prt_ray_batch rays;            /* origins, directions, tmax (NULL = no limit), count, ray_bias */
+    uint32_t k;                    /* slots per ray, 1..PRT_MAX_HITS */
+    uint32_t flags;                /* PRT_HITS_* */
+    const float * after_t;         /* the cursor: count each; all NULL or all given */
+    const int32_t * after_group;
+    const uint32_t * after_vertex0;
+} prt_hits_request;
+/* Every pointer may be NULL: that field is not written. */
+typedef struct prt_hits_buffers {
+    uint32_t * hit_count;          /* count */
+    float * t;                     /* count x k */
+    float * bw;                    /* count x k x 3 */
+    uint32_t * vertex0;            /* count x k */
+    int32_t * group;               /* count x k */
+    uint8_t * back;                /* count x k */
+} prt_hits_buffers;
+/* Host pointers (request arrays and buffers). */
+int prt_trace_hits(prt_ctx * ctx, const prt_hits_request * request, const prt_hits_buffers * out, uint32_t flags,
+                   prt_counters * counters);
+/* Device pointers on the context's device; the stream contract of prt_trace_rays_device. */
+int prt_trace_hits_device(prt_ctx * ctx, const prt_hits_request * request, const prt_hits_buffers * out, uint32_t flags,
+                          prt_counters * counters);
+
 /* ---- several devices behind one handle --------------------------------------------------------------------------------
  * SURVEY.md 8(b)'s prt_create(const int * device_ids, int n_dev): what the host mirror's Render() uses for n GPUs, in place
  * of the reference's one-rank-per-core partition + MPI_Gather (main.cpp:311-347).  The scene is replicated (as every MPI rank

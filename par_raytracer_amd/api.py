@@ -426,6 +426,74 @@ class Renderer:
         out["counters"] = counters
         return out
 
+    # (name, components per slot, numpy dtype) of prt_hits_buffers' fields; hit_count is per ray
+    HITS_FIELDS = (("hit_count", 0, np.uint32), ("t", 1, np.float32), ("bw", 3, np.float32), ("vertex0", 1, np.uint32), ("group", 1, np.int32),
+                   ("back", 1, np.uint8))
+
+    def trace_hits(self, origins, directions, k: int, *, tmax=None, ray_bias: float = 0.0, back_faces: bool = False, after=None,
+                   fields: Optional[Sequence[str]] = None, count_visits: bool = False) -> dict:
+        """The k nearest hits of n rays in key order (t, group, vertex0), front faces or both sides (prt_trace_hits, include/prt.h).
+
+        origins, directions: float32 (n, 3), contiguous - numpy arrays (host entry point, numpy results) or torch tensors on this
+        context's device (device entry point, tensors on that device).  k: slots per ray, 1..16.  tmax: None, or float32 (n,).
+        after: None, a previous result of this call (it then needs hit_count, t, group and vertex0: the cursor is each ray's last
+        filled slot, and a ray that had no hit gets nothing again), or a (t, group, vertex0) triple of float32, int32 and uint32
+        (torch: int32) arrays of shape (n,); group < 0 means no cursor for that ray.  fields: any of hit_count, t, bw, vertex0, group,
+        back (default all).  Returns {field: array} shaped (n,) for hit_count, (n, k) and (n, k, 3) for the others, plus
+        "counters" (PrtCounters).  Slots from hit_count on hold the miss record."""
+        spec = {name: (c, dt) for name, c, dt in self.HITS_FIELDS}
+        if fields is None:
+            fields = tuple(spec)
+        for f in fields:
+            if f not in spec:
+                raise ValueError("unknown hits field %r" % (f,))
+        k = int(k)
+        check, empty, ptr, sync, suffix = self._arrays(origins)
+        origins = check(origins, "origins", (None, 3))
+        n = int(origins.shape[0])
+        directions = check(directions, "directions", (n, 3))
+        if tmax is not None:
+            tmax = check(tmax, "tmax", (n,))
+        cursor = (None, None, None)
+        if isinstance(after, dict):
+            for f in ("hit_count", "t", "group", "vertex0"):
+                if f not in after:
+                    raise ValueError("after: a previous result needs the field %r" % (f,))
+            count, kk = after["hit_count"], int(after["t"].shape[1]) if len(after["t"].shape) == 2 else 0
+            check(after["t"], "after['t']", (n, kk)), check(count, "after['hit_count']", (n,), (np.uint32,))
+            if suffix:
+                import torch
+                rows = torch.arange(n, device=origins.device)
+                at = (count.long() - 1).clamp(min=0)
+                some = count > 0
+                cursor = (torch.where(some, after["t"][rows, at], torch.full_like(after["t"][:, 0], float("inf"))).contiguous(),
+                          torch.where(some, after["group"][rows, at], torch.zeros_like(after["group"][:, 0])).contiguous(),
+                          torch.where(some, after["vertex0"][rows, at], torch.zeros_like(after["vertex0"][:, 0])).contiguous())
+            else:
+                rows = np.arange(n)
+                at = np.maximum(count.astype(np.int64) - 1, 0)
+                some = count > 0
+                cursor = (np.ascontiguousarray(np.where(some, after["t"][rows, at], np.float32(np.inf)), np.float32),
+                          np.ascontiguousarray(np.where(some, after["group"][rows, at], 0), np.int32),
+                          np.ascontiguousarray(np.where(some, after["vertex0"][rows, at], 0), np.uint32))
+        elif after is not None:
+            if len(after) != 3:
+                raise ValueError("after must be a previous result or a (t, group, vertex0) triple")
+            cursor = (check(after[0], "after t", (n,)), check(after[1], "after group", (n,), (np.int32,)),
+                      check(after[2], "after vertex0", (n,), (np.uint32,)))
+        shape = lambda c: (n,) if c == 0 else ((n, k) if c == 1 else (n, k, c))    # noqa: E731
+        out = {f: empty(shape(spec[f][0]), spec[f][1]) for f in fields} if 1 <= k <= capi.MAX_HITS else {}
+        sync()
+        rq = capi.PrtHitsRequest(capi.PrtRayBatch(ptr(origins), ptr(directions), ptr(tmax), n, float(ray_bias)), k,
+                                 capi.HITS_BACK_FACES if back_faces else 0, *[ptr(c) for c in cursor])
+        hb = capi.PrtHitsBuffers(*[ptr(out[name]) if name in out else None for name, _, _ in self.HITS_FIELDS])
+        counters = PrtCounters()
+        flags = capi.FLAG_COUNT_VISITS if count_visits else 0
+        name = "prt_trace_hits" + suffix
+        self._check(getattr(self._lib, name)(self._ctx, C.byref(rq), C.byref(hb), flags, C.byref(counters)), name)
+        out["counters"] = counters
+        return out
+
     # (name, components per point, numpy dtype) of prt_closest_buffers' fields
     CLOSEST_POINT_FIELDS = (("dist2", 1, np.float32), ("point", 3, np.float32), ("bw", 3, np.float32), ("vertex0", 1, np.uint32),
                             ("group", 1, np.int32))

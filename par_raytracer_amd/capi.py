@@ -210,12 +210,24 @@ class PrtHemiBuffers(C.Structure):
     _fields_ = [("unoccluded", C.c_void_p), ("visibility", C.c_void_p), ("bent", C.c_void_p)]
 
 
+class PrtHitsRequest(C.Structure):
+    _fields_ = [("rays", PrtRayBatch), ("k", C.c_uint32), ("flags", C.c_uint32), ("after_t", C.c_void_p), ("after_group", C.c_void_p),
+                ("after_vertex0", C.c_void_p)]
+
+
+class PrtHitsBuffers(C.Structure):
+    _fields_ = [("hit_count", C.c_void_p), ("t", C.c_void_p), ("bw", C.c_void_p), ("vertex0", C.c_void_p), ("group", C.c_void_p),
+                ("back", C.c_void_p)]
+
+
 class PrtRadianceBatch(C.Structure):
     _fields_ = [("origins", C.c_void_p), ("directions", C.c_void_p), ("count", C.c_uint32), ("flags", C.c_uint32), ("first", C.c_uint64)]
 
 
 QUERY_CLOSEST, QUERY_OCCLUDED = 0, 1
 RAYS_CAMERA_STREAM = 1
+MAX_HITS = 16
+HITS_BACK_FACES = 1
 PIPELINE_DEFAULT, PIPELINE_MEGAKERNEL, PIPELINE_WAVEFRONT, PIPELINE_PERSISTENT, PIPELINE_POOL = 0, 1, 2, 3, 4
 FLAG_COUNT_VISITS = 0x100
 FLAG_TRYOUT = 0x200
@@ -235,7 +247,8 @@ PRT_SYMBOLS = ["prt_create", "prt_destroy", "prt_last_error", "prt_abi_version",
                "prt_sample_surface", "prt_sample_surface_device",
                "prt_sample_surface_backward", "prt_sample_surface_backward_device",
                "prt_hemisphere_visibility", "prt_hemisphere_visibility_device",
-               "prt_render_rays", "prt_render_rays_device"]
+               "prt_render_rays", "prt_render_rays_device",
+               "prt_trace_hits", "prt_trace_hits_device"]
 # PRT_REGION_* of include/prt.h, in index order (tests/test_host_side.py's header check keeps the symbol list in step; the
 # region test compares this list with the header's enum)
 REGION_NAMES = ["round", "topup", "topup_pass", "trace_outer", "refill", "walk_pass", "node_step", "node_descend", "node_pop", "node_push", "leaf",
@@ -360,6 +373,9 @@ def hip_lib() -> C.CDLL:
         if hasattr(lib, "prt_render_rays"):
             lib.prt_render_rays.argtypes = [C.c_void_p, C.POINTER(PrtRadianceBatch), C.POINTER(PrtParams), C.c_void_p, C.POINTER(PrtCounters)]
             lib.prt_render_rays_device.argtypes = lib.prt_render_rays.argtypes
+        if hasattr(lib, "prt_trace_hits"):
+            lib.prt_trace_hits.argtypes = [C.c_void_p, C.POINTER(PrtHitsRequest), C.POINTER(PrtHitsBuffers), C.c_uint32, C.POINTER(PrtCounters)]
+            lib.prt_trace_hits_device.argtypes = lib.prt_trace_hits.argtypes
         _hip = lib
     return _hip
 

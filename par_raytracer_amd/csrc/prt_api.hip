@@ -41,6 +41,7 @@
 #include "kernels_sample_grad.h"
 #include "kernels_hemi.h"
 #include "kernels_rays.h"
+#include "kernels_hits.h"
 #include "hammersley.h"
 
 using namespace prt;
@@ -281,6 +282,7 @@ struct prt_ctx {
     DevBuf<unsigned int> q_work;          // the batch's control words (BatchShared::work, dev_wave_loop.h)
     DevBuf<unsigned int> q_slow;          // rays handed to k_query_exact
     DevBuf<int> q_exact_stack;
+    DevBuf<int> q_hits_lists;             // k_hits_exact's list columns (HitsArgs::exact_lists, kernels_hits.h)
     DevBuf<float> q_io;                   // host entry point: the batch and the requested fields on the device
     DevBuf<unsigned char> q_occ;
     DevBuf<unsigned char> q_hemi_flags;   // prt_hemisphere_visibility: one byte per item of a pass
@@ -1361,12 +1363,17 @@ int ensure_leaf_map(prt_ctx * ctx, const char * who) {
 
 int ensure_signed_tables(prt_ctx * ctx, ClosestArgs & A);
 
+// Dwords of dynamic LDS a walk keeps behind its stack columns: prt_trace_hits' sorted lists, 2 k words per lane (kernels_hits.h).
+template <typename Args>
+size_t walk_list_dwords(const Args &, size_t) { return 0; }
+size_t walk_list_dwords(const HitsArgs & A, size_t lanes) { return 2 * (size_t)A.k * lanes; }
+
 // The fast walk on its persistent grid, then the exact kernel for the items it set aside; its fixed grid reads the list's length
 // on the device.
 template <typename Fast, typename Exact, typename Args>
 int launch_walk(prt_ctx * ctx, Fast fast, Exact exact, const Args & A, unsigned int fields) {
     constexpr int BLOCK = 256;
-    const size_t lds = stack_dwords(A.stack_lds_entries, BLOCK) * sizeof(int);
+    const size_t lds = (stack_dwords(A.stack_lds_entries, BLOCK) + walk_list_dwords(A, BLOCK)) * sizeof(int);
     const TraceRule rule = trace_rule(ctx, fast, lds);
     const TraceGrid g = trace_grid(ctx, rule.per_cu, rule.chunk_min, A.count);
     hipLaunchKernelGGL(fast, dim3(g.grid), dim3(BLOCK), lds, ctx->stream, ctx->scene, A, ctx->tables.q_leaf_map.p, fields, rule.keep_min, rule.node_min,
@@ -1438,6 +1445,29 @@ struct PointWalk {
     int launch(prt_ctx * ctx, const ClosestArgs & A, unsigned int fields, bool count) const {
         return count ? launch_walk(ctx, k_closest<256, true>, k_closest_exact<true>, A, fields)
                      : launch_walk(ctx, k_closest<256, false>, k_closest_exact<false>, A, fields);
+    }
+    int verdict(prt_ctx *, const DevCounters &) const { return 0; }
+};
+
+struct HitsWalk {
+    typedef HitsArgs Args;
+    bool back;
+    static const char * name() { return "prt_trace_hits"; }
+    int prepare(prt_ctx * ctx, HitsArgs & A) const {
+        A.replay_beyond = 64.0f * ctx->desc.scene_abs_max;
+        A.scene_max = ctx->desc.scene_abs_max;
+        HIP_TRY(ctx, ctx->q_hits_lists.ensure(2 * (size_t)HITS_MAX * 64 * 256));       // one column per lane of the exact kernel's grid
+        A.exact_lists = ctx->q_hits_lists.p;
+        return 0;
+    }
+    int tables(prt_ctx *, HitsArgs &, unsigned int) const { return 0; }
+    static void (*pad_kernel())(QueryArgs) { return k_query_pad; }                  // (a HitsArgs is a QueryArgs)
+    int launch(prt_ctx * ctx, const HitsArgs & A, unsigned int fields, bool count) const {
+        if (back)
+            return count ? launch_walk(ctx, k_hits<256, true, true>, k_hits_exact<true, true>, A, fields)
+                         : launch_walk(ctx, k_hits<256, true, false>, k_hits_exact<true, false>, A, fields);
+        return count ? launch_walk(ctx, k_hits<256, false, true>, k_hits_exact<false, true>, A, fields)
+                     : launch_walk(ctx, k_hits<256, false, false>, k_hits_exact<false, false>, A, fields);
     }
     int verdict(prt_ctx *, const DevCounters &) const { return 0; }
 };
@@ -1932,6 +1962,19 @@ int grad_backward(prt_ctx * ctx, const char * what, const Grad & q, uint32_t pos
     return grad_fill_info(ctx, scan, info);
 }
 
+// batch_pad's extent of a batch of rays on the host: the scene's, and the valid rays' biased origins (k_query_pad's rule;
+// work[BATCH_W_EXTENT] stays 0).
+float ray_batch_extent(const prt_ctx * ctx, const prt_ray_batch * batch) {
+    float extent = ctx->desc.scene_abs_max;
+    for (size_t i = 0; i < batch->count; ++i) {
+        const f3 o = ld3(batch->origins + 3 * i), d = ld3(batch->directions + 3 * i), ob = o + d * batch->ray_bias;
+        const bool ok = std::isfinite(o.x) && std::isfinite(o.y) && std::isfinite(o.z) && std::isfinite(d.x) && std::isfinite(d.y) &&
+                        std::isfinite(d.z) && std::isfinite(ob.x) && std::isfinite(ob.y) && std::isfinite(ob.z);
+        if (ok) extent = std::max(extent, std::max(std::max(fabsf(ob.x), fabsf(ob.y)), fabsf(ob.z)));
+    }
+    return extent;
+}
+
 // prt_trace_rays and prt_trace_rays_device after query_check: `device` says where the caller's arrays live.
 int trace_rays(prt_ctx * ctx, int mode, const prt_ray_batch * batch, const prt_hit_buffers * hits, uint32_t flags, prt_counters * counters,
                bool device) {
@@ -1957,15 +2000,63 @@ int trace_rays(prt_ctx * ctx, int mode, const prt_ray_batch * batch, const prt_h
     io.out(&A.occluded, n, fields & QF_OCCLUDED, false);
     HIP_TRY(ctx, io.carve(ctx->q_io));
     if (fields & QF_OCCLUDED) { HIP_TRY(ctx, ctx->q_occ.ensure(n)); A.occluded = ctx->q_occ.p; }
-    // batch_pad's extent from the valid rays' biased origins, on the host (k_query_pad's rule; work[BATCH_W_EXTENT] stays 0)
-    float extent = ctx->desc.scene_abs_max;
-    for (size_t i = 0; i < n; ++i) {
-        const f3 o = ld3(batch->origins + 3 * i), d = ld3(batch->directions + 3 * i), ob = o + d * batch->ray_bias;
-        const bool ok = std::isfinite(o.x) && std::isfinite(o.y) && std::isfinite(o.z) && std::isfinite(d.x) && std::isfinite(d.y) &&
-                        std::isfinite(d.z) && std::isfinite(ob.x) && std::isfinite(ob.y) && std::isfinite(ob.z);
-        if (ok) extent = std::max(extent, std::max(std::max(fabsf(ob.x), fabsf(ob.y)), fabsf(ob.z)));
+    A.pad_max = ray_batch_extent(ctx, batch);
+    hipStream_t stream = ctx->stream;
+    HIP_TRY(ctx, io.upload(stream));
+    if (const int rc = run_batch(ctx, walk, A, fields, (flags & PRT_FLAG_COUNT_VISITS) != 0, counters)) return rc;
+    HIP_TRY(ctx, io.download(stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    return 0;
+}
+
+// ---- K nearest hits (prt_trace_hits, kernels_hits.h) ----------------------------------------------------------------------------
+
+unsigned int hits_fields(const prt_hits_buffers * o) {
+    return (o->hit_count ? HITF_COUNT : 0) | (o->t ? HITF_T : 0) | (o->bw ? HITF_BW : 0) | (o->vertex0 ? HITF_VERTEX0 : 0) |
+           (o->group ? HITF_GROUP : 0) | (o->back ? HITF_BACK : 0);
+}
+
+// The checks both entry points share; 1 = nothing to trace (count 0: counters zeroed), 0 = go on, < 0 = error.
+int hits_check(prt_ctx * ctx, const prt_hits_request * q, const prt_hits_buffers * o, prt_counters * counters) {
+    if (!ctx) return -1;
+    if (!q || !o) { ctx->error = "prt_trace_hits: null request or buffers"; return -1; }
+    if (q->rays.count && (!q->rays.origins || !q->rays.directions)) { ctx->error = "prt_trace_hits: null origins or directions"; return -1; }
+    if (q->k < 1 || q->k > PRT_MAX_HITS) { ctx->error = "prt_trace_hits: k must be 1.." + std::to_string((int)PRT_MAX_HITS); return -1; }
+    if (q->flags & ~(uint32_t)PRT_HITS_BACK_FACES) { ctx->error = "prt_trace_hits: unknown flag"; return -1; }
+    const int given = (q->after_t ? 1 : 0) + (q->after_group ? 1 : 0) + (q->after_vertex0 ? 1 : 0);
+    if (given != 0 && given != 3) { ctx->error = "prt_trace_hits: after_t, after_group and after_vertex0 must all be given, or none"; return -1; }
+    if (!ctx->has_scene) { ctx->error = "prt_trace_hits: no scene uploaded"; return -2; }
+    if (q->rays.count == 0) {
+        if (counters) memset(counters, 0, sizeof(*counters));
+        return 1;
     }
-    A.pad_max = extent;
+    return 0;
+}
+
+// prt_trace_hits and prt_trace_hits_device after hits_check: `device` says where the caller's arrays live.
+int trace_hits(prt_ctx * ctx, const prt_hits_request * q, const prt_hits_buffers * o, uint32_t flags, prt_counters * counters, bool device) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t n = q->rays.count, slots = n * q->k;
+    const unsigned int fields = hits_fields(o);
+    HitsArgs A;
+    memset(&A, 0, sizeof(A));
+    A.origins = q->rays.origins; A.dirs = q->rays.directions; A.tmax = q->rays.tmax;
+    A.count = q->rays.count; A.ray_bias = q->rays.ray_bias;
+    A.k = q->k;
+    A.after_t = q->after_t; A.after_group = q->after_group; A.after_vertex0 = q->after_vertex0;
+    A.hit_count = o->hit_count; A.t = o->t; A.bw = o->bw; A.vertex0 = o->vertex0; A.group = o->group; A.back = o->back;
+    A.pad_max = -1.0f;                                     // the origins' extent is reduced on the device (k_query_pad)
+    const HitsWalk walk = { (q->flags & PRT_HITS_BACK_FACES) != 0 };
+    if (device) return run_batch(ctx, walk, A, fields, (flags & PRT_FLAG_COUNT_VISITS) != 0, counters);
+    // device copies: the rays, the cursor, then the requested fields (float-sized words; the back bytes last, rounded up)
+    StageList io;
+    io.in(&A.origins, 12 * n); io.in(&A.dirs, 12 * n); io.in(&A.tmax, 4 * n);
+    io.in(&A.after_t, 4 * n); io.in(&A.after_group, 4 * n); io.in(&A.after_vertex0, 4 * n);
+    io.out(&A.hit_count, 4 * n, fields & HITF_COUNT); io.out(&A.t, 4 * slots, fields & HITF_T); io.out(&A.bw, 12 * slots, fields & HITF_BW);
+    io.out(&A.vertex0, 4 * slots, fields & HITF_VERTEX0); io.out(&A.group, 4 * slots, fields & HITF_GROUP);
+    io.out(&A.back, slots, fields & HITF_BACK);
+    HIP_TRY(ctx, io.carve(ctx->q_io));
+    A.pad_max = ray_batch_extent(ctx, &q->rays);
     hipStream_t stream = ctx->stream;
     HIP_TRY(ctx, io.upload(stream));
     if (const int rc = run_batch(ctx, walk, A, fields, (flags & PRT_FLAG_COUNT_VISITS) != 0, counters)) return rc;
@@ -2484,7 +2575,7 @@ void prt_destroy(prt_ctx * ctx) {
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     ctx->arrays.release(); ctx->tables.release(); ctx->spec_dirs.release();
     ctx->sample_rgb.release(); ctx->frame_out.release(); ctx->counters.release(); ctx->ring_ws.release(); ctx->pixel_list.release(); ctx->wf_counts.release(); ctx->stack_spill.release(); ctx->pool_f4.release(); ctx->pool_park.release(); ctx->pool_fin.release(); ctx->pool_args.release(); ctx->adapt_f4.release(); ctx->wave_times.release();
-    ctx->q_work.release(); ctx->q_slow.release(); ctx->q_exact_stack.release(); ctx->q_io.release(); ctx->q_occ.release(); ctx->q_hemi_flags.release(); ctx->rays_words.release();
+    ctx->q_work.release(); ctx->q_slow.release(); ctx->q_exact_stack.release(); ctx->q_hits_lists.release(); ctx->q_io.release(); ctx->q_occ.release(); ctx->q_hemi_flags.release(); ctx->rays_words.release();
     ctx->rf_boxes.release(); ctx->rf_bounds.release(); ctx->rf_in.release();
     ctx->qg_words.release(); ctx->qg_io.release();
     ctx->sm_words.release();
@@ -2737,6 +2828,24 @@ int prt_trace_rays(prt_ctx * ctx, int mode, const prt_ray_batch * batch, const p
     if (chk) return chk > 0 ? 0 : chk;
     return trace_rays(ctx, mode, batch, hits, flags, counters, false);
     PRT_API_CATCH_RC(ctx, "prt_trace_rays")
+}
+
+int prt_trace_hits_device(prt_ctx * ctx, const prt_hits_request * request, const prt_hits_buffers * out, uint32_t flags,
+                          prt_counters * counters) {
+    PRT_API_TRY
+    const int chk = hits_check(ctx, request, out, counters);
+    if (chk) return chk > 0 ? 0 : chk;
+    return trace_hits(ctx, request, out, flags, counters, true);
+    PRT_API_CATCH_RC(ctx, "prt_trace_hits_device")
+}
+
+int prt_trace_hits(prt_ctx * ctx, const prt_hits_request * request, const prt_hits_buffers * out, uint32_t flags,
+                   prt_counters * counters) {
+    PRT_API_TRY
+    const int chk = hits_check(ctx, request, out, counters);
+    if (chk) return chk > 0 ? 0 : chk;
+    return trace_hits(ctx, request, out, flags, counters, false);
+    PRT_API_CATCH_RC(ctx, "prt_trace_hits")
 }
 
 int prt_closest_points_device(prt_ctx * ctx, const prt_point_batch * batch, const prt_closest_buffers * out, uint32_t flags,
